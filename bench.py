@@ -18,7 +18,12 @@ primary `roofline` is the kernel that reads the input planes, `roofline_kernels`
 timed kernel with its own algorithmic bytes and, when profiles/pmc_<workload>.json holds a
 PMC pass of the same configuration, its counted HBM traffic.
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task description).
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps, writes
+the last step's outputs when `--dump-outputs DIR` is given and prints the result line.  The
+other measurements (isolated launches per kernel, the end-to-end worker legs, the CPU baseline
+sweep) run only with `--full`.
+
+Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
 
@@ -67,6 +72,14 @@ def parse():
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--pool", type=int, default=480, help="distinct resident frames per GPU")
     p.add_argument("--seg", type=int, default=None)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the secondary measurements: isolated launches per "
+                        "kernel, the end-to-end worker legs (--no-e2e skips them) and the CPU baseline sweep "
+                        "(--no-cpu-baseline skips it); a run without it measures the headline alone")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step returned as DIR/<name>.npy "
+                        "(rank 0): jpeg_sizes (every frame's JPEG byte count), jpeg_checksums (two byte sums "
+                        "per frame) and jpeg_sample (the JPEG bytes of a fixed, seeded sample of the frames)")
     p.add_argument("--cpu-seconds", type=float, default=4.0,
                    help="CPU baseline: wall seconds per point of the core-count sweep")
     p.add_argument("--no-cpu-baseline", action="store_true")
@@ -498,6 +511,50 @@ def rooflines(kt, fpl, mean_jpeg, pmc, optimal, scaled, step_ms=None, seg=None):
     return primary, out
 
 
+# ------------------------------------------------------------------------ outputs
+DUMP_SAMPLE_BYTES = 12 << 20  # JPEG bytes in jpeg_sample.npy (float32: 48 MiB of the 64 MB a dump may take)
+DUMP_SEED = 20240
+
+
+def dump_sample_frames(sizes, budget=DUMP_SAMPLE_BYTES, seed=DUMP_SEED):
+    """The frames whose bytes go into jpeg_sample.npy: a seeded permutation of the step's
+    frames, taken in its order while their JPEGs fit in `budget` bytes (the first one always,
+    cut at the budget).  Fixed by the number of frames and their sizes alone."""
+    import numpy as np
+    order = np.random.default_rng(seed).permutation(len(sizes))
+    picked, used = [], 0
+    for i in order:
+        n = int(sizes[i])
+        if picked and used + n > budget:
+            break
+        picked.append(int(i))
+        used += min(n, budget)
+    return sorted(picked)
+
+
+def dump_outputs(dirname, sizes, jpegs):
+    """What the last timed step handed its caller, as float arrays: `sizes` is sync()'s array
+    (one JPEG byte count per frame), `jpegs` fetch_views()'s list (one JPEG per frame).
+      jpeg_sizes.npy      float64 [frames]     byte count of every frame's JPEG
+      jpeg_checksums.npy  float64 [frames, 2]  per frame: sum of its bytes, and sum of
+                                               byte[i] * (1 + i % 251); both exact in float64
+      jpeg_sample_frames.npy float64 [k]       the sampled frames' indices (dump_sample_frames)
+      jpeg_sample.npy     float32 [bytes]      the sampled frames' JPEG bytes, concatenated"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    sizes = np.asarray(sizes)
+    sums = np.zeros((len(jpegs), 2), np.float64)
+    for i, j in enumerate(jpegs):
+        b = np.frombuffer(j, np.uint8).astype(np.int64)
+        sums[i] = b.sum(), (b * (1 + np.arange(b.size, dtype=np.int64) % 251)).sum()
+    picked = dump_sample_frames(sizes)
+    sample = np.concatenate([np.frombuffer(jpegs[i], np.uint8) for i in picked])[:DUMP_SAMPLE_BYTES]
+    np.save(os.path.join(dirname, "jpeg_sizes.npy"), sizes.astype(np.float64))
+    np.save(os.path.join(dirname, "jpeg_checksums.npy"), sums)
+    np.save(os.path.join(dirname, "jpeg_sample_frames.npy"), np.asarray(picked, np.float64))
+    np.save(os.path.join(dirname, "jpeg_sample.npy"), sample.astype(np.float32))
+
+
 def torchrun_argv(gpus: int, argv, port: int):
     """`--gpus N` (N > 1) outside a launcher: the driver's own launch line, one rank per GPU."""
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={gpus}",
@@ -575,6 +632,11 @@ def main():
                        timing=False if a.no_kernel_timing else ("detail" if a.kernel_timing_detail else True),
                        huffman=HUFF, rst=a.rst, merge=True)
     bytes_out = []
+    last_sizes = [None]  # sync()'s array of the submit synced last (--dump-outputs)
+
+    def collect():
+        last_sizes[0] = enc.sync()
+        bytes_out.append(int(last_sizes[0].sum()))
 
     # Segments are pipelined enc.depth (mjg_queue_depth(): 2) deep, as mjg_submit queues them: later segments'
     # kernels are queued behind segment s's before s is synced, so the GPU does not idle while
@@ -585,11 +647,11 @@ def main():
         base = pool[(s % nseg_pool) * seg]
         enc.submit(device_ptr=base.data_ptr(), nframes=seg)
         if enc.pending == depth:
-            bytes_out.append(int(enc.sync().sum()))
+            collect()
 
     def drain_and_sync():
         while enc.pending:
-            bytes_out.append(int(enc.sync().sum()))
+            collect()
         torch.cuda.synchronize()
 
     def trace_marker():
@@ -628,6 +690,10 @@ def main():
     else:
         kt, nl = enc.kernel_times()
     dt = max_over_ranks(dt, dist if world > 1 else None, dev)
+    if a.dump_outputs and rank == 0:
+        # the timed region's drain synced the last step's submit last: its sizes, and the packed
+        # JPEGs the library still holds for it (before anything else is submitted)
+        dump_outputs(a.dump_outputs, last_sizes[0], enc.fetch_views())
 
     frames_total = a.steps * seg * world
     value = frames_total / dt
@@ -646,7 +712,7 @@ def main():
     # merged launch, as one two-segment list on a context of twice the frames)
     iso = []
     if not a.no_kernel_timing:
-        for k in (1, 2):
+        for k in ((1, 2) if a.full else ()):  # runs of their own: --full only
             if k > nseg_pool:
                 continue
             e2 = enc if k == 1 else MjpegEncoder(local, W, H, DW, DH, full_range=FULL, qscale=Q, max_batch=k * seg,
@@ -677,13 +743,13 @@ def main():
     out = None
     if rank == 0:
         e2e_res = None
-        if not a.no_e2e and world == 1 and a.content == "testsrc" and not a.rst:
+        if a.full and not a.no_e2e and world == 1 and a.content == "testsrc" and not a.rst:
             try:
                 e2e_res = e2e_child(a.workload, local, a.e2e_segments)
             except Exception as e:  # reported, never fatal for the GPU number
                 e2e_res = {"error": repr(e)}
         cpu = None
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             try:
                 cpu = cpu_baseline(a.cpu_seconds, a.workload, HUFF)
             except Exception as e:  # reported, never fatal for the GPU number
@@ -697,6 +763,7 @@ def main():
             "n_gpus": world,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": a.full,
             "prewarm": {"ms": a.prewarm_ms, "steps": prewarm,
                         "why": "untimed steps before the W warmup steps: the GPU runs at its idle clocks "
                                "for the first ~0.3 s of load (DESIGN §6)"},

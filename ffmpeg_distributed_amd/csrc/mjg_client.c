@@ -330,7 +330,11 @@ int main(int argc, char **argv) {
     close(sk);
     if (k == 1)  // a byte that is not the acknowledgement: another protocol; never resend
       return die(dev, "the resident encoder answered outside the MJG2 protocol", 0);
-    if (k < 0 && rerr != ECONNRESET && rerr != EPIPE)
+    // a send that met the closed connection (EPIPE / ECONNRESET: the encoder closed it before
+    // the request left) consumed nothing either: the same retry as a close before the 'A'
+    if (rc_send < 0 && rc_send != -ECONNRESET && rc_send != -EPIPE)
+      return die(dev, "sending the request to the resident encoder", -rc_send);
+    if (rc_send == 0 && k < 0 && rerr != ECONNRESET && rerr != EPIPE)
       return die(dev, "reading the resident encoder's acknowledgement", rerr);
     // EOF / reset before the 'A': the encoder closed this connection unread (idle exit);
     // nothing of the segment was consumed, so connect again (a few times at most)

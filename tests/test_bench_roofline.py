@@ -70,6 +70,29 @@ def test_no_pmc_gives_null_traffic(workload):
     assert primary["traffic"] is None and ents[0]["traffic"] is None
 
 
+def test_dump_outputs_writes_float_arrays_of_the_step(tmp_path):
+    """--dump-outputs: every frame's size and checksums, and the bytes of a sample of frames that
+    depends on the sizes alone (the same frames from two builds that agree), within its budget."""
+    import numpy as np
+    rng = np.random.default_rng(3)
+    jpegs = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in (700, 1, 513, 300, 90)]
+    sizes = np.array([len(j) for j in jpegs], np.uint64)
+    picked = bench.dump_sample_frames(sizes, budget=1000)
+    assert picked == bench.dump_sample_frames(sizes.copy(), budget=1000) and 1 <= len(picked) < 5
+    assert sum(int(sizes[i]) for i in picked) <= 1000
+    assert bench.dump_sample_frames(sizes, budget=10) != []       # one frame at least, cut at the budget
+    assert bench.dump_sample_frames(sizes) == [0, 1, 2, 3, 4]     # everything fits: every frame
+    bench.dump_outputs(str(tmp_path / "d"), sizes, jpegs)
+    got = {f: np.load(tmp_path / "d" / f) for f in ("jpeg_sizes.npy", "jpeg_checksums.npy",
+                                                     "jpeg_sample_frames.npy", "jpeg_sample.npy")}
+    assert got["jpeg_sizes.npy"].dtype == np.float64 and list(got["jpeg_sizes.npy"]) == [700, 1, 513, 300, 90]
+    assert got["jpeg_sample.npy"].dtype == np.float32
+    assert got["jpeg_sample.npy"].tobytes() == np.frombuffer(b"".join(jpegs), np.uint8).astype(np.float32).tobytes()
+    b = np.frombuffer(jpegs[2], np.uint8).astype(np.int64)
+    assert list(got["jpeg_checksums.npy"][2]) == [b.sum(), (b * (1 + np.arange(513) % 251)).sum()]
+    assert list(got["jpeg_sample_frames.npy"]) == [0, 1, 2, 3, 4]
+
+
 def test_gpus_without_launcher_runs_the_driver_launch_line():
     """`python bench.py --gpus N` outside torchrun re-runs itself under the driver's launch line
     (one rank per GPU, rendezvous on 127.0.0.1) as a child, with the same arguments."""

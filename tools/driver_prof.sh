@@ -7,7 +7,7 @@
 set -o pipefail
 TAG=${1:-r05}
 shift
-ARGS=${@:---gpus 1 --steps 20 --warmup 5}
+ARGS=${@:---gpus 1 --steps 20 --warmup 5 --full}  # --full: the isolated launches the timeline reports
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 O=gpurun_out/$TAG
