@@ -135,10 +135,6 @@ __device__ __forceinline__ int range_chroma(int p) {
 
 #define MJG_DESCALE(x, n) (((x) + (1 << ((n) - 1))) >> (n))
 
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u16x2 as_u16x2(uint32_t v) { return __builtin_bit_cast(u16x2, v); }
-__device__ __forceinline__ uint32_t as_u32(u16x2 v) { return __builtin_bit_cast(uint32_t, v); }
-
 // One 8-point jfdctint butterfly on p[0], p[S], ... p[7S] (CONST_BITS 13, PASS1_BITS 4).
 // ROW: pass 1 (d0/d4 << 4, others descale 9); !ROW: pass 2 (descale 4 / 17).  Every
 // stored value fits int16 for 8-bit input, so FFmpeg's int16 stores are identities here.
@@ -874,9 +870,18 @@ __device__ __forceinline__ void pack_chunk_short(const ShiftSink &q, uint32_t bi
 // Row pass of one chunk, lane = block: raw rows (8 little-endian words of 8 pixels) ->
 // the wave's LDS row image s_pk ([word][lane]; word c*4 + r/2 = column c of rows r, r+1 as
 // u16 pairs; output 0 as is, 1-7 + 16384).
+// Column skip (columns 2-7): every AC output of a column quantises to zero when the column's
+// row-pass values are small enough, |u_r| <= A for all 8 rows (open_ctx derives A from the
+// quantiser thresholds, s_lim[c - 2] = its fp32 form for column c).  When `watch` (wave-uniform)
+// is set the pass keeps, per column, the running maximum of |v| over the rows, v the value it
+// holds before the rounding add (one v_max3_f32 per column and row pair), and returns the
+// wave-uniform mask of the columns (bits 2-7) in which every active block of the chunk is within
+// the limit: column_screen leaves those columns out, their 8 screen bits are 0.  0 when not
+// watching.
 template <bool RC>
-__device__ __forceinline__ void row_pass(const uint64_t (&raw)[8], int tab, const uint8_t *s_rc,
-                                         uint32_t *s_pk, int lane) {
+__device__ __forceinline__ uint32_t row_pass(const uint64_t (&raw)[8], int tab, const uint8_t *s_rc,
+                                             uint32_t *s_pk, int lane, const float *s_lim, bool watch,
+                                             bool active) {
   // Row pass (jfdctint pass 1) in fp32, exactly: every value is an integer or a multiple
   // of 2^-10 below 2^14 (24 significant bits), each fma rounds nothing, and the DESCALE
   // floor((x + 256) / 512) is the single round-to-nearest-even of (x/512 + 2^-10) + M'
@@ -887,6 +892,8 @@ __device__ __forceinline__ void row_pass(const uint64_t (&raw)[8], int tab, cons
   // checked exhaustively in tests/test_oracle.py), OR'ed into the mantissa of M = 1.5*2^23:
   // values then carry the +M bias, which the butterfly's differences cancel and its sums
   // remove with one -2M.
+  // o[0] is final; o[1..7] are the values before the rounding add of kMc (o[4]: before its
+  // * 16 as well)
   auto row = [&](int r, float (&o)[8]) {
     const uint32_t lo = (uint32_t)raw[r], hi = (uint32_t)(raw[r] >> 32);
     float p[8];
@@ -921,28 +928,48 @@ __device__ __forceinline__ void row_pass(const uint64_t (&raw)[8], int tab, cons
     const float t7 = p[0] - p[7], t6 = p[1] - p[6], t5 = p[2] - p[5], t4 = p[3] - p[4];
     const float t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
     o[0] = __builtin_fmaf(t10 + t11, 16.0f, kM);  // the row sum: unbiased (0..32640)
-    o[4] = __builtin_fmaf(t10 - t11, 16.0f, kMc);
-    o[2] = __builtin_fmaf(t13, 10703.0f / 512, __builtin_fmaf(t12, 4433.0f / 512, kRnd)) + kMc;
-    o[6] = __builtin_fmaf(t13, 4433.0f / 512, __builtin_fmaf(t12, -10704.0f / 512, kRnd)) + kMc;
+    o[4] = t10 - t11;
+    o[2] = __builtin_fmaf(t13, 10703.0f / 512, __builtin_fmaf(t12, 4433.0f / 512, kRnd));
+    o[6] = __builtin_fmaf(t13, 4433.0f / 512, __builtin_fmaf(t12, -10704.0f / 512, kRnd));
     o[1] = __builtin_fmaf(t7, 11363.0f / 512, __builtin_fmaf(t6, 9633.0f / 512,
-           __builtin_fmaf(t5, 6437.0f / 512, __builtin_fmaf(t4, 2260.0f / 512, kRnd)))) + kMc;
+           __builtin_fmaf(t5, 6437.0f / 512, __builtin_fmaf(t4, 2260.0f / 512, kRnd))));
     o[3] = __builtin_fmaf(t7, 9633.0f / 512, __builtin_fmaf(t6, -2259.0f / 512,
-           __builtin_fmaf(t5, -11362.0f / 512, __builtin_fmaf(t4, -6436.0f / 512, kRnd)))) + kMc;
+           __builtin_fmaf(t5, -11362.0f / 512, __builtin_fmaf(t4, -6436.0f / 512, kRnd))));
     o[5] = __builtin_fmaf(t7, 6437.0f / 512, __builtin_fmaf(t6, -11362.0f / 512,
-           __builtin_fmaf(t5, 2261.0f / 512, __builtin_fmaf(t4, 9633.0f / 512, kRnd)))) + kMc;
+           __builtin_fmaf(t5, 2261.0f / 512, __builtin_fmaf(t4, 9633.0f / 512, kRnd))));
     o[7] = __builtin_fmaf(t7, 2260.0f / 512, __builtin_fmaf(t6, -6436.0f / 512,
-           __builtin_fmaf(t5, 9633.0f / 512, __builtin_fmaf(t4, -11363.0f / 512, kRnd)))) + kMc;
+           __builtin_fmaf(t5, 9633.0f / 512, __builtin_fmaf(t4, -11363.0f / 512, kRnd))));
   };
+  float m[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // max |v| of columns 2-7 over the rows so far
 #pragma unroll
   for (int rp = 0; rp < 4; rp++) {
     float a[8], b[8];
     row(2 * rp, a);
     row(2 * rp + 1, b);
+    if (watch) {
 #pragma unroll
-    for (int c = 0; c < 8; c++)
-      s_pk[(c * 4 + rp) * 64 + lane] = __builtin_amdgcn_perm(__float_as_uint(b[c]), __float_as_uint(a[c]), 0x05040100u);
+      for (int c = 2; c < 8; c++)
+        m[c - 2] = __builtin_fmaxf(__builtin_fmaxf(m[c - 2], __builtin_fabsf(a[c])), __builtin_fabsf(b[c]));
+    }
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+      const float fa = c == 0 ? a[c] : c == 4 ? __builtin_fmaf(a[c], 16.0f, kMc) : a[c] + kMc;
+      const float fb = c == 0 ? b[c] : c == 4 ? __builtin_fmaf(b[c], 16.0f, kMc) : b[c] + kMc;
+      s_pk[(c * 4 + rp) * 64 + lane] = __builtin_amdgcn_perm(__float_as_uint(fb), __float_as_uint(fa), 0x05040100u);
+    }
     __builtin_amdgcn_sched_barrier(0);
   }
+  uint32_t skip = 0;
+  if (watch) {
+    const float4 la = *(const float4 *)s_lim;
+    const float2 lb = *(const float2 *)(s_lim + 4);
+    const float lim[6] = {la.x, la.y, la.z, la.w, lb.x, lb.y};
+    const uint64_t act = __ballot(active);  // lanes past the segment's last block hold no picture
+#pragma unroll
+    for (int c = 2; c < 8; c++)
+      if ((__ballot(m[c - 2] > lim[c - 2]) & act) == 0ull) skip |= 1u << c;
+  }
+  return skip;
 }
 
   // Column pass (jfdctint pass 2) as a float *screen*: the products of pass 2 need up to
@@ -952,61 +979,28 @@ __device__ __forceinline__ void row_pass(const uint64_t (&raw)[8], int tab, cons
   // order; emit_block quantises the candidates exactly from the integer row image
   // (exact_coef).  Rows 0 and 4 (sums only) are exact, which gives the DC exactly:
   // (((x + 8) >> 4) + 32) >> 6 == floor((sum + 520) / 1024).
-// Adaptive skip test: st bit jp (wave-uniform, carried from chunk to chunk) records whether pair
-// jp's test skipped a column on the wave's previous test of it.  A pair is tested when it did,
-// or on every fourth chunk (retest); a pair whose columns are rarely skippable (detailed
-// content) then costs its test a quarter of the time (the test is ~20 VALU per pair).
+// Column skip: `skip` is row_pass's mask of the columns (2-7) whose AC outputs all quantise to
+// zero in every block of the chunk; they are left out, row image loads included.
 // The candidate bits are deposited straight at their zigzag positions (mlo: scan positions 0-31,
 // mhi: 32-63; r and col are compile-time after unrolling, so each bit costs a shift and an
 // and-or): the emission visits candidates in scan order with no scatter step.
-__device__ __forceinline__ void column_screen(const uint32_t *s_pk, int lane, const uint32_t *s_skip,
-                                              const float *s_thr, int &dc, uint32_t &mlo, uint32_t &mhi,
-                                              uint32_t &st, bool retest) {
+__device__ __forceinline__ void column_screen(const uint32_t *s_pk, int lane, const float *s_thr, int &dc,
+                                              uint32_t &mlo, uint32_t &mhi, uint32_t skip) {
 #pragma unroll
   for (int jp = 0; jp < 4; jp++) {
     __builtin_amdgcn_sched_barrier(0);  // one column pair in flight at a time
-    uint32_t w[8];  // w[4h + i]: column 2jp + h of rows 2i (low half), 2i + 1 (high half)
-#pragma unroll
-    for (int i = 0; i < 8; i++) w[i] = s_pk[(jp * 8 + i) * 64 + lane];
-    // Column skip (pairs 1-3): every AC output of a column quantises to zero when the
-    // column's row-pass values are small enough.  Rows 1-7 of pass 2 have coefficient
-    // sums 0, so |S_k| <= L1(row k) * R / 2 with R = max - min of the column; row 0 is
-    // the plain sum, |S_0| <= 8 max|u|.  open_ctx turns the quantiser thresholds into
-    // limits on R, max and min (u16 with the +16384 bias), tested with packed u16
-    // max/min and saturating subtracts; a column is skipped when every block of the
-    // chunk passes (wave ballot), its 8 screen bits are then 0.
-    bool skip0 = false, skip1 = false;
-    if (jp > 0 && (((st >> jp) & 1u) || retest)) {
-      u16x2 ma = as_u16x2(w[0]), na = ma, mb = as_u16x2(w[4]), nb = mb;
-#pragma unroll
-      for (int i = 1; i < 4; i++) {
-        ma = __builtin_elementwise_max(ma, as_u16x2(w[i]));
-        na = __builtin_elementwise_min(na, as_u16x2(w[i]));
-        mb = __builtin_elementwise_max(mb, as_u16x2(w[4 + i]));
-        nb = __builtin_elementwise_min(nb, as_u16x2(w[4 + i]));
-      }
-      // (column 2jp, column 2jp + 1): each column's even-row and odd-row halves combined
-      const u16x2 mx = __builtin_elementwise_max(as_u16x2(__builtin_amdgcn_perm(as_u32(mb), as_u32(ma), 0x05040100u)),
-                                                 as_u16x2(__builtin_amdgcn_perm(as_u32(mb), as_u32(ma), 0x07060302u)));
-      const u16x2 mn = __builtin_elementwise_min(as_u16x2(__builtin_amdgcn_perm(as_u32(nb), as_u32(na), 0x05040100u)),
-                                                 as_u16x2(__builtin_amdgcn_perm(as_u32(nb), as_u32(na), 0x07060302u)));
-      const uint32_t t =
-          as_u32(__builtin_elementwise_sub_sat(mx - mn, as_u16x2(s_skip[3 * jp - 3]))) |
-          as_u32(__builtin_elementwise_sub_sat(mx, as_u16x2(s_skip[3 * jp - 2]))) |
-          as_u32(__builtin_elementwise_sub_sat(as_u16x2(s_skip[3 * jp - 1]), mn));
-      skip0 = __ballot((t & 0xffffu) != 0u) == 0;
-      skip1 = __ballot((t >> 16) != 0u) == 0;
-      st = (skip0 || skip1) ? st | (1u << jp) : st & ~(1u << jp);
-    }
 #pragma unroll
     for (int h = 0; h < 2; h++) {
       __builtin_amdgcn_sched_barrier(0);  // one column at a time
       const int col = 2 * jp + h;
-      if (h ? skip1 : skip0) continue;  // wave-uniform: no candidates in this column
+      if ((skip >> col) & 1u) continue;  // wave-uniform: no candidates in this column
+      uint32_t w[4];  // column col of rows 2i (low half), 2i + 1 (high half)
+#pragma unroll
+      for (int i = 0; i < 4; i++) w[i] = s_pk[(col * 4 + i) * 64 + lane];
       float x[8];
 #pragma unroll
       for (int r = 0; r < 8; r++)
-        x[r] = __uint_as_float(__builtin_amdgcn_perm(0x4B400000u, w[4 * h + r / 2], (r & 1) ? 0x07060302u : 0x07060100u));
+        x[r] = __uint_as_float(__builtin_amdgcn_perm(0x4B400000u, w[r / 2], (r & 1) ? 0x07060302u : 0x07060100u));
       // x = M' + value (M' = kM for column 0, kMc for the others): differences cancel the
       // bias, sums drop it with one -2M'
       const float kB2 = col == 0 ? 2.0f * kM : 2.0f * kMc;
@@ -1103,7 +1097,7 @@ __global__ __launch_bounds__(64 * kWavesPerWg, MODE == kCount ? 4 : kEncWavesPer
   __shared__ uint8_t s_rc[RC ? 512 : 1];  // tv->pc: luma [0,256), chroma [256,512)
   __shared__ uint32_t s_desc[8];                   // block-of-MCU descriptors (EncGeom)
   __shared__ uint4 s_bd[16];                       // their plane fields (BlockDesc)
-  __shared__ uint32_t s_skip[12];        // column-skip limits, 3 u16x2 words per pair
+  __shared__ __attribute__((aligned(16))) float s_lim[8];  // column-skip limits of columns 2-7 (row_pass)
   __shared__ uint32_t s_pk_all[kWavesPerWg][32 * 64];  // quantised blocks, [word][lane]
   // emit_block_wave's stream words, pack_chunk_short's chunk words
   __shared__ uint32_t s_hv_all[MODE == kEmitDefault ? kWavesPerWg : 1][kHvWords];
@@ -1127,7 +1121,7 @@ __global__ __launch_bounds__(64 * kWavesPerWg, MODE == kCount ? 4 : kEncWavesPer
     s_desc[tid] = tabs[672 + tid];
   }
   init_block_desc(g, tabs, s_bd, tid);
-  if (tid < 12) s_skip[tid] = tabs[680 + tid];
+  if (tid < 6) s_lim[tid] = __uint_as_float(tabs[680 + tid]);
   if (RC)
     for (int i = tid; i < 512; i += 64 * kWavesPerWg)
       s_rc[i] = (uint8_t)(i < 256 ? range_luma(i) : range_chroma(i - 256));
@@ -1172,7 +1166,11 @@ __global__ __launch_bounds__(64 * kWavesPerWg, MODE == kCount ? 4 : kEncWavesPer
   uint64_t raw[8];
   bool fast = fetch_rows(raw, fb, ((uintptr_t)fb & 7) == 0, block_pos(g, bbase + b, s_bd), active);
   int carry = carry_finish(carry_row(fb, g, bbase, chunk, lane, s_bd), chunk, lane, rc, g, s_desc);
-  uint32_t skip_st = 0xeu;  // column_screen's adaptive skip test: test every pair first
+  // Adaptive column-skip test: skip_st (wave-uniform, carried from chunk to chunk) holds the
+  // columns that the wave's previous watched row pass found skippable.  The row pass watches
+  // when there were any, or on every fourth chunk (retest): content whose columns are rarely
+  // skippable (detailed pictures) then pays for the watch a quarter of the time.
+  uint32_t skip_st = 0xfcu;  // watch the first chunk
 
   while (true) {
     // the next unit is reserved at the top of this unit's last chunk (its rows are prefetched
@@ -1183,7 +1181,9 @@ __global__ __launch_bounds__(64 * kWavesPerWg, MODE == kCount ? 4 : kEncWavesPer
     const int tab = desc_tab(dsc);
     if (active && !fast) fetch_rows_edge(raw, fb, block_pos(g, bbase + b, s_bd));
     int dc = 0;
-    row_pass<RC>(raw, tab, s_rc, s_pk, lane);
+    const bool watch = skip_st != 0u || (t & 3) == 0;
+    const uint32_t skip = row_pass<RC>(raw, tab, s_rc, s_pk, lane, s_lim, watch, active);
+    if (watch) skip_st = skip;
     // prefetch the next chunk while this one is encoded
     const int cur_frame = frame, cur_chunk = chunk, cur_bbase = bbase;
     const bool cur_active = active;
@@ -1205,7 +1205,7 @@ __global__ __launch_bounds__(64 * kWavesPerWg, MODE == kCount ? 4 : kEncWavesPer
 
     uint32_t mlo = 0, mhi = 0;  // candidate mask, scan positions 0-31 / 32-63 (column_screen)
     if (cur_active) {
-      column_screen(s_pk, lane, s_skip, s_thr, dc, mlo, mhi, skip_st, (t & 3) == 0);
+      column_screen(s_pk, lane, s_thr, dc, mlo, mhi, skip);
       if (DBG && g.debug_coefs) {  // natural-order int16 pairs of the exact quantised block
         uint32_t *dst = (uint32_t *)(dbg_coefs +
                                      ((size_t)cur_frame * g.nmcu * g.bpm + cur_bbase + cur_chunk * 64 + lane) * 64);

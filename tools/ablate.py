@@ -33,8 +33,8 @@ EMIT = ("      emit_block(s_pk + lane, mask, diff, s_zd, s_m2, q);\n"
         "      q.finish();\n")
 WIDE = "    const uint64_t wide = wave_parallel_blocks(cur_active ? __popcll(mask) : 0);\n    if (cur_active && !((wide >> lane) & 1ull)) {\n"
 EXACT = "  const uint32_t *col = (const uint32_t *)((const uint8_t *)pkcol + d.w);\n"
-SCREEN = "      column_screen(s_pk, lane, s_skip, s_thr, dc, mlo, mhi, skip_st, (t & 3) == 0);"
-ROWPASS = "    row_pass<RC>(raw, tab, s_rc, s_pk, lane);"
+SCREEN = "      column_screen(s_pk, lane, s_thr, dc, mlo, mhi, skip);"
+ROWPASS = "    const uint32_t skip = row_pass<RC>(raw, tab, s_rc, s_pk, lane, s_lim, watch, active);"
 FBASE = "  auto frame_base = [&](int f) { return seg_frame(frames, f, g.frame_stride); };"
 RCIF = "    float t0, t1, t2, t3;\n    if (RC) {\n"
 RCBODY = """#pragma unroll
@@ -66,7 +66,7 @@ SUBS = {
                (WIDE, "    const uint64_t wide = 0;\n    if (cur_active && !((wide >> lane) & 1ull)) {\n")],
     "noexact": [(EXACT, "  if (d.x != 0u) return 1 + (int)(d.y & 1u);\n" + EXACT)],
     "noscreen": [(SCREEN, "      dc = (int)(s_pk[lane] & 255u) - 128;")],
-    "nodct": [(ROWPASS, "    {\n#pragma unroll\n      for (int r = 0; r < 8; r++) {\n"
+    "nodct": [(ROWPASS, "    const uint32_t skip = 0;\n    {\n#pragma unroll\n      for (int r = 0; r < 8; r++) {\n"
                         "        s_pk[(r * 4) * 64 + lane] = (uint32_t)raw[r];\n"
                         "        s_pk[(r * 4 + 1) * 64 + lane] = (uint32_t)(raw[r] >> 32);\n"
                         "      }\n    }"),

@@ -25,16 +25,16 @@ PATCHES = {
     # (profiles/r03_ab_serial_tail.txt)
     "serial_tail": lambda a: [("api.hip", "  HIP_TRY(hipStreamCreateWithPriority(&c->tail, hipStreamNonBlocking, greatest));\n",
                                "  c->tail = c->stream;\n")],
-    # no column skip test in the VALU column screen (profiles/r03_ab_column_skip.txt)
-    "no_skip": lambda a: [(K, "    if (jp > 0 && (((st >> jp) & 1u) || retest)) {\n", "    if (false) {\n")],
-    # the column skip test on every chunk (round 3's form, before the adaptive test)
-    "always_test": lambda a: [(K, "    if (jp > 0 && (((st >> jp) & 1u) || retest)) {\n", "    if (jp > 0) {\n")],
+    # no column skip: the row pass never watches (profiles/r03_ab_column_skip.txt)
+    "no_skip": lambda a: [(K, "    const bool watch = skip_st != 0u || (t & 3) == 0;\n", "    const bool watch = false;\n")],
+    # the row pass watches every chunk (round 3's form, before the adaptive test)
+    "always_test": lambda a: [(K, "    const bool watch = skip_st != 0u || (t & 3) == 0;\n", "    const bool watch = true;\n")],
     # wave-parallel block cost factor (profiles/r03_ab_wide_cost.txt)
     "wide_cost": lambda a: [(K, "const int cost = 4 * __popcll(hv[k])", f"const int cost = {int(a)} * __popcll(hv[k])")],
     # chunks per k_encode work unit, VALU stage (profiles/r03_ab_sched_units.txt)
-    "batch": lambda a: [(K, "constexpr int kBatchOf = MF ? 8 : 12;", f"constexpr int kBatchOf = MF ? 8 : {int(a)};")],
+    "batch": lambda a: [(K, "constexpr int kBatch = 12;", f"constexpr int kBatch = {int(a)};")],
     # k_encode scheduling barriers (profiles/r03_ab_sched_units.txt)
-    "no_sb_row": lambda a: [(K, "0x05040100u);\n    __builtin_amdgcn_sched_barrier(0);\n", "0x05040100u);\n")],
+    "no_sb_row": lambda a: [(K, "0x05040100u);\n    }\n    __builtin_amdgcn_sched_barrier(0);\n", "0x05040100u);\n    }\n")],
     "no_sb_pair": lambda a: [(K, "    __builtin_amdgcn_sched_barrier(0);  // one column pair in flight at a time\n", "")],
     "no_sb_col": lambda a: [(K, "      __builtin_amdgcn_sched_barrier(0);  // one column at a time\n", "")],
     # stuffing tail group size / rounds
@@ -77,7 +77,9 @@ PATCHES = {
     # record stores (timing probes: wrong tables / wrong replay; c1: 0.753 -> 0.658 / 0.817 ms,
     # profiles/r05/c1_count_ablation.txt).  Counting the DC and EOB symbols per distinct value
     # after the block (a ballot loop) instead of per lane measured slower: 0.791 vs 0.760 ms.
-    "cnt_noatomic": lambda a: [(K, "    atomicAdd(&hdc[cat], 1u);\n", ""), (K, "    atomicAdd(&hac[sym], 1u);\n", "")],
+    "cnt_noatomic": lambda a: [(K, "    atomicAdd(&hdc[cat & 7], 1u << ((cat >> 3) << 4));\n", ""),
+                               (K, "void ac(int sym, int, uint32_t mant) {\n    atomicAdd(&hac[sym & 127], 1u << ((sym >> 7) << 4));\n",
+                                "void ac(int sym, int, uint32_t mant) {\n")],
     "cnt_norec": lambda a: [(K, "    rec[n * 64] = (1u << 31) | ((uint32_t)cat << 16) | mant;\n", ""),
                             (K, "    rec[n * 64] = ((uint32_t)sym << 16) | mant;\n", "")],
     # occupancy probe: k_encode's workgroup LDS past 40 KB (3 workgroups, 3 waves per SIMD)
@@ -107,9 +109,9 @@ def _phase_clock(a):
          "  if (MODE == kEmitDefault && lane == 0 && gw < 16384) mjg_wave_t0[gw] = __builtin_amdgcn_s_memrealtime();\n"
          "  unsigned int ph_n = 0;\n"
          "  while (true) {\n    MJG_PH(7);\n    ph_n++;\n    // the next unit is reserved"),
-        (K, "      row_pass<RC>(raw, tab, s_rc, s_pk, lane);\n", "      row_pass<RC>(raw, tab, s_rc, s_pk, lane);\n    MJG_PH(0);\n"),
+        (K, "    if (watch) skip_st = skip;\n", "    if (watch) skip_st = skip;\n    MJG_PH(0);\n"),
         (K, "    uint32_t mlo = 0, mhi = 0;  // candidate mask", "    MJG_PH(1);\n    uint32_t mlo = 0, mhi = 0;  // candidate mask"),
-        (K, "    if (SCR) mask = ((uint64_t)mhi << 32) | mlo;\n", "    if (SCR) mask = ((uint64_t)mhi << 32) | mlo;\n    MJG_PH(2);\n"),
+        (K, "    const uint64_t mask = ((uint64_t)mhi << 32) | mlo;\n", "    const uint64_t mask = ((uint64_t)mhi << 32) | mlo;\n    MJG_PH(2);\n"),
         (K, "    if (cur_active && !((wide >> lane) & 1ull)) {", "    MJG_PH(3);\n    if (cur_active && !((wide >> lane) & 1ull)) {"),
         (K, "    if (wide) {  // the heavy blocks", "    MJG_PH(4);\n    if (wide) {  // the heavy blocks"),
         (K, "    const uint32_t qbits = cur_active ? q.bits : 0u;\n", "    MJG_PH(5);\n    const uint32_t qbits = cur_active ? q.bits : 0u;\n"),
