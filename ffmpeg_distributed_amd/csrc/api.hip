@@ -158,6 +158,7 @@ struct PlaneScale {
   size_t lds = 0;
   dim3 grid;
   int th = 32;  // k_scale tile height (64: the 2:1 filters, scale.hip)
+  bool copy = false;  // the plane keeps its size: k_plane_copy instead of k_scale's identity filters
 };
 
 // Per-submit state.  A context has kSlots slots so further mjg_submits can be queued before
@@ -231,7 +232,7 @@ struct mjg_ctx {
   int32_t qmat[64];
   int enc_grid = 0;             // persistent k_encode workgroups: every CU full (kEmitDefault)
   int enc_grid_cnt = 0;         // the same for the -huffman optimal counting pass (kCount: more LDS)
-  bool scale = false;
+  bool scale = false;           // the sws stage runs: the sizes or the chroma formats differ
   size_t in_frame_bytes = 0, enc_frame_bytes = 0;
   std::vector<uint8_t> hdr;
   uint8_t mprime[64];
@@ -304,13 +305,17 @@ void free_ctx(mjg_ctx *c) {
   delete c;
 }
 
-// chroma: plane subsampling shifts (hsub, vsub) select the siting get_local_pos(shift, -513)
+// chroma: the plane's subsampling shifts in the source format (s_hsub, s_vsub) and in the
+// encoded one (d_hsub, d_vsub) select the siting get_local_pos(shift, -513) of each side
+// (swscale's src / dst pixel formats; with the default siting every one comes to 128)
 int setup_plane_scale(mjg_ctx *c, PlaneScale &p, int sw, int sh, int dw, int dh, int chroma,
-                      int hsub, int vsub, bool bitexact) {
-  const int hpos = chroma ? sws_local_pos(hsub, -513) : sws_local_pos(0, 0);
-  const int vpos = chroma ? sws_local_pos(vsub, -513) : sws_local_pos(0, 0);
-  if (!make_sws_filter(sw, dw, 1 << 14, 4, bitexact, hpos, hpos, &p.hf) ||
-      !make_sws_filter(sh, dh, 1 << 12, 2, bitexact, vpos, vpos, &p.vf))
+                      int s_hsub, int s_vsub, int d_hsub, int d_vsub, bool bitexact) {
+  const int s_hpos = chroma ? sws_local_pos(s_hsub, -513) : sws_local_pos(0, 0);
+  const int s_vpos = chroma ? sws_local_pos(s_vsub, -513) : sws_local_pos(0, 0);
+  const int d_hpos = chroma ? sws_local_pos(d_hsub, -513) : sws_local_pos(0, 0);
+  const int d_vpos = chroma ? sws_local_pos(d_vsub, -513) : sws_local_pos(0, 0);
+  if (!make_sws_filter(sw, dw, 1 << 14, 4, bitexact, s_hpos, d_hpos, &p.hf) ||
+      !make_sws_filter(sh, dh, 1 << 12, 2, bitexact, s_vpos, d_vpos, &p.vf))
     return set_err(MJG_E_INVALID, "scale %dx%d -> %dx%d needs swscale's cascade (unsupported)", sw,
                    sh, dw, dh);
   for (int i = 1; i < dw; i++)
@@ -527,7 +532,7 @@ int alloc_slot(mjg_ctx *c, Slot &S) {
   return MJG_OK;
 }
 
-int open_ctx(int device, const mjg_config *cfg, mjg_ctx *c) {
+int open_ctx(int device, const mjg_config *cfg, int src_cf, mjg_ctx *c) {
   c->device = device;
   c->cfg = *cfg;
   const mjg_config &k = *cfg;
@@ -541,6 +546,8 @@ int open_ctx(int device, const mjg_config *cfg, mjg_ctx *c) {
     return set_err(MJG_E_INVALID, "bad SAR %d:%d", k.sar_num, k.sar_den);
   if (k.chroma_format < MJG_CHROMA_420 || k.chroma_format > MJG_CHROMA_444)
     return set_err(MJG_E_INVALID, "chroma_format %d", k.chroma_format);
+  if (src_cf < MJG_CHROMA_420 || src_cf > MJG_CHROMA_444)
+    return set_err(MJG_E_INVALID, "src_chroma_format %d", src_cf);
   constexpr uint32_t kKnownFlags = MJG_F_TIMING | MJG_F_DEBUG_COEFS | MJG_F_SWS_NO_BITEXACT | MJG_F_COM_ITU601 |
                                    MJG_F_HUFFMAN_OPTIMAL | MJG_F_RST | MJG_F_TIMING_DETAIL | MJG_F_MERGE;
   if (k.flags & ~kKnownFlags)  // retired bits (128, 256, 512: r05's FUSED / DCT_MFMA / DCT_VALU) included
@@ -558,10 +565,13 @@ int open_ctx(int device, const mjg_config *cfg, mjg_ctx *c) {
   HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
   HIP_TRY(hipStreamCreateWithPriority(&c->tail, hipStreamNonBlocking, greatest));
 
-  c->scale = (k.src_w != k.dst_w || k.src_h != k.dst_h);
+  // the sws stage: a resize, or a -pix_fmt conversion (source format != encoded format; in
+  // FFmpeg one swscale context does both, and tv->pc in the same pass)
   const int cf = k.chroma_format;
+  c->scale = (k.src_w != k.dst_w || k.src_h != k.dst_h || src_cf != cf);
   const int hsh = cf == MJG_CHROMA_444 ? 0 : 1, vsh = cf == MJG_CHROMA_420 ? 1 : 0;
-  const int scw = (k.src_w + hsh) >> hsh, sch = (k.src_h + vsh) >> vsh;
+  const int s_hsh = src_cf == MJG_CHROMA_444 ? 0 : 1, s_vsh = src_cf == MJG_CHROMA_420 ? 1 : 0;
+  const int scw = (k.src_w + s_hsh) >> s_hsh, sch = (k.src_h + s_vsh) >> s_vsh;
   const int w = k.dst_w, h = k.dst_h, cw = (w + hsh) >> hsh, ch = (h + vsh) >> vsh;
   c->in_frame_bytes = (size_t)k.src_w * k.src_h + 2 * (size_t)scw * sch;
   c->enc_frame_bytes = (size_t)w * h + 2 * (size_t)cw * ch;
@@ -720,9 +730,13 @@ int open_ctx(int device, const mjg_config *cfg, mjg_ctx *c) {
 
   if (c->scale) {
     const bool bitexact = !(k.flags & MJG_F_SWS_NO_BITEXACT);
-    if ((rc = setup_plane_scale(c, c->ps[0], k.src_w, k.src_h, w, h, 0, 0, 0, bitexact)) ||
-        (rc = setup_plane_scale(c, c->ps[1], scw, sch, cw, ch, 1, hsh, vsh, bitexact)))
+    if ((rc = setup_plane_scale(c, c->ps[0], k.src_w, k.src_h, w, h, 0, 0, 0, 0, 0, bitexact)) ||
+        (rc = setup_plane_scale(c, c->ps[1], scw, sch, cw, ch, 1, s_hsh, s_vsh, hsh, vsh, bitexact)))
       return rc;
+    // a plane that keeps its size (luma of a pure -pix_fmt conversion) is streamed by
+    // k_plane_copy; MJG_PLANE_COPY=0 sends it through k_scale's identity filters (A/B, tests)
+    const char *pc = getenv("MJG_PLANE_COPY");
+    const bool plane_copy = !(pc && atoi(pc) == 0);
     for (int p = 0; p < 2; p++) {
       ScaleGeom &sg = c->ps[p].g;
       sg.sw = p ? scw : k.src_w;
@@ -734,6 +748,7 @@ int open_ctx(int device, const mjg_config *cfg, mjg_ctx *c) {
       sg.s_fstride = (long long)c->in_frame_bytes;
       sg.d_fstride = (long long)c->enc_frame_bytes;
       sg.range = k.in_full_range ? 0 : (p ? 2 : 1);
+      c->ps[p].copy = plane_copy && sg.sw == sg.dw && sg.sh == sg.dh;
     }
   }
 
@@ -807,7 +822,7 @@ void launch_encode(mjg_ctx *c, Slot &S, const SegList &enc_in, int wgs, int ntas
 
 extern "C" {
 
-int mjg_version(void) { return 100; }
+int mjg_version(void) { return 101; }
 
 const char *mjg_last_error(void) { return g_err.c_str(); }
 
@@ -831,11 +846,11 @@ int mjg_device_numa_node(int device) {
   return node < 0 ? -1 : node;
 }
 
-int mjg_open(int device, const mjg_config *cfg, mjg_ctx **out) {
+int mjg_open_src(int device, const mjg_config *cfg, int src_chroma_format, mjg_ctx **out) {
   if (!cfg || !out) return set_err(MJG_E_INVALID, "null argument");
   *out = nullptr;
   mjg_ctx *c = new mjg_ctx();
-  const int rc = open_ctx(device, cfg, c);
+  const int rc = open_ctx(device, cfg, src_chroma_format, c);
   if (rc) {
     const std::string keep = g_err;
     free_ctx(c);
@@ -844,6 +859,11 @@ int mjg_open(int device, const mjg_config *cfg, mjg_ctx **out) {
   }
   *out = c;
   return MJG_OK;
+}
+
+int mjg_open(int device, const mjg_config *cfg, mjg_ctx **out) {
+  if (!cfg || !out) return set_err(MJG_E_INVALID, "null argument");
+  return mjg_open_src(device, cfg, cfg->chroma_format, out);
 }
 
 void mjg_close(mjg_ctx *ctx) { free_ctx(ctx); }
@@ -860,8 +880,8 @@ int mjg_header(const mjg_ctx *ctx, uint8_t *out, size_t cap, size_t *len) {
 }
 
 namespace {
-// mjg_submit's body; segs (mjg_submit_segments: device frames, no -vf scale) replaces the one
-// segment at `frames` as k_encode's input
+// mjg_submit's body; segs (mjg_submit_segments: device frames) replaces the one segment at
+// `frames` as the input of the sws stage, or of k_encode without one
 int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, const SegList *segs) {
   if (n < 1 || (size_t)n > c->slot_B || (!src_is_device && n > c->cfg.max_batch))
     return set_err(MJG_E_INVALID, "nframes %d not in 1..%d", n, c->cfg.max_batch);
@@ -918,6 +938,19 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
       auto magic = [](uint32_t d) { return d > 1 ? (uint32_t)((((uint64_t)1 << 32) + d - 1) / d) : 0u; };
       sg.gx_magic = magic((uint32_t)sg.gx);
       sg.gxy_magic = magic((uint32_t)sg.gxy);
+      if (ps.copy) {  // the plane keeps its size: streamed (scale.hip k_plane_copy)
+        const size_t pieces = ((size_t)sg.sw * (size_t)sg.sh) >> 4, per = (size_t)kCopyThreads * kCopyVecs;
+        sg.gxy = (int)std::max<size_t>(1, (pieces + per - 1) / per);
+        sg.gxy_magic = magic((uint32_t)sg.gxy);
+        const dim3 cgrid((unsigned)(sg.gxy * nz), 1, 1);
+        if (sg.range == 1)
+          k_plane_copy<1><<<cgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, sg);
+        else if (sg.range == 2)
+          k_plane_copy<2><<<cgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, sg);
+        else
+          k_plane_copy<0><<<cgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, sg);
+        continue;
+      }
       const dim3 grid((unsigned)(sg.gxy * nz), 1, 1);
 #define MJG_SCALE_LAUNCH3(HT, NPV, D4, TH)                                                          \
   do {                                                                                              \
@@ -1356,7 +1389,7 @@ int mjg_debug_coefs(mjg_ctx *c, int frame, int16_t *out, size_t nblocks) {
 
 int mjg_debug_planes(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
   if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
-  if (!c->scale) return set_err(MJG_E_STATE, "context does not scale");
+  if (!c->scale) return set_err(MJG_E_STATE, "context has no sws stage (same size, same chroma format)");
   if (pending_jobs(c) > 0) {  // the latest synced submit's planes
     const int rc = mjg_sync(c, nullptr, nullptr);
     if (rc) return rc;
@@ -1401,7 +1434,7 @@ int mjg_debug_huff_build(int device, const uint32_t *hist, int nframes, uint8_t 
 int mjg_debug_filter(mjg_ctx *c, int plane, int dir, int16_t *coeff, int32_t *pos, int *taps,
                      int *len) {
   if (!c) return set_err(MJG_E_INVALID, "null ctx");
-  if (!c->scale) return set_err(MJG_E_STATE, "context does not scale");
+  if (!c->scale) return set_err(MJG_E_STATE, "context has no sws stage (same size, same chroma format)");
   if (plane < 0 || plane > 1 || dir < 0 || dir > 1) return set_err(MJG_E_INVALID, "plane/dir");
   const SwsFilter &f = dir ? c->ps[plane].vf : c->ps[plane].hf;
   if (taps) *taps = f.taps;

@@ -295,7 +295,9 @@ __global__ __launch_bounds__(64 * scale_waves(TH)) void k_scale(const SegList sr
       swap32(W[1], W[3]);
       swap16(W[0], W[1]);
       swap16(W[2], W[3]);
-      *(u32x4 *)(d + (size_t)(y0 + 16 * wave + n) * g.d_stride + x0 + 16 * g4) = u32x4{W[0], W[1], W[2], W[3]};
+      // (d_stride = dw and the plane / frame offsets are any byte count: a 501-wide chroma plane
+      // at an odd offset, so the store's type promises no alignment; still one 16-byte store)
+      *(u32x4_a1 *)(d + (size_t)(y0 + 16 * wave + n) * g.d_stride + x0 + 16 * g4) = u32x4{W[0], W[1], W[2], W[3]};
       return;
     }
 #pragma unroll
@@ -401,6 +403,64 @@ __global__ __launch_bounds__(64 * scale_waves(TH)) void k_scale(const SegList sr
       acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t, cp[k * ps]),
                                    __builtin_bit_cast(short2_t, ALIAS ? (uint32_t)vg[k] : vr[1 + k]), acc, false);
     d[(size_t)y * g.d_stride + x0 + lane] = (uint8_t)min(max(acc >> 19, 0), 255);
+  }
+}
+
+// A plane the sws stage leaves at its size (sw == dw, sh == dh: luma of a pure -pix_fmt
+// conversion, 4:4:4 -> yuvj420p).  swscale still runs it through the 15-bit intermediate with
+// one-tap identity filters (16384, 4096): per byte p
+//   clip_u8(((64 << 12) + 4096 range(p << 7)) >> 19)
+// which is p itself without a range conversion, and else a function of the byte alone: a
+// 256-entry table in LDS, built here with k_scale's own sws_range.  The plane's rows are
+// contiguous on both sides (strides = widths), so it is one byte string per (plane, frame):
+// streamed as 16-byte pieces aligned on the destination (d_scaled; the frames there are
+// enc_frame_bytes apart and the plane offsets any byte count), loaded from the source at
+// whatever alignment that leaves (frames in_frame_bytes apart, a caller's device pointer),
+// with the bytes before the first and after the last whole piece copied one by one by the
+// (plane, frame)'s first workgroup.  ScaleGeom as for k_scale (sizes, offsets, nf, range);
+// gxy = workgroups per (plane, frame), each kCopyThreads x kCopyVecs pieces.
+constexpr int kCopyThreads = 256;  // = the table's entries
+constexpr int kCopyVecs = 4;       // pieces per thread, all loaded before the first is stored
+template <int RANGE>
+__global__ __launch_bounds__(kCopyThreads) void k_plane_copy(const SegList src, uint8_t *__restrict__ dst,
+                                                             ScaleGeom g) {
+  __shared__ __attribute__((aligned(16))) uint8_t tab[256];
+  const int tid = threadIdx.x;
+  if (RANGE) {
+    const int h = sws_range(tid << 7, RANGE);  // (255 << 7 < 32767: hScale8To15's clip never acts)
+    tab[tid] = (uint8_t)min(max(((64 << 12) + h * 4096) >> 19, 0), 255);
+    __syncthreads();
+  }
+  const int t = blockIdx.x;
+  const int z = div_magic(t, g.gxy_magic, g.gxy), blk = t - z * g.gxy;
+  const int pl = z >= g.nf, f = z - (pl ? g.nf : 0);
+  const uint8_t *s = seg_frame(src, f, g.s_fstride) + g.s_off + (pl ? g.s_poff : 0);
+  uint8_t *d = dst + (size_t)f * g.d_fstride + g.d_off + (pl ? g.d_poff : 0);
+  const size_t nb = (size_t)g.sw * (size_t)g.sh;
+  const size_t head = min((size_t)(-(uintptr_t)d & 15), nb);
+  const size_t nv = (nb - head) >> 4;  // whole pieces: bytes [head, head + 16 nv) of the plane
+  auto conv = [&](uint32_t w) -> uint32_t {
+    if (!RANGE) return w;
+    return (uint32_t)tab[w & 255u] | ((uint32_t)tab[(w >> 8) & 255u] << 8) |
+           ((uint32_t)tab[(w >> 16) & 255u] << 16) | ((uint32_t)tab[w >> 24] << 24);
+  };
+  const size_t k0 = (size_t)blk * (kCopyThreads * kCopyVecs) + tid;
+  u32x4 v[kCopyVecs];
+#pragma unroll
+  for (int i = 0; i < kCopyVecs; i++) {
+    const size_t k = k0 + (size_t)i * kCopyThreads;
+    v[i] = k < nv ? *(const u32x4_a1 *)(s + head + 16 * k) : u32x4{0, 0, 0, 0};
+  }
+#pragma unroll
+  for (int i = 0; i < kCopyVecs; i++) {
+    const size_t k = k0 + (size_t)i * kCopyThreads;
+    if (k < nv)
+      *(u32x4 *)(d + head + 16 * k) = u32x4{conv(v[i][0]), conv(v[i][1]), conv(v[i][2]), conv(v[i][3])};
+  }
+  if (blk == 0 && tid < 16) {
+    const size_t a = (size_t)tid, b = head + 16 * nv + (size_t)tid;
+    if (a < head) d[a] = RANGE ? tab[s[a]] : s[a];
+    if (b < nb) d[b] = RANGE ? tab[s[b]] : s[b];
   }
 }
 

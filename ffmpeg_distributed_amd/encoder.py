@@ -6,7 +6,9 @@ ffmpeg_distributed.py:131-141), restricted to the profile
 
 Host-side wrapper over libmjgpu.so; frames are packed planar YUV (yuv420p / yuvj420p by
 default, 4:2:2 and 4:4:4 with `chroma=`), i.e. what `ffmpeg -f rawvideo -pix_fmt yuv4xxp`
-writes.  No CPU fallback.
+writes.  `src_chroma=` names the input frames' format when `-pix_fmt` asks for another one
+than the input's (`chroma=` is then the encoded format): the chroma planes are resampled on
+the GPU as swscale does it.  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -56,7 +58,7 @@ class MjpegEncoder:
                  sar=(1, 1), max_batch: int = 16, timing: bool = False,
                  debug_coefs: bool = False, sws_bitexact: bool = True, com_itu601: bool = False,
                  huffman: str = "default", chroma: str = "420", rst: bool = False,
-                 merge: bool = False):
+                 merge: bool = False, src_chroma: Optional[str] = None):
         self._L = _lib.load()
         self.device = int(device)
         self.src_w, self.src_h = int(src_w), int(src_h)
@@ -89,13 +91,23 @@ class MjpegEncoder:
         self.chroma = str(chroma)
         if self.chroma not in _lib.CHROMA_FORMATS:
             raise ValueError(f"chroma {chroma!r}")
+        # the input frames' format (None: the encoded one); frame_bytes follows it
+        self.src_chroma = self.chroma if src_chroma is None else str(src_chroma)
+        if self.src_chroma not in _lib.CHROMA_FORMATS:
+            raise ValueError(f"src_chroma {src_chroma!r}")
         self.rst = bool(rst)
         sar = sar or (0, 0)
         cfg = MjgConfig(self.src_w, self.src_h, self.dst_w, self.dst_h, int(bool(full_range)),
                         int(qscale), int(sar[0]), int(sar[1]), self.max_batch, flags,
                         _lib.CHROMA_FORMATS[self.chroma])
         h = C.c_void_p()
-        check(self._L.mjg_open(self.device, C.byref(cfg), C.byref(h)))
+        if self.src_chroma == self.chroma:
+            check(self._L.mjg_open(self.device, C.byref(cfg), C.byref(h)))
+        elif not hasattr(self._L, "mjg_open_src"):
+            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_src")
+        else:
+            check(self._L.mjg_open_src(self.device, C.byref(cfg), _lib.CHROMA_FORMATS[self.src_chroma],
+                                       C.byref(h)))
         self._h = h
         self.frame_bytes = int(self._L.mjg_frame_bytes(h))
         self._queued = deque()        # (nframes, host buffer kept alive) per queued submit
@@ -298,6 +310,8 @@ class MjpegEncoder:
         return out
 
     def debug_planes(self, frame: int = 0) -> np.ndarray:
+        """The encoder-input planes (after the scale / range / chroma stage) of a frame of the
+        last synced submit: packed planar, dst size, the encoded format `chroma`."""
         n = i420_frame_bytes(self.dst_w, self.dst_h, self.chroma)
         out = np.zeros(n, np.uint8)
         check(self._L.mjg_debug_planes(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)), n))

@@ -8,8 +8,8 @@ plus
   - the slice-threaded (RST) layout: -slices N (N > 1), or -thread_type slice with -threads
     other than 1 (mpegvideo's slice_context_count > 1: DRI + one restart interval per MCU
     row; mjpegenc.c then forces -huffman default);
-  - -pix_fmt yuvj420p / yuvj422p / yuvj444p (the output sampling; the worker checks it
-    against the input's, since a chroma resample is not on the GPU path);
+  - -pix_fmt yuvj420p / yuvj422p / yuvj444p (the output sampling; when the input's has more
+    chroma samples the GPU path down-samples, worker.resample_plan);
   - options that do not change the video bitstream: -an -sn -dn -y -threads N
     -thread_type frame -f matroska -map 0:v[:0].
 """

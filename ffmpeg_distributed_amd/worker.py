@@ -12,8 +12,9 @@ runs the reference command line with the real ffmpeg as a child (same output, CP
 Input: Matroska with V_UNCOMPRESSED I420/Y42B/444P video and YUV4MPEG2 are read natively;
 any other codec (the splitter's lossless x264 segments, fd.py:198-202) is decoded by an
 `ffmpeg ... -f yuv4mpegpipe` child feeding this process (SURVEY §8f "splitter decode").
-A -pix_fmt whose sampling differs from the input's needs a chroma resample, which is not on
-the GPU path: the decoded frames then go to the real ffmpeg as y4m (`ffmpeg_fallthrough`).
+A -pix_fmt with fewer chroma samples than the input's (444 -> 422, 444 -> 420, 422 -> 420) is
+converted on the GPU (`resample_plan`); one with more needs an up-sampling nobody asks for:
+the decoded frames then go to the real ffmpeg as y4m (`ffmpeg_fallthrough`).
 """
 from __future__ import annotations
 
@@ -431,6 +432,30 @@ def ffmpeg_fallthrough(src: Source, args: List[str], stdout, stderr=None) -> int
     return rc or src.close()
 
 
+# -pix_fmt conversions the GPU path takes: (input sampling, requested sampling)
+GPU_RESAMPLE_PAIRS = {("444", "422"), ("444", "420"), ("422", "420")}
+
+
+def resample_plan(prof, info):
+    """What -pix_fmt means for a segment: (src_chroma, dst_chroma), the input frames' format
+    and the one to encode (equal without -pix_fmt or when it names the input's), or, for a
+    conversion outside the GPU path (the up-sampling pairs), the reason as a str."""
+    src = info.chroma
+    dst = prof.chroma or src
+    if dst == src or (src, dst) in GPU_RESAMPLE_PAIRS:
+        return src, dst
+    return f"-pix_fmt needs {src} -> {dst} chroma resampling"
+
+
+def encoder_key(prof, info, dst_w, dst_h, sar, com_itu601, batch):
+    """What an encoder context kept between segments (serve / resident mode) depends on: the
+    input's shape and format and everything of the profile the context is opened with, the
+    encoded chroma format (-pix_fmt) included."""
+    src_chroma, dst_chroma = resample_plan(prof, info)
+    return (info.width, info.height, dst_w, dst_h, info.full_range, prof.qscale, sar,
+            com_itu601, prof.huffman, src_chroma, dst_chroma, prof.rst, batch)
+
+
 def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cache=None,
         batch_bytes: Optional[int] = None, opts: Optional[Options] = None) -> int:
     """One segment, stdin -> stdout.  `cache` (serve / resident mode): a dict that keeps the
@@ -449,11 +474,12 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
 
     src = Source(stdin, opts.read_threads, stderr)
     info = src.info
-    if prof.chroma is not None and prof.chroma != info.chroma:
-        stderr.write(f"gpu:{device}: -pix_fmt needs {info.chroma} -> {prof.chroma} chroma resampling; "
-                     f"running ffmpeg on the CPU\n")
+    plan = resample_plan(prof, info)
+    if isinstance(plan, str):
+        stderr.write(f"gpu:{device}: {plan}; running ffmpeg on the CPU\n")
         stderr.flush()
         return ffmpeg_fallthrough(src, args, stdout, stderr)
+    src_chroma, dst_chroma = plan
     dst_w, dst_h = prof.scale or (info.width, info.height)
     bind_numa(device)  # before the reader threads and the batch buffers
     from .encoder import MjpegEncoder, PinnedBuffer   # GPU work starts here
@@ -461,8 +487,7 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
     batch = batch_frames(opts, info.frame_bytes)
 
     sar = profile.scaled_sar(info.sar, (info.width, info.height), (dst_w, dst_h))
-    key = (info.width, info.height, dst_w, dst_h, info.full_range, prof.qscale, sar,
-           opts.com_itu601 and not info.full_range, prof.huffman, info.chroma, prof.rst, batch)
+    key = encoder_key(prof, info, dst_w, dst_h, sar, opts.com_itu601 and not info.full_range, batch)
     nbuf = NBUF
     if cache is not None and cache.get("key") == key:
         enc, bufs, obufs = cache["enc"], cache["bufs"], cache["obufs"]
@@ -472,7 +497,7 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
         enc = MjpegEncoder(device, info.width, info.height, dst_w, dst_h, full_range=info.full_range,
                            qscale=prof.qscale, sar=sar, max_batch=batch,
                            com_itu601=opts.com_itu601 and not info.full_range, huffman=prof.huffman,
-                           chroma=info.chroma, rst=prof.rst)
+                           chroma=dst_chroma, src_chroma=src_chroma, rst=prof.rst)
         bufs = [PinnedBuffer(batch * enc.frame_bytes) for _ in range(nbuf)]
         # page-locked output buffers: the packets are DMA'd into one (enc.fetch_into) and the
         # muxer writes them from it; regrown when a submit's JPEGs do not fit

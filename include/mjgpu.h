@@ -7,6 +7,8 @@
  * and launched/supervised at ffmpeg_distributed.py:139-141 (FFMPEGProc.run,
  * ffmpeg_distributed.py:59-91).  For the north-star profile
  *     [-vf scale=W:H:flags=bicubic] -c:v mjpeg -q:v N -dct int -huffman default -bitexact
+ * (and `-pix_fmt yuvj420p|yuvj422p` from a 4:4:4 or 4:2:2 input: the chroma down-sampling
+ * FFmpeg's auto-inserted scaler does, taken to be its default bicubic)
  * this library replaces the arithmetic that worker runs (swscale bicubic + tv->pc
  * range conversion, jfdctint + quantiser + default-table Huffman + 0xFF stuffing)
  * and the Python host code in ffmpeg_distributed_amd/ (worker.py, dispatcher.py)
@@ -67,7 +69,8 @@ extern "C" {
                                   mjg_submit is a launch of its own, launched inside the call */
 
 /* Kernel ids for mjg_kernel_times() */
-#define MJG_K_SCALE 0          /* bicubic hscale + range + vscale (per plane) */
+#define MJG_K_SCALE 0          /* bicubic hscale + range + vscale (per plane; a plane that keeps
+                                  its size: the streaming copy) */
 #define MJG_K_ENCODE 1         /* load + FDCT + quant + Huffman -> chunk bits */
 #define MJG_K_SCAN_BITS 2      /* per-frame exclusive scan of chunk bit lengths      */
 #define MJG_K_COUNT_FF 3       /* realign chunk bits, pad, count 0xFF per chunk group */
@@ -85,7 +88,8 @@ typedef struct mjg_config {
   int32_t sar_num, sar_den;  /* JFIF APP0 density; 0/0 omits APP0 (unknown SAR)        */
   int32_t max_batch;         /* most frames one mjg_submit() may carry                 */
   uint32_t flags;            /* MJG_F_*                                                */
-  int32_t chroma_format;     /* MJG_CHROMA_*; frames are packed planar Y, Cb, Cr       */
+  int32_t chroma_format;     /* MJG_CHROMA_* of the encoded JPEG (and of the input frames unless
+                                mjg_open_src says otherwise); packed planar Y, Cb, Cr   */
 } mjg_config;
 
 typedef struct mjg_ctx mjg_ctx;
@@ -105,9 +109,19 @@ int mjg_device_numa_node(int device);
  * `ffmpeg ... <remote_args>` worker's codec/scaler initialisation
  * (ffmpeg_distributed.py:131-138). */
 int mjg_open(int device, const mjg_config *cfg, mjg_ctx **out);
+/* mjg_open for input frames in another chroma format than the encoded one (`-pix_fmt`):
+ * the frames are src_w x src_h in src_chroma_format (MJG_CHROMA_*), the JPEGs dst_w x dst_h in
+ * cfg->chroma_format.  The conversion is swscale's: one bicubic pass per plane from the
+ * source plane size to the encoded one (default chroma siting; tv->pc in the same pass; a
+ * plane that keeps its size, luma without -vf scale, goes through one-tap identity filters,
+ * which the library runs as a streaming copy with the tv->pc byte table).  Any pair of
+ * formats is accepted; the worker sends the down-sampling pairs (444->422, 444->420,
+ * 422->420) here.  mjg_open(d, cfg, out) = mjg_open_src(d, cfg, cfg->chroma_format, out).
+ * (mjg_version() >= 101.) */
+int mjg_open_src(int device, const mjg_config *cfg, int src_chroma_format, mjg_ctx **out);
 void mjg_close(mjg_ctx *ctx);
 
-/* Bytes of one packed planar input frame (src_w x src_h in cfg->chroma_format). */
+/* Bytes of one packed planar input frame (src_w x src_h in the source chroma format). */
 size_t mjg_frame_bytes(const mjg_ctx *ctx);
 /* The per-config JPEG header (SOI .. SOS) every frame starts with.  With
  * MJG_F_HUFFMAN_OPTIMAL each frame carries its own DHT; this returns the header with the
@@ -195,10 +209,12 @@ int mjg_sws_filter(int src_len, int dst_len, int one, int align, int bitexact, i
  * in coding order (4:2:0: Y0 Y1 Y2 Y3 Cb Cr per MCU).  Needs MJG_F_DEBUG_COEFS. */
 int mjg_debug_coefs(mjg_ctx *ctx, int frame, int16_t *out, size_t nblocks);
 /* The full-range encoder-input planes (after scale/range stage) of frame `frame`,
- * packed planar at dst size.  Only for a scaling config. */
+ * packed planar at dst size in the encoded chroma format.  Only for a config whose sws stage
+ * runs (src size != dst size, or source chroma format != encoded one). */
 int mjg_debug_planes(mjg_ctx *ctx, int frame, uint8_t *out, size_t cap);
 /* Filter tables the context generated: plane 0 = luma, 1 = chroma; dir 0 = horizontal,
- * 1 = vertical.  taps/len may be queried with coeff == NULL. */
+ * 1 = vertical.  taps/len may be queried with coeff == NULL.  As mjg_debug_planes: only when
+ * the sws stage runs. */
 int mjg_debug_filter(mjg_ctx *ctx, int plane, int dir, int16_t *coeff, int32_t *pos,
                      int *taps, int *len);
 /* -huffman optimal's table builder (k_huff_build) on given symbol counts, on GPU `device`:
