@@ -234,6 +234,12 @@ struct mjg_ctx {
   int enc_grid_cnt = 0;         // the same for the -huffman optimal counting pass (kCount: more LDS)
   bool scale = false;           // the sws stage runs: the sizes or the chroma formats differ
   size_t in_frame_bytes = 0, enc_frame_bytes = 0;
+  // the crop rectangle (mjg_open_crop; the whole frame otherwise): the input of the sws stage,
+  // or of k_encode without one
+  long long src_off[3] = {0, 0, 0};  // byte offsets of the rectangle's Y, U, V planes in a source frame
+  long long src_cplane = 0;     // bytes of one source chroma plane (U to V)
+  bool enc_ua = false;          // k_encode<.., UA>: a crop read in place whose geometry can fail
+                                // fetch_rows' alignment test (MJG_UNALIGNED_FETCH=0: never)
   std::vector<uint8_t> hdr;
   uint8_t mprime[64];
 
@@ -532,7 +538,8 @@ int alloc_slot(mjg_ctx *c, Slot &S) {
   return MJG_OK;
 }
 
-int open_ctx(int device, const mjg_config *cfg, int src_cf, mjg_ctx *c) {
+// crop: x, y, w, h in luma samples of the source frame, or nullptr for the whole frame
+int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, mjg_ctx *c) {
   c->device = device;
   c->cfg = *cfg;
   const mjg_config &k = *cfg;
@@ -548,13 +555,24 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, mjg_ctx *c) {
     return set_err(MJG_E_INVALID, "chroma_format %d", k.chroma_format);
   if (src_cf < MJG_CHROMA_420 || src_cf > MJG_CHROMA_444)
     return set_err(MJG_E_INVALID, "src_chroma_format %d", src_cf);
+  // the rectangle (the frame sizes and the source format are valid here)
+  const int s_hsh = src_cf == MJG_CHROMA_444 ? 0 : 1, s_vsh = src_cf == MJG_CHROMA_420 ? 1 : 0;
+  const int cx = crop ? crop[0] : 0, cy = crop ? crop[1] : 0;
+  const int crw = crop ? crop[2] : k.src_w, crh = crop ? crop[3] : k.src_h;  // the sws stage's / k_encode's input size
+  if (crw < 1 || crh < 1)
+    return set_err(MJG_E_INVALID, "crop %dx%d at (%d,%d): the size is not positive", crw, crh, cx, cy);
+  if (cx < 0 || cy < 0 || cx > k.src_w - crw || cy > k.src_h - crh)
+    return set_err(MJG_E_INVALID, "crop %dx%d at (%d,%d) is outside the %dx%d frame", crw, crh, cx, cy, k.src_w,
+                   k.src_h);
+  if ((cx & ((1 << s_hsh) - 1)) || (cy & ((1 << s_vsh) - 1)))
+    return set_err(MJG_E_INVALID, "crop %dx%d at (%d,%d): the position is not a multiple of the source's chroma "
+                   "sub-sampling (%dx%d)", crw, crh, cx, cy, 1 << s_hsh, 1 << s_vsh);
   constexpr uint32_t kKnownFlags = MJG_F_TIMING | MJG_F_DEBUG_COEFS | MJG_F_SWS_NO_BITEXACT | MJG_F_COM_ITU601 |
                                    MJG_F_HUFFMAN_OPTIMAL | MJG_F_RST | MJG_F_TIMING_DETAIL | MJG_F_MERGE;
   if (k.flags & ~kKnownFlags)  // retired bits (128, 256, 512: r05's FUSED / DCT_MFMA / DCT_VALU) included
     return set_err(MJG_E_INVALID, "unknown flags 0x%x", k.flags & ~kKnownFlags);
   if ((k.flags & MJG_F_RST) && (k.flags & MJG_F_HUFFMAN_OPTIMAL))
     return set_err(MJG_E_INVALID, "RST (slice threading) forces -huffman default");
-
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return set_err(MJG_E_INVALID, "device %d of %d", device, ndev);
@@ -568,10 +586,16 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, mjg_ctx *c) {
   // the sws stage: a resize, or a -pix_fmt conversion (source format != encoded format; in
   // FFmpeg one swscale context does both, and tv->pc in the same pass)
   const int cf = k.chroma_format;
-  c->scale = (k.src_w != k.dst_w || k.src_h != k.dst_h || src_cf != cf);
+  c->scale = (crw != k.dst_w || crh != k.dst_h || src_cf != cf);
   const int hsh = cf == MJG_CHROMA_444 ? 0 : 1, vsh = cf == MJG_CHROMA_420 ? 1 : 0;
-  const int s_hsh = src_cf == MJG_CHROMA_444 ? 0 : 1, s_vsh = src_cf == MJG_CHROMA_420 ? 1 : 0;
   const int scw = (k.src_w + s_hsh) >> s_hsh, sch = (k.src_h + s_vsh) >> s_vsh;
+  // the rectangle's chroma planes: at (cx >> hs, cy >> vs), the chroma size of a crw x crh frame
+  // (inside the source's: cx, cy are multiples of the sub-sampling)
+  const int ccw = (crw + s_hsh) >> s_hsh, cch = (crh + s_vsh) >> s_vsh;
+  c->src_cplane = (long long)scw * sch;
+  c->src_off[0] = (long long)cy * k.src_w + cx;
+  c->src_off[1] = (long long)k.src_w * k.src_h + (long long)(cy >> s_vsh) * scw + (cx >> s_hsh);
+  c->src_off[2] = c->src_off[1] + c->src_cplane;
   const int w = k.dst_w, h = k.dst_h, cw = (w + hsh) >> hsh, ch = (h + vsh) >> vsh;
   c->in_frame_bytes = (size_t)k.src_w * k.src_h + 2 * (size_t)scw * sch;
   c->enc_frame_bytes = (size_t)w * h + 2 * (size_t)cw * ch;
@@ -602,13 +626,35 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, mjg_ctx *c) {
   // task t / nchunks by magic (exact while t * nchunks < 2^40, t < max_batch * nseg * nchunks)
   if ((unsigned long long)k.max_batch * g.nseg * g.nchunks * g.nchunks >= ((unsigned long long)1 << 40))
     return set_err(MJG_E_INVALID, "max_batch %d too large for this frame size", k.max_batch);
-  g.y_stride = w;
-  g.c_stride = cw;
-  g.u_off = (long long)w * h;
-  g.v_off = g.u_off + (long long)cw * ch;
-  g.frame_stride = (long long)c->enc_frame_bytes;
-  if (c->enc_frame_bytes >= ((size_t)1 << 32))  // k_encode addresses a frame with 32-bit offsets
-    return set_err(MJG_E_INVALID, "frame of %zu bytes", c->enc_frame_bytes);
+  if (c->scale) {  // k_encode reads the sws stage's packed output
+    g.y_stride = w;
+    g.c_stride = cw;
+    g.u_off = (long long)w * h;
+    g.v_off = g.u_off + (long long)cw * ch;
+    g.frame_stride = (long long)c->enc_frame_bytes;
+  } else {
+    // k_encode reads the source frames in place: rows at the source planes' strides, the block
+    // offsets from the rectangle's first luma byte (submit_impl adds src_off[0] to the frame
+    // pointers), the planes w x h / cw x ch of it (fetch_rows_edge's clamps).  The whole frame:
+    // exactly the packed values above.
+    g.y_stride = k.src_w;
+    g.c_stride = scw;
+    g.u_off = c->src_off[1] - c->src_off[0];
+    g.v_off = c->src_off[2] - c->src_off[0];
+    g.frame_stride = (long long)c->in_frame_bytes;
+  }
+  // k_encode addresses a frame with 32-bit offsets
+  if (c->enc_frame_bytes >= ((size_t)1 << 32) || (!c->scale && c->in_frame_bytes >= ((size_t)1 << 32)))
+    return set_err(MJG_E_INVALID, "frame of %zu bytes", std::max(c->enc_frame_bytes, c->in_frame_bytes));
+  // the fetch at any alignment: only for a crop read in place, and only when a plane offset, a
+  // row stride or the frame stride is no multiple of 8 (else every interior block already
+  // passes the alignment test, given an aligned frame pointer, as for uncropped frames)
+  {
+    const char *ua = getenv("MJG_UNALIGNED_FETCH");
+    const bool is_crop = cx || cy || crw != k.src_w || crh != k.src_h;
+    const long long bits = c->src_off[0] | c->src_off[1] | c->src_off[2] | g.y_stride | g.c_stride | g.frame_stride;
+    c->enc_ua = is_crop && !c->scale && (bits & 7) != 0 && !(ua && atoi(ua) == 0);
+  }
   g.range_convert = (!c->scale && !k.in_full_range) ? 1 : 0;
   g.debug_coefs = (k.flags & MJG_F_DEBUG_COEFS) ? 1 : 0;
 
@@ -730,8 +776,9 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, mjg_ctx *c) {
 
   if (c->scale) {
     const bool bitexact = !(k.flags & MJG_F_SWS_NO_BITEXACT);
-    if ((rc = setup_plane_scale(c, c->ps[0], k.src_w, k.src_h, w, h, 0, 0, 0, 0, 0, bitexact)) ||
-        (rc = setup_plane_scale(c, c->ps[1], scw, sch, cw, ch, 1, s_hsh, s_vsh, hsh, vsh, bitexact)))
+    // the filters for the rectangle's planes: their edge taps replicate the crop's edge
+    if ((rc = setup_plane_scale(c, c->ps[0], crw, crh, w, h, 0, 0, 0, 0, 0, bitexact)) ||
+        (rc = setup_plane_scale(c, c->ps[1], ccw, cch, cw, ch, 1, s_hsh, s_vsh, hsh, vsh, bitexact)))
       return rc;
     // a plane that keeps its size (luma of a pure -pix_fmt conversion) is streamed by
     // k_plane_copy; MJG_PLANE_COPY=0 sends it through k_scale's identity filters (A/B, tests)
@@ -739,11 +786,12 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, mjg_ctx *c) {
     const bool plane_copy = !(pc && atoi(pc) == 0);
     for (int p = 0; p < 2; p++) {
       ScaleGeom &sg = c->ps[p].g;
-      sg.sw = p ? scw : k.src_w;
-      sg.sh = p ? sch : k.src_h;
+      sg.sw = p ? ccw : crw;
+      sg.sh = p ? cch : crh;
       sg.dw = p ? cw : w;
       sg.dh = p ? ch : h;
-      sg.s_stride = sg.sw;
+      sg.s_stride = p ? scw : k.src_w;  // rows of the source plane (wider than sw under a crop)
+      sg.sw_magic = sg.sw > 1 ? (uint32_t)((((uint64_t)1 << 32) + (uint32_t)sg.sw - 1) / (uint32_t)sg.sw) : 0u;
       sg.d_stride = sg.dw;
       sg.s_fstride = (long long)c->in_frame_bytes;
       sg.d_fstride = (long long)c->enc_frame_bytes;
@@ -797,17 +845,25 @@ int launch_write(mjg_ctx *c, Slot &S, int n, bool reset_status) {
 }
 
 
-template <int MODE, bool DBG>
-void launch_encode2(mjg_ctx *c, Slot &S, const SegList &enc_in, int wgs, int ntasks) {
+template <int MODE, bool DBG, bool UA>
+void launch_encode3(mjg_ctx *c, Slot &S, const SegList &enc_in, int wgs, int ntasks) {
   const EncGeom &g = c->geom;
   if (g.range_convert)
-    k_encode<true, MODE, DBG><<<wgs, 64 * kWavesPerWg, 0, S.st>>>(
+    k_encode<true, MODE, DBG, UA><<<wgs, 64 * kWavesPerWg, 0, S.st>>>(
         enc_in, g, c->d_tabs, S.d_scratch, S.d_chunk_bits, S.d_dbg, S.d_work, ntasks, S.d_hist,
         S.d_stage_bits, S.d_syms, S.d_symn);
   else
-    k_encode<false, MODE, DBG><<<wgs, 64 * kWavesPerWg, 0, S.st>>>(
+    k_encode<false, MODE, DBG, UA><<<wgs, 64 * kWavesPerWg, 0, S.st>>>(
         enc_in, g, c->d_tabs, S.d_scratch, S.d_chunk_bits, S.d_dbg, S.d_work, ntasks, S.d_hist,
         S.d_stage_bits, S.d_syms, S.d_symn);
+}
+
+template <int MODE, bool DBG>
+void launch_encode2(mjg_ctx *c, Slot &S, const SegList &enc_in, int wgs, int ntasks) {
+  if (c->enc_ua)  // a crop read in place at any alignment (fetch_rows<UA>)
+    launch_encode3<MODE, DBG, true>(c, S, enc_in, wgs, ntasks);
+  else
+    launch_encode3<MODE, DBG, false>(c, S, enc_in, wgs, ntasks);
 }
 
 template <int MODE>
@@ -822,7 +878,7 @@ void launch_encode(mjg_ctx *c, Slot &S, const SegList &enc_in, int wgs, int ntas
 
 extern "C" {
 
-int mjg_version(void) { return 101; }
+int mjg_version(void) { return 102; }
 
 const char *mjg_last_error(void) { return g_err.c_str(); }
 
@@ -846,11 +902,12 @@ int mjg_device_numa_node(int device) {
   return node < 0 ? -1 : node;
 }
 
-int mjg_open_src(int device, const mjg_config *cfg, int src_chroma_format, mjg_ctx **out) {
+namespace {
+int open_any(int device, const mjg_config *cfg, int src_chroma_format, const int *crop, mjg_ctx **out) {
   if (!cfg || !out) return set_err(MJG_E_INVALID, "null argument");
   *out = nullptr;
   mjg_ctx *c = new mjg_ctx();
-  const int rc = open_ctx(device, cfg, src_chroma_format, c);
+  const int rc = open_ctx(device, cfg, src_chroma_format, crop, c);
   if (rc) {
     const std::string keep = g_err;
     free_ctx(c);
@@ -859,6 +916,17 @@ int mjg_open_src(int device, const mjg_config *cfg, int src_chroma_format, mjg_c
   }
   *out = c;
   return MJG_OK;
+}
+}  // namespace
+
+int mjg_open_crop(int device, const mjg_config *cfg, int src_chroma_format, int crop_x, int crop_y, int crop_w,
+                  int crop_h, mjg_ctx **out) {
+  const int crop[4] = {crop_x, crop_y, crop_w, crop_h};
+  return open_any(device, cfg, src_chroma_format, crop, out);
+}
+
+int mjg_open_src(int device, const mjg_config *cfg, int src_chroma_format, mjg_ctx **out) {
+  return open_any(device, cfg, src_chroma_format, nullptr, out);
 }
 
 int mjg_open(int device, const mjg_config *cfg, mjg_ctx **out) {
@@ -922,12 +990,12 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
       PlaneScale &ps = c->ps[p ? 1 : 0];
       ScaleGeom sg = p ? cg : lg;
       sg.nf = n;
-      sg.s_off = sg.d_off = sg.s_poff = sg.d_poff = 0;
+      sg.d_off = sg.s_poff = sg.d_poff = 0;
+      sg.s_off = c->src_off[p];  // the (cropped) plane's first byte in a source frame
       if (p) {
-        sg.s_off = (long long)c->cfg.src_w * c->cfg.src_h + (p - 1) * (long long)cg.sw * cg.sh;
         sg.d_off = g.u_off + (p - 1) * (long long)g.cw * g.ch;
         if (uv1) {
-          sg.s_poff = (long long)cg.sw * cg.sh;
+          sg.s_poff = c->src_cplane;
           sg.d_poff = (long long)g.cw * g.ch;
         }
       }
@@ -943,7 +1011,14 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
         sg.gxy = (int)std::max<size_t>(1, (pieces + per - 1) / per);
         sg.gxy_magic = magic((uint32_t)sg.gxy);
         const dim3 cgrid((unsigned)(sg.gxy * nz), 1, 1);
-        if (sg.range == 1)
+        if (sg.s_stride != sg.sw) {  // a rectangle of wider rows (crop)
+          if (sg.range == 1)
+            k_plane_copy<1, true><<<cgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, sg);
+          else if (sg.range == 2)
+            k_plane_copy<2, true><<<cgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, sg);
+          else
+            k_plane_copy<0, true><<<cgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, sg);
+        } else if (sg.range == 1)
           k_plane_copy<1><<<cgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, sg);
         else if (sg.range == 2)
           k_plane_copy<2><<<cgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, sg);
@@ -990,6 +1065,8 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
       enc_in.p[k] = S.d_scaled;
       enc_in.f0[k] = k ? INT_MAX : 0;
     }
+  } else {  // in place: EncGeom's offsets count from the rectangle's first luma byte (0: whole frames)
+    for (int k = 0; k < kMaxSegs; k++) enc_in.p[k] += c->src_off[0];
   }
   const int ntasks = g.nchunks * g.nseg * n;
   const int nsegs = g.nseg * n;  // entropy-coded segments of this submit

@@ -640,18 +640,26 @@ __device__ __forceinline__ BlockPos block_pos(const EncGeom &g, int b, const uin
 // refetches with fetch_rows_edge.  Unconditional loads: no per-lane branch and no zeroing of
 // the row registers around them.  fb: the frame's base (wave-uniform, 8-byte aligned when
 // fb_aligned).
+// UA (a cropped encoder input): the window starts at any byte of wider rows, so
+// no alignment is asked of base, offset or stride; the same eight 8-byte loads, through a
+// type aligned to 1 (gfx950 global loads take any address: the same global_load_dwordx2, the
+// same 16 VGPRs).  Only blocks that touch the window's right or bottom edge (pw, ph: the crop
+// size) then go to fetch_rows_edge.
+typedef uint64_t u64_a1 __attribute__((aligned(1)));
+template <bool UA = false>
 __device__ __forceinline__ bool fetch_rows(uint64_t (&raw)[8], const uint8_t *fb, bool fb_aligned, const BlockPos &p,
                                            bool active) {
   // offsets < the frame size < 2^32, operands < 2^24
   const uint32_t off = p.poff + (uint32_t)__umul24((uint32_t)p.y0, (uint32_t)p.stride) + (uint32_t)p.x0;
-  const bool fast = fb_aligned && active && (p.x0 + 8 <= p.pw) && (p.y0 + 8 <= p.ph) &&
-                    ((off | (uint32_t)p.stride) & 7) == 0;
+  const bool fast = UA ? active && (p.x0 + 8 <= p.pw) && (p.y0 + 8 <= p.ph)
+                       : fb_aligned && active && (p.x0 + 8 <= p.pw) && (p.y0 + 8 <= p.ph) &&
+                             ((off | (uint32_t)p.stride) & 7) == 0;
   uint32_t o = fast ? off : 0u;
   const uint32_t st = fast ? (uint32_t)p.stride : 0u;
   // plain loads: a chunk's row segments straddle 64-B sectors shared with the
   // neighbouring chunk, which L2 keeps for its wave (nontemporal loads read 1.64x)
 #pragma unroll
-  for (int r = 0; r < 8; r++, o += st) raw[r] = *(const uint64_t *)(fb + o);
+  for (int r = 0; r < 8; r++, o += st) raw[r] = UA ? *(const u64_a1 *)(fb + o) : *(const uint64_t *)(fb + o);
   return fast;
 }
 
@@ -721,13 +729,17 @@ constexpr int kBatch = 12;
 // lane 56+i holding block chunk*64-8+i of the segment.  Quantised DC = (pixel sum + 32) >> 6
 // exactly.  carry_row: lane loads row (lane & 7) of block (lane >> 3) of those 8 blocks
 // (issued early so the load overlaps a chunk's work); carry_finish reduces them.
+template <bool UA = false>  // UA: fetch_rows' (the row's 8 bytes at any alignment)
 __device__ __forceinline__ uint64_t carry_row(const uint8_t *fb, const EncGeom &g, int bbase, int chunk, int lane,
                                               const uint4 *s_bd) {
   if (chunk == 0) return 0;
   const BlockPos p = block_pos(g, bbase + chunk * 64 - 8 + (lane >> 3), s_bd);
   const uint8_t *row = fb + p.poff + (size_t)min(p.y0 + (lane & 7), p.ph - 1) * p.stride;
-  if (p.x0 + 8 <= p.pw && (((uintptr_t)(row + p.x0)) & 7) == 0)
+  if (UA) {
+    if (p.x0 + 8 <= p.pw) return *(const u64_a1 *)(row + p.x0);
+  } else if (p.x0 + 8 <= p.pw && (((uintptr_t)(row + p.x0)) & 7) == 0) {
     return *(const uint64_t *)(row + p.x0);
+  }
   uint64_t w = 0;
   for (int x = 0; x < 8; x++) w |= (uint64_t)row[min(p.x0 + x, p.pw - 1)] << (8 * x);
   return w;
@@ -1079,7 +1091,9 @@ struct XcdUnits {
 // neither its branch nor its live scalars (k_encode is short of SGPRs: they spill to VGPR lanes).
 // (The DCT stage on the matrix cores, dct_mfma, r02-r05, was retired in r06: slower or equal on
 // every BASELINE config once the VALU screen skipped columns, profiles/HISTORY.md §4c.)
-template <bool RC, int MODE, bool DBG = false>  // RC: yuv420p (tv) input without scale -> swscale tv->pc per pixel
+// UA: the row fetch of a cropped encoder input (fetch_rows); the context launches it only for a
+// crop whose geometry can fail the alignment test, every other launch is the UA = false kernel.
+template <bool RC, int MODE, bool DBG = false, bool UA = false>  // RC: yuv420p (tv) input without scale -> swscale tv->pc per pixel
 __global__ __launch_bounds__(64 * kWavesPerWg, MODE == kCount ? 4 : kEncWavesPerEU) void k_encode(
     const SegList frames, EncGeom g, const uint32_t *__restrict__ tabs,
     uint32_t *__restrict__ scratch, uint32_t *__restrict__ chunk_bits,
@@ -1164,8 +1178,8 @@ __global__ __launch_bounds__(64 * kWavesPerWg, MODE == kCount ? 4 : kEncWavesPer
   auto frame_base = [&](int f) { return seg_frame(frames, f, g.frame_stride); };
   const uint8_t *fb = frame_base(frame);
   uint64_t raw[8];
-  bool fast = fetch_rows(raw, fb, ((uintptr_t)fb & 7) == 0, block_pos(g, bbase + b, s_bd), active);
-  int carry = carry_finish(carry_row(fb, g, bbase, chunk, lane, s_bd), chunk, lane, rc, g, s_desc);
+  bool fast = fetch_rows<UA>(raw, fb, ((uintptr_t)fb & 7) == 0, block_pos(g, bbase + b, s_bd), active);
+  int carry = carry_finish(carry_row<UA>(fb, g, bbase, chunk, lane, s_bd), chunk, lane, rc, g, s_desc);
   // Adaptive column-skip test: skip_st (wave-uniform, carried from chunk to chunk) holds the
   // columns that the wave's previous watched row pass found skippable.  The row pass watches
   // when there were any, or on every fourth chunk (retest): content whose columns are rarely
@@ -1198,10 +1212,10 @@ __global__ __launch_bounds__(64 * kWavesPerWg, MODE == kCount ? 4 : kEncWavesPer
       b = chunk * 64 + lane;
       active = b < nblk;
       fb = frame_base(frame);
-      fast = fetch_rows(raw, fb, ((uintptr_t)fb & 7) == 0, block_pos(g, bbase + b, s_bd), active);
+      fast = fetch_rows<UA>(raw, fb, ((uintptr_t)fb & 7) == 0, block_pos(g, bbase + b, s_bd), active);
     }
     // a new batch starts at an arbitrary chunk: fetch its predecessors' rows now
-    const uint64_t crow = (new_batch && tn >= 0) ? carry_row(fb, g, bbase, chunk, lane, s_bd) : 0;
+    const uint64_t crow = (new_batch && tn >= 0) ? carry_row<UA>(fb, g, bbase, chunk, lane, s_bd) : 0;
 
     uint32_t mlo = 0, mhi = 0;  // candidate mask, scan positions 0-31 / 32-63 (column_screen)
     if (cur_active) {

@@ -52,6 +52,8 @@ struct ScaleGeom {
   long long s_off, d_off;        // plane offset inside a frame
   long long s_fstride, d_fstride;  // frame strides
   int nf;                        // frames per plane: blockIdx.z >= nf is the next plane (U, V in one launch)
+  uint32_t sw_magic;             // k_plane_copy of a rectangle: ceil(2^32 / sw) (0 when sw == 1); in
+                                 // the padding before s_poff, so the fields after it stay where they were
   long long s_poff, d_poff;      // that plane's offset from this one
   int htaps, vtaps;              // htaps multiple of 4 (filterAlign 4), vtaps even
   int npv;                       // coefficient pairs per output row (vtaps/2 + 1)
@@ -419,9 +421,15 @@ __global__ __launch_bounds__(64 * scale_waves(TH)) void k_scale(const SegList sr
 // with the bytes before the first and after the last whole piece copied one by one by the
 // (plane, frame)'s first workgroup.  ScaleGeom as for k_scale (sizes, offsets, nf, range);
 // gxy = workgroups per (plane, frame), each kCopyThreads x kCopyVecs pieces.
+// RECT (a cropped source): the plane is a rectangle of wider rows, sw bytes of
+// every s_stride, and the destination the same byte string as before.  Byte j of it is column
+// j % sw of row j / sw (multiply-high, div_magic: j < 2^28); a piece inside one source row is
+// still one unaligned 16-byte load, a piece that runs over a row end is gathered byte by byte
+// (16 / sw of the pieces).  The loads of all of a thread's pieces, gathered ones included, are
+// issued before its first store.  The context launches RECT only when s_stride != sw.
 constexpr int kCopyThreads = 256;  // = the table's entries
 constexpr int kCopyVecs = 4;       // pieces per thread, all loaded before the first is stored
-template <int RANGE>
+template <int RANGE, bool RECT = false>
 __global__ __launch_bounds__(kCopyThreads) void k_plane_copy(const SegList src, uint8_t *__restrict__ dst,
                                                              ScaleGeom g) {
   __shared__ __attribute__((aligned(16))) uint8_t tab[256];
@@ -444,12 +452,34 @@ __global__ __launch_bounds__(kCopyThreads) void k_plane_copy(const SegList src, 
     return (uint32_t)tab[w & 255u] | ((uint32_t)tab[(w >> 8) & 255u] << 8) |
            ((uint32_t)tab[(w >> 16) & 255u] << 16) | ((uint32_t)tab[w >> 24] << 24);
   };
+  // the 16 source bytes of the piece at byte j of the plane (RECT: j < nb - 15 < 2^28)
+  auto piece = [&](size_t j) -> u32x4 {
+    if (!RECT) return *(const u32x4_a1 *)(s + j);
+    int row = div_magic((int)j, g.sw_magic, g.sw), col = (int)j - row * g.sw;
+    const uint8_t *rp = s + (size_t)row * g.s_stride;
+    if (col + 16 <= g.sw) return *(const u32x4_a1 *)(rp + col);
+    u32x4 w = {0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+      if (col >= g.sw) {  // (sw >= 1: at most one row step per byte)
+        col = 0;
+        rp += g.s_stride;
+      }
+      w[i >> 2] |= (uint32_t)rp[col++] << (8 * (i & 3));
+    }
+    return w;
+  };
+  auto byte_at = [&](size_t j) -> uint8_t {  // one source byte (the head and the tail)
+    if (!RECT) return s[j];
+    const int row = div_magic((int)j, g.sw_magic, g.sw);
+    return s[(size_t)row * g.s_stride + ((int)j - row * g.sw)];
+  };
   const size_t k0 = (size_t)blk * (kCopyThreads * kCopyVecs) + tid;
   u32x4 v[kCopyVecs];
 #pragma unroll
   for (int i = 0; i < kCopyVecs; i++) {
     const size_t k = k0 + (size_t)i * kCopyThreads;
-    v[i] = k < nv ? *(const u32x4_a1 *)(s + head + 16 * k) : u32x4{0, 0, 0, 0};
+    v[i] = k < nv ? piece(head + 16 * k) : u32x4{0, 0, 0, 0};
   }
 #pragma unroll
   for (int i = 0; i < kCopyVecs; i++) {
@@ -459,8 +489,8 @@ __global__ __launch_bounds__(kCopyThreads) void k_plane_copy(const SegList src, 
   }
   if (blk == 0 && tid < 16) {
     const size_t a = (size_t)tid, b = head + 16 * nv + (size_t)tid;
-    if (a < head) d[a] = RANGE ? tab[s[a]] : s[a];
-    if (b < nb) d[b] = RANGE ? tab[s[b]] : s[b];
+    if (a < head) d[a] = RANGE ? tab[byte_at(a)] : byte_at(a);
+    if (b < nb) d[b] = RANGE ? tab[byte_at(b)] : byte_at(b);
   }
 }
 

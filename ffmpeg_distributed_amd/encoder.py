@@ -1,14 +1,15 @@
 """GPU MJPEG encoder: the per-segment encode that the reference's worker runs
 (`ffmpeg -f matroska -i pipe: <remote_args> -f matroska pipe:`,
 ffmpeg_distributed.py:131-141), restricted to the profile
-`[-vf scale=W:H:flags=bicubic] -c:v mjpeg -q:v N -dct int [-huffman default|optimal] -bitexact`
+`[-vf [crop=w:h:x:y,]scale=W:H:flags=bicubic] -c:v mjpeg -q:v N -dct int [-huffman default|optimal] -bitexact`
 (+ `-slices N` / `-thread_type slice` for the RST layout).
 
 Host-side wrapper over libmjgpu.so; frames are packed planar YUV (yuv420p / yuvj420p by
 default, 4:2:2 and 4:4:4 with `chroma=`), i.e. what `ffmpeg -f rawvideo -pix_fmt yuv4xxp`
 writes.  `src_chroma=` names the input frames' format when `-pix_fmt` asks for another one
 than the input's (`chroma=` is then the encoded format): the chroma planes are resampled on
-the GPU as swscale does it.  No CPU fallback.
+the GPU as swscale does it.  `crop=(x, y, w, h)` makes a rectangle of the input frames the
+encoder's (or the scaler's) input; the frames handed over stay whole.  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -58,12 +59,19 @@ class MjpegEncoder:
                  sar=(1, 1), max_batch: int = 16, timing: bool = False,
                  debug_coefs: bool = False, sws_bitexact: bool = True, com_itu601: bool = False,
                  huffman: str = "default", chroma: str = "420", rst: bool = False,
-                 merge: bool = False, src_chroma: Optional[str] = None):
+                 merge: bool = False, src_chroma: Optional[str] = None, crop=None):
         self._L = _lib.load()
         self.device = int(device)
         self.src_w, self.src_h = int(src_w), int(src_h)
-        self.dst_w = int(dst_w if dst_w is not None else src_w)
-        self.dst_h = int(dst_h if dst_h is not None else src_h)
+        # crop: (x, y, w, h) in luma samples of the src_w x src_h frames, resolved as
+        # profile.resolve_crop does (x, y multiples of the source's sub-sampling); the encoded
+        # size defaults to the rectangle's.  None: whole frames, through mjg_open / mjg_open_src
+        self.crop = None if crop is None else tuple(int(v) for v in crop)
+        if self.crop is not None and len(self.crop) != 4:
+            raise ValueError(f"crop {crop!r}: (x, y, w, h)")
+        in_w, in_h = (self.src_w, self.src_h) if self.crop is None else self.crop[2:]
+        self.dst_w = int(dst_w if dst_w is not None else in_w)
+        self.dst_h = int(dst_h if dst_h is not None else in_h)
         self.max_batch = int(max_batch)
         flags = 0
         if timing == "detail":
@@ -101,7 +109,12 @@ class MjpegEncoder:
                         int(qscale), int(sar[0]), int(sar[1]), self.max_batch, flags,
                         _lib.CHROMA_FORMATS[self.chroma])
         h = C.c_void_p()
-        if self.src_chroma == self.chroma:
+        if self.crop is not None:
+            if not hasattr(self._L, "mjg_open_crop"):
+                raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_crop")
+            check(self._L.mjg_open_crop(self.device, C.byref(cfg), _lib.CHROMA_FORMATS[self.src_chroma],
+                                        *self.crop, C.byref(h)))
+        elif self.src_chroma == self.chroma:
             check(self._L.mjg_open(self.device, C.byref(cfg), C.byref(h)))
         elif not hasattr(self._L, "mjg_open_src"):
             raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_src")

@@ -3,8 +3,14 @@
 arguments fall outside it (the worker then runs the real ffmpeg unchanged).
 
 Supported profile (BASELINE north star, plus FFmpeg's default -huffman optimal):
-    [-vf scale=W:H[:flags=bicubic...]] -c:v mjpeg -q:v N -dct int [-huffman default|optimal] -bitexact
-plus
+    [-vf FILTERS] -c:v mjpeg -q:v N -dct int [-huffman default|optimal] -bitexact
+with FILTERS one of
+    scale=W:H[:flags=bicubic...]
+    crop=w:h[:x:y]                          (also w= / out_w=, h= / out_h=, x=, y=; keep_aspect=0, exact=0)
+    crop=...,scale=W:H[:flags=bicubic...]   (in this order)
+where the crop values are decimal integers (no expressions); `Profile.crop` is the request as
+given and `resolve_crop` turns it into a rectangle of a given input (vf_crop.c's rounding,
+defaults and clamping: DESIGN §4.8), plus
   - the slice-threaded (RST) layout: -slices N (N > 1), or -thread_type slice with -threads
     other than 1 (mpegvideo's slice_context_count > 1: DRI + one restart interval per MCU
     row; mjpegenc.c then forces -huffman default);
@@ -30,6 +36,9 @@ class Profile:
     huffman: str = "optimal"         # mjpegenc.c "huffman" option, default optimal
     rst: bool = False                # slice threading: DRI + RST per MCU row
     chroma: Optional[str] = None     # "420"/"422"/"444" from -pix_fmt (None: the input's)
+    # -vf crop=...: the request as given, {"w", "h", "x", "y"} -> int or None (absent), unresolved
+    # (resolve_crop needs the input's size and format); None: no crop
+    crop: Optional[dict] = None
 
 
 class Unsupported(ValueError):
@@ -46,9 +55,85 @@ def effective_qscale(q: float) -> int:
 _FLAGS_OK = {"bicubic", "accurate_rnd", "bitexact", "full_chroma_int", "full_chroma_inp"}
 
 
+class CropError(ValueError):
+    """A crop request that does not fit the input (ffmpeg fails to configure the filter)."""
+
+
+_CROP_KEYS = {"w": "w", "out_w": "w", "h": "h", "out_h": "h", "x": "x", "y": "y"}
+
+
+def _parse_crop(f: str) -> dict:
+    """`crop=...` -> {"w", "h", "x", "y"}: int, or None where the option is absent."""
+    out = {"w": None, "h": None, "x": None, "y": None}
+    pos = 0
+    for p in f[len("crop="):].split(":"):
+        if "=" in p:
+            k, v = p.split("=", 1)
+        else:
+            if pos >= 4:
+                raise Unsupported(f"crop option {p!r} (positional options are w:h:x:y)")
+            k, v = "whxy"[pos], p
+            pos += 1
+        if k in ("keep_aspect", "exact"):
+            if v != "0":
+                raise Unsupported(f"crop {k}={v} (only {k}=0 is GPU-accelerated)")
+            continue
+        if k not in _CROP_KEYS:
+            raise Unsupported(f"crop option {k!r}")
+        if not (v.isascii() and v.isdigit()):
+            raise Unsupported(f"crop {k}={v} (an expression; only decimal integer literals are GPU-accelerated)")
+        out[_CROP_KEYS[k]] = int(v)
+    return out
+
+
+def _parse_vf(vf: str):
+    """-vf value -> (crop request or None, scale size or None, sws flags)."""
+    if ";" in vf:
+        raise Unsupported(f"filter graph {vf!r} (only crop, scale or crop,scale is GPU-accelerated)")
+    fs = vf.split(",")
+    names = [f.split("=", 1)[0] for f in fs]
+    if len(fs) > 2:
+        raise Unsupported(f"filter graph {vf!r}: {len(fs)} filters (only crop, scale or crop,scale is "
+                          f"GPU-accelerated)")
+    if names == ["scale", "crop"]:
+        raise Unsupported(f"filter graph {vf!r}: scale before crop (only crop,scale in this order is "
+                          f"GPU-accelerated)")
+    if names == ["crop"] and "=" in fs[0]:
+        return _parse_crop(fs[0]), None, ("bicubic",)
+    if names == ["crop", "scale"] and "=" in fs[0]:
+        scale, flags = _parse_scale(fs[1])
+        return _parse_crop(fs[0]), scale, flags
+    if len(fs) == 1:
+        scale, flags = _parse_scale(vf)
+        return None, scale, flags
+    raise Unsupported(f"filter graph {vf!r} (only crop, scale or crop,scale is GPU-accelerated)")
+
+
+def resolve_crop(spec: dict, in_w: int, in_h: int, src_chroma: str) -> Tuple[int, int, int, int]:
+    """The rectangle (x, y, w, h) a crop request selects from an in_w x in_h input in
+    `src_chroma` ("420"/"422"/"444": the decoded format, which the filter sees before any
+    -pix_fmt conversion), as vf_crop.c config_input / filter_frame do with exact=0: absent w / h
+    are the input's, both rounded down to the chroma sub-sampling; absent x / y centre the
+    rectangle, given ones are clamped into the frame, both then rounded down alike.  A size
+    below 1 or beyond the input raises CropError (ffmpeg fails; nothing is passed through)."""
+    hs, vs = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}[str(src_chroma)]
+    w = in_w if spec.get("w") is None else int(spec["w"])
+    h = in_h if spec.get("h") is None else int(spec["h"])
+    w &= ~((1 << hs) - 1)
+    h &= ~((1 << vs) - 1)
+    if w < 1 or h < 1 or w > in_w or h > in_h:
+        raise CropError(f"Invalid too big or non positive size for width '{w}' or height '{h}' "
+                        f"(crop of a {in_w}x{in_h} input)")
+    x = (in_w - w) // 2 if spec.get("x") is None else max(0, min(int(spec["x"]), in_w - w))
+    y = (in_h - h) // 2 if spec.get("y") is None else max(0, min(int(spec["y"]), in_h - h))
+    x &= ~((1 << hs) - 1)
+    y &= ~((1 << vs) - 1)
+    return x, y, w, h
+
+
 def _parse_scale(vf: str) -> Tuple[Tuple[int, int], Tuple[str, ...]]:
     if "," in vf or ";" in vf or not vf.startswith("scale="):
-        raise Unsupported(f"filter graph {vf!r} (only a single scale=W:H is GPU-accelerated)")
+        raise Unsupported(f"filter graph {vf!r} (only crop, scale or crop,scale is GPU-accelerated)")
     parts = vf[len("scale="):].split(":")
     kv, pos = {}, []
     for p in parts:
@@ -107,6 +192,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
     thread_type = "slice+frame"       # AVCodecContext default: FF_THREAD_FRAME | FF_THREAD_SLICE
     chroma = None
     scale = None
+    crop = None
     flags: Tuple[str, ...] = ("bicubic",)
     i = 0
 
@@ -147,7 +233,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
             if any(name != "bitexact" for _, name in _flag_ops(v)):
                 raise Unsupported(f"-fflags {v}")
         elif o in ("-vf", "-filter:v"):
-            scale, flags = _parse_scale(val())
+            crop, scale, flags = _parse_vf(val())
         elif o in ("-an", "-sn", "-dn", "-y"):
             pass
         elif o in ("-threads", "-threads:v"):
@@ -197,7 +283,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
     if rst:
         huff = "default"  # mjpegenc.c: slice_context_count > 1 forces HUFFMAN_TABLE_DEFAULT
     return Profile(qscale=effective_qscale(q), q_arg=q, scale=scale, sws_flags=flags, huffman=huff,
-                   rst=rst, chroma=chroma)
+                   rst=rst, chroma=chroma, crop=crop)
 
 
 PIX_FMT_CHROMA = {"yuvj420p": "420", "yuvj422p": "422", "yuvj444p": "444"}

@@ -15,6 +15,9 @@ any other codec (the splitter's lossless x264 segments, fd.py:198-202) is decode
 A -pix_fmt with fewer chroma samples than the input's (444 -> 422, 444 -> 420, 422 -> 420) is
 converted on the GPU (`resample_plan`); one with more needs an up-sampling nobody asks for:
 the decoded frames then go to the real ffmpeg as y4m (`ffmpeg_fallthrough`).
+A `-vf crop=...` is resolved against the segment's input (profile.resolve_crop) and read by
+the GPU as a rectangle of the whole frames; a request that does not fit the input fails as
+ffmpeg does (one line on stderr, exit code 1).
 """
 from __future__ import annotations
 
@@ -447,13 +450,14 @@ def resample_plan(prof, info):
     return f"-pix_fmt needs {src} -> {dst} chroma resampling"
 
 
-def encoder_key(prof, info, dst_w, dst_h, sar, com_itu601, batch):
+def encoder_key(prof, info, dst_w, dst_h, sar, com_itu601, batch, rect=None):
     """What an encoder context kept between segments (serve / resident mode) depends on: the
     input's shape and format and everything of the profile the context is opened with, the
-    encoded chroma format (-pix_fmt) included."""
+    encoded chroma format (-pix_fmt) and the resolved crop rectangle (x, y, w, h) included."""
     src_chroma, dst_chroma = resample_plan(prof, info)
     return (info.width, info.height, dst_w, dst_h, info.full_range, prof.qscale, sar,
-            com_itu601, prof.huffman, src_chroma, dst_chroma, prof.rst, batch)
+            com_itu601, prof.huffman, src_chroma, dst_chroma, prof.rst, batch,
+            None if rect is None else tuple(rect))
 
 
 def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cache=None,
@@ -480,14 +484,27 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
         stderr.flush()
         return ffmpeg_fallthrough(src, args, stdout, stderr)
     src_chroma, dst_chroma = plan
-    dst_w, dst_h = prof.scale or (info.width, info.height)
+    # -vf crop: the rectangle of this input (the filter sees the decoded format); the scale
+    # filter, the SAR and the encoded size then start from its size
+    rect = None
+    if prof.crop is not None:
+        try:
+            rect = profile.resolve_crop(prof.crop, info.width, info.height, src_chroma)
+        except profile.CropError as e:  # ffmpeg fails to configure the filter: no pass-through
+            stderr.write(f"gpu:{device}: crop: {e}\n")
+            stderr.flush()
+            src.close(kill=True)
+            return 1
+    in_size = (info.width, info.height) if rect is None else (rect[2], rect[3])
+    dst_w, dst_h = prof.scale or in_size
     bind_numa(device)  # before the reader threads and the batch buffers
     from .encoder import MjpegEncoder, PinnedBuffer   # GPU work starts here
 
     batch = batch_frames(opts, info.frame_bytes)
 
-    sar = profile.scaled_sar(info.sar, (info.width, info.height), (dst_w, dst_h))
-    key = encoder_key(prof, info, dst_w, dst_h, sar, opts.com_itu601 and not info.full_range, batch)
+    # (a crop leaves the SAR as it is: keep_aspect=0; scaled_sar of equal sizes only reduces it)
+    sar = profile.scaled_sar(info.sar, in_size, (dst_w, dst_h))
+    key = encoder_key(prof, info, dst_w, dst_h, sar, opts.com_itu601 and not info.full_range, batch, rect)
     nbuf = NBUF
     if cache is not None and cache.get("key") == key:
         enc, bufs, obufs = cache["enc"], cache["bufs"], cache["obufs"]
@@ -497,7 +514,7 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
         enc = MjpegEncoder(device, info.width, info.height, dst_w, dst_h, full_range=info.full_range,
                            qscale=prof.qscale, sar=sar, max_batch=batch,
                            com_itu601=opts.com_itu601 and not info.full_range, huffman=prof.huffman,
-                           chroma=dst_chroma, src_chroma=src_chroma, rst=prof.rst)
+                           chroma=dst_chroma, src_chroma=src_chroma, rst=prof.rst, crop=rect)
         bufs = [PinnedBuffer(batch * enc.frame_bytes) for _ in range(nbuf)]
         # page-locked output buffers: the packets are DMA'd into one (enc.fetch_into) and the
         # muxer writes them from it; regrown when a submit's JPEGs do not fit

@@ -6,9 +6,10 @@
  *     nice -n10 ionice -c3 ffmpeg -f matroska -i pipe: <remote_args> -f matroska pipe:
  * and launched/supervised at ffmpeg_distributed.py:139-141 (FFMPEGProc.run,
  * ffmpeg_distributed.py:59-91).  For the north-star profile
- *     [-vf scale=W:H:flags=bicubic] -c:v mjpeg -q:v N -dct int -huffman default -bitexact
+ *     [-vf [crop=w:h:x:y,]scale=W:H:flags=bicubic] -c:v mjpeg -q:v N -dct int -huffman default -bitexact
  * (and `-pix_fmt yuvj420p|yuvj422p` from a 4:4:4 or 4:2:2 input: the chroma down-sampling
- * FFmpeg's auto-inserted scaler does, taken to be its default bicubic)
+ * FFmpeg's auto-inserted scaler does, taken to be its default bicubic; `-vf crop=...` alone or
+ * before the scale: a rectangle of the decoded frames, mjg_open_crop)
  * this library replaces the arithmetic that worker runs (swscale bicubic + tv->pc
  * range conversion, jfdctint + quantiser + default-table Huffman + 0xFF stuffing)
  * and the Python host code in ffmpeg_distributed_amd/ (worker.py, dispatcher.py)
@@ -119,6 +120,23 @@ int mjg_open(int device, const mjg_config *cfg, mjg_ctx **out);
  * 422->420) here.  mjg_open(d, cfg, out) = mjg_open_src(d, cfg, cfg->chroma_format, out).
  * (mjg_version() >= 101.) */
 int mjg_open_src(int device, const mjg_config *cfg, int src_chroma_format, mjg_ctx **out);
+/* mjg_open_src for a rectangle of the input frames (`-vf crop=w:h:x:y`, alone or before
+ * `scale`): crop_w x crop_h luma samples at (crop_x, crop_y) of the src_w x src_h frame, its
+ * chroma planes at (crop_x >> hs, crop_y >> vs) with the chroma size of a crop_w x crop_h frame
+ * (hs, vs: the source format's sub-sampling shifts).  The rectangle is the input of the sws
+ * stage, which runs when crop_w x crop_h != dst_w x dst_h or the formats differ (its filters are
+ * made for the rectangle: the edge taps replicate the crop's edge), and else of k_encode, which
+ * then reads the frames in place.  cfg->src_w / src_h stay the decoded frame size:
+ * mjg_frame_bytes, host submits and device pointers are whole frames as before.
+ * MJG_E_INVALID (before any HIP call, with a message that names the rectangle) for a
+ * non-positive size, a rectangle outside the frame, or a crop_x / crop_y that is not a multiple
+ * of the source format's sub-sampling.  mjg_open_src(d, cfg, f, out) =
+ * mjg_open_crop(d, cfg, f, 0, 0, src_w, src_h, out), with the same launches.
+ * MJG_UNALIGNED_FETCH=0 in the environment at open keeps k_encode's aligned-only row fetch for
+ * a crop read in place (misaligned blocks then load byte by byte; A/B runs and tests).
+ * (mjg_version() >= 102.) */
+int mjg_open_crop(int device, const mjg_config *cfg, int src_chroma_format,
+                  int crop_x, int crop_y, int crop_w, int crop_h, mjg_ctx **out);
 void mjg_close(mjg_ctx *ctx);
 
 /* Bytes of one packed planar input frame (src_w x src_h in the source chroma format). */
