@@ -159,6 +159,9 @@ struct PlaneScale {
   dim3 grid;
   int th = 32;  // k_scale tile height (64: the 2:1 filters, scale.hip)
   bool copy = false;  // the plane keeps its size: k_plane_copy instead of k_scale's identity filters
+  bool stream = false;  // k_scale_stream: the tile's window does not fit LDS (or MJG_SCALE_STREAM=1)
+  bool hcl = false;     // ... with the strip's h coefficients staged in LDS
+  StreamGeom sq{};
 };
 
 // Per-submit state.  A context has kSlots slots so further mjg_submits can be queued before
@@ -314,8 +317,35 @@ void free_ctx(mjg_ctx *c) {
 // chroma: the plane's subsampling shifts in the source format (s_hsub, s_vsub) and in the
 // encoded one (d_hsub, d_vsub) select the siting get_local_pos(shift, -513) of each side
 // (swscale's src / dst pixel formats; with the default siting every one comes to 128)
+// k_scale_stream's chunk rows, ring, window stride and LDS bytes (scale.hip) for a plane whose
+// widest strip window is max_nw dwords: the most rows per chunk that fit 64 KB (two window
+// halves and a ring of npv + R pairs), with the strip's h coefficients and the band's v filter
+// rows staged beside them when they fit.  False when nothing fits (no filter below 256 taps:
+// the ring is at most 130 pairs, 33 KB, and two halves of two window rows at most 18 KB).
+bool plan_scale_stream(int max_nw, int ht, int npv, StreamGeom *q, bool *hcl, size_t *lds) {
+  const int npc = max_nw / 4;  // (max_nw is a multiple of 4)
+  for (int R = 16; R >= 2; R >>= 1)
+    for (int stage = 3; stage >= 0; stage--) {  // bit 1: h coefficients, bit 0: v filter rows
+      const int rp = npv + R;
+      const size_t need = (2 * (size_t)R * max_nw + (size_t)rp * kScaleTileW +
+                           ((stage & 2) ? (size_t)kScaleTileW * (ht / 2) : 0) +
+                           ((stage & 1) ? (size_t)kStreamBand * npv : 0)) * 4;
+      if (need > 64 * 1024 || R * npc > kStreamThreads * kStreamMaxPieces) continue;
+      q->R = R;
+      q->rp = rp;
+      q->rs = max_nw;
+      q->npc = npc;
+      q->npc_magic = npc > 1 ? (uint32_t)((((uint64_t)1 << 32) + (uint32_t)npc - 1) / (uint32_t)npc) : 0u;
+      q->vcl = stage & 1;
+      *hcl = (stage & 2) != 0;
+      *lds = need;
+      return true;
+    }
+  return false;
+}
+
 int setup_plane_scale(mjg_ctx *c, PlaneScale &p, int sw, int sh, int dw, int dh, int chroma,
-                      int s_hsub, int s_vsub, int d_hsub, int d_vsub, bool bitexact) {
+                      int s_hsub, int s_vsub, int d_hsub, int d_vsub, bool bitexact, bool force_stream) {
   const int s_hpos = chroma ? sws_local_pos(s_hsub, -513) : sws_local_pos(0, 0);
   const int s_vpos = chroma ? sws_local_pos(s_vsub, -513) : sws_local_pos(0, 0);
   const int d_hpos = chroma ? sws_local_pos(d_hsub, -513) : sws_local_pos(0, 0);
@@ -405,9 +435,14 @@ int setup_plane_scale(mjg_ctx *c, PlaneScale &p, int sw, int sh, int dw, int dh,
     g.lds_win_words = 2 * max_pairs * max_nw;
     p.lds = ((size_t)g.lds_win_words + (size_t)max_pairs * kScaleTileW + (size_t)th * (npv + 1)) * 4;
   }
-  if (p.lds > 64 * 1024)
-    return set_err(MJG_E_INVALID, "scale ratio too large for one LDS tile (%zu B)", p.lds);
   p.grid = dim3((dw + kScaleTileW - 1) / kScaleTileW, (dh + th - 1) / th, 1);
+  // past one LDS tile (about 4:1), or on request for a plane whose size changes: k_scale_stream
+  p.stream = p.lds > 64 * 1024 || (force_stream && (sw != dw || sh != dh));
+  if (p.stream) {
+    if (!plan_scale_stream(max_nw, ht, npv, &p.sq, &p.hcl, &p.lds))
+      return set_err(MJG_E_INVALID, "scale %dx%d -> %dx%d: no streaming plan fits LDS", sw, sh, dw, dh);
+    p.grid = dim3((dw + kScaleTileW - 1) / kScaleTileW, (dh + kStreamBand - 1) / kStreamBand, 1);
+  }
   int rc;
   if ((rc = dmalloc(&p.hcp, hcp.size())) || (rc = dmalloc(&p.hp, (size_t)dw)) ||
       (rc = dmalloc(&p.vcp, vcp.size())) || (rc = dmalloc(&p.vps, (size_t)dh)) ||
@@ -426,7 +461,7 @@ int setup_plane_scale(mjg_ctx *c, PlaneScale &p, int sw, int sh, int dw, int dh,
   g.mf_bx0 = g.mf_bx1 = 0;
   g.mf_hs = 0;
   const int gxt = (dw + kScaleTileW - 1) / kScaleTileW;
-  if (p.d4 && ht == 8 && th >= 64 && gxt >= 3) {
+  if (!p.stream && p.d4 && ht == 8 && th >= 64 && gxt >= 3) {
     const int xa = kScaleTileW, xb = kScaleTileW * (gxt - 1);
     bool ok = true;
     for (int x = xa; x < xb && ok; x++) {
@@ -777,8 +812,12 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, mjg
   if (c->scale) {
     const bool bitexact = !(k.flags & MJG_F_SWS_NO_BITEXACT);
     // the filters for the rectangle's planes: their edge taps replicate the crop's edge
-    if ((rc = setup_plane_scale(c, c->ps[0], crw, crh, w, h, 0, 0, 0, 0, 0, bitexact)) ||
-        (rc = setup_plane_scale(c, c->ps[1], ccw, cch, cw, ch, 1, s_hsh, s_vsh, hsh, vsh, bitexact)))
+    // MJG_SCALE_STREAM=1: every plane whose size changes through k_scale_stream (A/B, tests);
+    // unset or auto: only the planes past one k_scale tile
+    const char *ss = getenv("MJG_SCALE_STREAM");
+    const bool force_stream = ss && atoi(ss) == 1;
+    if ((rc = setup_plane_scale(c, c->ps[0], crw, crh, w, h, 0, 0, 0, 0, 0, bitexact, force_stream)) ||
+        (rc = setup_plane_scale(c, c->ps[1], ccw, cch, cw, ch, 1, s_hsh, s_vsh, hsh, vsh, bitexact, force_stream)))
       return rc;
     // a plane that keeps its size (luma of a pure -pix_fmt conversion) is streamed by
     // k_plane_copy; MJG_PLANE_COPY=0 sends it through k_scale's identity filters (A/B, tests)
@@ -878,7 +917,7 @@ void launch_encode(mjg_ctx *c, Slot &S, const SegList &enc_in, int wgs, int ntas
 
 extern "C" {
 
-int mjg_version(void) { return 102; }
+int mjg_version(void) { return 103; }
 
 const char *mjg_last_error(void) { return g_err.c_str(); }
 
@@ -1027,6 +1066,28 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
         continue;
       }
       const dim3 grid((unsigned)(sg.gxy * nz), 1, 1);
+      if (ps.stream) {  // past one LDS tile: strips x bands (scale.hip k_scale_stream)
+#define MJG_STREAM_LAUNCH(D4, RANGE)                                                                          \
+  do {                                                                                                        \
+    if (ps.hcl)                                                                                               \
+      k_scale_stream<D4, RANGE, true><<<grid, kStreamThreads, ps.lds, S.st>>>(in_sl, S.d_scaled, sg, ps.sq,   \
+                                                                              ps.hcp, ps.hp, ps.vcp, ps.vps, ps.hsum); \
+    else                                                                                                      \
+      k_scale_stream<D4, RANGE, false><<<grid, kStreamThreads, ps.lds, S.st>>>(in_sl, S.d_scaled, sg, ps.sq,  \
+                                                                               ps.hcp, ps.hp, ps.vcp, ps.vps, ps.hsum); \
+  } while (0)
+        if (ps.d4) {
+          if (sg.range == 1) MJG_STREAM_LAUNCH(true, 1);
+          else if (sg.range == 2) MJG_STREAM_LAUNCH(true, 2);
+          else MJG_STREAM_LAUNCH(true, 0);
+        } else {
+          if (sg.range == 1) MJG_STREAM_LAUNCH(false, 1);
+          else if (sg.range == 2) MJG_STREAM_LAUNCH(false, 2);
+          else MJG_STREAM_LAUNCH(false, 0);
+        }
+#undef MJG_STREAM_LAUNCH
+        continue;
+      }
 #define MJG_SCALE_LAUNCH3(HT, NPV, D4, TH)                                                          \
   do {                                                                                              \
     if (sg.range == 1)                                                                              \
@@ -1462,6 +1523,14 @@ int mjg_debug_coefs(mjg_ctx *c, int frame, int16_t *out, size_t nblocks) {
   const size_t f = (size_t)L.jf0[c->last_job] + (size_t)frame;
   HIP_TRY(hipMemcpy(out, L.d_dbg + f * nb * 64, nb * 64 * sizeof(int16_t), hipMemcpyDeviceToHost));
   return MJG_OK;
+}
+
+int mjg_debug_scale_path(mjg_ctx *c, int plane) {
+  if (!c) return set_err(MJG_E_INVALID, "null context");
+  if (plane < 0 || plane > 1) return set_err(MJG_E_INVALID, "plane must be 0 (luma) or 1 (chroma)");
+  if (!c->scale) return 0;
+  const PlaneScale &p = c->ps[plane];
+  return p.copy ? 1 : p.stream ? 3 : 2;
 }
 
 int mjg_debug_planes(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {

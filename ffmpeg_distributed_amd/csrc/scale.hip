@@ -408,6 +408,213 @@ __global__ __launch_bounds__(64 * scale_waves(TH)) void k_scale(const SegList sr
   }
 }
 
+// k_scale_stream: the same arithmetic for the ratios whose tile window does not fit LDS (past
+// about 4:1).  One workgroup (4 waves) = one strip of 64 output columns x one band
+// of kStreamBand output rows of a (plane, frame).  It walks down the band's source row pairs
+// [vps[y0], vps[ye - 1] + npv) in chunks of q.R rows, one barrier per chunk:
+//   load:   the chunk's rows of the strip's byte window (dwords [cb, cb + q.rs) of each row, one
+//           row stride for every strip) as 16-byte pieces at any alignment, thread t pieces
+//           t, t + 256, ..: the LDS image is the pieces in order, chunk c in half c & 1 of a
+//           double window.  Chunk c + 2 is issued (to registers) in iteration c and stored in
+//           iteration c + 1, after that iteration's h-pass: a whole iteration hides the loads.
+//           A piece that crosses the row end is gathered byte by byte inside the row.
+//   h-pass: a wave takes row pairs of the chunk (R 16: four rows at once, each coefficient word
+//           read once for the four), lane = output column, and writes the int16 pair into a
+//           ring of q.rp pair rows: pair p in slot (p - p0) % rp.  The coefficients are staged
+//           once per workgroup as [word][lane] (HCL) or, when a wide filter leaves no room,
+//           read from the table in global memory.
+//   v-pass: after the barrier, the output rows whose last pair is now in the ring (one ballot
+//           over the band's pair starts, which a wave holds one per lane) go to the waves
+//           round-robin: the filter row from LDS (q.vcl: the band's rows staged once) or by
+//           scalar loads, npv ring rows of the lane's column, one byte stored per lane.
+// rp >= npv + R: while a wave still reads the rows that chunk c completed (they start after pair
+// e - R/2 - npv, e = the end of chunk c), another may write chunk c + 1's pairs [e, e + R/2), into
+// slots that held pairs < e + R/2 - rp.
+struct StreamGeom {
+  int R;               // source rows per chunk: 16, 8, 4 or 2
+  int rp;              // ring slots (row pairs)
+  int rs;              // window row stride (dwords) = 4 npc
+  int npc;             // 16-byte pieces per window row
+  uint32_t npc_magic;  // ceil(2^32 / npc), 0 when npc == 1
+  int vcl;             // 1: the band's v filter rows staged in LDS
+};
+constexpr int kStreamThreads = 256;
+constexpr int kStreamMaxPieces = 4;  // pieces per thread and chunk (the host keeps R npc within it)
+constexpr int kStreamBand = 64;
+
+// hScale8To15 + range conversion of NR consecutive window rows for one output column: the
+// arithmetic of hscale_lds<0, D4>, the coefficient words (stride hstr) read once for all rows
+template <int NR, bool D4>
+__device__ __forceinline__ void hscale_rows(const uint32_t *win, int rs, int off, const int32_t *hc, int hstr,
+                                            int htaps, int range, int hs, int *out) {
+  const uint32_t *q = win + (off >> 2);
+  const uint32_t sh = (uint32_t)(off & 3) * 8;
+  uint32_t lo[NR];
+  int a0[NR], a1[NR];
+#pragma unroll
+  for (int r = 0; r < NR; r++) {
+    lo[r] = q[r * rs];
+    a0[r] = a1[r] = 0;
+  }
+#pragma unroll 2
+  for (int k = 0; k < htaps; k += 4) {
+    const int32_t c0 = hc[(k >> 1) * hstr], c1 = hc[((k >> 1) + 1) * hstr];
+#pragma unroll
+    for (int r = 0; r < NR; r++) {
+      const uint32_t hi = q[r * rs + (k >> 2) + 1];
+      const uint32_t w = __builtin_amdgcn_alignbit(hi, lo[r], sh);  // taps k..k+3
+      lo[r] = hi;
+      if (D4) {
+        a0[r] = __builtin_amdgcn_sdot4((int)w, c0, a0[r], false);
+        a1[r] = __builtin_amdgcn_sdot4((int)w, c1, a1[r], false);
+      } else {
+        a0[r] = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t, __builtin_amdgcn_perm(0u, w, 0x0c010c00u)),
+                                       __builtin_bit_cast(short2_t, c0), a0[r], false);
+        a0[r] = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t, __builtin_amdgcn_perm(0u, w, 0x0c030c02u)),
+                                       __builtin_bit_cast(short2_t, c1), a0[r], false);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < NR; r++)
+    out[r] = sws_range(min(D4 ? a0[r] + (a1[r] >> 7) + hs : a0[r] >> 7, 32767), range);
+}
+
+template <bool D4, int RANGE, bool HCL>
+__global__ __launch_bounds__(kStreamThreads) void k_scale_stream(const SegList src, uint8_t *__restrict__ dst,
+                                                                 ScaleGeom g, StreamGeom q,
+                                                                 const int32_t *__restrict__ hcp,    // [dw][htaps/2]
+                                                                 const int32_t *__restrict__ hp,     // [dw]
+                                                                 const int32_t *__restrict__ vcp,    // [dh][npv]
+                                                                 const int32_t *__restrict__ vps,    // [dh]
+                                                                 const int32_t *__restrict__ hsum) {  // D4: [dw]
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int t = blockIdx.x;  // strip, band, then (plane, frame): ScaleGeom's 1-D grid
+  const int z = div_magic(t, g.gxy_magic, g.gxy), rem = t - z * g.gxy;
+  const int by = div_magic(rem, g.gx_magic, g.gx), bx = rem - by * g.gx;
+  const int x0 = bx * kScaleTileW, y0 = by * kStreamBand;
+  const int pl = z >= g.nf, f = z - (pl ? g.nf : 0);
+  const uint8_t *s = seg_frame(src, f, g.s_fstride) + g.s_off + (pl ? g.s_poff : 0);
+  uint8_t *d = dst + (size_t)f * g.d_fstride + g.d_off + (pl ? g.d_poff : 0);
+  const int xe = min(x0 + kScaleTileW, g.dw), ye = min(y0 + kStreamBand, g.dh);
+  const int npv = g.npv, hw = g.htaps >> 1, R = q.R, hr = R >> 1, rs = q.rs, rp = q.rp;
+  const int p0 = vps[y0], p1 = vps[ye - 1] + npv;  // row pairs [p0, p1)
+  const int cb = hp[x0] & ~3;
+  uint32_t *win = smem;                     // [2][R][rs]: chunk c in half c & 1
+  uint32_t *ring = smem + 2 * R * rs;       // [rp][64]
+  uint32_t *hcl = ring + rp * 64;           // HCL: [hw][64]
+  uint32_t *vcl = hcl + (HCL ? 64 * hw : 0);  // q.vcl: the band's v filter rows, [ye - y0][npv]
+  const int x = min(x0 + lane, g.dw - 1);  // clamped: tail lanes redo the last column
+  const int off = hp[x] - cb;
+  const int hs = D4 ? hsum[x] : 0;
+  const int vpl = vps[min(y0 + lane, ye - 1)];  // the band's pair starts, row y0 + lane (a band: 64 rows)
+  if (HCL)
+    for (int i = tid; i < 64 * hw; i += kStreamThreads)
+      hcl[i] = (uint32_t)hcp[(size_t)min(x0 + (i & 63), g.dw - 1) * hw + (i >> 6)];
+  if (q.vcl)
+    for (int i = tid; i < (ye - y0) * npv; i += kStreamThreads) vcl[i] = (uint32_t)vcp[(size_t)y0 * npv + i];
+  const int32_t *hc = HCL ? (const int32_t *)hcl + lane : hcp + (size_t)x * hw;
+  const int hstr = HCL ? 64 : 1;
+  const int npieces = R * q.npc;
+  u32x4 v[kStreamMaxPieces];
+  // the pieces of the chunk that starts at row pair pc (rows clamped to the plane: the rows past
+  // it only meet zero coefficients, as do the bytes past the row end, staged as zeros)
+  auto load_chunk = [&](int pc) {
+#pragma unroll
+    for (int i = 0; i < kStreamMaxPieces; i++) {
+      const int idx = tid + kStreamThreads * i;
+      v[i] = u32x4{0, 0, 0, 0};
+      if (idx < npieces) {
+        const int r = div_magic(idx, q.npc_magic, q.npc), col = cb + 16 * (idx - r * q.npc);
+        const uint8_t *rpn = s + (size_t)min(2 * pc + r, g.sh - 1) * g.s_stride;
+        if (col + 16 <= g.sw) {
+          v[i] = *(const u32x4_a1 *)(rpn + col);
+        } else if (col < g.sw) {  // the piece crosses the row end: its bytes inside the row only
+          // (a rolled loop: at most one piece per row takes it, and sixteen predicated byte
+          // loads per piece and call site would be most of the kernel's code)
+          uint64_t wl = 0, wh = 0;
+#pragma unroll 1
+          for (int b = 0; b < min(g.sw - col, 8); b++) wl |= (uint64_t)rpn[col + b] << (8 * b);
+#pragma unroll 1
+          for (int b = 8; b < g.sw - col; b++) wh |= (uint64_t)rpn[col + b] << (8 * (b - 8));
+          v[i] = u32x4{(uint32_t)wl, (uint32_t)(wl >> 32), (uint32_t)wh, (uint32_t)(wh >> 32)};
+        }
+      }
+    }
+  };
+  auto store_chunk = [&](int half) {
+#pragma unroll
+    for (int i = 0; i < kStreamMaxPieces; i++) {
+      const int idx = tid + kStreamThreads * i;
+      if (idx < npieces) *(u32x4 *)(win + half * R * rs + 4 * idx) = D4 ? v[i] ^ 0x80808080u : v[i];
+    }
+  };
+  load_chunk(p0);
+  store_chunk(0);
+  if (p0 + hr < p1) load_chunk(p0 + hr);
+  __syncthreads();
+  int ynext = y0, sb = 0, half = 0;  // the first row not yet written; the chunk's first ring slot
+  for (int pc = p0; pc < p1; pc += hr) {
+    const int pend = pc + hr;
+    const uint32_t *wc = win + half * R * rs;
+    if (R == 16) {
+      int h[4];
+      hscale_rows<4, D4>(wc + 4 * wave * rs, rs, off, hc, hstr, g.htaps, RANGE, hs, h);
+      int sl = sb + 2 * wave;
+      sl -= sl >= rp ? rp : 0;
+      ring[sl * 64 + lane] = ((uint32_t)h[0] & 0xffffu) | ((uint32_t)h[1] << 16);
+      sl = sl + 1 == rp ? 0 : sl + 1;
+      ring[sl * 64 + lane] = ((uint32_t)h[2] & 0xffffu) | ((uint32_t)h[3] << 16);
+    } else {
+      for (int i = wave; i < hr; i += kStreamThreads / 64) {
+        int h[2];
+        hscale_rows<2, D4>(wc + 2 * i * rs, rs, off, hc, hstr, g.htaps, RANGE, hs, h);
+        int sl = sb + i;
+        sl -= sl >= rp ? rp : 0;
+        ring[sl * 64 + lane] = ((uint32_t)h[0] & 0xffffu) | ((uint32_t)h[1] << 16);
+      }
+    }
+    // the next chunk (loaded a whole iteration ago) into the other half, then the one after it
+    // into the registers: one barrier per chunk orders the window halves and the ring
+    if (pend < p1) {
+      store_chunk(half ^ 1);
+      if (pend + hr < p1) load_chunk(pend + hr);
+    }
+    __syncthreads();
+    // the rows this chunk completes: [ynext, yr) (vps is monotone: a prefix of the lanes)
+    const int yr = y0 + __popcll(__ballot(y0 + lane < ye && vpl + npv <= pend));
+    for (int y = ynext + wave; y < yr; y += kStreamThreads / 64) {
+      const int yb = __builtin_amdgcn_readfirstlane(y - y0);
+      // vps[y] > pc - npv (the row was not complete before this chunk), < pc + R/2
+      int sl = sb + (__builtin_amdgcn_readlane(vpl, yb) - pc);
+      sl += sl < 0 ? rp : 0;
+      sl -= sl >= rp ? rp : 0;
+      int acc = 64 << 12;
+      if (q.vcl) {
+        const uint32_t *vr = vcl + yb * npv;  // uniform address: LDS broadcast
+        for (int k = 0; k < npv; k++) {
+          acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t, ring[sl * 64 + lane]),
+                                       __builtin_bit_cast(short2_t, vr[k]), acc, false);
+          sl = sl + 1 == rp ? 0 : sl + 1;
+        }
+      } else {
+        const int32_t *vg = vcp + (size_t)(y0 + yb) * npv;  // uniform address: scalar loads
+        for (int k = 0; k < npv; k++) {
+          acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t, ring[sl * 64 + lane]),
+                                       __builtin_bit_cast(short2_t, vg[k]), acc, false);
+          sl = sl + 1 == rp ? 0 : sl + 1;
+        }
+      }
+      if (x0 + lane < xe) d[(size_t)y * g.d_stride + x0 + lane] = (uint8_t)min(max(acc >> 19, 0), 255);
+    }
+    ynext = yr;
+    sb += hr;
+    sb -= sb >= rp ? rp : 0;
+    half ^= 1;
+  }
+}
+
 // A plane the sws stage leaves at its size (sw == dw, sh == dh: luma of a pure -pix_fmt
 // conversion, 4:4:4 -> yuvj420p).  swscale still runs it through the 15-bit intermediate with
 // one-tap identity filters (16384, 4096): per byte p

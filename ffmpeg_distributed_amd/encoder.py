@@ -330,6 +330,11 @@ class MjpegEncoder:
         check(self._L.mjg_debug_planes(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)), n))
         return out
 
+    def scale_path(self, plane: int) -> int:
+        """Which kernel the sws stage runs for a plane (0 luma, 1 chroma): 0 none, 1 k_plane_copy,
+        2 k_scale (one LDS tile), 3 k_scale_stream (past about 4:1, or MJG_SCALE_STREAM=1)."""
+        return check(self._L.mjg_debug_scale_path(self._h, int(plane)))
+
     def debug_filter(self, plane: int, direction: int):
         taps, ln = C.c_int(), C.c_int()
         check(self._L.mjg_debug_filter(self._h, plane, direction, None, None, C.byref(taps),

@@ -10,7 +10,11 @@ with FILTERS one of
     crop=...,scale=W:H[:flags=bicubic...]   (in this order)
 where the crop values are decimal integers (no expressions); `Profile.crop` is the request as
 given and `resolve_crop` turns it into a rectangle of a given input (vf_crop.c's rounding,
-defaults and clamping: DESIGN §4.8), plus
+defaults and clamping: DESIGN §4.8).  The scale may be any size pair whose bicubic filters stay
+below 256 taps in each direction, on the luma and the chroma planes: down to about 64:1
+(3840x2160 -> 64x36 runs), and any upscale.  At 256 taps or more swscale cascades two scalers,
+which the GPU path does not: the worker finds that out before it touches the GPU
+(worker.scale_cascade_reason) and sends the segment to ffmpeg on the CPU.  Plus
   - the slice-threaded (RST) layout: -slices N (N > 1), or -thread_type slice with -threads
     other than 1 (mpegvideo's slice_context_count > 1: DRI + one restart interval per MCU
     row; mjpegenc.c then forces -huffman default);

@@ -22,6 +22,7 @@ ffmpeg does (one line on stderr, exit code 1).
 from __future__ import annotations
 
 import argparse
+import ctypes as C
 import json
 import os
 import queue
@@ -460,6 +461,29 @@ def encoder_key(prof, info, dst_w, dst_h, sar, com_itu601, batch, rect=None):
             None if rect is None else tuple(rect))
 
 
+_CHROMA_SHIFTS = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}
+
+
+def scale_cascade_reason(in_size, out_size, src_chroma, dst_chroma) -> Optional[str]:
+    """None when the sws stage takes in_size -> out_size (luma and chroma planes, both
+    directions), else the reason: a bicubic filter of 256 taps or more, for which swscale
+    cascades two scalers and the library has no kernel.  Device-free (mjg_sws_filter)."""
+    from . import _lib
+    L = _lib.load()
+    (sw, sh), (dw, dh) = in_size, out_size
+    planes = [((sw, sh), (dw, dh))]
+    (shs, svs), (dhs, dvs) = _CHROMA_SHIFTS[str(src_chroma)], _CHROMA_SHIFTS[str(dst_chroma)]
+    planes.append((((sw + shs) >> shs, (sh + svs) >> svs), ((dw + dhs) >> dhs, (dh + dvs) >> dvs)))
+    for (pw, ph), (qw, qh) in planes:
+        if (pw, ph) == (qw, qh):
+            continue  # the plane keeps its size: no filter
+        taps = C.c_int()
+        for s_len, d_len, one, align in ((pw, qw, 1 << 14, 4), (ph, qh, 1 << 12, 2)):
+            if L.mjg_sws_filter(s_len, d_len, one, align, 1, 128, 128, None, 0, None, C.byref(taps)) < 0:
+                return f"scale {sw}x{sh} -> {dw}x{dh} needs swscale's cascade"
+    return None
+
+
 def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cache=None,
         batch_bytes: Optional[int] = None, opts: Optional[Options] = None) -> int:
     """One segment, stdin -> stdout.  `cache` (serve / resident mode): a dict that keeps the
@@ -497,6 +521,13 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
             return 1
     in_size = (info.width, info.height) if rect is None else (rect[2], rect[3])
     dst_w, dst_h = prof.scale or in_size
+    # the one scale the library refuses (a filter of 256 taps or more, about 64:1), decided here
+    # without a device: as the up-sampling -pix_fmt pairs, the segment goes to ffmpeg
+    why = scale_cascade_reason(in_size, (dst_w, dst_h), src_chroma, dst_chroma)
+    if why is not None:
+        stderr.write(f"gpu:{device}: {why}; running ffmpeg on the CPU\n")
+        stderr.flush()
+        return ffmpeg_fallthrough(src, args, stdout, stderr)
     bind_numa(device)  # before the reader threads and the batch buffers
     from .encoder import MjpegEncoder, PinnedBuffer   # GPU work starts here
 

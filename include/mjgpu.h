@@ -108,7 +108,11 @@ int mjg_device_numa_node(int device);
 /* Create a context on `device`: validates cfg, builds quant/Huffman/filter tables,
  * allocates device buffers for cfg->max_batch frames.  Replaces one
  * `ffmpeg ... <remote_args>` worker's codec/scaler initialisation
- * (ffmpeg_distributed.py:131-138). */
+ * (ffmpeg_distributed.py:131-138).  -vf scale: any size pair whose bicubic filters stay below
+ * 256 taps per direction and plane (down to about 64:1; mjg_sws_filter tells, without a device).
+ * Past that swscale cascades two scalers, which the library does not: MJG_E_INVALID ("needs
+ * swscale's cascade").  Planes down to about 4:1 run on k_scale (one LDS tile per output tile),
+ * steeper ones on k_scale_stream (mjg_debug_scale_path). */
 int mjg_open(int device, const mjg_config *cfg, mjg_ctx **out);
 /* mjg_open for input frames in another chroma format than the encoded one (`-pix_fmt`):
  * the frames are src_w x src_h in src_chroma_format (MJG_CHROMA_*), the JPEGs dst_w x dst_h in
@@ -166,7 +170,7 @@ int mjg_header(const mjg_ctx *ctx, uint8_t *out, size_t cap, size_t *len);
 int mjg_submit(mjg_ctx *ctx, const uint8_t *frames, int nframes, int src_is_device);
 /* Several segments in one submit: segment k's seg_nframes[k] packed I420 frames at device
  * pointer seg_frames[k] (on ctx's device), nsegs in 1..mjg_max_segments(), the total within
- * max_batch.  One launch of each kernel (k_scale, k_encode, the tail) covers all
+ * max_batch.  One launch of each kernel (the sws stage's, k_encode, the tail) covers all
  * of them, so the launch's ramp and drain are paid once; the output is the frames in segment
  * order, exactly the bytes of one mjg_submit per segment.  The resident encoder / a GPU worker
  * with several segments queued on one GPU (ffmpeg_distributed.py:139-141 once per segment)
@@ -230,6 +234,12 @@ int mjg_debug_coefs(mjg_ctx *ctx, int frame, int16_t *out, size_t nblocks);
  * packed planar at dst size in the encoded chroma format.  Only for a config whose sws stage
  * runs (src size != dst size, or source chroma format != encoded one). */
 int mjg_debug_planes(mjg_ctx *ctx, int frame, uint8_t *out, size_t cap);
+/* Which kernel the sws stage runs for a plane (0 = luma, 1 = chroma): 0 no sws stage for it (the
+ * context has none), 1 k_plane_copy (the plane keeps its size), 2 k_scale (one LDS tile per 64-column
+ * tile: down to about 4:1), 3 k_scale_stream (any ratio whose filters stay below 256 taps, about
+ * 64:1; also every resized plane with MJG_SCALE_STREAM=1 in the environment at open, for A/B runs
+ * and tests).  A negative MJG_E_* code for a bad argument.  (mjg_version() >= 103.) */
+int mjg_debug_scale_path(mjg_ctx *ctx, int plane);
 /* Filter tables the context generated: plane 0 = luma, 1 = chroma; dir 0 = horizontal,
  * 1 = vertical.  taps/len may be queried with coeff == NULL.  As mjg_debug_planes: only when
  * the sws stage runs. */
