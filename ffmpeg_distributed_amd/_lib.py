@@ -37,7 +37,7 @@ MJG_NUM_KERNELS = len(KERNEL_NAMES)
 
 # Every symbol include/mjgpu.h declares (checked by tests/test_abi.py).
 EXPORTS = (
-    "mjg_version", "mjg_last_error", "mjg_device_count", "mjg_device_numa_node", "mjg_open", "mjg_open_src", "mjg_open_crop", "mjg_close",
+    "mjg_version", "mjg_last_error", "mjg_device_count", "mjg_device_numa_node", "mjg_open", "mjg_open_src", "mjg_open_crop", "mjg_open_pad", "mjg_close",
     "mjg_frame_bytes", "mjg_header", "mjg_submit", "mjg_sync", "mjg_fetch", "mjg_fetch_host",
     "mjg_output_device", "mjg_stream", "mjg_queue_depth", "mjg_ctx_queue_depth", "mjg_submit_segments", "mjg_max_segments", "mjg_host_alloc", "mjg_host_free",
     "mjg_kernel_times", "mjg_build_header", "mjg_sws_filter", "mjg_debug_coefs",
@@ -86,6 +86,8 @@ def load():
             L.mjg_open_src.argtypes = [C.c_int, C.POINTER(MjgConfig), C.c_int, C.POINTER(vp)]
         if hasattr(L, "mjg_open_crop"):  # absent from libraries built before 1.2 (A/B builds)
             L.mjg_open_crop.argtypes = [C.c_int, C.POINTER(MjgConfig)] + [C.c_int] * 5 + [C.POINTER(vp)]
+        if hasattr(L, "mjg_open_pad"):  # absent from libraries built before 1.4 (A/B builds)
+            L.mjg_open_pad.argtypes = [C.c_int, C.POINTER(MjgConfig)] + [C.c_int] * 9 + [C.POINTER(vp)]
         L.mjg_close.argtypes = [vp]
         L.mjg_close.restype = None
         L.mjg_frame_bytes.argtypes = [vp]
@@ -127,7 +129,7 @@ def load():
         # MJG_LIBRARY may lack mjg_queue_depth / mjg_ctx_queue_depth: the queue is then two
         # deep, no merging; and the multi-segment submit, which encoder.submit_segments guards)
         late = (("mjg_queue_depth", "mjg_ctx_queue_depth", "mjg_submit_segments", "mjg_max_segments",
-                 "mjg_debug_huff_build", "mjg_open_src", "mjg_open_crop", "mjg_debug_scale_path")
+                 "mjg_debug_huff_build", "mjg_open_src", "mjg_open_crop", "mjg_open_pad", "mjg_debug_scale_path")
                 if os.environ.get("MJG_LIBRARY") else ())
         for name in EXPORTS:
             if name not in late:

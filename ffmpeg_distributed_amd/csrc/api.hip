@@ -241,6 +241,11 @@ struct mjg_ctx {
   // or of k_encode without one
   long long src_off[3] = {0, 0, 0};  // byte offsets of the rectangle's Y, U, V planes in a source frame
   long long src_cplane = 0;     // bytes of one source chroma plane (U to V)
+  // -vf pad (mjg_open_pad): the encoded frames are a canvas with the sws stage's output (the
+  // picture, cfg.dst_w x dst_h) at (pad_x, pad_y); has_pad is false for the trivial rectangle
+  bool has_pad = false;
+  PadGeom pad[2] = {};          // 0 luma, 1 chroma: the canvas plane, the picture's place, the border byte
+  long long pad_doff[2] = {0, 0};  // the picture's first byte in its canvas plane (k_scale's d_off adds it)
   bool enc_ua = false;          // k_encode<.., UA>: a crop read in place whose geometry can fail
                                 // fetch_rows' alignment test (MJG_UNALIGNED_FETCH=0: never)
   std::vector<uint8_t> hdr;
@@ -574,7 +579,9 @@ int alloc_slot(mjg_ctx *c, Slot &S) {
 }
 
 // crop: x, y, w, h in luma samples of the source frame, or nullptr for the whole frame
-int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, mjg_ctx *c) {
+// pad: x, y, w, h in luma samples of the encoded frame (the picture's place and the canvas size),
+// or nullptr for no pad
+int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, const int *pad, mjg_ctx *c) {
   c->device = device;
   c->cfg = *cfg;
   const mjg_config &k = *cfg;
@@ -602,6 +609,28 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, mjg
   if ((cx & ((1 << s_hsh) - 1)) || (cy & ((1 << s_vsh) - 1)))
     return set_err(MJG_E_INVALID, "crop %dx%d at (%d,%d): the position is not a multiple of the source's chroma "
                    "sub-sampling (%dx%d)", crw, crh, cx, cy, 1 << s_hsh, 1 << s_vsh);
+  // the pad (the encoded format and the picture size are valid here): the trivial rectangle is no pad
+  const int e_hsh = k.chroma_format == MJG_CHROMA_444 ? 0 : 1, e_vsh = k.chroma_format == MJG_CHROMA_420 ? 1 : 0;
+  const int px = pad ? pad[0] : 0, py = pad ? pad[1] : 0;
+  const int pw = pad ? pad[2] : k.dst_w, ph = pad ? pad[3] : k.dst_h;
+  if (pw < 1 || ph < 1)
+    return set_err(MJG_E_INVALID, "pad %dx%d with the picture at (%d,%d): the size is not positive", pw, ph, px, py);
+  if (pw > 16384 || ph > 16384)
+    return set_err(MJG_E_INVALID, "pad %dx%d with the picture at (%d,%d): the size is beyond 16384", pw, ph, px, py);
+  if (px < 0 || py < 0 || px > pw - k.dst_w || py > ph - k.dst_h)
+    return set_err(MJG_E_INVALID, "pad %dx%d with the picture at (%d,%d): the %dx%d picture is outside the canvas",
+                   pw, ph, px, py, k.dst_w, k.dst_h);
+  c->has_pad = px != 0 || py != 0 || pw != k.dst_w || ph != k.dst_h;
+  if (c->has_pad) {
+    const int mh = (1 << e_hsh) - 1, mv = (1 << e_vsh) - 1;
+    if ((px & mh) || (pw & mh) || (py & mv) || (ph & mv))
+      return set_err(MJG_E_INVALID, "pad %dx%d with the picture at (%d,%d): not multiples of the encoded format's "
+                     "chroma sub-sampling (%dx%d)", pw, ph, px, py, 1 << e_hsh, 1 << e_vsh);
+    if ((k.dst_w & mh) || (k.dst_h & mv))
+      return set_err(MJG_E_INVALID, "pad %dx%d with the picture at (%d,%d): the %dx%d picture is not a multiple of "
+                     "the encoded format's chroma sub-sampling (%dx%d)", pw, ph, px, py, k.dst_w, k.dst_h,
+                     1 << e_hsh, 1 << e_vsh);
+  }
   constexpr uint32_t kKnownFlags = MJG_F_TIMING | MJG_F_DEBUG_COEFS | MJG_F_SWS_NO_BITEXACT | MJG_F_COM_ITU601 |
                                    MJG_F_HUFFMAN_OPTIMAL | MJG_F_RST | MJG_F_TIMING_DETAIL | MJG_F_MERGE;
   if (k.flags & ~kKnownFlags)  // retired bits (128, 256, 512: r05's FUSED / DCT_MFMA / DCT_VALU) included
@@ -621,7 +650,8 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, mjg
   // the sws stage: a resize, or a -pix_fmt conversion (source format != encoded format; in
   // FFmpeg one swscale context does both, and tv->pc in the same pass)
   const int cf = k.chroma_format;
-  c->scale = (crw != k.dst_w || crh != k.dst_h || src_cf != cf);
+  // (a pad always runs it: k_encode then reads the canvas in d_scaled as any other sws output)
+  c->scale = (crw != k.dst_w || crh != k.dst_h || src_cf != cf || c->has_pad);
   const int hsh = cf == MJG_CHROMA_444 ? 0 : 1, vsh = cf == MJG_CHROMA_420 ? 1 : 0;
   const int scw = (k.src_w + s_hsh) >> s_hsh, sch = (k.src_h + s_vsh) >> s_vsh;
   // the rectangle's chroma planes: at (cx >> hs, cy >> vs), the chroma size of a crw x crh frame
@@ -631,7 +661,20 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, mjg
   c->src_off[0] = (long long)cy * k.src_w + cx;
   c->src_off[1] = (long long)k.src_w * k.src_h + (long long)(cy >> s_vsh) * scw + (cx >> s_hsh);
   c->src_off[2] = c->src_off[1] + c->src_cplane;
-  const int w = k.dst_w, h = k.dst_h, cw = (w + hsh) >> hsh, ch = (h + vsh) >> vsh;
+  // the encoded frame: the canvas under a pad, else the picture (the sws stage's output, or the
+  // source rectangle itself); pcw x pch: the picture's chroma planes
+  const int w = pw, h = ph, cw = (w + hsh) >> hsh, ch = (h + vsh) >> vsh;
+  const int pcw = (k.dst_w + hsh) >> hsh, pch = (k.dst_h + vsh) >> vsh;
+  for (int p = 0; p < 2; p++) {
+    PadGeom &q = c->pad[p];
+    q.cw = p ? cw : w;
+    q.ch = p ? ch : h;
+    q.cw_magic = q.cw > 1 ? (uint32_t)((((uint64_t)1 << 32) + (uint32_t)q.cw - 1) / (uint32_t)q.cw) : 0u;
+    q.px = p ? px >> hsh : px;
+    q.py = p ? py >> vsh : py;
+    q.fill = p ? 128 : 0;
+    c->pad_doff[p] = (long long)q.py * q.cw + q.px;
+  }
   c->in_frame_bytes = (size_t)k.src_w * k.src_h + 2 * (size_t)scw * sch;
   c->enc_frame_bytes = (size_t)w * h + 2 * (size_t)cw * ch;
 
@@ -816,8 +859,8 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, mjg
     // unset or auto: only the planes past one k_scale tile
     const char *ss = getenv("MJG_SCALE_STREAM");
     const bool force_stream = ss && atoi(ss) == 1;
-    if ((rc = setup_plane_scale(c, c->ps[0], crw, crh, w, h, 0, 0, 0, 0, 0, bitexact, force_stream)) ||
-        (rc = setup_plane_scale(c, c->ps[1], ccw, cch, cw, ch, 1, s_hsh, s_vsh, hsh, vsh, bitexact, force_stream)))
+    if ((rc = setup_plane_scale(c, c->ps[0], crw, crh, k.dst_w, k.dst_h, 0, 0, 0, 0, 0, bitexact, force_stream)) ||
+        (rc = setup_plane_scale(c, c->ps[1], ccw, cch, pcw, pch, 1, s_hsh, s_vsh, hsh, vsh, bitexact, force_stream)))
       return rc;
     // a plane that keeps its size (luma of a pure -pix_fmt conversion) is streamed by
     // k_plane_copy; MJG_PLANE_COPY=0 sends it through k_scale's identity filters (A/B, tests)
@@ -827,11 +870,11 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, mjg
       ScaleGeom &sg = c->ps[p].g;
       sg.sw = p ? ccw : crw;
       sg.sh = p ? cch : crh;
-      sg.dw = p ? cw : w;
-      sg.dh = p ? ch : h;
+      sg.dw = p ? pcw : k.dst_w;
+      sg.dh = p ? pch : k.dst_h;
       sg.s_stride = p ? scw : k.src_w;  // rows of the source plane (wider than sw under a crop)
       sg.sw_magic = sg.sw > 1 ? (uint32_t)((((uint64_t)1 << 32) + (uint32_t)sg.sw - 1) / (uint32_t)sg.sw) : 0u;
-      sg.d_stride = sg.dw;
+      sg.d_stride = c->pad[p].cw;  // the encoded plane's rows: dw, or the wider canvas under a pad
       sg.s_fstride = (long long)c->in_frame_bytes;
       sg.d_fstride = (long long)c->enc_frame_bytes;
       sg.range = k.in_full_range ? 0 : (p ? 2 : 1);
@@ -917,7 +960,7 @@ void launch_encode(mjg_ctx *c, Slot &S, const SegList &enc_in, int wgs, int ntas
 
 extern "C" {
 
-int mjg_version(void) { return 103; }
+int mjg_version(void) { return 104; }
 
 const char *mjg_last_error(void) { return g_err.c_str(); }
 
@@ -942,11 +985,12 @@ int mjg_device_numa_node(int device) {
 }
 
 namespace {
-int open_any(int device, const mjg_config *cfg, int src_chroma_format, const int *crop, mjg_ctx **out) {
+int open_any(int device, const mjg_config *cfg, int src_chroma_format, const int *crop, const int *pad,
+             mjg_ctx **out) {
   if (!cfg || !out) return set_err(MJG_E_INVALID, "null argument");
   *out = nullptr;
   mjg_ctx *c = new mjg_ctx();
-  const int rc = open_ctx(device, cfg, src_chroma_format, crop, c);
+  const int rc = open_ctx(device, cfg, src_chroma_format, crop, pad, c);
   if (rc) {
     const std::string keep = g_err;
     free_ctx(c);
@@ -961,11 +1005,17 @@ int open_any(int device, const mjg_config *cfg, int src_chroma_format, const int
 int mjg_open_crop(int device, const mjg_config *cfg, int src_chroma_format, int crop_x, int crop_y, int crop_w,
                   int crop_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h};
-  return open_any(device, cfg, src_chroma_format, crop, out);
+  return open_any(device, cfg, src_chroma_format, crop, nullptr, out);
+}
+
+int mjg_open_pad(int device, const mjg_config *cfg, int src_chroma_format, int crop_x, int crop_y, int crop_w,
+                 int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
+  const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
+  return open_any(device, cfg, src_chroma_format, crop, pad, out);
 }
 
 int mjg_open_src(int device, const mjg_config *cfg, int src_chroma_format, mjg_ctx **out) {
-  return open_any(device, cfg, src_chroma_format, nullptr, out);
+  return open_any(device, cfg, src_chroma_format, nullptr, nullptr, out);
 }
 
 int mjg_open(int device, const mjg_config *cfg, mjg_ctx **out) {
@@ -1038,6 +1088,8 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
           sg.d_poff = (long long)g.cw * g.ch;
         }
       }
+      const long long plane_off = sg.d_off;        // the encoded (canvas) plane in a frame
+      sg.d_off += c->pad_doff[p ? 1 : 0];          // the picture's first byte in it (0 without a pad)
       // one dimension: tiles x planes x frames (scale.hip decodes it by multiply-high)
       const int nz = p && uv1 ? 2 * n : n;
       sg.gx = (int)ps.grid.x;
@@ -1045,6 +1097,24 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
       auto magic = [](uint32_t d) { return d > 1 ? (uint32_t)((((uint64_t)1 << 32) + d - 1) / d) : 0u; };
       sg.gx_magic = magic((uint32_t)sg.gx);
       sg.gxy_magic = magic((uint32_t)sg.gxy);
+      if (c->has_pad) {  // the border, and with it a plane that keeps its size (scale.hip k_pad_plane)
+        const PadGeom &pq = c->pad[p ? 1 : 0];
+        ScaleGeom pg = sg;
+        pg.d_off = plane_off;
+        const size_t pieces = ((size_t)pq.cw * (size_t)pq.ch) >> 4, per = (size_t)kCopyThreads * kCopyVecs;
+        pg.gxy = (int)std::max<size_t>(1, (pieces + per - 1) / per);
+        pg.gxy_magic = magic((uint32_t)pg.gxy);
+        const dim3 pgrid((unsigned)(pg.gxy * nz), 1, 1);
+        if (!ps.copy)
+          k_pad_plane<0, false><<<pgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, pg, pq);
+        else if (pg.range == 1)
+          k_pad_plane<1, true><<<pgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, pg, pq);
+        else if (pg.range == 2)
+          k_pad_plane<2, true><<<pgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, pg, pq);
+        else
+          k_pad_plane<0, true><<<pgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, pg, pq);
+        if (ps.copy) continue;
+      }
       if (ps.copy) {  // the plane keeps its size: streamed (scale.hip k_plane_copy)
         const size_t pieces = ((size_t)sg.sw * (size_t)sg.sh) >> 4, per = (size_t)kCopyThreads * kCopyVecs;
         sg.gxy = (int)std::max<size_t>(1, (pieces + per - 1) / per);
@@ -1530,7 +1600,7 @@ int mjg_debug_scale_path(mjg_ctx *c, int plane) {
   if (plane < 0 || plane > 1) return set_err(MJG_E_INVALID, "plane must be 0 (luma) or 1 (chroma)");
   if (!c->scale) return 0;
   const PlaneScale &p = c->ps[plane];
-  return p.copy ? 1 : p.stream ? 3 : 2;
+  return p.copy ? (c->has_pad ? 4 : 1) : p.stream ? 3 : 2;
 }
 
 int mjg_debug_planes(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {

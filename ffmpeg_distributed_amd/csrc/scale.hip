@@ -297,8 +297,9 @@ __global__ __launch_bounds__(64 * scale_waves(TH)) void k_scale(const SegList sr
       swap32(W[1], W[3]);
       swap16(W[0], W[1]);
       swap16(W[2], W[3]);
-      // (d_stride = dw and the plane / frame offsets are any byte count: a 501-wide chroma plane
-      // at an odd offset, so the store's type promises no alignment; still one 16-byte store)
+      // (d_stride = dw, or the wider canvas row under a pad, and the plane / frame offsets are any
+      // byte count: a 501-wide chroma plane at an odd offset, so the store's type promises no
+      // alignment; still one 16-byte store.  These tiles are whole: columns x0 .. x0 + 63 < dw)
       *(u32x4_a1 *)(d + (size_t)(y0 + 16 * wave + n) * g.d_stride + x0 + 16 * g4) = u32x4{W[0], W[1], W[2], W[3]};
       return;
     }
@@ -699,6 +700,149 @@ __global__ __launch_bounds__(kCopyThreads) void k_plane_copy(const SegList src, 
     if (a < head) d[a] = RANGE ? tab[byte_at(a)] : byte_at(a);
     if (b < nb) d[b] = RANGE ? tab[byte_at(b)] : byte_at(b);
   }
+}
+
+// k_pad_plane: `-vf pad`.  The encoder's input is a canvas of q.cw x q.ch bytes
+// per plane with the picture (g.dw x g.dh: the sws stage's output plane) at column q.px, row
+// q.py and a constant byte (q.fill: 0 luma, 128 chroma) everywhere else.  Destination-driven as
+// k_plane_copy: the canvas plane of a (plane, frame) is one byte string (rows at their width),
+// cut into 16-byte pieces aligned on the destination; piece k covers bytes [head + 16 k, + 16),
+// byte j is column j % cw of row j / cw (multiply-high, div_magic: j < 2^28).  ScaleGeom as for
+// k_plane_copy (the source rectangle: sw, sh, s_stride, s_off, s_fstride, s_poff; nf, gxy) with
+// d_off / d_poff the canvas plane's offset in a frame and the next plane's from it.
+//   COPY (the plane keeps its size: the picture comes straight from the source rectangle, through
+//   the tv->pc byte table of k_plane_copy): a piece inside one picture row is one unaligned
+//   16-byte load, a piece in the border the constant, any other piece is put together byte by
+//   byte (picture bytes loaded, the rest constant); every piece is then one aligned 16-byte
+//   store, after all of the thread's loads.
+//   !COPY (k_scale / k_scale_stream write the picture into the canvas, d_stride = cw): no loads.
+//   Pieces inside the picture are skipped, pieces in the border are one 16-byte store, the others
+//   store their border bytes one by one and touch no picture byte, so the launch order of the
+//   two kernels does not matter.
+// The up to 15 bytes before the first and after the last whole piece go byte by byte in the
+// (plane, frame)'s first workgroup.
+struct PadGeom {
+  int cw, ch;         // canvas plane size
+  uint32_t cw_magic;  // ceil(2^32 / cw), 0 when cw == 1
+  int px, py;         // the picture's first column and row in the canvas plane
+  int fill;           // the border byte
+};
+
+template <int RANGE, bool COPY>
+__global__ __launch_bounds__(kCopyThreads) void k_pad_plane(const SegList src, uint8_t *__restrict__ dst,
+                                                            ScaleGeom g, PadGeom q) {
+  __shared__ __attribute__((aligned(16))) uint8_t tab[256];
+  const int tid = threadIdx.x;
+  if (COPY && RANGE) {
+    const int h = sws_range(tid << 7, RANGE);
+    tab[tid] = (uint8_t)min(max(((64 << 12) + h * 4096) >> 19, 0), 255);
+    __syncthreads();
+  }
+  const int t = blockIdx.x;
+  const int z = div_magic(t, g.gxy_magic, g.gxy), blk = t - z * g.gxy;
+  const int pl = z >= g.nf, f = z - (pl ? g.nf : 0);
+  const uint8_t *s = COPY ? seg_frame(src, f, g.s_fstride) + g.s_off + (pl ? g.s_poff : 0) : nullptr;
+  uint8_t *d = dst + (size_t)f * g.d_fstride + g.d_off + (pl ? g.d_poff : 0);
+  const int nb = q.cw * q.ch;  // < 2^28 (16384 x 16384)
+  const int head = min((int)(-(uintptr_t)d & 15), nb);
+  const int nv = (nb - head) >> 4;
+  const int pxe = q.px + g.dw, pye = q.py + g.dh;  // the picture's end column and row (COPY: dw = sw, dh = sh)
+  const uint32_t fw = (uint32_t)q.fill * 0x01010101u;
+  auto conv1 = [&](uint32_t b) -> uint32_t { return RANGE ? (uint32_t)tab[b] : b; };
+  auto conv = [&](uint32_t w) -> uint32_t {
+    if (!RANGE) return w;
+    return (uint32_t)tab[w & 255u] | ((uint32_t)tab[(w >> 8) & 255u] << 8) |
+           ((uint32_t)tab[(w >> 16) & 255u] << 16) | ((uint32_t)tab[w >> 24] << 24);
+  };
+  auto in_pic = [&](int row, int col) -> bool { return row >= q.py && row < pye && col >= q.px && col < pxe; };
+  // piece kinds: 0 inside the picture (COPY: v holds its source bytes, to convert), 1 border,
+  // 2 mixed (COPY: v holds the final bytes)
+  const int k0 = blk * (kCopyThreads * kCopyVecs) + tid;
+  u32x4 v[kCopyVecs];
+  int kind[kCopyVecs], prow[kCopyVecs], pcol[kCopyVecs];
+#pragma unroll
+  for (int i = 0; i < kCopyVecs; i++) {
+    const int k = k0 + i * kCopyThreads;
+    v[i] = u32x4{fw, fw, fw, fw};
+    kind[i] = 1;
+    prow[i] = pcol[i] = 0;
+    if (k < nv) {
+      const int j = head + 16 * k;
+      const int r0 = div_magic(j, q.cw_magic, q.cw), c0 = j - r0 * q.cw;
+      const int r1 = div_magic(j + 15, q.cw_magic, q.cw);
+      prow[i] = r0;
+      pcol[i] = c0;
+      if (r1 < q.py || r0 >= pye || (r0 == r1 && (c0 + 16 <= q.px || c0 >= pxe))) {
+        kind[i] = 1;
+      } else if (r0 == r1 && c0 >= q.px && c0 + 16 <= pxe) {
+        kind[i] = 0;
+        if (COPY) v[i] = *(const u32x4_a1 *)(s + (size_t)(r0 - q.py) * g.s_stride + (c0 - q.px));
+      } else {
+        kind[i] = 2;
+        if (COPY) {  // (rolled: a few pieces per row take it)
+          uint64_t wl = 0, wh = 0;
+          int row = r0, col = c0;
+#pragma unroll 1
+          for (int b = 0; b < 16; b++) {
+            if (col >= q.cw) {  // (cw >= 1: at most one row step per byte)
+              col = 0;
+              row++;
+            }
+            const uint64_t x = in_pic(row, col)
+                                   ? conv1(s[(size_t)(row - q.py) * g.s_stride + (col - q.px)])
+                                   : (uint32_t)q.fill;
+            if (b < 8) wl |= x << (8 * b);
+            else wh |= x << (8 * (b - 8));
+            col++;
+          }
+          v[i] = u32x4{(uint32_t)wl, (uint32_t)(wl >> 32), (uint32_t)wh, (uint32_t)(wh >> 32)};
+        }
+      }
+    }
+  }
+  // the head and tail bytes (first workgroup): loaded here, stored last
+  const bool edge = blk == 0 && tid < 16;
+  const int ja = tid, jb = head + 16 * nv + tid;
+  bool wa = false, wb = false;
+  uint32_t va = (uint32_t)q.fill, vb = (uint32_t)q.fill;
+  if (edge) {
+    if (ja < head) {
+      const int row = div_magic(ja, q.cw_magic, q.cw), col = ja - row * q.cw;
+      const bool in = in_pic(row, col);
+      wa = COPY || !in;
+      if (COPY && in) va = conv1(s[(size_t)(row - q.py) * g.s_stride + (col - q.px)]);
+    }
+    if (jb < nb) {
+      const int row = div_magic(jb, q.cw_magic, q.cw), col = jb - row * q.cw;
+      const bool in = in_pic(row, col);
+      wb = COPY || !in;
+      if (COPY && in) vb = conv1(s[(size_t)(row - q.py) * g.s_stride + (col - q.px)]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < kCopyVecs; i++) {
+    const int k = k0 + i * kCopyThreads;
+    if (k >= nv) continue;
+    uint8_t *dp = d + head + 16 * (size_t)k;
+    if (kind[i] == 1 || (COPY && kind[i] == 2)) {
+      *(u32x4 *)dp = v[i];
+    } else if (kind[i] == 0) {
+      if (COPY) *(u32x4 *)dp = u32x4{conv(v[i][0]), conv(v[i][1]), conv(v[i][2]), conv(v[i][3])};
+    } else {  // !COPY, mixed: the border bytes only
+      int row = prow[i], col = pcol[i];
+#pragma unroll 1
+      for (int b = 0; b < 16; b++) {
+        if (col >= q.cw) {
+          col = 0;
+          row++;
+        }
+        if (!in_pic(row, col)) dp[b] = (uint8_t)q.fill;
+        col++;
+      }
+    }
+  }
+  if (wa) d[ja] = (uint8_t)va;
+  if (wb) d[jb] = (uint8_t)vb;
 }
 
 }  // namespace mjg

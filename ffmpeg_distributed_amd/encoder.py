@@ -1,7 +1,7 @@
 """GPU MJPEG encoder: the per-segment encode that the reference's worker runs
 (`ffmpeg -f matroska -i pipe: <remote_args> -f matroska pipe:`,
 ffmpeg_distributed.py:131-141), restricted to the profile
-`[-vf [crop=w:h:x:y,]scale=W:H:flags=bicubic] -c:v mjpeg -q:v N -dct int [-huffman default|optimal] -bitexact`
+`[-vf [crop=w:h:x:y,][scale=W:H:flags=bicubic][,pad=W:H:x:y]] -c:v mjpeg -q:v N -dct int [-huffman default|optimal] -bitexact`
 (+ `-slices N` / `-thread_type slice` for the RST layout).
 
 Host-side wrapper over libmjgpu.so; frames are packed planar YUV (yuv420p / yuvj420p by
@@ -9,7 +9,9 @@ default, 4:2:2 and 4:4:4 with `chroma=`), i.e. what `ffmpeg -f rawvideo -pix_fmt
 writes.  `src_chroma=` names the input frames' format when `-pix_fmt` asks for another one
 than the input's (`chroma=` is then the encoded format): the chroma planes are resampled on
 the GPU as swscale does it.  `crop=(x, y, w, h)` makes a rectangle of the input frames the
-encoder's (or the scaler's) input; the frames handed over stay whole.  No CPU fallback.
+encoder's (or the scaler's) input; the frames handed over stay whole.  `pad=(x, y, W, H)` puts
+the picture (dst_w x dst_h) at (x, y) of a black W x H canvas, which is what gets encoded
+(`-vf ...,pad=W:H:x:y`).  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -59,7 +61,7 @@ class MjpegEncoder:
                  sar=(1, 1), max_batch: int = 16, timing: bool = False,
                  debug_coefs: bool = False, sws_bitexact: bool = True, com_itu601: bool = False,
                  huffman: str = "default", chroma: str = "420", rst: bool = False,
-                 merge: bool = False, src_chroma: Optional[str] = None, crop=None):
+                 merge: bool = False, src_chroma: Optional[str] = None, crop=None, pad=None):
         self._L = _lib.load()
         self.device = int(device)
         self.src_w, self.src_h = int(src_w), int(src_h)
@@ -72,6 +74,13 @@ class MjpegEncoder:
         in_w, in_h = (self.src_w, self.src_h) if self.crop is None else self.crop[2:]
         self.dst_w = int(dst_w if dst_w is not None else in_w)
         self.dst_h = int(dst_h if dst_h is not None else in_h)
+        # pad: (x, y, W, H) in luma samples of the encoded frames, resolved as profile.resolve_pad
+        # does: the picture (dst_w x dst_h, the sws stage's output) at (x, y) of a W x H canvas.
+        # enc_w x enc_h is what the JPEGs hold: the canvas, or the picture without a pad
+        self.pad = None if pad is None else tuple(int(v) for v in pad)
+        if self.pad is not None and len(self.pad) != 4:
+            raise ValueError(f"pad {pad!r}: (x, y, W, H)")
+        self.enc_w, self.enc_h = (self.dst_w, self.dst_h) if self.pad is None else self.pad[2:]
         self.max_batch = int(max_batch)
         flags = 0
         if timing == "detail":
@@ -109,7 +118,13 @@ class MjpegEncoder:
                         int(qscale), int(sar[0]), int(sar[1]), self.max_batch, flags,
                         _lib.CHROMA_FORMATS[self.chroma])
         h = C.c_void_p()
-        if self.crop is not None:
+        if self.pad is not None:
+            if not hasattr(self._L, "mjg_open_pad"):
+                raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_pad")
+            rect = self.crop if self.crop is not None else (0, 0, self.src_w, self.src_h)
+            check(self._L.mjg_open_pad(self.device, C.byref(cfg), _lib.CHROMA_FORMATS[self.src_chroma],
+                                       *rect, *self.pad, C.byref(h)))
+        elif self.crop is not None:
             if not hasattr(self._L, "mjg_open_crop"):
                 raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_crop")
             check(self._L.mjg_open_crop(self.device, C.byref(cfg), _lib.CHROMA_FORMATS[self.src_chroma],
@@ -316,7 +331,7 @@ class MjpegEncoder:
 
     def debug_coefs(self, frame: int = 0) -> np.ndarray:
         mcu_w = 8 if self.chroma == "444" else 16
-        nmcu = ((self.dst_w + mcu_w - 1) // mcu_w) * ((self.dst_h + 15) // 16)
+        nmcu = ((self.enc_w + mcu_w - 1) // mcu_w) * ((self.enc_h + 15) // 16)
         out = np.zeros((nmcu * (8 if self.chroma == "422" else 6), 64), np.int16)
         check(self._L.mjg_debug_coefs(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_int16)),
                                       out.shape[0]))
@@ -324,15 +339,17 @@ class MjpegEncoder:
 
     def debug_planes(self, frame: int = 0) -> np.ndarray:
         """The encoder-input planes (after the scale / range / chroma stage) of a frame of the
-        last synced submit: packed planar, dst size, the encoded format `chroma`."""
-        n = i420_frame_bytes(self.dst_w, self.dst_h, self.chroma)
+        last synced submit: packed planar, enc_w x enc_h (dst size; the canvas under a pad), the
+        encoded format `chroma`."""
+        n = i420_frame_bytes(self.enc_w, self.enc_h, self.chroma)
         out = np.zeros(n, np.uint8)
         check(self._L.mjg_debug_planes(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)), n))
         return out
 
     def scale_path(self, plane: int) -> int:
         """Which kernel the sws stage runs for a plane (0 luma, 1 chroma): 0 none, 1 k_plane_copy,
-        2 k_scale (one LDS tile), 3 k_scale_stream (past about 4:1, or MJG_SCALE_STREAM=1)."""
+        2 k_scale (one LDS tile), 3 k_scale_stream (past about 4:1, or MJG_SCALE_STREAM=1),
+        4 k_pad_plane (the plane keeps its size under a pad)."""
         return check(self._L.mjg_debug_scale_path(self._h, int(plane)))
 
     def debug_filter(self, plane: int, direction: int):

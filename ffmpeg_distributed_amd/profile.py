@@ -8,9 +8,16 @@ with FILTERS one of
     scale=W:H[:flags=bicubic...]
     crop=w:h[:x:y]                          (also w= / out_w=, h= / out_h=, x=, y=; keep_aspect=0, exact=0)
     crop=...,scale=W:H[:flags=bicubic...]   (in this order)
+    any of these, or nothing, followed by
+    pad=W:H[:x:y[:black]]                   (also width= / w=, height= / h=, x=, y=, color= / c=; last)
 where the crop values are decimal integers (no expressions); `Profile.crop` is the request as
 given and `resolve_crop` turns it into a rectangle of a given input (vf_crop.c's rounding,
-defaults and clamping: DESIGN §4.8).  The scale may be any size pair whose bicubic filters stay
+defaults and clamping: DESIGN §4.8).  The pad values are decimal integers too (W / H 0 or absent:
+the input's; a negative x / y centres), plus the two centring expressions x=(ow-iw)/2 and
+y=(oh-ih)/2; the colour is black; `Profile.pad` is the request as given and `resolve_pad` turns it
+into the picture's place and the canvas size for a given input (vf_pad.c's centring and rounding:
+DESIGN §4.10).  Any other pad expression or colour, `eval=`, `aspect=`, and a pad that is not
+the last filter are outside the profile.  The scale may be any size pair whose bicubic filters stay
 below 256 taps in each direction, on the luma and the chroma planes: down to about 64:1
 (3840x2160 -> 64x36 runs), and any upscale.  At 256 taps or more swscale cascades two scalers,
 which the GPU path does not: the worker finds that out before it touches the GPU
@@ -43,6 +50,9 @@ class Profile:
     # -vf crop=...: the request as given, {"w", "h", "x", "y"} -> int or None (absent), unresolved
     # (resolve_crop needs the input's size and format); None: no crop
     crop: Optional[dict] = None
+    # -vf ...,pad=...: the request as given, {"w", "h", "x", "y"} -> int, None (absent) or, for x / y,
+    # the centring expression; unresolved (resolve_pad needs the pad's input size and format); None: no pad
+    pad: Optional[dict] = None
 
 
 class Unsupported(ValueError):
@@ -90,8 +100,94 @@ def _parse_crop(f: str) -> dict:
     return out
 
 
+class PadError(ValueError):
+    """A pad request that does not fit its input (ffmpeg fails to configure the filter)."""
+
+
+PAD_CENTRE = {"x": "(ow-iw)/2", "y": "(oh-ih)/2"}   # the two expressions taken, each for its own option
+_PAD_KEYS = {"width": "w", "w": "w", "height": "h", "h": "h", "x": "x", "y": "y", "color": "color", "c": "color"}
+
+
+def _parse_pad(f: str) -> dict:
+    """`pad=...` -> {"w", "h", "x", "y"}: w / h int or None (absent); x / y int (a negative one
+    centres), the centring expression as given (PAD_CENTRE), or None (absent).  Only black."""
+    out = {"w": None, "h": None, "x": None, "y": None}
+    pos = 0
+    order = ("w", "h", "x", "y", "color")
+    for p in f[len("pad="):].split(":"):
+        if "=" in p:
+            k, v = p.split("=", 1)
+        else:
+            if pos >= len(order):
+                raise Unsupported(f"pad option {p!r} (positional options are width:height:x:y:color)")
+            k, v = order[pos], p
+            pos += 1
+        if k in ("eval", "aspect"):
+            raise Unsupported(f"pad {k}={v} (not GPU-accelerated)")
+        if k not in _PAD_KEYS:
+            raise Unsupported(f"pad option {k!r}")
+        k = _PAD_KEYS[k]
+        if k == "color":
+            if v != "black":
+                raise Unsupported(f"pad color={v} (only black is GPU-accelerated)")
+        elif v.isascii() and v.isdigit():
+            out[k] = int(v)
+        elif k in "xy" and v.startswith("-") and v[1:].isascii() and v[1:].isdigit():
+            out[k] = -int(v[1:])
+        elif k in "xy" and v == PAD_CENTRE[k]:
+            out[k] = v
+        else:
+            raise Unsupported(f"pad {k}={v} (an expression; only decimal integers and the centring forms "
+                              f"x={PAD_CENTRE['x']}, y={PAD_CENTRE['y']} are GPU-accelerated)")
+    return out
+
+
+def resolve_pad(spec: dict, in_w: int, in_h: int, chroma: str) -> Tuple[int, int, int, int]:
+    """(x, y, W, H): where a pad request puts an in_w x in_h input and the canvas size, in
+    `chroma` ("420"/"422"/"444": the format the filter sees), as vf_pad.c config_input does: an
+    absent or zero W / H is the input's; an x / y that is negative, asked to centre, or leaves
+    the input past the canvas edge becomes (W - in_w) / 2 (C truncation); then W, x are rounded
+    down to the horizontal and H, y to the vertical sub-sampling.  A canvas the input does not
+    fit in raises PadError (ffmpeg fails; nothing is passed through)."""
+    hs, vs = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}[str(chroma)]
+    W = int(spec.get("w") or 0) or in_w
+    H = int(spec.get("h") or 0) or in_h
+
+    def place(v, size, canvas):
+        v = 0 if v is None else v
+        if isinstance(v, str) or v < 0 or v + size > canvas:
+            d = canvas - size
+            v = d // 2 if d >= 0 else -((-d) // 2)
+        return int(v)
+
+    x, y = place(spec.get("x"), in_w, W), place(spec.get("y"), in_h, H)
+    W &= ~((1 << hs) - 1)
+    x &= ~((1 << hs) - 1)
+    H &= ~((1 << vs) - 1)
+    y &= ~((1 << vs) - 1)
+    if x < 0 or y < 0 or W <= 0 or H <= 0 or x + in_w > W or y + in_h > H:
+        raise PadError(f"Input area {x}:{y}:{x + in_w}:{y + in_h} not within the padded area 0:0:{W}:{H} "
+                       f"or zero-sized (pad of a {in_w}x{in_h} input)")
+    return x, y, W, H
+
+
 def _parse_vf(vf: str):
-    """-vf value -> (crop request or None, scale size or None, sws flags)."""
+    """-vf value -> (crop request or None, scale size or None, sws flags, pad request or None)."""
+    fs = vf.split(",")
+    names = [f.split("=", 1)[0] for f in fs]
+    if ";" not in vf and "pad" in names[:-1]:
+        raise Unsupported(f"filter graph {vf!r}: pad is not the last filter (only [crop,][scale,]pad in this "
+                          f"order is GPU-accelerated)")
+    if ";" not in vf and names[-1] == "pad" and "=" in fs[-1] and len(fs) <= 3:
+        pad = _parse_pad(fs[-1])
+        if len(fs) == 1:
+            return None, None, ("bicubic",), pad
+        return _parse_crop_scale(",".join(fs[:-1])) + (pad,)
+    return _parse_crop_scale(vf) + (None,)
+
+
+def _parse_crop_scale(vf: str):
+    """[crop][,scale] -> (crop request or None, scale size or None, sws flags)."""
     if ";" in vf:
         raise Unsupported(f"filter graph {vf!r} (only crop, scale or crop,scale is GPU-accelerated)")
     fs = vf.split(",")
@@ -197,6 +293,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
     chroma = None
     scale = None
     crop = None
+    pad = None
     flags: Tuple[str, ...] = ("bicubic",)
     i = 0
 
@@ -237,7 +334,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
             if any(name != "bitexact" for _, name in _flag_ops(v)):
                 raise Unsupported(f"-fflags {v}")
         elif o in ("-vf", "-filter:v"):
-            crop, scale, flags = _parse_vf(val())
+            crop, scale, flags, pad = _parse_vf(val())
         elif o in ("-an", "-sn", "-dn", "-y"):
             pass
         elif o in ("-threads", "-threads:v"):
@@ -287,7 +384,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
     if rst:
         huff = "default"  # mjpegenc.c: slice_context_count > 1 forces HUFFMAN_TABLE_DEFAULT
     return Profile(qscale=effective_qscale(q), q_arg=q, scale=scale, sws_flags=flags, huffman=huff,
-                   rst=rst, chroma=chroma, crop=crop)
+                   rst=rst, chroma=chroma, crop=crop, pad=pad)
 
 
 PIX_FMT_CHROMA = {"yuvj420p": "420", "yuvj422p": "422", "yuvj444p": "444"}

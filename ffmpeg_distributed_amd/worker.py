@@ -18,6 +18,10 @@ the decoded frames then go to the real ffmpeg as y4m (`ffmpeg_fallthrough`).
 A `-vf crop=...` is resolved against the segment's input (profile.resolve_crop) and read by
 the GPU as a rectangle of the whole frames; a request that does not fit the input fails as
 ffmpeg does (one line on stderr, exit code 1).
+A `pad=...` at the end of the graph is resolved against the picture it follows (the scale's
+output, the crop's rectangle or the input: profile.resolve_pad) and encoded as a black canvas
+around it; a picture whose size is no multiple of the format's chroma sub-sampling, and a pad
+with a -pix_fmt conversion but no scale in front of it, go to the real ffmpeg.
 """
 from __future__ import annotations
 
@@ -436,6 +440,8 @@ def ffmpeg_fallthrough(src: Source, args: List[str], stdout, stderr=None) -> int
     return rc or src.close()
 
 
+_CHROMA_SHIFTS = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}
+
 # -pix_fmt conversions the GPU path takes: (input sampling, requested sampling)
 GPU_RESAMPLE_PAIRS = {("444", "422"), ("444", "420"), ("422", "420")}
 
@@ -451,17 +457,32 @@ def resample_plan(prof, info):
     return f"-pix_fmt needs {src} -> {dst} chroma resampling"
 
 
-def encoder_key(prof, info, dst_w, dst_h, sar, com_itu601, batch, rect=None):
+def encoder_key(prof, info, dst_w, dst_h, sar, com_itu601, batch, rect=None, pad=None):
     """What an encoder context kept between segments (serve / resident mode) depends on: the
     input's shape and format and everything of the profile the context is opened with, the
-    encoded chroma format (-pix_fmt) and the resolved crop rectangle (x, y, w, h) included."""
+    encoded chroma format (-pix_fmt), the resolved crop rectangle (x, y, w, h) and the resolved
+    pad (x, y, W, H) included."""
     src_chroma, dst_chroma = resample_plan(prof, info)
     return (info.width, info.height, dst_w, dst_h, info.full_range, prof.qscale, sar,
             com_itu601, prof.huffman, src_chroma, dst_chroma, prof.rst, batch,
-            None if rect is None else tuple(rect))
+            None if rect is None else tuple(rect), None if pad is None else tuple(pad))
 
 
-_CHROMA_SHIFTS = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}
+def pad_fallthrough_reason(prof, in_size, src_chroma, dst_chroma) -> Optional[str]:
+    """Why a graph that ends in `pad` runs on the CPU for this input, or None: in_size is the
+    pad's input (the picture).  A picture whose width or height is no multiple of the format's
+    sub-sampling: vf_pad copies the area rounded down and paints the last column or row, which
+    the GPU path does not restate.  A -pix_fmt conversion without a scale: FFmpeg's converter
+    then runs after the pad and filters across the border."""
+    if prof.scale is None and src_chroma != dst_chroma:
+        return (f"pad before the {src_chroma} -> {dst_chroma} -pix_fmt conversion (no scale in the graph: the "
+                f"converter runs after the pad)")
+    hs, vs = _CHROMA_SHIFTS[str(dst_chroma)]
+    w, h = in_size
+    if w & ((1 << hs) - 1) or h & ((1 << vs) - 1):
+        return (f"pad of a {w}x{h} picture in {dst_chroma}: the size is no multiple of the chroma "
+                f"sub-sampling ({1 << hs}x{1 << vs})")
+    return None
 
 
 def scale_cascade_reason(in_size, out_size, src_chroma, dst_chroma) -> Optional[str]:
@@ -521,6 +542,23 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
             return 1
     in_size = (info.width, info.height) if rect is None else (rect[2], rect[3])
     dst_w, dst_h = prof.scale or in_size
+    # -vf ...,pad: the canvas around the picture (dst_w x dst_h).  With a scale in front the pad
+    # sees the encoded format (the scale converts), else the input's, which is then the encoded one
+    pad = None
+    if prof.pad is not None:
+        why = pad_fallthrough_reason(prof, (dst_w, dst_h), src_chroma, dst_chroma)
+        if why is not None:
+            stderr.write(f"gpu:{device}: {why}; running ffmpeg on the CPU\n")
+            stderr.flush()
+            return ffmpeg_fallthrough(src, args, stdout, stderr)
+        try:
+            pad = profile.resolve_pad(prof.pad, dst_w, dst_h, dst_chroma)
+        except profile.PadError as e:  # ffmpeg fails to configure the filter: no pass-through
+            stderr.write(f"gpu:{device}: pad: {e}\n")
+            stderr.flush()
+            src.close(kill=True)
+            return 1
+    enc_w, enc_h = (dst_w, dst_h) if pad is None else pad[2:]
     # the one scale the library refuses (a filter of 256 taps or more, about 64:1), decided here
     # without a device: as the up-sampling -pix_fmt pairs, the segment goes to ffmpeg
     why = scale_cascade_reason(in_size, (dst_w, dst_h), src_chroma, dst_chroma)
@@ -533,9 +571,10 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
 
     batch = batch_frames(opts, info.frame_bytes)
 
-    # (a crop leaves the SAR as it is: keep_aspect=0; scaled_sar of equal sizes only reduces it)
+    # (a crop leaves the SAR as it is: keep_aspect=0; scaled_sar of equal sizes only reduces it;
+    # a pad leaves it alone too: the scale's SAR, from the picture's size, not the canvas's)
     sar = profile.scaled_sar(info.sar, in_size, (dst_w, dst_h))
-    key = encoder_key(prof, info, dst_w, dst_h, sar, opts.com_itu601 and not info.full_range, batch, rect)
+    key = encoder_key(prof, info, dst_w, dst_h, sar, opts.com_itu601 and not info.full_range, batch, rect, pad)
     nbuf = NBUF
     if cache is not None and cache.get("key") == key:
         enc, bufs, obufs = cache["enc"], cache["bufs"], cache["obufs"]
@@ -545,7 +584,7 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
         enc = MjpegEncoder(device, info.width, info.height, dst_w, dst_h, full_range=info.full_range,
                            qscale=prof.qscale, sar=sar, max_batch=batch,
                            com_itu601=opts.com_itu601 and not info.full_range, huffman=prof.huffman,
-                           chroma=dst_chroma, src_chroma=src_chroma, rst=prof.rst, crop=rect)
+                           chroma=dst_chroma, src_chroma=src_chroma, rst=prof.rst, crop=rect, pad=pad)
         bufs = [PinnedBuffer(batch * enc.frame_bytes) for _ in range(nbuf)]
         # page-locked output buffers: the packets are DMA'd into one (enc.fetch_into) and the
         # muxer writes them from it; regrown when a submit's JPEGs do not fit
@@ -554,7 +593,7 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
             cache.update(key=key, enc=enc, bufs=bufs, obufs=obufs)
     prog = Progress(stderr, info.fps, prof.qscale)
     prog.duration(src.duration)
-    mkv = container.MkvWriter(stdout, dst_w, dst_h, info.fps, sar)
+    mkv = container.MkvWriter(stdout, enc_w, enc_h, info.fps, sar)
 
     # NBUF page-locked batches: the reader fills one while two are queued on the GPU (the
     # encoder takes a second submit before the first is synced, so its kernels run back to

@@ -6,10 +6,11 @@
  *     nice -n10 ionice -c3 ffmpeg -f matroska -i pipe: <remote_args> -f matroska pipe:
  * and launched/supervised at ffmpeg_distributed.py:139-141 (FFMPEGProc.run,
  * ffmpeg_distributed.py:59-91).  For the north-star profile
- *     [-vf [crop=w:h:x:y,]scale=W:H:flags=bicubic] -c:v mjpeg -q:v N -dct int -huffman default -bitexact
+ *     [-vf [crop=w:h:x:y,][scale=W:H:flags=bicubic][,pad=W:H:x:y]] -c:v mjpeg -q:v N -dct int -huffman default -bitexact
  * (and `-pix_fmt yuvj420p|yuvj422p` from a 4:4:4 or 4:2:2 input: the chroma down-sampling
  * FFmpeg's auto-inserted scaler does, taken to be its default bicubic; `-vf crop=...` alone or
- * before the scale: a rectangle of the decoded frames, mjg_open_crop)
+ * before the scale: a rectangle of the decoded frames, mjg_open_crop; `pad=...` as the last
+ * filter: the picture on a black canvas, mjg_open_pad)
  * this library replaces the arithmetic that worker runs (swscale bicubic + tv->pc
  * range conversion, jfdctint + quantiser + default-table Huffman + 0xFF stuffing)
  * and the Python host code in ffmpeg_distributed_amd/ (worker.py, dispatcher.py)
@@ -141,6 +142,23 @@ int mjg_open_src(int device, const mjg_config *cfg, int src_chroma_format, mjg_c
  * (mjg_version() >= 102.) */
 int mjg_open_crop(int device, const mjg_config *cfg, int src_chroma_format,
                   int crop_x, int crop_y, int crop_w, int crop_h, mjg_ctx **out);
+/* mjg_open_crop with a letterbox (`-vf pad=W:H:x:y` as the last filter, after crop and / or
+ * scale): the JPEGs are pad_w x pad_h with the picture -- the sws stage's output, cfg->dst_w x
+ * dst_h, which stay the picture's size as src_w / src_h stay the decoded frame's under a crop --
+ * at (pad_x, pad_y) and black everywhere else: Y = 0, Cb = Cr = 128 in the full-range encoder
+ * input, for tv and for full-range sources alike.  mjg_header, the MCU grid and mjg_debug_planes
+ * follow the canvas, mjg_frame_bytes the source.  With a pad the sws stage always runs: a plane
+ * whose size changes is written into the canvas by k_scale / k_scale_stream (rows at the canvas
+ * stride), the border by k_pad_plane, which also copies a plane that keeps its size (through
+ * the tv->pc byte table).  The trivial rectangle (0, 0, dst_w, dst_h) is no pad:
+ * mjg_open_crop(d, cfg, f, x, y, w, h, out) = mjg_open_pad(d, cfg, f, x, y, w, h, 0, 0, dst_w,
+ * dst_h, out), with the same launches.  MJG_E_INVALID (before any HIP call, with a message that
+ * names the pad) for a non-positive canvas size, a picture outside the canvas, and, when the
+ * rectangle is not the trivial one, a pad_x / pad_y / pad_w / pad_h or a dst_w / dst_h that is
+ * not a multiple of the encoded format's sub-sampling.  (mjg_version() >= 104.) */
+int mjg_open_pad(int device, const mjg_config *cfg, int src_chroma_format,
+                 int crop_x, int crop_y, int crop_w, int crop_h,
+                 int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
 void mjg_close(mjg_ctx *ctx);
 
 /* Bytes of one packed planar input frame (src_w x src_h in the source chroma format). */
@@ -231,14 +249,15 @@ int mjg_sws_filter(int src_len, int dst_len, int one, int align, int bitexact, i
  * in coding order (4:2:0: Y0 Y1 Y2 Y3 Cb Cr per MCU).  Needs MJG_F_DEBUG_COEFS. */
 int mjg_debug_coefs(mjg_ctx *ctx, int frame, int16_t *out, size_t nblocks);
 /* The full-range encoder-input planes (after scale/range stage) of frame `frame`,
- * packed planar at dst size in the encoded chroma format.  Only for a config whose sws stage
+ * packed planar at dst size (under a pad: the canvas size) in the encoded chroma format.  Only for a config whose sws stage
  * runs (src size != dst size, or source chroma format != encoded one). */
 int mjg_debug_planes(mjg_ctx *ctx, int frame, uint8_t *out, size_t cap);
 /* Which kernel the sws stage runs for a plane (0 = luma, 1 = chroma): 0 no sws stage for it (the
  * context has none), 1 k_plane_copy (the plane keeps its size), 2 k_scale (one LDS tile per 64-column
  * tile: down to about 4:1), 3 k_scale_stream (any ratio whose filters stay below 256 taps, about
  * 64:1; also every resized plane with MJG_SCALE_STREAM=1 in the environment at open, for A/B runs
- * and tests).  A negative MJG_E_* code for a bad argument.  (mjg_version() >= 103.) */
+ * and tests), 4 k_pad_plane (the plane keeps its size under a pad: copied into the canvas with its
+ * border; mjg_version() >= 104).  A negative MJG_E_* code for a bad argument.  (mjg_version() >= 103.) */
 int mjg_debug_scale_path(mjg_ctx *ctx, int plane);
 /* Filter tables the context generated: plane 0 = luma, 1 = chroma; dir 0 = horizontal,
  * 1 = vertical.  taps/len may be queried with coeff == NULL.  As mjg_debug_planes: only when
