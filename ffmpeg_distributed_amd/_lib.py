@@ -42,6 +42,7 @@ EXPORTS = (
     "mjg_output_device", "mjg_stream", "mjg_queue_depth", "mjg_ctx_queue_depth", "mjg_submit_segments", "mjg_max_segments", "mjg_host_alloc", "mjg_host_free",
     "mjg_kernel_times", "mjg_build_header", "mjg_sws_filter", "mjg_debug_coefs",
     "mjg_debug_planes", "mjg_debug_filter", "mjg_debug_huff_build", "mjg_debug_scale_path",
+    "mjg_debug_encode_path",
 )
 
 
@@ -122,6 +123,9 @@ def load():
         if hasattr(L, "mjg_debug_scale_path"):  # absent from libraries built before 1.3 (A/B builds)
             L.mjg_debug_scale_path.argtypes = [vp, C.c_int]
             L.mjg_debug_scale_path.restype = C.c_int
+        if hasattr(L, "mjg_debug_encode_path"):  # absent from libraries built before 1.5 (A/B builds)
+            L.mjg_debug_encode_path.argtypes = [vp]
+            L.mjg_debug_encode_path.restype = C.c_int
         L.mjg_build_header.argtypes = [C.POINTER(MjgConfig), u8p, sz, C.POINTER(sz)]
         L.mjg_sws_filter.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_int16), sz, C.POINTER(C.c_int32),
                                                      C.POINTER(C.c_int)]
@@ -129,7 +133,8 @@ def load():
         # MJG_LIBRARY may lack mjg_queue_depth / mjg_ctx_queue_depth: the queue is then two
         # deep, no merging; and the multi-segment submit, which encoder.submit_segments guards)
         late = (("mjg_queue_depth", "mjg_ctx_queue_depth", "mjg_submit_segments", "mjg_max_segments",
-                 "mjg_debug_huff_build", "mjg_open_src", "mjg_open_crop", "mjg_open_pad", "mjg_debug_scale_path")
+                 "mjg_debug_huff_build", "mjg_open_src", "mjg_open_crop", "mjg_open_pad", "mjg_debug_scale_path",
+                 "mjg_debug_encode_path")
                 if os.environ.get("MJG_LIBRARY") else ())
         for name in EXPORTS:
             if name not in late:

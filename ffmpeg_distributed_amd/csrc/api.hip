@@ -960,7 +960,7 @@ void launch_encode(mjg_ctx *c, Slot &S, const SegList &enc_in, int wgs, int ntas
 
 extern "C" {
 
-int mjg_version(void) { return 104; }
+int mjg_version(void) { return 105; }
 
 const char *mjg_last_error(void) { return g_err.c_str(); }
 
@@ -1601,6 +1601,11 @@ int mjg_debug_scale_path(mjg_ctx *c, int plane) {
   if (!c->scale) return 0;
   const PlaneScale &p = c->ps[plane];
   return p.copy ? (c->has_pad ? 4 : 1) : p.stream ? 3 : 2;
+}
+
+int mjg_debug_encode_path(mjg_ctx *c) {
+  if (!c) return set_err(MJG_E_INVALID, "null context");
+  return (c->scale ? 0 : 1) | (c->enc_ua ? 2 : 0);
 }
 
 int mjg_debug_planes(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {

@@ -352,6 +352,14 @@ class MjpegEncoder:
         4 k_pad_plane (the plane keeps its size under a pad)."""
         return check(self._L.mjg_debug_scale_path(self._h, int(plane)))
 
+    def encode_path(self) -> int:
+        """Which k_encode the context launches, as bits (mjg_debug_encode_path): 1 it reads the
+        source frames in place (no sws stage), 2 the UA instantiation (a crop read in place whose
+        geometry can fail the 8-byte alignment test)."""
+        if not hasattr(self._L, "mjg_debug_encode_path"):
+            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_debug_encode_path")
+        return check(self._L.mjg_debug_encode_path(self._h))
+
     def debug_filter(self, plane: int, direction: int):
         taps, ln = C.c_int(), C.c_int()
         check(self._L.mjg_debug_filter(self._h, plane, direction, None, None, C.byref(taps),

@@ -259,6 +259,12 @@ int mjg_debug_planes(mjg_ctx *ctx, int frame, uint8_t *out, size_t cap);
  * and tests), 4 k_pad_plane (the plane keeps its size under a pad: copied into the canvas with its
  * border; mjg_version() >= 104).  A negative MJG_E_* code for a bad argument.  (mjg_version() >= 103.) */
 int mjg_debug_scale_path(mjg_ctx *ctx, int plane);
+/* Which k_encode the context launches, as bits: 1 k_encode reads the source frames in place (no
+ * sws stage: same size, same format, no pad; under a crop the rectangle at the source's strides),
+ * 2 the UA instantiation (fetch_rows at any alignment: a crop read in place with a plane offset,
+ * a row stride or the frame stride that is no multiple of 8, unless MJG_UNALIGNED_FETCH=0 at
+ * open).  A negative MJG_E_* code for a null context.  Host state only.  (mjg_version() >= 105.) */
+int mjg_debug_encode_path(mjg_ctx *ctx);
 /* Filter tables the context generated: plane 0 = luma, 1 = chroma; dir 0 = horizontal,
  * 1 = vertical.  taps/len may be queried with coeff == NULL.  As mjg_debug_planes: only when
  * the sws stage runs. */

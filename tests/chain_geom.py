@@ -1,0 +1,317 @@
+"""Device-free geometry of the encoder for the GPU tests of the filter chain
+(tests/test_chain_geom.py, tests/test_gpu_chain.py): a restatement, from the sizes alone, of what
+open_ctx (csrc/api.hip) derives, so that a test can assert *before* it opens a context that its
+shape reaches the path it means to check.
+
+  - enc_geom / unit_starts: k_encode's segments, chunks and tasks, and the (frame, segment,
+    chunk) at which each work unit of kBatch tasks starts (a unit that starts at chunk != 0
+    recomputes its DC predictors from pixel rows: carry_row);
+  - copy_span: workgroups and vector slots a plane of n bytes takes in k_plane_copy / k_pad_plane;
+  - predict_paths: what mjg_debug_encode_path and mjg_debug_scale_path will report for a
+    crop / -pix_fmt / scale / pad configuration (the rules of open_ctx and setup_plane_scale; the
+    filters come from the library's own device-free mjg_sws_filter).
+
+kBatch, kCopyThreads, kCopyVecs and the tile kernel's constants are parsed from the kernel
+sources, so a change there moves these values and a hollowed-out test fails its precondition."""
+import os
+import re
+from collections import namedtuple
+
+from ffmpeg_distributed_amd import _lib
+from ffmpeg_distributed_amd.encoder import CHROMA_SHIFTS, chroma_size
+
+_CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ffmpeg_distributed_amd", "csrc")
+
+
+def _const(path, name):
+    with open(os.path.join(_CSRC, path)) as f:
+        m = re.search(r"constexpr\s+int\s+" + name + r"\s*=\s*(\d+)\s*;", f.read())
+    assert m, (path, name)
+    return int(m.group(1))
+
+
+K_BATCH = _const("kernels.hip", "kBatch")
+COPY_THREADS = _const("scale.hip", "kCopyThreads")
+COPY_VECS = _const("scale.hip", "kCopyVecs")
+SCALE_TILE_W = _const("scale.hip", "kScaleTileW")
+SCALE_LOAD_ROWS = _const("scale.hip", "kScaleLoadRows")
+SCALE_ALIAS_WORDS = _const("scale.hip", "kScaleAliasWords")
+
+EncGeom = namedtuple("EncGeom", "mbw mbh nseg seg_blocks nchunks ntasks")
+
+
+def enc_geom(w, h, chroma, rst=False, nframes=1):
+    """open_ctx's values for an encoded w x h frame in `chroma` (under a pad: the canvas)."""
+    bpm = 8 if chroma == "422" else 6
+    lmw = 8 if chroma == "444" else 16
+    mbw, mbh = (w + lmw - 1) // lmw, (h + 15) // 16
+    rst = bool(rst) and mbh > 1
+    nseg = mbh if rst else 1
+    seg_blocks = (mbw if rst else mbw * mbh) * bpm
+    nchunks = (seg_blocks + 63) // 64
+    return EncGeom(mbw, mbh, nseg, seg_blocks, nchunks, nchunks * nseg * nframes)
+
+
+def unit_starts(w, h, chroma, rst=False, nframes=1):
+    """[(frame, segment, chunk)] of the first task of every work unit: task t is chunk
+    t % nchunks of segment (t / nchunks) % nseg of frame t / (nchunks nseg); unit u starts at
+    task u kBatch (k_encode, task_pos)."""
+    g = enc_geom(w, h, chroma, rst, nframes)
+    out = []
+    for t in range(0, g.ntasks, K_BATCH):
+        seg = t // g.nchunks
+        out.append((seg // g.nseg, seg % g.nseg, t % g.nchunks))
+    return out
+
+
+def mid_segment_units(w, h, chroma, rst=False, nframes=1):
+    """The units that start inside a segment (chunk != 0)."""
+    return [u for u in unit_starts(w, h, chroma, rst, nframes) if u[2] != 0]
+
+
+def _mcu_tables():
+    """open_ctx's kPlane / kDx / kDy: per format, the plane and the 8x8 position in its MCU of every
+    block of an MCU in coding order."""
+    with open(os.path.join(_CSRC, "api.hip")) as f:
+        src = f.read()
+    out = {}
+    for name in ("kPlane", "kDx", "kDy"):
+        m = re.search(name + r"\[3\]\[8\]\s*=\s*\{(.*?)\};", src)
+        assert m, name
+        rows = re.findall(r"\{([^{}]*)\}", m.group(1))
+        assert len(rows) == 3, name
+        out[name] = [[int(v) for v in r.split(",")] for r in rows]
+    return out
+
+
+_MCU = _mcu_tables()
+_FMT = {"420": 0, "422": 1, "444": 2}
+
+
+def block_pos(w, h, chroma, b):
+    """(plane, x0, y0, plane width, plane height) of block b of a frame in coding order
+    (kernels.hip block_pos with open_ctx's descriptors)."""
+    f = _FMT[chroma]
+    bpm = 8 if chroma == "422" else 6
+    lmw, cmh = (8 if chroma == "444" else 16), (8 if chroma == "420" else 16)
+    mbw = (w + lmw - 1) // lmw
+    m, i = divmod(b, bpm)
+    my, mx = divmod(m, mbw)
+    pl = _MCU["kPlane"][f][i]
+    xs, ys = (lmw, 16) if pl == 0 else (8, cmh)
+    pw, ph = (w, h) if pl == 0 else chroma_size(w, h, chroma)
+    return pl, mx * xs + 8 * _MCU["kDx"][f][i], my * ys + 8 * _MCU["kDy"][f][i], pw, ph
+
+
+def carry_preds(w, h, chroma, rst=False, nframes=1):
+    """For every unit that starts inside a segment, (frame, segment, chunk, {plane: interior}): of
+    the 8 blocks before the unit's first one, whose pixel rows carry_row loads, the last block of
+    each plane (the DC predictor of that plane's first block in the chunk), and whether it lies
+    inside the picture (x0 + 8 <= plane width: carry_row's one 8-byte load per row, at any
+    alignment under UA) or on its right edge (the byte loop with the clamp)."""
+    g = enc_geom(w, h, chroma, rst, nframes)
+    out = []
+    for fr, seg, chunk in mid_segment_units(w, h, chroma, rst, nframes):
+        last = {}
+        for b in range(seg * g.seg_blocks + chunk * 64 - 8, seg * g.seg_blocks + chunk * 64):
+            pl, x0, _, pw, _ = block_pos(w, h, chroma, b)
+            last[pl] = x0 + 8 <= pw
+        out.append((fr, seg, chunk, last))
+    return out
+
+
+def copy_span(nbytes):
+    """(workgroups, vector slots in use) for one (plane, frame) of nbytes in the copy kernels:
+    16-byte pieces, kCopyThreads x kCopyVecs of them per workgroup, slot i of thread tid holding
+    piece tid + i kCopyThreads (the launch sizes its grid from nbytes >> 4; an unaligned head can
+    make the kernel's own piece count one less)."""
+    pieces = nbytes >> 4
+    per = COPY_THREADS * COPY_VECS
+    wgs = max(1, (pieces + per - 1) // per)
+    slots = COPY_VECS if wgs > 1 else min(COPY_VECS, max(1, (pieces + COPY_THREADS - 1) // COPY_THREADS))
+    return wgs, slots
+
+
+# mjg_debug_scale_path's values
+NONE, COPY, TILE, STREAM, PADCOPY = 0, 1, 2, 3, 4
+IN_PLACE, UA = 1, 2  # mjg_debug_encode_path's bits
+
+
+def taps_ok(sw, sh, dw, dh):
+    """Both filters of one plane stay below 256 taps (else swscale cascades: open refuses)."""
+    try:
+        _lib.sws_filter(sw, dw, 1 << 14, 4)
+        _lib.sws_filter(sh, dh, 1 << 12, 2)
+        return True
+    except _lib.MjgError:
+        return False
+
+
+def tile_lds(sw, sh, dw, dh):
+    """Bytes of LDS k_scale would need for one tile of a sw x sh -> dw x dh plane
+    (setup_plane_scale: past 64 KiB the plane goes to k_scale_stream).  Every plane's filter
+    positions are 128 (sws_local_pos with the default chroma siting), mjg_sws_filter's default."""
+    hc, hpos = _lib.sws_filter(sw, dw, 1 << 14, 4)
+    vc, vpos = _lib.sws_filter(sh, dh, 1 << 12, 2)
+    ht, vt = (hc.shape[1] + 3) & ~3, vc.shape[1]
+    npv = vt // 2 + 1
+    vps = [int(p) >> 1 for p in vpos]
+    max_nw = 0
+    for x0 in range(0, dw, SCALE_TILE_W):
+        xe, cb = min(x0 + SCALE_TILE_W, dw), int(hpos[x0]) & ~3
+        max_nw = max(max_nw, ((((int(hpos[xe - 1]) + ht - cb + 3) >> 2) + 1) + 3) & ~3)
+
+    def tile_pairs(th):
+        return max(vps[min(y0 + th, dh) - 1] + npv - vps[y0] for y0 in range(0, dh, th))
+
+    # scale_waves(64) = 4, scale_loads_per_wave(64) = 5
+    th = 64 if (ht == 8 and npv == 5 and max_nw <= SCALE_ALIAS_WORDS and sw >= 16
+                and 2 * tile_pairs(64) <= 4 * 5 * SCALE_LOAD_ROWS) else 32
+    mp = tile_pairs(th)
+    if th >= 64:
+        return 2 * mp * SCALE_ALIAS_WORDS * 4 + 64
+    return (2 * mp * max_nw + mp * SCALE_TILE_W + th * (npv + 1)) * 4
+
+
+def plane_path(sw, sh, dw, dh, has_pad, plane_copy=True):
+    if plane_copy and (sw, sh) == (dw, dh):
+        return PADCOPY if has_pad else COPY
+    return STREAM if tile_lds(sw, sh, dw, dh) > 64 * 1024 else TILE
+
+
+def predict_paths(w, h, src, rect, dst, dw, dh, pad, unaligned_fetch=True, plane_copy=True):
+    """(encode_path, (luma scale_path, chroma scale_path), RECT) of a context on w x h frames in
+    `src`, cropped to rect (None: whole frames), encoded in `dst` at dw x dh (None: the
+    rectangle's size) on the canvas pad = (x, y, W, H) (None: no pad).  RECT: the luma copy is
+    k_plane_copy's rectangle form.  unaligned_fetch / plane_copy: MJG_UNALIGNED_FETCH /
+    MJG_PLANE_COPY not 0 at open."""
+    x, y, rw, rh = rect or (0, 0, w, h)
+    dw, dh = dw or rw, dh or rh
+    has_pad = pad is not None and tuple(pad) != (0, 0, dw, dh)
+    scale = (rw, rh) != (dw, dh) or src != dst or has_pad
+    shs, svs = CHROMA_SHIFTS[src]
+    scw, sch = chroma_size(w, h, src)
+    if not scale:
+        off0 = y * w + x
+        off1 = w * h + (y >> svs) * scw + (x >> shs)
+        off2 = off1 + scw * sch
+        is_crop = (x, y, rw, rh) != (0, 0, w, h)
+        bits = off0 | off1 | off2 | w | scw | (w * h + 2 * scw * sch)
+        return IN_PLACE | (UA if is_crop and (bits & 7) and unaligned_fetch else 0), (NONE, NONE), False
+    ccw, cch = chroma_size(rw, rh, src)
+    pcw, pch = chroma_size(dw, dh, dst)
+    luma = plane_path(rw, rh, dw, dh, has_pad, plane_copy)
+    chroma = plane_path(ccw, cch, pcw, pch, has_pad, plane_copy)
+    return 0, (luma, chroma), luma == COPY and rw != w
+
+
+# ------------------------------------------------------------------ the seeded sweep of the chain
+DOWN = {"444": ("444", "422", "420"), "422": ("422", "420"), "420": ("420",)}  # never up-sampling
+SUBMITS = ("host", "dev_odd", "segments", "merged")
+MODES = ({}, {"huffman": "optimal"}, {"rst": True})
+FEATURES = ("crop_in_place_ua", "crop_in_place_aligned", "rect_copy", "pad_copy", "pad_with_scale", "stream") + SUBMITS
+
+Config = namedtuple("Config", "w h src rect dst dw dh pad full q kw submit nframes fseed")
+
+
+def sweep_configs(seed, count):
+    """`count` drawn configurations of crop -> convert / scale -> pad -> encode.  Source 64..420 x
+    48..260 in any format; the encoded format the source's or a down-sampling of it; a crop in 2
+    of 3 (the rectangle at least half the frame each way; for one crop in 2 the frame width and
+    the rectangle's x are cut to multiples of 16, which is what the aligned read in place needs);
+    a resize in 1 of 2, 2:1 to 6:1 down per direction; a pad in 1 of 2 with margins of 0..40;
+    range, q, default / optimal / rst and the submit mode.  Every value is drawn before the
+    rules are tested; a draw whose padded picture breaks the encoded format's sub-sampling, or
+    whose filters reach 256 taps, is dropped and drawn again."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    out = []
+    while len(out) < count:
+        w, h = int(rng.integers(64, 421)), int(rng.integers(48, 261))
+        src = ("420", "422", "444")[int(rng.integers(3))]
+        dst = DOWN[src][int(rng.integers(len(DOWN[src])))]
+        crop, snap = int(rng.integers(3)) < 2, bool(rng.integers(2))
+        fr = rng.uniform(0.5, 1.0, 2)
+        fo = rng.uniform(0.0, 1.0, 2)
+        resize = bool(rng.integers(2))
+        rx, ry = rng.uniform(2.0, 6.0, 2)
+        padded = bool(rng.integers(2))
+        ml, mr, mt, mb = (int(v) for v in rng.integers(0, 41, 4))
+        full = bool(rng.integers(2))
+        q = (2, 5, 31)[int(rng.integers(3))]
+        kw = MODES[int(rng.integers(3))]
+        submit = SUBMITS[int(rng.integers(4))]
+        nframes = 2 if submit in ("segments", "merged") else 1 + int(rng.integers(2))
+        fseed = int(rng.integers(1 << 30))
+        shs, svs = CHROMA_SHIFTS[src]
+        rect = None
+        if crop:
+            if snap:
+                w &= ~15
+            rw, rh = max(8, int(w * fr[0])), max(8, int(h * fr[1]))
+            x, y = int((w - rw) * fo[0]), int((h - rh) * fo[1])
+            if snap:
+                x &= ~15
+            rect = (x & ~((1 << shs) - 1), y & ~((1 << svs) - 1), rw, rh)
+        iw, ih = rect[2:] if rect else (w, h)
+        dw, dh = (max(8, int(round(iw / rx))), max(8, int(round(ih / ry)))) if resize else (None, None)
+        pw, ph = dw or iw, dh or ih
+        hs, vs = CHROMA_SHIFTS[dst]  # the margins are cut to the encoded format's sub-sampling
+        ml, mr, mt, mb = ml & ~((1 << hs) - 1), mr & ~((1 << hs) - 1), mt & ~((1 << vs) - 1), mb & ~((1 << vs) - 1)
+        pad = (ml, mt, pw + ml + mr, ph + mt + mb) if padded and (ml or mr or mt or mb) else None
+        if pad is not None and ((pw & ((1 << hs) - 1)) or (ph & ((1 << vs) - 1))):
+            continue  # a picture of odd size cannot be padded in a sub-sampled format
+        if (iw, ih) != (pw, ph) or src != dst or pad is not None:  # the sws stage runs: its filters
+            ccw, cch = chroma_size(iw, ih, src)
+            pcw, pch = chroma_size(pw, ph, dst)
+            if not (taps_ok(iw, ih, pw, ph) and taps_ok(ccw, cch, pcw, pch)):
+                continue
+        out.append(Config(w, h, src, rect, dst, dw, dh, pad, full, q, kw, submit, nframes, fseed))
+    return out
+
+
+def features(cfg, enc_path, paths):
+    """The FEATURES a configuration carries, from its encode path and scale paths (predicted by
+    predict_paths, or as the context reports them)."""
+    crop = cfg.rect is not None and tuple(cfg.rect) != (0, 0, cfg.w, cfg.h)
+    f = {cfg.submit}
+    if crop and enc_path == (IN_PLACE | UA):
+        f.add("crop_in_place_ua")
+    if crop and enc_path == IN_PLACE:
+        f.add("crop_in_place_aligned")
+    if paths[0] == COPY and crop and cfg.rect[2] != cfg.w:
+        f.add("rect_copy")
+    if PADCOPY in paths:
+        f.add("pad_copy")
+    if cfg.pad is not None and (TILE in paths or STREAM in paths):
+        f.add("pad_with_scale")
+    if STREAM in paths:
+        f.add("stream")
+    return f
+
+
+def count_features(sets):
+    return {k: sum(k in s for s in sets) for k in FEATURES}
+
+
+def predicted_counts(cfgs):
+    sets = []
+    for c in cfgs:
+        enc_path, paths, _ = predict_paths(c.w, c.h, c.src, c.rect, c.dst, c.dw, c.dh, c.pad)
+        sets.append(features(c, enc_path, paths))
+    return count_features(sets)
+
+
+# The sweep of tests/test_gpu_chain.py: the seed, and per part of 30 configurations the number
+# that carry each feature, counted by predicted_counts (tests/test_chain_geom.py checks that).
+SWEEP_SEED = 93  # of seeds 1..3000 the one whose eight smallest counts below are largest
+SWEEP_FLOORS = [
+    {"crop_in_place_ua": 5, "crop_in_place_aligned": 2, "rect_copy": 4, "pad_copy": 4, "pad_with_scale": 4, "stream": 2,
+     "host": 7, "dev_odd": 7, "segments": 10, "merged": 6},
+    {"crop_in_place_ua": 2, "crop_in_place_aligned": 2, "rect_copy": 2, "pad_copy": 4, "pad_with_scale": 11, "stream": 2,
+     "host": 7, "dev_odd": 9, "segments": 6, "merged": 8},
+    {"crop_in_place_ua": 4, "crop_in_place_aligned": 3, "rect_copy": 2, "pad_copy": 2, "pad_with_scale": 6, "stream": 2,
+     "host": 11, "dev_odd": 12, "segments": 5, "merged": 2},
+    {"crop_in_place_ua": 3, "crop_in_place_aligned": 2, "rect_copy": 1, "pad_copy": 3, "pad_with_scale": 9, "stream": 1,
+     "host": 6, "dev_odd": 11, "segments": 7, "merged": 6},
+]

@@ -52,6 +52,18 @@ def test_version_and_error_string():
     assert isinstance(L.mjg_last_error(), bytes)
 
 
+def test_encode_path_hook_is_declared_exported_and_refuses_a_null_context():
+    """mjg_debug_encode_path (1.5): in the header with the signature the binding uses, in the
+    binding list and the library; without a context it is an error code, not a path."""
+    assert re.search(r"\bint\s+mjg_debug_encode_path\s*\(\s*mjg_ctx\s*\*\s*ctx\s*\)\s*;", HEADER)
+    assert "mjg_debug_encode_path" in _lib.EXPORTS and "mjg_debug_encode_path" in declared()
+    L = _lib.load()
+    assert L.mjg_version() == 105
+    assert L.mjg_debug_encode_path.argtypes == [C.c_void_p] and L.mjg_debug_encode_path.restype is C.c_int
+    assert L.mjg_debug_encode_path(None) == _lib.MJG_E_INVALID
+    assert b"null" in L.mjg_last_error()
+
+
 def test_build_header_size_query_and_capacity_error():
     L = _lib.load()
     cfg = _lib.MjgConfig(1920, 1080, 1920, 1080, 1, 5, 1, 1, 1, 0)

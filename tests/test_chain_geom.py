@@ -1,0 +1,167 @@
+"""tests/chain_geom.py against values computed by hand for the shapes of tests/test_gpu_chain.py
+(no GPU).  The hand values assume kBatch = 12 and 256 x 4 pieces per copy workgroup; the first
+test says so, so that a change of those constants points here before it fails a sum below."""
+import pytest
+
+import chain_geom as cg
+from chain_geom import COPY, NONE, PADCOPY, STREAM, TILE, IN_PLACE, UA
+
+
+def test_constants_parsed_from_the_kernel_sources():
+    assert (cg.K_BATCH, cg.COPY_THREADS, cg.COPY_VECS) == (12, 256, 4)
+    assert (cg.SCALE_TILE_W, cg.SCALE_LOAD_ROWS, cg.SCALE_ALIAS_WORDS) == (64, 7, 36)
+
+
+@pytest.mark.parametrize("w,h,c,rst,n,want", [
+    # 250x150 4:2:0: 16 x 10 MCUs of 6 blocks = 960 blocks = 15 chunks
+    (250, 150, "420", False, 3, (16, 10, 1, 960, 15, 45)),
+    # 4:2:2: 8 blocks per MCU = 1280 blocks = 20 chunks
+    (250, 150, "422", False, 3, (16, 10, 1, 1280, 20, 60)),
+    # 4:4:4: MCUs 8 wide, 32 x 10 of 6 blocks = 1920 blocks = 30 chunks
+    (250, 150, "444", False, 3, (32, 10, 1, 1920, 30, 90)),
+    # RST 350x40 4:4:4: 44 MCUs per row = 264 blocks = 5 chunks, 3 rows
+    (350, 40, "444", True, 3, (44, 3, 3, 264, 5, 45)),
+    # 224x128 4:2:0: 14 x 8 MCUs = 672 blocks = 10.5 -> 11 chunks
+    (224, 128, "420", False, 3, (14, 8, 1, 672, 11, 33)),
+    (224, 128, "420", True, 3, (14, 8, 8, 84, 2, 48)),
+    # one MCU row: RST has nothing to restart
+    (72, 16, "420", True, 2, (5, 1, 1, 30, 1, 2)),
+    (72, 40, "420", False, 3, (5, 3, 1, 90, 2, 6)),
+])
+def test_enc_geom(w, h, c, rst, n, want):
+    assert tuple(cg.enc_geom(w, h, c, rst, n)) == want
+
+
+@pytest.mark.parametrize("w,h,c,rst,n,want", [
+    (250, 150, "420", False, 3, [(0, 0, 0), (0, 0, 12), (1, 0, 9), (2, 0, 6)]),
+    (250, 150, "422", False, 3, [(0, 0, 0), (0, 0, 12), (1, 0, 4), (1, 0, 16), (2, 0, 8)]),
+    (250, 150, "444", False, 3, [(0, 0, 0), (0, 0, 12), (0, 0, 24), (1, 0, 6), (1, 0, 18), (2, 0, 0),
+                                 (2, 0, 12), (2, 0, 24)]),
+    # 15 tasks per frame: task 12 = row 2 chunk 2, task 24 = frame 1 task 9 = row 1 chunk 4,
+    # task 36 = frame 2 task 6 = row 1 chunk 1
+    (350, 40, "444", True, 3, [(0, 0, 0), (0, 2, 2), (1, 1, 4), (2, 1, 1)]),
+    (224, 128, "420", False, 3, [(0, 0, 0), (1, 0, 1), (2, 0, 2)]),
+    (256, 128, "420", False, 3, [(0, 0, 0), (1, 0, 0), (2, 0, 0)]),   # 12 chunks: every unit a whole frame
+    (200, 100, "420", False, 3, [(0, 0, 0), (1, 0, 3), (2, 0, 6)]),   # 13 x 7 x 6 = 546 blocks = 9 chunks
+])
+def test_unit_starts(w, h, c, rst, n, want):
+    assert cg.unit_starts(w, h, c, rst, n) == want
+    assert cg.mid_segment_units(w, h, c, rst, n) == [u for u in want if u[2]]
+
+
+@pytest.mark.parametrize("w,h,c,b,want", [
+    (250, 150, "420", 0, (0, 0, 0, 250, 150)), (250, 150, "420", 3, (0, 8, 8, 250, 150)),
+    (250, 150, "420", 4, (1, 0, 0, 125, 75)), (250, 150, "420", 5, (2, 0, 0, 125, 75)),
+    # block 765: Y3 of MCU 127 = the last MCU (15) of MCU row 7: x0 = 240 + 8, y0 = 112 + 8
+    (250, 150, "420", 765, (0, 248, 120, 250, 150)), (250, 150, "420", 766, (1, 120, 56, 125, 75)),
+    # 4:2:2: Cb above Cb, 16 chroma rows per MCU; block 8 * 17 + 5 = MCU 17 = (1, 1), the lower Cb
+    (250, 150, "422", 141, (1, 8, 24, 125, 150)),
+    # 4:4:4: MCUs 8 wide; block 6 * 33 + 1 = MCU 33 = (1, 1), the lower Y
+    (250, 150, "444", 199, (0, 8, 24, 250, 150)), (250, 150, "444", 203, (2, 8, 24, 250, 150)),
+])
+def test_block_pos(w, h, c, b, want):
+    assert cg.block_pos(w, h, c, b) == want
+
+
+def test_carry_preds():
+    """250 wide: 16 (32) MCUs a row, units start at the first MCU of a row and need the DCs of
+    the last, partial MCU before it (x0 = 248 luma, 120 chroma: past pw - 8).  234 wide: 15 MCUs,
+    chunk 12 starts at MCU 128 = row 8, MCU 8: its predecessors are interior."""
+    for c in ("420", "422", "444"):
+        assert not any(any(p[3].values()) for p in cg.carry_preds(250, 150, c, False, 3))
+    assert cg.carry_preds(234, 150, "420", False, 3) == [(0, 0, 12, {0: True, 1: True, 2: True}),
+                                                         (1, 0, 9, {0: True, 1: True, 2: True}),
+                                                         (2, 0, 6, {0: True, 1: True, 2: True})]
+    assert [(p[2], all(p[3].values())) for p in cg.carry_preds(234, 150, "444", False, 3)] == [
+        (12, True), (24, True), (7, True), (19, True), (2, True), (14, False), (26, True)]
+    assert all(all(p[3].values()) for p in cg.carry_preds(350, 40, "444", True, 3))
+    assert all(all(p[3].values()) for p in cg.carry_preds(224, 128, "420", False, 3))
+
+
+@pytest.mark.parametrize("nbytes,want", [
+    (64 * 48, (1, 1)),         # 192 pieces: the largest pad-only plane of tests/test_gpu_pad.py
+    (101 * 57, (1, 2)),        # 359 pieces: the largest rectangle of tests/test_gpu_crop.py
+    (250 * 140, (3, 4)),       # 2187 pieces
+    (125 * 70, (1, 3)),        # 546 pieces: slots 0 to 2
+    (320 * 180, (4, 4)),       # 3600 pieces
+    (251 * 141, (3, 4)),       # 2211 pieces
+    (251 * 151, (3, 4)),       # 2368 pieces
+    (256 * 144, (3, 4)),       # 2304 pieces
+    (16384, (1, 4)), (16384 + 16, (2, 4)), (15, (1, 1)), (4096, (1, 1)), (4096 + 16, (1, 2)),
+])
+def test_copy_span(nbytes, want):
+    assert cg.copy_span(nbytes) == want
+
+
+@pytest.mark.parametrize("args,want", [
+    # crop in place from 300-byte rows: UA; MJG_UNALIGNED_FETCH=0: the plain kernel
+    ((300, 200, "420", (2, 6, 250, 150), "420", None, None, None), (IN_PLACE | UA, (NONE, NONE), False)),
+    ((300, 200, "444", (3, 5, 250, 150), "444", None, None, None), (IN_PLACE | UA, (NONE, NONE), False)),
+    # 256x160 4:2:0: offsets 16 * 256 + 16, 40960 + 8 * 128 + 8, + 10240; strides 256, 128; 61440 a frame
+    ((256, 160, "420", (16, 16, 224, 128), "420", None, None, None), (IN_PLACE, (NONE, NONE), False)),
+    ((256, 160, "420", (0, 16, 256, 128), "420", None, None, None), (IN_PLACE, (NONE, NONE), False)),
+    ((256, 160, "420", (16, 16, 200, 100), "420", None, None, None), (IN_PLACE, (NONE, NONE), False)),
+    ((256, 160, "420", (8, 16, 224, 128), "420", None, None, None), (IN_PLACE | UA, (NONE, NONE), False)),  # chroma x = 4
+    ((256, 160, "420", None, "420", None, None, None), (IN_PLACE, (NONE, NONE), False)),
+    ((130, 66, "420", (0, 0, 130, 66), "420", None, None, None), (IN_PLACE, (NONE, NONE), False)),  # no crop: never UA
+    # pad only, from whole frames and from a crop
+    ((200, 84, "420", None, "420", None, None, (26, 28, 250, 140)), (0, (PADCOPY, PADCOPY), False)),
+    ((300, 200, "420", (2, 6, 200, 84), "420", None, None, (26, 28, 250, 140)), (0, (PADCOPY, PADCOPY), False)),
+    ((200, 84, "420", None, "420", None, None, (0, 0, 200, 84)), (IN_PLACE, (NONE, NONE), False)),  # the trivial pad
+    # -pix_fmt under a crop: luma by the rectangle copy
+    ((300, 200, "444", (3, 5, 251, 151), "420", None, None, None), (0, (COPY, TILE), True)),
+    ((300, 200, "444", None, "422", None, None, None), (0, (COPY, TILE), False)),
+    # the shapes of tests/test_gpu_scale_stream.py and tests/test_gpu_pad.py, as they run there
+    ((256, 160, "420", None, "420", 32, 20, (6, 10, 48, 36)), (0, (STREAM, TILE), False)),
+    ((1100, 700, "420", None, "420", 200, 100, (28, 22, 256, 144)), (0, (STREAM, STREAM), False)),  # chroma 5.5:1
+    ((384, 240, "444", None, "420", 128, 80, None), (0, (TILE, STREAM), False)),
+    ((320, 200, "420", (30, 20, 262, 151), "420", 49, 28, None), (0, (TILE, TILE), False)),
+    ((640, 400, "420", (30, 20, 523, 301), "420", 97, 55, None), (0, (STREAM, TILE), False)),
+    ((1000, 600, "420", None, "420", 500, 300, (6, 10, 512, 320)), (0, (TILE, TILE), False)),
+])
+def test_predict_paths(args, want):
+    assert cg.predict_paths(*args) == want
+
+
+def test_predict_paths_switches():
+    a = (300, 200, "420", (2, 6, 250, 150), "420", None, None, None)
+    assert cg.predict_paths(*a, unaligned_fetch=False) == (IN_PLACE, (NONE, NONE), False)
+    b = (300, 200, "444", (3, 5, 251, 151), "420", None, None, None)
+    assert cg.predict_paths(*b, plane_copy=False) == (0, (TILE, TILE), False)
+
+
+def test_tile_lds_of_a_shape_the_suite_names():
+    """tests/test_gpu_scale_stream.py: 262x151 -> 49x28 is one tile of 62,464 B."""
+    assert cg.tile_lds(262, 151, 49, 28) == 62464
+    assert cg.tile_lds(256, 160, 32, 20) > 64 * 1024
+
+
+def test_sweep_draw_and_its_floors():
+    """The sweep of tests/test_gpu_chain.py, counted without a GPU: 120 configurations that keep
+    the rules (no up-sampling, the crop inside the frame at the source's sub-sampling, a padded
+    picture at the encoded format's), and per part of 30 exactly the feature counts the GPU tests
+    use as floors."""
+    cfgs = cg.sweep_configs(cg.SWEEP_SEED, 120)
+    assert len(cfgs) == 120 and cfgs == cg.sweep_configs(cg.SWEEP_SEED, 120)
+    for c in cfgs:
+        assert 64 <= c.w <= 420 and 48 <= c.h <= 260 and c.dst in cg.DOWN[c.src]
+        iw, ih = c.w, c.h
+        if c.rect:
+            x, y, iw, ih = c.rect
+            shs, svs = cg.CHROMA_SHIFTS[c.src]
+            assert 0 <= x <= c.w - iw and 0 <= y <= c.h - ih and x % (1 << shs) == 0 and y % (1 << svs) == 0
+        if c.dw:
+            assert 2 * c.dw <= iw + 1 and 6 * c.dw >= iw - 3 or c.dw == 8
+            assert 2 * c.dh <= ih + 1 and 6 * c.dh >= ih - 3 or c.dh == 8
+        if c.pad:
+            hs, vs = cg.CHROMA_SHIFTS[c.dst]
+            pw, ph = c.dw or iw, c.dh or ih
+            assert not ((c.pad[0] | c.pad[2] | pw) & ((1 << hs) - 1) or (c.pad[1] | c.pad[3] | ph) & ((1 << vs) - 1))
+            assert c.pad[0] + pw <= c.pad[2] and c.pad[1] + ph <= c.pad[3] and c.pad[2:] != (pw, ph)
+        assert c.nframes in (1, 2) and (c.nframes == 2 or c.submit in ("host", "dev_odd"))
+    parts = [cg.predicted_counts(cfgs[i * 30:(i + 1) * 30]) for i in range(4)]
+    assert parts == cg.SWEEP_FLOORS
+    assert all(v >= 1 for p in parts for v in p.values())
+    total = {k: sum(p[k] for p in parts) for k in cg.FEATURES}
+    assert total == {"crop_in_place_ua": 14, "crop_in_place_aligned": 9, "rect_copy": 9, "pad_copy": 13,
+                     "pad_with_scale": 30, "stream": 7, "host": 31, "dev_odd": 39, "segments": 28, "merged": 22}
