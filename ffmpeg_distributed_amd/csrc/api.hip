@@ -10,6 +10,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "mjgpu.h"
@@ -21,7 +23,6 @@
 using namespace mjg;
 
 namespace {
-
 
 thread_local std::string g_err = "no error";
 
@@ -149,12 +150,41 @@ int dmalloc(T **p, size_t count) {
   return MJG_OK;
 }
 
+// ceil(2^32 / d) for the kernels' divisions by multiply-high (div_magic), 0 when d is 1; and
+// ceil(2^40 / d) for k_encode's task index (EncGeom)
+uint32_t magic32(uint32_t d) { return d > 1 ? (uint32_t)((((uint64_t)1 << 32) + d - 1) / d) : 0u; }
+unsigned long long magic40(unsigned long long d) { return (((unsigned long long)1 << 40) + d - 1) / d; }
+
+// mpegvideo_enc.c encode_picture FMT_MJPEG matrix + ff_convert_matrix (qscale -> 8); qmat may be null
+void quant_matrix(int qscale, uint8_t mprime[64], int32_t *qmat) {
+  for (int i = 0; i < 64; i++) {
+    const int v = std::min(255, i == 0 ? 8 : ((kMpeg1Intra[i] * qscale) >> 3));
+    mprime[i] = (uint8_t)v;
+    if (qmat) qmat[i] = (int32_t)((2ull << 21) / (uint64_t)(16 * v));
+  }
+}
+
+// all of a launch's frames in one buffer: one segment at p
+SegList one_seg(const uint8_t *p) {
+  SegList sl;
+  for (int k = 0; k < kMaxSegs; k++) sl.p[k] = p, sl.f0[k] = k ? INT_MAX : 0;
+  return sl;
+}
+
+// an environment switch, read at open
+int env_int(const char *name, int unset) {
+  const char *e = getenv(name);
+  return e ? atoi(e) : unset;
+}
+
+bool is_tail_kernel(int k) { return k == MJG_K_SCAN_BITS || k == MJG_K_COUNT_FF || k == MJG_K_SCAN_FF || k == MJG_K_WRITE; }
+
 struct PlaneScale {
   SwsFilter hf, vf;
   int32_t *hcp = nullptr, *hp = nullptr, *vcp = nullptr, *vps = nullptr, *hsum = nullptr;
   int32_t *mfb = nullptr;  // k_scale's matrix-core h-pass: the B fragments (ScaleGeom::mf_*)
   bool d4 = false;  // h coefficients in the v_dot4 hi/lo byte layout (k_scale D4)
-  ScaleGeom g{};
+  ScaleGeom g{};    // the plane's sizes and strides (plan_geometry) and its filters' fields (plan_plane_scale)
   size_t lds = 0;
   dim3 grid;
   int th = 32;  // k_scale tile height (64: the 2:1 filters, scale.hip)
@@ -163,6 +193,26 @@ struct PlaneScale {
   bool hcl = false;     // ... with the strip's h coefficients staged in LDS
   StreamGeom sq{};
 };
+
+// One launch of the sws stage's plan, built at open (build_plan): per plane (0 luma, 1 chroma: U
+// and V share it) under a pad the border (k_pad_plane), then the picture (k_scale, k_scale_stream
+// or k_plane_copy; a padded plane that keeps its size is k_pad_plane<.., COPY> alone).  `launch`
+// (null: no such pass) is the launcher of the kernel instantiation the plane's filters, range and
+// geometry select; g holds every ScaleGeom field that no submit changes (submit_impl adds nf, the
+// U+V pairing and V's offsets).
+struct Pass;
+using PassFn = void (*)(const Pass &p, const ScaleGeom &g, const SegList &in, uint8_t *dst, int nz, hipStream_t st);
+struct Pass {
+  PassFn launch = nullptr;
+  int block = 0;    // threads per workgroup; the grid is g.gxy workgroups per (plane, frame)
+  size_t lds = 0;   // dynamic LDS bytes
+  ScaleGeom g{};
+  PadGeom pad{};    // k_pad_plane
+  const PlaneScale *ps = nullptr;  // the filters' device tables and StreamGeom
+};
+
+struct Slot;
+using EncodeFn = void (*)(const mjg_ctx *c, Slot &S, const SegList &enc_in, int wgs, int ntasks);
 
 // Per-submit state.  A context has kSlots slots so further mjg_submits can be queued before
 // the first is synced; everything a submit's results and its overflow re-write need lives
@@ -245,7 +295,6 @@ struct mjg_ctx {
   // picture, cfg.dst_w x dst_h) at (pad_x, pad_y); has_pad is false for the trivial rectangle
   bool has_pad = false;
   PadGeom pad[2] = {};          // 0 luma, 1 chroma: the canvas plane, the picture's place, the border byte
-  long long pad_doff[2] = {0, 0};  // the picture's first byte in its canvas plane (k_scale's d_off adds it)
   bool enc_ua = false;          // k_encode<.., UA>: a crop read in place whose geometry can fail
                                 // fetch_rows' alignment test (MJG_UNALIGNED_FETCH=0: never)
   std::vector<uint8_t> hdr;
@@ -258,6 +307,8 @@ struct mjg_ctx {
   bool optimal = false;        // -huffman optimal
   size_t dht_pos = 0, dht_end = 0;
   PlaneScale ps[2];  // 0 luma, 1 chroma (U and V share)
+  Pass pass[2][2];   // ... and their launches
+  EncodeFn enc_count = nullptr, enc_emit = nullptr;  // k_encode<.., kCount / kEmitDefault, ..> of this context
   size_t slot_B = 0, slot_NC = 0, slot_NS = 0;  // slot sizes: frames, chunks and segments per frame
 
   Slot slot[kSlots];
@@ -319,9 +370,6 @@ void free_ctx(mjg_ctx *c) {
   delete c;
 }
 
-// chroma: the plane's subsampling shifts in the source format (s_hsub, s_vsub) and in the
-// encoded one (d_hsub, d_vsub) select the siting get_local_pos(shift, -513) of each side
-// (swscale's src / dst pixel formats; with the default siting every one comes to 128)
 // k_scale_stream's chunk rows, ring, window stride and LDS bytes (scale.hip) for a plane whose
 // widest strip window is max_nw dwords: the most rows per chunk that fit 64 KB (two window
 // halves and a ring of npv + R pairs), with the strip's h coefficients and the band's v filter
@@ -340,7 +388,7 @@ bool plan_scale_stream(int max_nw, int ht, int npv, StreamGeom *q, bool *hcl, si
       q->rp = rp;
       q->rs = max_nw;
       q->npc = npc;
-      q->npc_magic = npc > 1 ? (uint32_t)((((uint64_t)1 << 32) + (uint32_t)npc - 1) / (uint32_t)npc) : 0u;
+      q->npc_magic = magic32((uint32_t)npc);
       q->vcl = stage & 1;
       *hcl = (stage & 2) != 0;
       *lds = need;
@@ -349,16 +397,30 @@ bool plan_scale_stream(int max_nw, int ht, int npv, StreamGeom *q, bool *hcl, si
   return false;
 }
 
-int setup_plane_scale(mjg_ctx *c, PlaneScale &p, int sw, int sh, int dw, int dh, int chroma,
-                      int s_hsub, int s_vsub, int d_hsub, int d_vsub, bool bitexact, bool force_stream) {
-  const int s_hpos = chroma ? sws_local_pos(s_hsub, -513) : sws_local_pos(0, 0);
-  const int s_vpos = chroma ? sws_local_pos(s_vsub, -513) : sws_local_pos(0, 0);
-  const int d_hpos = chroma ? sws_local_pos(d_hsub, -513) : sws_local_pos(0, 0);
-  const int d_vpos = chroma ? sws_local_pos(d_vsub, -513) : sws_local_pos(0, 0);
-  if (!make_sws_filter(sw, dw, 1 << 14, 4, bitexact, s_hpos, d_hpos, &p.hf) ||
-      !make_sws_filter(sh, dh, 1 << 12, 2, bitexact, s_vpos, d_vpos, &p.vf))
-    return set_err(MJG_E_INVALID, "scale %dx%d -> %dx%d needs swscale's cascade (unsupported)", sw,
-                   sh, dw, dh);
+// A context's rectangles, resolved by check_config
+struct Layout {
+  int cx, cy, crw, crh;        // the crop rectangle in the source frame: the sws stage's / k_encode's input
+  int px, py, pw, ph;          // the picture's place in the canvas and the canvas size (no pad: the picture)
+  bool has_pad;                // false for the trivial rectangle
+  int s_hsh, s_vsh, hsh, vsh;  // chroma shifts of the source format and of the encoded one
+};
+
+// A plane's filter tables as the kernels read them (plan_plane_scale), before their upload
+struct ScaleTabs {
+  std::vector<int32_t> hcp, vcp, vps, hsum, mfb;  // mfb empty: no matrix-core pass
+};
+
+// The host step of a plane's scale setup, for the sizes in p.g: the two SwsFilters, the
+// coefficient / position tables and the tile, stream and matrix-core decisions (p.g's filter
+// fields, p.lds, p.grid).  chroma: the plane's subsampling shifts in the source format and in the
+// encoded one select the siting get_local_pos(shift, -513) of each side (swscale's src / dst
+// pixel formats; with the default siting every one comes to 128)
+int plan_plane_scale(PlaneScale &p, ScaleTabs &t, const Layout &lay, bool chroma, bool bitexact, bool force_stream) {
+  const int sw = p.g.sw, sh = p.g.sh, dw = p.g.dw, dh = p.g.dh;
+  auto pos = [&](int shift) { return chroma ? sws_local_pos(shift, -513) : sws_local_pos(0, 0); };
+  if (!make_sws_filter(sw, dw, 1 << 14, 4, bitexact, pos(lay.s_hsh), pos(lay.hsh), &p.hf) ||
+      !make_sws_filter(sh, dh, 1 << 12, 2, bitexact, pos(lay.s_vsh), pos(lay.vsh), &p.vf))
+    return set_err(MJG_E_INVALID, "scale %dx%d -> %dx%d needs swscale's cascade (unsupported)", sw, sh, dw, dh);
   for (int i = 1; i < dw; i++)
     if (p.hf.pos[i] < p.hf.pos[i - 1]) return set_err(MJG_E_INVALID, "non-monotone hscale");
   for (int i = 1; i < dh; i++)
@@ -375,10 +437,13 @@ int setup_plane_scale(mjg_ctx *c, PlaneScale &p, int sw, int sh, int dw, int dh,
   // h: coefficient pairs per output column; v: pairs starting at the even row <= pos[y],
   // shifted by its parity and zero-padded to npv = vt/2 + 1 pairs
   const int npv = vt / 2 + 1;
-  std::vector<int32_t> hcp((size_t)dw * (ht / 2)), vcp((size_t)dh * npv, 0), vps(dh);
+  std::vector<int32_t> &hcp = t.hcp, &vcp = t.vcp, &vps = t.vps, &hsum = t.hsum;
+  hcp.assign((size_t)dw * (ht / 2), 0);
+  vcp.assign((size_t)dh * npv, 0);
+  vps.assign(dh, 0);
+  hsum.assign(dw, 0);
   // D4 layout when every coefficient splits as 128 ch + cl, ch int8, cl in [-64, 64): per 4
   // taps one word of ch bytes and one of cl bytes (else the int16 pair layout)
-  std::vector<int32_t> hsum(dw, 0);
   p.d4 = true;
   for (size_t i = 0; i < p.hf.coeff.size(); i++)
     if (p.hf.coeff[i] < -128 * 128 - 64 || p.hf.coeff[i] >= 127 * 128 + 64) p.d4 = false;
@@ -448,16 +513,6 @@ int setup_plane_scale(mjg_ctx *c, PlaneScale &p, int sw, int sh, int dw, int dh,
       return set_err(MJG_E_INVALID, "scale %dx%d -> %dx%d: no streaming plan fits LDS", sw, sh, dw, dh);
     p.grid = dim3((dw + kScaleTileW - 1) / kScaleTileW, (dh + kStreamBand - 1) / kStreamBand, 1);
   }
-  int rc;
-  if ((rc = dmalloc(&p.hcp, hcp.size())) || (rc = dmalloc(&p.hp, (size_t)dw)) ||
-      (rc = dmalloc(&p.vcp, vcp.size())) || (rc = dmalloc(&p.vps, (size_t)dh)) ||
-      (rc = dmalloc(&p.hsum, (size_t)dw)))
-    return rc;
-  HIP_TRY(hipMemcpy(p.hsum, hsum.data(), (size_t)dw * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(p.hcp, hcp.data(), hcp.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(p.hp, p.hf.pos.data(), (size_t)dw * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(p.vcp, vcp.data(), vcp.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(p.vps, vps.data(), (size_t)dh * 4, hipMemcpyHostToDevice));
   // The matrix-core h-pass (scale.hip, scale_hpass_mf) for the interior tile columns when they
   // all share one filter at a 2-byte step (exact 2:1): B[k][n] = the hi (lo) byte of tap
   // k - 2n - d of that filter (0 outside the 8 taps), k the byte of a 64-byte window that starts
@@ -475,7 +530,8 @@ int setup_plane_scale(mjg_ctx *c, PlaneScale &p, int sw, int sh, int dw, int dh,
     }
     if (ok) {
       const int d = p.hf.pos[xa] & 3;
-      std::vector<int32_t> mfb(kMvFragOff + 3 * 64 * 4, 0);
+      std::vector<int32_t> &mfb = t.mfb;
+      mfb.assign(kMvFragOff + 3 * 64 * 4, 0);
       for (int l = 0; l < 64; l++)
         for (int j = 0; j < 16; j++) {
           const int k = 16 * (l >> 4) + j, n = l & 15, t = k - 2 * n - d;
@@ -519,14 +575,23 @@ int setup_plane_scale(mjg_ctx *c, PlaneScale &p, int sw, int sh, int dw, int dh,
         g.mv_by1 = gyt - 1;
         g.mv_k = 128 * fsum + (64 << 12);
       }
-      if ((rc = dmalloc(&p.mfb, mfb.size()))) return rc;
-      HIP_TRY(hipMemcpy(p.mfb, mfb.data(), mfb.size() * 4, hipMemcpyHostToDevice));
       g.mf_bx0 = 1;
       g.mf_bx1 = gxt - 1;
       g.mf_hs = hsum[xa];
     }
   }
-  (void)c;
+  return MJG_OK;
+}
+
+// ... and the upload step
+int upload_plane_scale(PlaneScale &p, const ScaleTabs &t) {
+  const std::pair<int32_t **, const std::vector<int32_t> *> up[] = {
+      {&p.hsum, &t.hsum}, {&p.hcp, &t.hcp}, {&p.hp, &p.hf.pos}, {&p.vcp, &t.vcp}, {&p.vps, &t.vps}, {&p.mfb, &t.mfb}};
+  for (const auto &u : up) {
+    if (const int rc = dmalloc(u.first, u.second->size())) return rc;
+    if (!u.second->empty())
+      HIP_TRY(hipMemcpy(*u.first, u.second->data(), u.second->size() * 4, hipMemcpyHostToDevice));
+  }
   return MJG_OK;
 }
 
@@ -578,19 +643,15 @@ int alloc_slot(mjg_ctx *c, Slot &S) {
   return MJG_OK;
 }
 
+// open, step 1: the config, the rectangle and the pad (no device, no environment).
 // crop: x, y, w, h in luma samples of the source frame, or nullptr for the whole frame
 // pad: x, y, w, h in luma samples of the encoded frame (the picture's place and the canvas size),
 // or nullptr for no pad
-int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, const int *pad, mjg_ctx *c) {
-  c->device = device;
-  c->cfg = *cfg;
-  const mjg_config &k = *cfg;
-  if (k.src_w < 1 || k.src_h < 1 || k.dst_w < 1 || k.dst_h < 1 || k.src_w > 16384 ||
-      k.src_h > 16384 || k.dst_w > 16384 || k.dst_h > 16384)
+int check_config(const mjg_config &k, int src_cf, const int *crop, const int *pad, Layout *lay) {
+  if (std::min({k.src_w, k.src_h, k.dst_w, k.dst_h}) < 1 || std::max({k.src_w, k.src_h, k.dst_w, k.dst_h}) > 16384)
     return set_err(MJG_E_INVALID, "bad frame size %dx%d -> %dx%d", k.src_w, k.src_h, k.dst_w, k.dst_h);
   if (k.qscale < 1 || k.qscale > 31) return set_err(MJG_E_INVALID, "qscale %d not in 1..31", k.qscale);
-  if (k.max_batch < 1 || k.max_batch > 65535)
-    return set_err(MJG_E_INVALID, "max_batch %d not in 1..65535", k.max_batch);
+  if (k.max_batch < 1 || k.max_batch > 65535) return set_err(MJG_E_INVALID, "max_batch %d not in 1..65535", k.max_batch);
   if (k.sar_num < 0 || k.sar_den < 0 || k.sar_num > 65535 || k.sar_den > 65535)
     return set_err(MJG_E_INVALID, "bad SAR %d:%d", k.sar_num, k.sar_den);
   if (k.chroma_format < MJG_CHROMA_420 || k.chroma_format > MJG_CHROMA_444)
@@ -604,8 +665,7 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, con
   if (crw < 1 || crh < 1)
     return set_err(MJG_E_INVALID, "crop %dx%d at (%d,%d): the size is not positive", crw, crh, cx, cy);
   if (cx < 0 || cy < 0 || cx > k.src_w - crw || cy > k.src_h - crh)
-    return set_err(MJG_E_INVALID, "crop %dx%d at (%d,%d) is outside the %dx%d frame", crw, crh, cx, cy, k.src_w,
-                   k.src_h);
+    return set_err(MJG_E_INVALID, "crop %dx%d at (%d,%d) is outside the %dx%d frame", crw, crh, cx, cy, k.src_w, k.src_h);
   if ((cx & ((1 << s_hsh) - 1)) || (cy & ((1 << s_vsh) - 1)))
     return set_err(MJG_E_INVALID, "crop %dx%d at (%d,%d): the position is not a multiple of the source's chroma "
                    "sub-sampling (%dx%d)", crw, crh, cx, cy, 1 << s_hsh, 1 << s_vsh);
@@ -620,8 +680,8 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, con
   if (px < 0 || py < 0 || px > pw - k.dst_w || py > ph - k.dst_h)
     return set_err(MJG_E_INVALID, "pad %dx%d with the picture at (%d,%d): the %dx%d picture is outside the canvas",
                    pw, ph, px, py, k.dst_w, k.dst_h);
-  c->has_pad = px != 0 || py != 0 || pw != k.dst_w || ph != k.dst_h;
-  if (c->has_pad) {
+  const bool has_pad = px != 0 || py != 0 || pw != k.dst_w || ph != k.dst_h;
+  if (has_pad) {
     const int mh = (1 << e_hsh) - 1, mv = (1 << e_vsh) - 1;
     if ((px & mh) || (pw & mh) || (py & mv) || (ph & mv))
       return set_err(MJG_E_INVALID, "pad %dx%d with the picture at (%d,%d): not multiples of the encoded format's "
@@ -637,22 +697,22 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, con
     return set_err(MJG_E_INVALID, "unknown flags 0x%x", k.flags & ~kKnownFlags);
   if ((k.flags & MJG_F_RST) && (k.flags & MJG_F_HUFFMAN_OPTIMAL))
     return set_err(MJG_E_INVALID, "RST (slice threading) forces -huffman default");
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return set_err(MJG_E_INVALID, "device %d of %d", device, ndev);
-  HIP_TRY(hipSetDevice(device));
-  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  for (hipStream_t &st : c->more) HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  int least = 0, greatest = 0;  // the tail's workgroups first (see kSlots)
-  HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-  HIP_TRY(hipStreamCreateWithPriority(&c->tail, hipStreamNonBlocking, greatest));
+  *lay = Layout{cx, cy, crw, crh, px, py, pw, ph, has_pad, s_hsh, s_vsh, e_hsh, e_vsh};
+  return MJG_OK;
+}
 
+// open, step 2: the geometry (no device, no environment): EncGeom, PadGeom, the source offsets,
+// the frame byte counts, scale / has_pad / rst, enc_ua (unaligned_fetch: MJG_UNALIGNED_FETCH is
+// not 0) and the sizes and strides of the sws stage's planes.
+int plan_geometry(const mjg_config &k, int src_cf, const Layout &lay, bool unaligned_fetch, mjg_ctx *c) {
+  const int cx = lay.cx, cy = lay.cy, crw = lay.crw, crh = lay.crh, px = lay.px, py = lay.py;
+  const int s_hsh = lay.s_hsh, s_vsh = lay.s_vsh, hsh = lay.hsh, vsh = lay.vsh;
+  c->has_pad = lay.has_pad;
   // the sws stage: a resize, or a -pix_fmt conversion (source format != encoded format; in
   // FFmpeg one swscale context does both, and tv->pc in the same pass)
   const int cf = k.chroma_format;
   // (a pad always runs it: k_encode then reads the canvas in d_scaled as any other sws output)
   c->scale = (crw != k.dst_w || crh != k.dst_h || src_cf != cf || c->has_pad);
-  const int hsh = cf == MJG_CHROMA_444 ? 0 : 1, vsh = cf == MJG_CHROMA_420 ? 1 : 0;
   const int scw = (k.src_w + s_hsh) >> s_hsh, sch = (k.src_h + s_vsh) >> s_vsh;
   // the rectangle's chroma planes: at (cx >> hs, cy >> vs), the chroma size of a crw x crh frame
   // (inside the source's: cx, cy are multiples of the sub-sampling)
@@ -663,17 +723,16 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, con
   c->src_off[2] = c->src_off[1] + c->src_cplane;
   // the encoded frame: the canvas under a pad, else the picture (the sws stage's output, or the
   // source rectangle itself); pcw x pch: the picture's chroma planes
-  const int w = pw, h = ph, cw = (w + hsh) >> hsh, ch = (h + vsh) >> vsh;
+  const int w = lay.pw, h = lay.ph, cw = (w + hsh) >> hsh, ch = (h + vsh) >> vsh;
   const int pcw = (k.dst_w + hsh) >> hsh, pch = (k.dst_h + vsh) >> vsh;
   for (int p = 0; p < 2; p++) {
     PadGeom &q = c->pad[p];
     q.cw = p ? cw : w;
     q.ch = p ? ch : h;
-    q.cw_magic = q.cw > 1 ? (uint32_t)((((uint64_t)1 << 32) + (uint32_t)q.cw - 1) / (uint32_t)q.cw) : 0u;
+    q.cw_magic = magic32((uint32_t)q.cw);
     q.px = p ? px >> hsh : px;
     q.py = p ? py >> vsh : py;
     q.fill = p ? 128 : 0;
-    c->pad_doff[p] = (long long)q.py * q.cw + q.px;
   }
   c->in_frame_bytes = (size_t)k.src_w * k.src_h + 2 * (size_t)scw * sch;
   c->enc_frame_bytes = (size_t)w * h + 2 * (size_t)cw * ch;
@@ -684,13 +743,13 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, con
   g.cw = cw;
   g.ch = ch;
   g.bpm = cf == MJG_CHROMA_422 ? 8 : 6;
-  g.bpm_magic = (uint32_t)((((uint64_t)1 << 32) + (uint64_t)g.bpm - 1) / (uint64_t)g.bpm);
+  g.bpm_magic = magic32((uint32_t)g.bpm);
   g.lmw = cf == MJG_CHROMA_444 ? 8 : 16;
   g.cmh = cf == MJG_CHROMA_420 ? 8 : 16;
   g.mbw = (w + g.lmw - 1) / g.lmw;
   const int mbh = (h + 15) / 16;
   g.nmcu = g.mbw * mbh;
-  g.mbw_magic = g.mbw > 1 ? (uint32_t)((((uint64_t)1 << 32) + (uint64_t)g.mbw - 1) / (uint64_t)g.mbw) : 0u;
+  g.mbw_magic = magic32((uint32_t)g.mbw);
   if ((uint64_t)(g.nmcu + 64) * (uint64_t)g.mbw >= ((uint64_t)1 << 32))
     return set_err(MJG_E_INVALID, "frame too large (%d MCUs)", g.nmcu);
   // RST: one segment per MCU row (mpegvideo clips the slice count to mb_height, so a
@@ -699,61 +758,56 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, con
   g.nseg = c->rst ? mbh : 1;
   g.seg_blocks = (c->rst ? g.mbw : g.nmcu) * g.bpm;
   g.nchunks = (g.seg_blocks + 63) / 64;  // chunks of 64 blocks (one wave each) per segment
-  g.nchunks_magic = (((unsigned long long)1 << 40) + (unsigned long long)g.nchunks - 1) / (unsigned long long)g.nchunks;
-  g.nseg_magic = (((unsigned long long)1 << 40) + (unsigned long long)g.nseg - 1) / (unsigned long long)g.nseg;
+  g.nchunks_magic = magic40((unsigned long long)g.nchunks);
+  g.nseg_magic = magic40((unsigned long long)g.nseg);
   // task t / nchunks by magic (exact while t * nchunks < 2^40, t < max_batch * nseg * nchunks)
   if ((unsigned long long)k.max_batch * g.nseg * g.nchunks * g.nchunks >= ((unsigned long long)1 << 40))
     return set_err(MJG_E_INVALID, "max_batch %d too large for this frame size", k.max_batch);
-  if (c->scale) {  // k_encode reads the sws stage's packed output
-    g.y_stride = w;
-    g.c_stride = cw;
-    g.u_off = (long long)w * h;
-    g.v_off = g.u_off + (long long)cw * ch;
-    g.frame_stride = (long long)c->enc_frame_bytes;
-  } else {
-    // k_encode reads the source frames in place: rows at the source planes' strides, the block
-    // offsets from the rectangle's first luma byte (submit_impl adds src_off[0] to the frame
-    // pointers), the planes w x h / cw x ch of it (fetch_rows_edge's clamps).  The whole frame:
-    // exactly the packed values above.
-    g.y_stride = k.src_w;
-    g.c_stride = scw;
-    g.u_off = c->src_off[1] - c->src_off[0];
-    g.v_off = c->src_off[2] - c->src_off[0];
-    g.frame_stride = (long long)c->in_frame_bytes;
-  }
+  // k_encode reads the sws stage's packed output, or the source frames in place: rows at the
+  // source planes' strides, the block offsets from the rectangle's first luma byte (submit_impl
+  // adds src_off[0] to the frame pointers), the planes w x h / cw x ch of it (fetch_rows_edge's
+  // clamps).  The whole frame in place: exactly the packed values.
+  g.y_stride = c->scale ? w : k.src_w;
+  g.c_stride = c->scale ? cw : scw;
+  g.u_off = c->scale ? (long long)w * h : c->src_off[1] - c->src_off[0];
+  g.v_off = c->scale ? g.u_off + (long long)cw * ch : c->src_off[2] - c->src_off[0];
+  g.frame_stride = (long long)(c->scale ? c->enc_frame_bytes : c->in_frame_bytes);
   // k_encode addresses a frame with 32-bit offsets
   if (c->enc_frame_bytes >= ((size_t)1 << 32) || (!c->scale && c->in_frame_bytes >= ((size_t)1 << 32)))
     return set_err(MJG_E_INVALID, "frame of %zu bytes", std::max(c->enc_frame_bytes, c->in_frame_bytes));
   // the fetch at any alignment: only for a crop read in place, and only when a plane offset, a
   // row stride or the frame stride is no multiple of 8 (else every interior block already
   // passes the alignment test, given an aligned frame pointer, as for uncropped frames)
-  {
-    const char *ua = getenv("MJG_UNALIGNED_FETCH");
-    const bool is_crop = cx || cy || crw != k.src_w || crh != k.src_h;
-    const long long bits = c->src_off[0] | c->src_off[1] | c->src_off[2] | g.y_stride | g.c_stride | g.frame_stride;
-    c->enc_ua = is_crop && !c->scale && (bits & 7) != 0 && !(ua && atoi(ua) == 0);
-  }
+  const bool is_crop = cx || cy || crw != k.src_w || crh != k.src_h;
+  const long long bits = c->src_off[0] | c->src_off[1] | c->src_off[2] | g.y_stride | g.c_stride | g.frame_stride;
+  c->enc_ua = is_crop && !c->scale && (bits & 7) != 0 && unaligned_fetch;
   g.range_convert = (!c->scale && !k.in_full_range) ? 1 : 0;
   g.debug_coefs = (k.flags & MJG_F_DEBUG_COEFS) ? 1 : 0;
-
-  // mpegvideo_enc.c encode_picture FMT_MJPEG matrix + ff_convert_matrix (qscale -> 8).
-  for (int i = 0; i < 64; i++) {
-    int v = i == 0 ? 8 : ((kMpeg1Intra[i] * k.qscale) >> 3);
-    v = v > 255 ? 255 : v;
-    c->mprime[i] = (uint8_t)v;
-    c->qmat[i] = (int32_t)((2ull << 21) / (uint64_t)(16 * v));
+  for (int p = 0; p < 2 && c->scale; p++) {  // the sws stage's planes: the rectangle's -> the picture's
+    ScaleGeom &sg = c->ps[p].g;
+    sg.sw = p ? ccw : crw;
+    sg.sh = p ? cch : crh;
+    sg.dw = p ? pcw : k.dst_w;
+    sg.dh = p ? pch : k.dst_h;
+    sg.s_stride = p ? scw : k.src_w;  // rows of the source plane (wider than sw under a crop)
+    sg.sw_magic = magic32((uint32_t)sg.sw);
+    sg.d_stride = c->pad[p].cw;  // the encoded plane's rows: dw, or the wider canvas under a pad
+    sg.s_fstride = (long long)c->in_frame_bytes;
+    sg.d_fstride = (long long)c->enc_frame_bytes;
+    sg.range = k.in_full_range ? 0 : (p ? 2 : 1);
   }
-  c->hdr = build_header(w, h, c->mprime, k.sar_num, k.sar_den, (k.flags & MJG_F_COM_ITU601) != 0, cf,
-                        c->rst, &c->dht_pos, &c->dht_end);
-  c->optimal = (k.flags & MJG_F_HUFFMAN_OPTIMAL) != 0;
+  return MJG_OK;
+}
 
-  // device table block: [0,256) AC luma, [256,512) AC chroma, [512,528) DC luma,
-  // [528,544) DC chroma ((len << 16) | code), [544,608) qmat column-major ([col][row]),
-  // [608,672) k_encode's screening thresholds B^2 (fp32 bits, [col][row]): a quantised AC
-  // coefficient is nonzero iff |u| >= T = ceil(5*2^18 / qmat) (dct_quantize_c intra
-  // rounding), i.e. |pass-2 sum| >= 16T - 8 (rows 0, 4: DESCALE 4, exact in fp32) or
-  // >= T*2^17 - 2^16 (other rows); the latter is widened by 2048 > the fp32 error (< 2^9).
-  uint32_t tabs[kTabWords] = {0};
+// open, step 3 (no device, no environment): the device table block for an encoded format cf
+// (bpm blocks per MCU) and the quantiser qmat.  [0,256) AC luma, [256,512) AC chroma, [512,528)
+// DC luma, [528,544) DC chroma ((len << 16) | code), [544,608) qmat column-major ([col][row]),
+// [608,672) k_encode's screening thresholds B^2 (fp32 bits, [col][row]): a quantised AC
+// coefficient is nonzero iff |u| >= T = ceil(5*2^18 / qmat) (dct_quantize_c intra
+// rounding), i.e. |pass-2 sum| >= 16T - 8 (rows 0, 4: DESCALE 4, exact in fp32) or
+// >= T*2^17 - 2^16 (other rows); the latter is widened by 2048 > the fp32 error (< 2^9).
+void build_tabs(int cf, int bpm, const int32_t qmat[64], uint32_t tabs[kTabWords]) {
+  memset(tabs, 0, kTabWords * sizeof(uint32_t));
   build_huffman(tabs, kBitsAcLum, kValAcLum);
   build_huffman(tabs + 256, kBitsAcChr, kValAcChr);
   uint32_t dc[256];
@@ -761,10 +815,10 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, con
   for (int i = 0; i < 16; i++) tabs[512 + i] = dc[i];
   build_huffman(dc, kBitsDcChr, kValDc);
   for (int i = 0; i < 16; i++) tabs[528 + i] = dc[i];
-  for (int i = 0; i < 64; i++) tabs[544 + (i & 7) * 8 + (i >> 3)] = (uint32_t)c->qmat[i];  // [col][row]
+  for (int i = 0; i < 64; i++) tabs[544 + (i & 7) * 8 + (i >> 3)] = (uint32_t)qmat[i];  // [col][row]
   for (int i = 1; i < 64; i++) {
     const int ro = i >> 3;
-    const uint32_t qm = (uint32_t)c->qmat[i];
+    const uint32_t qm = (uint32_t)qmat[i];
     const double Ti = (double)(((5u << 18) + qm - 1) / qm);  // ceil(5*2^18 / qmat)
     const double B = (ro == 0 || ro == 4) ? 16.0 * Ti - 8.5 : Ti * 131072.0 - 65536.0 - 2048.0;
     const float b2 = (float)(B * B);
@@ -788,7 +842,7 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, con
     for (int col = 2; col < 8; col++) {
       long long rmax = 65535, amax = 0;
       for (int ro = 0; ro < 8; ro++) {
-        const long long qm = c->qmat[ro * 8 + col];
+        const long long qm = qmat[ro * 8 + col];
         const long long T = ((5ll << 18) + qm - 1) / qm;
         if (ro == 0) {
           amax = std::max(0ll, 2 * T - 2);
@@ -813,43 +867,161 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, con
     static const uint8_t kPlane[3][8] = {{0, 0, 0, 0, 1, 2}, {0, 0, 0, 0, 1, 1, 2, 2}, {0, 0, 1, 1, 2, 2}};
     static const uint8_t kDx[3][8] = {{0, 1, 0, 1, 0, 0}, {0, 1, 0, 1, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};
     static const uint8_t kDy[3][8] = {{0, 0, 1, 1, 0, 0}, {0, 0, 1, 1, 0, 1, 0, 1}, {0, 1, 0, 1, 0, 1}};
-    for (int j = 0; j < g.bpm; j++) {
+    for (int j = 0; j < bpm; j++) {
       const int pl = kPlane[cf][j];
       int delta = 0;  // distance back to the previous block of plane pl (wrapping to the previous MCU)
-      for (int d = 1; d <= g.bpm && !delta; d++)
-        if (kPlane[cf][((j - d) % g.bpm + g.bpm) % g.bpm] == pl) delta = d;
+      for (int d = 1; d <= bpm && !delta; d++)
+        if (kPlane[cf][((j - d) % bpm + bpm) % bpm] == pl) delta = d;
       tabs[672 + j] = (uint32_t)pl | (pl ? 4u : 0u) | ((uint32_t)kDx[cf][j] << 3) |
                       ((uint32_t)kDy[cf][j] << 4) | ((uint32_t)delta << 8);
     }
   }
+}
 
-  const size_t NC = (size_t)g.nchunks * g.nseg, NS = (size_t)g.nseg;
+// The launchers of the plan, one instantiation per kernel instantiation; build_plan and
+// pick_encode choose among them with the context's values.
+template <int HT, int NPV, bool D4, int RANGE, int TH>
+void launch_tile(const Pass &p, const ScaleGeom &g, const SegList &in, uint8_t *dst, int nz, hipStream_t st) {
+  const PlaneScale &t = *p.ps;
+  k_scale<HT, NPV, D4, RANGE, TH><<<g.gxy * nz, p.block, p.lds, st>>>(in, dst, g, t.hcp, t.hp, t.vcp, t.vps, t.hsum, t.mfb);
+}
+template <bool D4, int RANGE, bool HCL>
+void launch_stream(const Pass &p, const ScaleGeom &g, const SegList &in, uint8_t *dst, int nz, hipStream_t st) {
+  const PlaneScale &t = *p.ps;
+  k_scale_stream<D4, RANGE, HCL><<<g.gxy * nz, p.block, p.lds, st>>>(in, dst, g, t.sq, t.hcp, t.hp, t.vcp, t.vps, t.hsum);
+}
+template <int RANGE, bool RECT>
+void launch_copy(const Pass &p, const ScaleGeom &g, const SegList &in, uint8_t *dst, int nz, hipStream_t st) {
+  k_plane_copy<RANGE, RECT><<<g.gxy * nz, p.block, 0, st>>>(in, dst, g);
+}
+template <int RANGE, bool COPY>
+void launch_pad(const Pass &p, const ScaleGeom &g, const SegList &in, uint8_t *dst, int nz, hipStream_t st) {
+  k_pad_plane<RANGE, COPY><<<g.gxy * nz, p.block, 0, st>>>(in, dst, g, p.pad);
+}
+
+// A run-time flag or range (ScaleGeom::range, 0..2) as a compile-time constant: f gets it as a
+// std::integral_constant, so one expression instantiates every cell of a kernel family
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <typename F>
+auto with_bool(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <typename F>
+auto with_range(int r, F f) { return r == 1 ? f(int_c<1>{}) : r == 2 ? f(int_c<2>{}) : f(int_c<0>{}); }
+
+// The sws stage's launches for luma and chroma (mjg_ctx::pass) from the planes' geometry and filters
+void build_plan(mjg_ctx *c) {
+  // workgroups per (plane, frame) of the copy kernels, and their magic, for a plane of `bytes`
+  auto copy_grid = [](Pass &q, size_t bytes) {
+    const size_t pieces = bytes >> 4, per = (size_t)kCopyThreads * kCopyVecs;
+    q.block = kCopyThreads;
+    q.g.gxy = (int)std::max<size_t>(1, (pieces + per - 1) / per);
+    q.g.gxy_magic = magic32((uint32_t)q.g.gxy);
+  };
+  for (int p = 0; p < 2; p++) {
+    const PlaneScale &ps = c->ps[p];
+    Pass *next = c->pass[p];
+    ScaleGeom g = ps.g;
+    const long long plane_off = p ? c->geom.u_off : 0;  // the encoded (canvas) plane in a frame
+    g.s_off = c->src_off[p];               // the (cropped) plane's first byte in a source frame
+    g.d_off = plane_off + (long long)c->pad[p].py * c->pad[p].cw + c->pad[p].px;  // the picture's first byte in it
+    // one dimension: tiles x planes x frames (scale.hip decodes it by multiply-high)
+    g.gx = (int)ps.grid.x;
+    g.gxy = (int)(ps.grid.x * ps.grid.y);
+    g.gx_magic = magic32((uint32_t)g.gx);
+    g.gxy_magic = magic32((uint32_t)g.gxy);
+    if (c->has_pad) {  // the border, and with it a plane that keeps its size (scale.hip k_pad_plane)
+      Pass &b = *next++;
+      b.pad = c->pad[p];
+      b.g = g;
+      b.g.d_off = plane_off;
+      copy_grid(b, (size_t)b.pad.cw * (size_t)b.pad.ch);
+      b.launch = launch_pad<0, false>;
+      if (ps.copy) b.launch = with_range(g.range, [](auto r) -> PassFn { return launch_pad<decltype(r)::value, true>; });
+      if (ps.copy) continue;
+    }
+    Pass &m = *next;
+    m.ps = &ps;
+    m.g = g;
+    if (ps.copy) {  // the plane keeps its size: streamed (scale.hip k_plane_copy)
+      copy_grid(m, (size_t)g.sw * (size_t)g.sh);
+      m.launch = with_range(g.range, [&](auto r) -> PassFn {
+        if (g.s_stride != g.sw) return launch_copy<decltype(r)::value, true>;  // a rectangle of wider rows (crop)
+        return launch_copy<decltype(r)::value, false>;
+      });
+      continue;
+    }
+    m.block = ps.stream ? kStreamThreads : 64 * scale_waves(ps.th);
+    m.lds = ps.lds;
+    m.launch = with_bool(ps.d4, [&](auto d4) {
+      return with_range(g.range, [&](auto r) -> PassFn {
+        constexpr bool D4 = decltype(d4)::value;
+        constexpr int R = decltype(r)::value;
+        if (ps.stream && ps.hcl) return launch_stream<D4, R, true>;  // past one LDS tile: strips x bands
+        if (ps.stream) return launch_stream<D4, R, false>;
+        if (g.htaps == 8 && g.npv == 5 && ps.th == 64) return launch_tile<8, 5, D4, R, 64>;  // 2:1 downscale (4K -> 1080p)
+        if (g.htaps == 8 && g.npv == 5) return launch_tile<8, 5, D4, R, 32>;  // ... whose windows miss the 64-row fast path
+        if (g.htaps == 4 && g.npv == 3) return launch_tile<4, 3, D4, R, 32>;  // upscale / mild downscale
+        return launch_tile<0, 0, D4, R, 32>;
+      });
+    });
+  }
+}
+
+// RC, DBG, UA: EncGeom's range_convert and debug_coefs, and the context's enc_ua (a crop read in
+// place at any alignment, fetch_rows<UA>)
+template <bool RC, int MODE, bool DBG, bool UA>
+void launch_encode(const mjg_ctx *c, Slot &S, const SegList &enc_in, int wgs, int ntasks) {
+  k_encode<RC, MODE, DBG, UA><<<wgs, 64 * kWavesPerWg, 0, S.st>>>(enc_in, c->geom, c->d_tabs, S.d_scratch, S.d_chunk_bits,
+      S.d_dbg, S.d_work, ntasks, S.d_hist, S.d_stage_bits, S.d_syms, S.d_symn);
+}
+template <int MODE>
+EncodeFn pick_encode(const mjg_ctx *c) {
+  return with_bool(c->geom.range_convert, [&](auto rc) {
+    return with_bool(c->geom.debug_coefs, [&](auto dbg) {
+      return with_bool(c->enc_ua, [](auto ua) -> EncodeFn {
+        return launch_encode<decltype(rc)::value, MODE, decltype(dbg)::value, decltype(ua)::value>;
+      });
+    });
+  });
+}
+
+// open, step 4: the device part: streams, the merge depth, the tables' upload, the sws stage's
+// filters and launch plan, the k_encode launchers and grid, slot 0
+int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
+  const mjg_config &k = c->cfg;
+  const EncGeom &g = c->geom;
+  const int device = c->device;
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return set_err(MJG_E_INVALID, "device %d of %d", device, ndev);
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  for (hipStream_t &st : c->more) HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  int least = 0, greatest = 0;  // the tail's workgroups first (see kSlots)
+  HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+  HIP_TRY(hipStreamCreateWithPriority(&c->tail, hipStreamNonBlocking, greatest));
+
+  c->slot_NC = (size_t)g.nchunks * g.nseg;
+  c->slot_NS = (size_t)g.nseg;
   // merging (kMerge): opt-in with MJG_F_MERGE (a held submit's frames are read after mjg_submit
   // returns); MJG_MERGE=1 turns it off for a process (A/B), =2..4 sets the jobs per launch
-  c->merge = 1;
-  if (k.flags & MJG_F_MERGE) {
-    c->merge = kMerge;
-    if (const char *e = getenv("MJG_MERGE")) c->merge = std::max(1, std::min(kMaxSegs, atoi(e)));
-  }
-  if (const char *e = getenv("MJG_MERGE_HOLD")) c->hold_idle = atoi(e) != 0;
+  c->merge = (k.flags & MJG_F_MERGE) ? std::max(1, std::min(kMaxSegs, env_int("MJG_MERGE", kMerge))) : 1;
+  c->hold_idle = env_int("MJG_MERGE_HOLD", 1) != 0;
   if (c->merge > 1) {  // slot buffers for merge * max_batch frames: within a share of free memory
     size_t fr = 0, tot = 0;
     HIP_TRY(hipMemGetInfo(&fr, &tot));
-    const double per_frame = 2.0 * (double)NC * kSlotWords * 4 + 2.0 * (double)c->enc_frame_bytes;
+    const double per_frame = 2.0 * (double)c->slot_NC * kSlotWords * 4 + 2.0 * (double)c->enc_frame_bytes;
     if (kSlots * (double)c->merge * (double)k.max_batch * per_frame > kMergeMemShare * (double)fr) c->merge = 1;
   }
   if ((unsigned long long)k.max_batch * c->merge * g.nseg * g.nchunks * g.nchunks >= ((unsigned long long)1 << 40))
     c->merge = 1;  // merged launches would overflow k_encode's task magic (checked for max_batch above)
-  const size_t B = (size_t)k.max_batch * (size_t)c->merge;  // frames one launch may carry
+  c->slot_B = (size_t)k.max_batch * (size_t)c->merge;  // frames one launch may carry
   int rc;
   if ((rc = dmalloc(&c->d_tabs, kTabWords)) || (rc = dmalloc(&c->d_hdr, c->hdr.size()))) return rc;
-  c->slot_B = B;
-  c->slot_NC = NC;
-  c->slot_NS = NS;
   c->timing = (k.flags & (MJG_F_TIMING | MJG_F_TIMING_DETAIL)) != 0;
   c->timing_detail = (k.flags & MJG_F_TIMING_DETAIL) != 0;
-  c->timing_tail = c->timing && !c->timing_detail && !(getenv("MJG_TIMING_NOTAIL") && atoi(getenv("MJG_TIMING_NOTAIL")));
-  HIP_TRY(hipMemcpy(c->d_tabs, tabs, sizeof tabs, hipMemcpyHostToDevice));
+  c->timing_tail = c->timing && !c->timing_detail && !env_int("MJG_TIMING_NOTAIL", 0);
+  HIP_TRY(hipMemcpy(c->d_tabs, tabs, kTabWords * sizeof(uint32_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(c->d_hdr, c->hdr.data(), c->hdr.size(), hipMemcpyHostToDevice));
 
   if (c->scale) {
@@ -857,36 +1029,25 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, con
     // the filters for the rectangle's planes: their edge taps replicate the crop's edge
     // MJG_SCALE_STREAM=1: every plane whose size changes through k_scale_stream (A/B, tests);
     // unset or auto: only the planes past one k_scale tile
-    const char *ss = getenv("MJG_SCALE_STREAM");
-    const bool force_stream = ss && atoi(ss) == 1;
-    if ((rc = setup_plane_scale(c, c->ps[0], crw, crh, k.dst_w, k.dst_h, 0, 0, 0, 0, 0, bitexact, force_stream)) ||
-        (rc = setup_plane_scale(c, c->ps[1], ccw, cch, pcw, pch, 1, s_hsh, s_vsh, hsh, vsh, bitexact, force_stream)))
-      return rc;
+    const bool force_stream = env_int("MJG_SCALE_STREAM", 0) == 1;
     // a plane that keeps its size (luma of a pure -pix_fmt conversion) is streamed by
     // k_plane_copy; MJG_PLANE_COPY=0 sends it through k_scale's identity filters (A/B, tests)
-    const char *pc = getenv("MJG_PLANE_COPY");
-    const bool plane_copy = !(pc && atoi(pc) == 0);
+    const bool plane_copy = env_int("MJG_PLANE_COPY", 1) != 0;
     for (int p = 0; p < 2; p++) {
-      ScaleGeom &sg = c->ps[p].g;
-      sg.sw = p ? ccw : crw;
-      sg.sh = p ? cch : crh;
-      sg.dw = p ? pcw : k.dst_w;
-      sg.dh = p ? pch : k.dst_h;
-      sg.s_stride = p ? scw : k.src_w;  // rows of the source plane (wider than sw under a crop)
-      sg.sw_magic = sg.sw > 1 ? (uint32_t)((((uint64_t)1 << 32) + (uint32_t)sg.sw - 1) / (uint32_t)sg.sw) : 0u;
-      sg.d_stride = c->pad[p].cw;  // the encoded plane's rows: dw, or the wider canvas under a pad
-      sg.s_fstride = (long long)c->in_frame_bytes;
-      sg.d_fstride = (long long)c->enc_frame_bytes;
-      sg.range = k.in_full_range ? 0 : (p ? 2 : 1);
-      c->ps[p].copy = plane_copy && sg.sw == sg.dw && sg.sh == sg.dh;
+      PlaneScale &ps = c->ps[p];
+      ScaleTabs t;
+      if ((rc = plan_plane_scale(ps, t, lay, p != 0, bitexact, force_stream)) || (rc = upload_plane_scale(ps, t))) return rc;
+      ps.copy = plane_copy && ps.g.sw == ps.g.dw && ps.g.sh == ps.g.dh;
     }
+    build_plan(c);
   }
+  c->enc_count = pick_encode<kCount>(c);
+  c->enc_emit = pick_encode<kEmitDefault>(c);
 
   // persistent k_encode grid: every CU filled with as many workgroups as fit
   int ncu = 0, per_cu = 0;
   HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-      &per_cu, (const void *)k_encode<true, kEmitDefault>, 64 * kWavesPerWg, 0));
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_encode<true, kEmitDefault>, 64 * kWavesPerWg, 0));
   c->enc_grid = std::max(1, ncu * std::max(1, per_cu));
   // -huffman optimal's counting pass is launched with the same grid (4 workgroups per CU: its
   // histograms are 16-bit counter pairs, profiles/r05/c1_count_occupancy_ab.txt)
@@ -895,12 +1056,29 @@ int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, con
   return alloc_slot(c, c->slot[0]);
 }
 
+int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, const int *pad, mjg_ctx *c) {
+  c->device = device;
+  c->cfg = *cfg;
+  const mjg_config &k = *cfg;
+  Layout lay;
+  int rc;
+  if ((rc = check_config(k, src_cf, crop, pad, &lay))) return rc;
+  if ((rc = plan_geometry(k, src_cf, lay, env_int("MJG_UNALIGNED_FETCH", 1) != 0, c))) return rc;
+  quant_matrix(k.qscale, c->mprime, c->qmat);
+  c->hdr = build_header(c->geom.w, c->geom.h, c->mprime, k.sar_num, k.sar_den, (k.flags & MJG_F_COM_ITU601) != 0,
+                        k.chroma_format, c->rst, &c->dht_pos, &c->dht_end);
+  c->optimal = (k.flags & MJG_F_HUFFMAN_OPTIMAL) != 0;
+  uint32_t tabs[kTabWords];
+  build_tabs(k.chroma_format, c->geom.bpm, c->qmat, tabs);
+  return open_device(c, lay, tabs);
+}
+
 // HIP events: with MJG_F_TIMING around scale, huff, encode and the whole tail (scan .. write,
 // reported as MJG_K_TAIL); with MJG_F_TIMING_DETAIL around every kernel (each event record
 // costs ~10 us of GPU idle between the short tail kernels).
 void tmark(mjg_ctx *c, Slot &S, int k, int end) {
   if (!c->timing) return;
-  const bool tail = k == MJG_K_SCAN_BITS || k == MJG_K_COUNT_FF || k == MJG_K_SCAN_FF || k == MJG_K_WRITE;
+  const bool tail = is_tail_kernel(k);
   if (tail && !c->timing_detail) return;
   (void)hipEventRecord(S.ev[k][end], tail ? c->tail : S.st);
 }
@@ -924,36 +1102,6 @@ int launch_write(mjg_ctx *c, Slot &S, int n, bool reset_status) {
   HIP_TRY(hipMemcpyAsync(S.h_status, S.d_status, 4, hipMemcpyDeviceToHost, c->tail));
   HIP_TRY(hipEventRecord(S.done, c->tail));
   return MJG_OK;
-}
-
-
-template <int MODE, bool DBG, bool UA>
-void launch_encode3(mjg_ctx *c, Slot &S, const SegList &enc_in, int wgs, int ntasks) {
-  const EncGeom &g = c->geom;
-  if (g.range_convert)
-    k_encode<true, MODE, DBG, UA><<<wgs, 64 * kWavesPerWg, 0, S.st>>>(
-        enc_in, g, c->d_tabs, S.d_scratch, S.d_chunk_bits, S.d_dbg, S.d_work, ntasks, S.d_hist,
-        S.d_stage_bits, S.d_syms, S.d_symn);
-  else
-    k_encode<false, MODE, DBG, UA><<<wgs, 64 * kWavesPerWg, 0, S.st>>>(
-        enc_in, g, c->d_tabs, S.d_scratch, S.d_chunk_bits, S.d_dbg, S.d_work, ntasks, S.d_hist,
-        S.d_stage_bits, S.d_syms, S.d_symn);
-}
-
-template <int MODE, bool DBG>
-void launch_encode2(mjg_ctx *c, Slot &S, const SegList &enc_in, int wgs, int ntasks) {
-  if (c->enc_ua)  // a crop read in place at any alignment (fetch_rows<UA>)
-    launch_encode3<MODE, DBG, true>(c, S, enc_in, wgs, ntasks);
-  else
-    launch_encode3<MODE, DBG, false>(c, S, enc_in, wgs, ntasks);
-}
-
-template <int MODE>
-void launch_encode(mjg_ctx *c, Slot &S, const SegList &enc_in, int wgs, int ntasks) {
-  if (c->geom.debug_coefs)
-    launch_encode2<MODE, true>(c, S, enc_in, wgs, ntasks);
-  else
-    launch_encode2<MODE, false>(c, S, enc_in, wgs, ntasks);
 }
 
 }  // namespace
@@ -1059,143 +1207,33 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
     HIP_TRY(hipMemcpyAsync(S.d_stage, frames, (size_t)n * c->in_frame_bytes, hipMemcpyHostToDevice, S.st));
     src = S.d_stage;
   }
-  SegList in_sl;  // the submit's input frames: the caller's segments, or one at src
-  if (segs) {
-    in_sl = *segs;
-  } else {
-    for (int k = 0; k < kMaxSegs; k++) {
-      in_sl.p[k] = src;
-      in_sl.f0[k] = k ? INT_MAX : 0;
-    }
-  }
+  const SegList in_sl = segs ? *segs : one_seg(src);  // the submit's input frames: the caller's segments, or one at src
   SegList enc_in = in_sl;
   if (c->scale) {
     tmark(c, S, MJG_K_SCALE, 0);
-    const ScaleGeom &lg = c->ps[0].g, &cg = c->ps[1].g;
     // luma, then U and V in one launch (same filters; blockIdx.z >= n is V) while 2n fits the
     // grid's z range, else one launch each
     const bool uv1 = 2 * n <= 65535;
+    const long long d_cplane = (long long)g.cw * g.ch;
     for (int p = 0; p < (uv1 ? 2 : 3); p++) {
-      PlaneScale &ps = c->ps[p ? 1 : 0];
-      ScaleGeom sg = p ? cg : lg;
-      sg.nf = n;
-      sg.d_off = sg.s_poff = sg.d_poff = 0;
-      sg.s_off = c->src_off[p];  // the (cropped) plane's first byte in a source frame
-      if (p) {
-        sg.d_off = g.u_off + (p - 1) * (long long)g.cw * g.ch;
-        if (uv1) {
+      for (const Pass &ps : c->pass[p ? 1 : 0]) {
+        if (!ps.launch) continue;
+        ScaleGeom sg = ps.g;
+        sg.nf = n;
+        if (p && uv1) {
           sg.s_poff = c->src_cplane;
-          sg.d_poff = (long long)g.cw * g.ch;
+          sg.d_poff = d_cplane;
         }
-      }
-      const long long plane_off = sg.d_off;        // the encoded (canvas) plane in a frame
-      sg.d_off += c->pad_doff[p ? 1 : 0];          // the picture's first byte in it (0 without a pad)
-      // one dimension: tiles x planes x frames (scale.hip decodes it by multiply-high)
-      const int nz = p && uv1 ? 2 * n : n;
-      sg.gx = (int)ps.grid.x;
-      sg.gxy = (int)(ps.grid.x * ps.grid.y);
-      auto magic = [](uint32_t d) { return d > 1 ? (uint32_t)((((uint64_t)1 << 32) + d - 1) / d) : 0u; };
-      sg.gx_magic = magic((uint32_t)sg.gx);
-      sg.gxy_magic = magic((uint32_t)sg.gxy);
-      if (c->has_pad) {  // the border, and with it a plane that keeps its size (scale.hip k_pad_plane)
-        const PadGeom &pq = c->pad[p ? 1 : 0];
-        ScaleGeom pg = sg;
-        pg.d_off = plane_off;
-        const size_t pieces = ((size_t)pq.cw * (size_t)pq.ch) >> 4, per = (size_t)kCopyThreads * kCopyVecs;
-        pg.gxy = (int)std::max<size_t>(1, (pieces + per - 1) / per);
-        pg.gxy_magic = magic((uint32_t)pg.gxy);
-        const dim3 pgrid((unsigned)(pg.gxy * nz), 1, 1);
-        if (!ps.copy)
-          k_pad_plane<0, false><<<pgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, pg, pq);
-        else if (pg.range == 1)
-          k_pad_plane<1, true><<<pgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, pg, pq);
-        else if (pg.range == 2)
-          k_pad_plane<2, true><<<pgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, pg, pq);
-        else
-          k_pad_plane<0, true><<<pgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, pg, pq);
-        if (ps.copy) continue;
-      }
-      if (ps.copy) {  // the plane keeps its size: streamed (scale.hip k_plane_copy)
-        const size_t pieces = ((size_t)sg.sw * (size_t)sg.sh) >> 4, per = (size_t)kCopyThreads * kCopyVecs;
-        sg.gxy = (int)std::max<size_t>(1, (pieces + per - 1) / per);
-        sg.gxy_magic = magic((uint32_t)sg.gxy);
-        const dim3 cgrid((unsigned)(sg.gxy * nz), 1, 1);
-        if (sg.s_stride != sg.sw) {  // a rectangle of wider rows (crop)
-          if (sg.range == 1)
-            k_plane_copy<1, true><<<cgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, sg);
-          else if (sg.range == 2)
-            k_plane_copy<2, true><<<cgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, sg);
-          else
-            k_plane_copy<0, true><<<cgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, sg);
-        } else if (sg.range == 1)
-          k_plane_copy<1><<<cgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, sg);
-        else if (sg.range == 2)
-          k_plane_copy<2><<<cgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, sg);
-        else
-          k_plane_copy<0><<<cgrid, kCopyThreads, 0, S.st>>>(in_sl, S.d_scaled, sg);
-        continue;
-      }
-      const dim3 grid((unsigned)(sg.gxy * nz), 1, 1);
-      if (ps.stream) {  // past one LDS tile: strips x bands (scale.hip k_scale_stream)
-#define MJG_STREAM_LAUNCH(D4, RANGE)                                                                          \
-  do {                                                                                                        \
-    if (ps.hcl)                                                                                               \
-      k_scale_stream<D4, RANGE, true><<<grid, kStreamThreads, ps.lds, S.st>>>(in_sl, S.d_scaled, sg, ps.sq,   \
-                                                                              ps.hcp, ps.hp, ps.vcp, ps.vps, ps.hsum); \
-    else                                                                                                      \
-      k_scale_stream<D4, RANGE, false><<<grid, kStreamThreads, ps.lds, S.st>>>(in_sl, S.d_scaled, sg, ps.sq,  \
-                                                                               ps.hcp, ps.hp, ps.vcp, ps.vps, ps.hsum); \
-  } while (0)
-        if (ps.d4) {
-          if (sg.range == 1) MJG_STREAM_LAUNCH(true, 1);
-          else if (sg.range == 2) MJG_STREAM_LAUNCH(true, 2);
-          else MJG_STREAM_LAUNCH(true, 0);
-        } else {
-          if (sg.range == 1) MJG_STREAM_LAUNCH(false, 1);
-          else if (sg.range == 2) MJG_STREAM_LAUNCH(false, 2);
-          else MJG_STREAM_LAUNCH(false, 0);
+        if (p == 2) {  // V on its own
+          sg.s_off += c->src_cplane;
+          sg.d_off += d_cplane;
         }
-#undef MJG_STREAM_LAUNCH
-        continue;
+        ps.launch(ps, sg, in_sl, S.d_scaled, p && uv1 ? 2 * n : n, S.st);
       }
-#define MJG_SCALE_LAUNCH3(HT, NPV, D4, TH)                                                          \
-  do {                                                                                              \
-    if (sg.range == 1)                                                                              \
-      k_scale<HT, NPV, D4, 1, TH><<<grid, 64 * scale_waves(TH), ps.lds, S.st>>>(in_sl, S.d_scaled, sg, ps.hcp,        \
-                                                                    ps.hp, ps.vcp, ps.vps, ps.hsum, ps.mfb); \
-    else if (sg.range == 2)                                                                         \
-      k_scale<HT, NPV, D4, 2, TH><<<grid, 64 * scale_waves(TH), ps.lds, S.st>>>(in_sl, S.d_scaled, sg, ps.hcp,        \
-                                                                    ps.hp, ps.vcp, ps.vps, ps.hsum, ps.mfb); \
-    else                                                                                            \
-      k_scale<HT, NPV, D4, 0, TH><<<grid, 64 * scale_waves(TH), ps.lds, S.st>>>(in_sl, S.d_scaled, sg, ps.hcp,        \
-                                                                    ps.hp, ps.vcp, ps.vps, ps.hsum, ps.mfb); \
-  } while (0)
-#define MJG_SCALE_LAUNCH(HT, NPV, TH)      \
-  do {                                     \
-    if (ps.d4)                             \
-      MJG_SCALE_LAUNCH3(HT, NPV, true, TH);  \
-    else                                   \
-      MJG_SCALE_LAUNCH3(HT, NPV, false, TH); \
-  } while (0)
-      if (sg.htaps == 8 && sg.npv == 5 && ps.th == 128)  // 2:1 downscale (4K -> 1080p), tall tiles
-        MJG_SCALE_LAUNCH(8, 5, 128);
-      else if (sg.htaps == 8 && sg.npv == 5 && ps.th == 64)
-        MJG_SCALE_LAUNCH(8, 5, 64);
-      else if (sg.htaps == 8 && sg.npv == 5)
-        MJG_SCALE_LAUNCH(8, 5, 32);
-      else if (sg.htaps == 4 && sg.npv == 3)  // upscale / mild downscale
-        MJG_SCALE_LAUNCH(4, 3, 32);
-      else
-        MJG_SCALE_LAUNCH(0, 0, 32);
-#undef MJG_SCALE_LAUNCH
-#undef MJG_SCALE_LAUNCH3
     }
     tmark(c, S, MJG_K_SCALE, 1);
     HIP_TRY(hipGetLastError());
-    for (int k = 0; k < kMaxSegs; k++) {  // k_encode reads the scaled frames, one buffer
-      enc_in.p[k] = S.d_scaled;
-      enc_in.f0[k] = k ? INT_MAX : 0;
-    }
+    enc_in = one_seg(S.d_scaled);  // k_encode reads the scaled frames, one buffer
   } else {  // in place: EncGeom's offsets count from the rectangle's first luma byte (0: whole frames)
     for (int k = 0; k < kMaxSegs; k++) enc_in.p[k] += c->src_off[0];
   }
@@ -1205,7 +1243,7 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
   if (c->optimal) {  // pass 1: symbol counts per frame, then the frame's tables
     tmark(c, S, MJG_K_HUFF, 0);
     HIP_TRY(hipMemsetAsync(S.d_hist, 0, (size_t)n * kFrameTabWords * 4, S.st));
-    launch_encode<kCount>(c, S, enc_in, std::min(wgs, c->enc_grid_cnt), ntasks);
+    c->enc_count(c, S, enc_in, std::min(wgs, c->enc_grid_cnt), ntasks);
     HIP_TRY(hipMemsetAsync(S.d_work, 0, (size_t)kXcds * kCtrStride * 4, S.st));  // unit counters for pass 2
     k_huff_build<<<n * 4, 64, 0, S.st>>>(S.d_hist, S.d_ftabs, S.d_dht, S.d_dht_nval);
     tmark(c, S, MJG_K_HUFF, 1);
@@ -1214,10 +1252,9 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
   tmark(c, S, MJG_K_ENCODE, 0);
   if (c->optimal)
     k_emit_syms<<<c->enc_grid * kEmitGridMul, 64 * kWavesPerWg, 0, S.st>>>(g, c->d_tabs, S.d_ftabs, S.d_syms, S.d_symn,
-                                                             S.d_scratch, S.d_chunk_bits, S.d_stage_bits,
-                                                                  ntasks);
+                                                                           S.d_scratch, S.d_chunk_bits, S.d_stage_bits, ntasks);
   else
-    launch_encode<kEmitDefault>(c, S, enc_in, wgs, ntasks);
+    c->enc_emit(c, S, enc_in, wgs, ntasks);
   tmark(c, S, MJG_K_ENCODE, 1);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(S.enc_done, S.st));
@@ -1226,9 +1263,8 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
   tmark(c, S, MJG_K_SCAN_BITS, 0);
   const int ndone = 1;  // k_scan_ff's frame ticket
   if (c->rst)
-    k_scan_bits_seg<<<(nsegs + 3) / 4, 256, 0, c->tail>>>(S.d_chunk_bits, S.d_chunk_off, S.d_frame_bits,
-                                                            g.nchunks, nsegs, S.d_work, S.d_status, S.d_done,
-                                                            ndone);
+    k_scan_bits_seg<<<(nsegs + 3) / 4, 256, 0, c->tail>>>(S.d_chunk_bits, S.d_chunk_off, S.d_frame_bits, g.nchunks, nsegs,
+                                                          S.d_work, S.d_status, S.d_done, ndone);
   else
     k_scan_bits<<<n, 1024, 0, c->tail>>>(S.d_chunk_bits, S.d_chunk_off, S.d_frame_bits, g.nchunks,
                                            S.d_work, S.d_status, S.d_done, ndone);
@@ -1307,6 +1343,14 @@ int try_launch_held(mjg_ctx *c, bool at_sync) {
   if (c->held < c->merge && (c->nout > 0 || c->hold_idle)) return MJG_OK;
   if (at_sync && c->head == c->last) return MJG_OK;
   return launch_held(c);
+}
+
+// The readers of the last synced job (fetch, debug_coefs): with no mjg_sync since the last
+// mjg_submit they sync the oldest queued job first (the submit -> fetch pattern)
+int sync_for_read(mjg_ctx *c) {
+  if (pending_jobs(c) > 0 && !c->synced_since_submit)
+    if (const int rc = mjg_sync(c, nullptr, nullptr)) return rc;
+  return c->last < 0 ? set_err(MJG_E_STATE, "nothing submitted") : MJG_OK;
 }
 }  // namespace
 
@@ -1406,7 +1450,7 @@ int mjg_sync(mjg_ctx *c, uint64_t *frame_sizes, uint64_t *total) {
         for (int k = 0; k < MJG_NUM_KERNELS; k++) {
           if (k == MJG_K_SCALE && !c->scale) continue;
           if (k == MJG_K_HUFF && !c->optimal) continue;
-          const bool tail = k == MJG_K_SCAN_BITS || k == MJG_K_COUNT_FF || k == MJG_K_SCAN_FF || k == MJG_K_WRITE;
+          const bool tail = is_tail_kernel(k);
           if (tail != c->timing_detail && (tail || k == MJG_K_TAIL)) continue;
           if (k == MJG_K_TAIL && !c->timing_tail) continue;
           float ms = 0.f;
@@ -1443,11 +1487,7 @@ int mjg_sync(mjg_ctx *c, uint64_t *frame_sizes, uint64_t *total) {
 // 0.1 s per 1080p segment in some worker processes and 2 ms in others.
 int mjg_fetch_host(mjg_ctx *c, const uint8_t **data, size_t *len) {
   if (!c || !data) return set_err(MJG_E_INVALID, "null argument");
-  if (pending_jobs(c) > 0 && !c->synced_since_submit) {
-    const int rc = mjg_sync(c, nullptr, nullptr);
-    if (rc) return rc;
-  }
-  if (c->last < 0) return set_err(MJG_E_STATE, "nothing submitted");
+  if (const int rc = sync_for_read(c)) return rc;
   const Slot &L = c->slot[c->last];
   const uint64_t total = c->last_total;
   HIP_TRY(hipSetDevice(c->device));
@@ -1456,11 +1496,7 @@ int mjg_fetch_host(mjg_ctx *c, const uint8_t **data, size_t *len) {
     c->h_fetch = nullptr;
     c->h_fetch_cap = 0;
     const size_t cap = total + total / 4 + 4096;
-    if (hipHostMalloc((void **)&c->h_fetch, cap, hipHostMallocDefault) != hipSuccess) {
-      c->h_fetch = nullptr;
-      (void)hipGetLastError();
-      return set_err(MJG_E_NOMEM, "hipHostMalloc(%zu) failed", cap);
-    }
+    if (const int rc = mjg_host_alloc(cap, (void **)&c->h_fetch)) return rc;
     c->h_fetch_cap = cap;
   }
   if (total) HIP_TRY(hipMemcpy(c->h_fetch, L.d_out + c->last_off, total, hipMemcpyDeviceToHost));
@@ -1473,11 +1509,7 @@ int mjg_fetch_host(mjg_ctx *c, const uint8_t **data, size_t *len) {
 // (mjg_host_alloc), else mjg_fetch_host and a copy.
 int mjg_fetch(mjg_ctx *c, uint8_t *out, size_t cap) {
   if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
-  if (pending_jobs(c) > 0 && !c->synced_since_submit) {
-    const int rc = mjg_sync(c, nullptr, nullptr);
-    if (rc) return rc;
-  }
-  if (c->last < 0) return set_err(MJG_E_STATE, "nothing submitted");
+  if (const int rc = sync_for_read(c)) return rc;
   if (cap < c->last_total) return set_err(MJG_E_CAPACITY, "fetch needs %llu bytes", (unsigned long long)c->last_total);
   HIP_TRY(hipSetDevice(c->device));
   // page-locked caller memory (mjg_host_alloc): one DMA straight into it, no staging copy
@@ -1550,10 +1582,7 @@ int mjg_build_header(const mjg_config *cfg, uint8_t *out, size_t cap, size_t *le
   if (cfg->sar_num < 0 || cfg->sar_den < 0 || cfg->sar_num > 65535 || cfg->sar_den > 65535)
     return set_err(MJG_E_INVALID, "bad SAR %d:%d", cfg->sar_num, cfg->sar_den);
   uint8_t mp[64];
-  for (int i = 0; i < 64; i++) {
-    const int v = i == 0 ? 8 : ((kMpeg1Intra[i] * cfg->qscale) >> 3);
-    mp[i] = (uint8_t)(v > 255 ? 255 : v);
-  }
+  quant_matrix(cfg->qscale, mp, nullptr);
   const bool rst = (cfg->flags & MJG_F_RST) && (cfg->dst_h + 15) / 16 > 1;
   const std::vector<uint8_t> h = build_header(cfg->dst_w, cfg->dst_h, mp, cfg->sar_num, cfg->sar_den,
                                              (cfg->flags & MJG_F_COM_ITU601) != 0, cfg->chroma_format, rst);
@@ -1580,11 +1609,7 @@ int mjg_sws_filter(int src_len, int dst_len, int one, int align, int bitexact, i
 int mjg_debug_coefs(mjg_ctx *c, int frame, int16_t *out, size_t nblocks) {
   if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
   if (!c->geom.debug_coefs) return set_err(MJG_E_STATE, "context opened without MJG_F_DEBUG_COEFS");
-  if (pending_jobs(c) > 0 && !c->synced_since_submit) {
-    const int rc = mjg_sync(c, nullptr, nullptr);
-    if (rc) return rc;
-  }
-  if (c->last < 0) return set_err(MJG_E_STATE, "nothing submitted");
+  if (const int rc = sync_for_read(c)) return rc;
   const Slot &L = c->slot[c->last];
   const size_t nb = (size_t)c->geom.nmcu * c->geom.bpm;  // dbg buffer: frame-major, coding order
   if (frame < 0 || frame >= L.jn[c->last_job]) return set_err(MJG_E_INVALID, "frame %d", frame);

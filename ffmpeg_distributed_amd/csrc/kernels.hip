@@ -36,7 +36,7 @@ constexpr int kSlotWords = (64 * kMaxBlockBits + 31) / 32;  // one chunk = 64 bl
 // The row image (s_pk) holds row-pass output 0 (the row sum, 0..32640) unbiased and outputs
 // 1-7 (|value| <= 16320) + 16384, so every u16 is below 2^15 and reads as the same value
 // when v_dot2_i32_i16 takes it as int16 (exact_coef: no sign fix-up).
-constexpr int kTabWords = 704;  // device table block, see open_ctx
+constexpr int kTabWords = 704;  // device table block, see build_tabs (api.hip)
 constexpr float kM = 12582912.0f;
 constexpr float kMc = 12599296.0f;  // kM + 16384: the row image's bias for outputs 1-7
 constexpr float kRnd = 0x1p-10f;
@@ -883,7 +883,7 @@ __device__ __forceinline__ void pack_chunk_short(const ShiftSink &q, uint32_t bi
 // the wave's LDS row image s_pk ([word][lane]; word c*4 + r/2 = column c of rows r, r+1 as
 // u16 pairs; output 0 as is, 1-7 + 16384).
 // Column skip (columns 2-7): every AC output of a column quantises to zero when the column's
-// row-pass values are small enough, |u_r| <= A for all 8 rows (open_ctx derives A from the
+// row-pass values are small enough, |u_r| <= A for all 8 rows (build_tabs derives A from the
 // quantiser thresholds, s_lim[c - 2] = its fp32 form for column c).  When `watch` (wave-uniform)
 // is set the pass keeps, per column, the running maximum of |v| over the rows, v the value it
 // holds before the rounding add (one v_max3_f32 per column and row pair), and returns the

@@ -40,7 +40,7 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 constexpr int kScaleTileW = 64;
 constexpr int kScaleLoadRows = 7;  // fast window path: rows x 9 pieces per wave-instruction
 __host__ __device__ constexpr int scale_loads_per_wave(int th) { return th >= 64 ? 5 : 3; }
-// waves per workgroup for a tile height (128-row tiles: 8 waves, 512 threads)
+// waves per workgroup for a tile height (128-row tiles, which no context launches: 8 waves, 512 threads)
 __host__ __device__ constexpr int scale_waves(int th) { return th == 128 ? 8 : 4; }
 constexpr int kScaleAliasWords = 36;  // TH 64: LDS row stride (dwords), the widest fast window
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));

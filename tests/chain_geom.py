@@ -7,8 +7,9 @@ shape reaches the path it means to check.
     chunk) at which each work unit of kBatch tasks starts (a unit that starts at chunk != 0
     recomputes its DC predictors from pixel rows: carry_row);
   - copy_span: workgroups and vector slots a plane of n bytes takes in k_plane_copy / k_pad_plane;
+  - scale_variant / copy_pad_cells: the kernel instantiation build_plan picks for a plane;
   - predict_paths: what mjg_debug_encode_path and mjg_debug_scale_path will report for a
-    crop / -pix_fmt / scale / pad configuration (the rules of open_ctx and setup_plane_scale; the
+    crop / -pix_fmt / scale / pad configuration (the rules of plan_geometry and plan_plane_scale; the
     filters come from the library's own device-free mjg_sws_filter).
 
 kBatch, kCopyThreads, kCopyVecs and the tile kernel's constants are parsed from the kernel
@@ -36,12 +37,15 @@ COPY_VECS = _const("scale.hip", "kCopyVecs")
 SCALE_TILE_W = _const("scale.hip", "kScaleTileW")
 SCALE_LOAD_ROWS = _const("scale.hip", "kScaleLoadRows")
 SCALE_ALIAS_WORDS = _const("scale.hip", "kScaleAliasWords")
+STREAM_THREADS = _const("scale.hip", "kStreamThreads")
+STREAM_MAX_PIECES = _const("scale.hip", "kStreamMaxPieces")
+STREAM_BAND = _const("scale.hip", "kStreamBand")
 
 EncGeom = namedtuple("EncGeom", "mbw mbh nseg seg_blocks nchunks ntasks")
 
 
 def enc_geom(w, h, chroma, rst=False, nframes=1):
-    """open_ctx's values for an encoded w x h frame in `chroma` (under a pad: the canvas)."""
+    """plan_geometry's values for an encoded w x h frame in `chroma` (under a pad: the canvas)."""
     bpm = 8 if chroma == "422" else 6
     lmw = 8 if chroma == "444" else 16
     mbw, mbh = (w + lmw - 1) // lmw, (h + 15) // 16
@@ -70,7 +74,7 @@ def mid_segment_units(w, h, chroma, rst=False, nframes=1):
 
 
 def _mcu_tables():
-    """open_ctx's kPlane / kDx / kDy: per format, the plane and the 8x8 position in its MCU of every
+    """build_tabs's kPlane / kDx / kDy: per format, the plane and the 8x8 position in its MCU of every
     block of an MCU in coding order."""
     with open(os.path.join(_CSRC, "api.hip")) as f:
         src = f.read()
@@ -90,7 +94,7 @@ _FMT = {"420": 0, "422": 1, "444": 2}
 
 def block_pos(w, h, chroma, b):
     """(plane, x0, y0, plane width, plane height) of block b of a frame in coding order
-    (kernels.hip block_pos with open_ctx's descriptors)."""
+    (kernels.hip block_pos with build_tabs's descriptors)."""
     f = _FMT[chroma]
     bpm = 8 if chroma == "422" else 6
     lmw, cmh = (8 if chroma == "444" else 16), (8 if chroma == "420" else 16)
@@ -147,10 +151,11 @@ def taps_ok(sw, sh, dw, dh):
         return False
 
 
-def tile_lds(sw, sh, dw, dh):
-    """Bytes of LDS k_scale would need for one tile of a sw x sh -> dw x dh plane
-    (setup_plane_scale: past 64 KiB the plane goes to k_scale_stream).  Every plane's filter
-    positions are 128 (sws_local_pos with the default chroma siting), mjg_sws_filter's default."""
+def _tile_plan(sw, sh, dw, dh):
+    """(ht, npv, th, max_nw, LDS bytes, d4) of k_scale's tile for a sw x sh -> dw x dh plane
+    (plan_plane_scale).  Every plane's filter positions are 128 (sws_local_pos with the default
+    chroma siting), mjg_sws_filter's default.  d4: every h coefficient splits into the hi / lo
+    bytes of the v_dot4 layout."""
     hc, hpos = _lib.sws_filter(sw, dw, 1 << 14, 4)
     vc, vpos = _lib.sws_filter(sh, dh, 1 << 12, 2)
     ht, vt = (hc.shape[1] + 3) & ~3, vc.shape[1]
@@ -169,8 +174,47 @@ def tile_lds(sw, sh, dw, dh):
                 and 2 * tile_pairs(64) <= 4 * 5 * SCALE_LOAD_ROWS) else 32
     mp = tile_pairs(th)
     if th >= 64:
-        return 2 * mp * SCALE_ALIAS_WORDS * 4 + 64
-    return (2 * mp * max_nw + mp * SCALE_TILE_W + th * (npv + 1)) * 4
+        lds = 2 * mp * SCALE_ALIAS_WORDS * 4 + 64
+    else:
+        lds = (2 * mp * max_nw + mp * SCALE_TILE_W + th * (npv + 1)) * 4
+    d4 = bool(int(hc.min()) >= -128 * 128 - 64 and int(hc.max()) < 127 * 128 + 64)
+    return ht, npv, th, max_nw, lds, d4
+
+
+def tile_lds(sw, sh, dw, dh):
+    """Bytes of LDS k_scale would need for one tile of a sw x sh -> dw x dh plane
+    (plan_plane_scale: past 64 KiB the plane goes to k_scale_stream)."""
+    return _tile_plan(sw, sh, dw, dh)[4]
+
+
+def stream_hcl(max_nw, ht, npv):
+    """plan_scale_stream's choice for a plane whose widest strip window is max_nw dwords: whether
+    the first plan that fits 64 KiB (chunk rows R from 16 down by halving, staging 3 down to 0)
+    stages the strip's h coefficients in LDS; None when nothing fits."""
+    npc = max_nw // 4
+    R = 16
+    while R >= 2:
+        for stage in (3, 2, 1, 0):
+            need = (2 * R * max_nw + (npv + R) * SCALE_TILE_W + (SCALE_TILE_W * (ht // 2) if stage & 2 else 0)
+                    + (STREAM_BAND * npv if stage & 1 else 0)) * 4
+            if need <= 64 * 1024 and R * npc <= STREAM_THREADS * STREAM_MAX_PIECES:
+                return bool(stage & 2)
+        R >>= 1
+    return None
+
+
+def scale_variant(sw, sh, dw, dh, force_stream=False):
+    """The kernel family and template key build_plan selects for a sw x sh -> dw x dh plane (with
+    MJG_PLANE_COPY unset; force_stream: MJG_SCALE_STREAM=1): ("copy",), ("stream", d4, hcl) or
+    ("tile", (HT, NPV, TH), d4).  Each family has one instantiation per range beside."""
+    if (sw, sh) == (dw, dh):
+        return ("copy",)
+    ht, npv, th, max_nw, lds, d4 = _tile_plan(sw, sh, dw, dh)
+    if lds > 64 * 1024 or force_stream:
+        return ("stream", d4, stream_hcl(max_nw, ht, npv))
+    if (ht, npv) == (8, 5):
+        return ("tile", (8, 5, th), d4)
+    return ("tile", (4, 3, 32) if (ht, npv) == (4, 3) else (0, 0, 32), d4)
 
 
 def plane_path(sw, sh, dw, dh, has_pad, plane_copy=True):
@@ -203,6 +247,26 @@ def predict_paths(w, h, src, rect, dst, dw, dh, pad, unaligned_fetch=True, plane
     luma = plane_path(rw, rh, dw, dh, has_pad, plane_copy)
     chroma = plane_path(ccw, cch, pcw, pch, has_pad, plane_copy)
     return 0, (luma, chroma), luma == COPY and rw != w
+
+
+def copy_pad_cells(w, h, src, rect, dst, dw, dh, pad, full):
+    """The instantiations of the copy and pad kernels a configuration launches, as build_plan picks
+    them: ("copy", RANGE, RECT) for k_plane_copy, ("pad", RANGE, COPY) for k_pad_plane.  RANGE is 0
+    for full-range input, else 1 for luma and 2 for chroma; RECT: the plane's source rows are wider
+    than the rectangle's; a border around a scaled picture is k_pad_plane<0, false>."""
+    _, _, rw, _ = rect or (0, 0, w, h)
+    _, paths, _ = predict_paths(w, h, src, rect, dst, dw, dh, pad)
+    wide = (rw != w, chroma_size(rw, 2, src)[0] != chroma_size(w, 2, src)[0])
+    out = set()
+    for p in (0, 1):
+        rng = 0 if full else 1 + p
+        if paths[p] == COPY:
+            out.add(("copy", rng, wide[p]))
+        elif paths[p] == PADCOPY:
+            out.add(("pad", rng, True))
+        elif paths[p] in (TILE, STREAM) and pad is not None and tuple(pad) != (0, 0, dw, dh):
+            out.add(("pad", 0, False))
+    return out
 
 
 # ------------------------------------------------------------------ the seeded sweep of the chain

@@ -165,3 +165,74 @@ def test_sweep_draw_and_its_floors():
     total = {k: sum(p[k] for p in parts) for k in cg.FEATURES}
     assert total == {"crop_in_place_ua": 14, "crop_in_place_aligned": 9, "rect_copy": 9, "pad_copy": 13,
                      "pad_with_scale": 30, "stream": 7, "host": 31, "dev_odd": 39, "segments": 28, "merged": 22}
+
+
+# One plane shape (source -> destination) per kernel instantiation family that build_plan can pick
+# for a resized plane and that some filter reaches: tests/test_gpu_chain.py runs each as 4:4:4 in
+# and out (luma and chroma the same plane size, so both take the arm), tv range (the arm's range 1
+# and range 2 instantiations) and full range (its range 0 one).
+ARM_SHAPES = [
+    ((64, 48, 32, 24), ("tile", (8, 5, 64), True)),      # 2:1, the 64-row tile
+    ((12, 24, 6, 12), ("tile", (8, 5, 32), True)),       # 2:1 from a source narrower than 16
+    ((64, 48, 128, 96), ("tile", (4, 3, 32), False)),    # 1:2 up: the full-weight edge tap is no D4 coefficient
+    ((64, 24, 63, 48), ("tile", (4, 3, 32), True)),      # h 64:63 down (4 taps, none of full weight), v 1:2 up
+    ((96, 72, 32, 24), ("tile", (0, 0, 32), True)),      # 3:1: 12 h taps, the run-time tap counts
+    ((64, 48, 64, 24), ("tile", (0, 0, 32), False)),     # h identity (one tap of 16384), v 2:1
+    ((256, 160, 32, 20), ("stream", True, True)),        # 8:1
+    ((40, 1000, 80, 17), ("stream", False, True)),       # h 1:2 up, 234 v taps
+    ((3968, 64, 65, 16), ("stream", True, False)),       # 244 h taps: the strip's h coefficients do not fit LDS
+]
+# The arms build_plan can name that no filter reaches, and why.  Of all h filters between widths
+# 1..399 (mjg_sws_filter) only 4-tap ones hold a coefficient outside D4's range (16384: an
+# upscale's full-weight edge tap, the identity); a filter of more taps spreads its weight.
+ARMS_NOT_REACHED = {
+    ("tile", (8, 5, 64), False): "an 8-tap h filter has no coefficient past D4's range",
+    ("tile", (8, 5, 32), False): "the same filters",
+    ("stream", False, False): "coefficients past D4's range come with 4 h taps, whose 512 B of rows always fit LDS",
+}
+
+
+def test_arm_shapes_cover_every_reachable_arm():
+    """Each shape of ARM_SHAPES reaches the arm it is listed for (scale_variant, from the library's
+    own filters), and with ARMS_NOT_REACHED they are every [tile shape or hcl][d4] cell of the host's
+    selection: 4 tile shapes and 2 stream forms, each with and without D4."""
+    for shape, arm in ARM_SHAPES:
+        assert cg.scale_variant(*shape) == arm, shape
+        assert cg.plane_path(*shape, False) == (STREAM if arm[0] == "stream" else TILE)
+    every = {("tile", t, d4) for t in ((8, 5, 64), (8, 5, 32), (4, 3, 32), (0, 0, 32)) for d4 in (False, True)}
+    every |= {("stream", d4, hcl) for d4 in (False, True) for hcl in (False, True)}
+    reached = {arm for _, arm in ARM_SHAPES}
+    assert len(reached) == len(ARM_SHAPES) and not reached & set(ARMS_NOT_REACHED)
+    assert reached | set(ARMS_NOT_REACHED) == every
+    assert cg.scale_variant(64, 48, 64, 48) == ("copy",)
+    assert cg.scale_variant(64, 48, 32, 24, force_stream=True)[0] == "stream"
+    # everything a case moves stays small: at most a few hundred KB of source planes
+    assert max(3 * s[0] * s[1] for s, _ in ARM_SHAPES) <= 800 * 1024
+
+
+def test_copy_and_pad_cells_are_reached_by_the_gpu_tests():
+    """The ten instantiations k_plane_copy<RANGE, RECT> and k_pad_plane<RANGE, COPY> (+ <0, false>),
+    and a configuration of the GPU tests that launches each (restated from those tests)."""
+    pad = (26, 28, 250, 140)
+    reached = set()
+    for full in (False, True):
+        # tests/test_gpu_chain.py: PAD_COPY's first row, the rectangle copy, the border around a scaled picture
+        reached |= cg.copy_pad_cells(200, 84, "420", None, "420", None, None, pad, full)
+        reached |= cg.copy_pad_cells(300, 200, "444", (3, 5, 251, 151), "420", None, None, None, full)
+        reached |= cg.copy_pad_cells(1100, 700, "420", None, "420", 200, 100, (28, 22, 256, 144), full)
+        # tests/test_gpu_chroma_resample.py: a down-sampling pair without a resize (luma: the plain copy)
+        reached |= cg.copy_pad_cells(33, 17, "444", None, "420", None, None, None, full)
+        # tests/test_gpu_chain.py CHROMA_COPY: 4:2:0 -> 4:4:4 at half size, chroma keeps its size
+        for rect in CHROMA_COPY_RECTS:
+            reached |= cg.copy_pad_cells(300, 200, "420", rect, "444", *CHROMA_COPY_SIZE[rect], None, full)
+    assert reached == ({("copy", r, rect) for r in (0, 1, 2) for rect in (False, True)}
+                       | {("pad", r, True) for r in (0, 1, 2)} | {("pad", 0, False)})
+    # without the CHROMA_COPY cases no GPU test reaches k_plane_copy<2, ..>: the up-sampling pair of
+    # tests/test_gpu_chroma_resample.py keeps the frame size, so its chroma planes are scaled 1:2
+    assert cg.copy_pad_cells(34, 18, "420", None, "444", None, None, None, False) == {("copy", 1, False)}
+
+
+# tests/test_gpu_chain.py CHROMA_COPY: the rectangles of the 300x200 4:2:0 source (None: whole
+# frames) and the 4:4:4 size at which the chroma planes keep theirs
+CHROMA_COPY_RECTS = (None, (2, 6, 250, 150))
+CHROMA_COPY_SIZE = {None: (150, 100), (2, 6, 250, 150): (125, 75)}

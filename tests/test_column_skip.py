@@ -1,6 +1,6 @@
 """k_encode's column skip, decided in the row pass: a column (2-7) of a chunk is left out of the
 column screen when max|u| of the column over all 8 rows of all 64 blocks is at most
-A_c = min(amax_c, floor(Rmax_c / 2)) (open_ctx; restated by test_kernel_arith._skip_limits).
+A_c = min(amax_c, floor(Rmax_c / 2)) (build_tabs; restated by test_kernel_arith._skip_limits).
 
 The sweeps put one patterned block into every chunk of 1024x16 frames (6 chunks, 63 flat blocks
 each) and step its amplitude from frame to frame across the limit of every column; the CPU part

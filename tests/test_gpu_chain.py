@@ -12,10 +12,12 @@ import pytest
 
 import chain_geom as cg
 import oracle
+import test_gpu_scale_stream as scale_stream
 from chain_geom import COPY, IN_PLACE, NONE, PADCOPY, STREAM, TILE, UA
 from chroma_resample_ref import composed_planes, source_frames
 from crop_ref import crop_frame, same_inside
 from pad_ref import BORDER, pad_planes
+from test_chain_geom import ARM_SHAPES, CHROMA_COPY_RECTS, CHROMA_COPY_SIZE
 from ffmpeg_distributed_amd.encoder import CHROMA_SHIFTS, MjpegEncoder, chroma_size, i420_frame_bytes, split_i420
 
 pytestmark = pytest.mark.gpu
@@ -312,6 +314,26 @@ def test_crop_with_pix_fmt_rect_copy_past_one_workgroup(dst, full, copy_kernel, 
         check_planes(enc, planes, dst)
 
 
+@pytest.mark.parametrize("full", [False, True], ids=["tv", "full"])
+@pytest.mark.parametrize("rect", CHROMA_COPY_RECTS, ids=["whole_frames", "crop"])
+def test_chroma_plane_copy_beside_a_scaled_luma(rect, full):
+    """k_plane_copy<2, ..> (tv range: the chroma byte table) and its RECT form on a chroma plane:
+    4:2:0 to 4:4:4 at half size, so luma is scaled 2:1 and the chroma planes keep their size; under
+    the crop they are 125 bytes out of 150-byte rows."""
+    w, h, src, dst = 300, 200, "420", "444"
+    dw, dh = CHROMA_COPY_SIZE[rect]
+    assert cg.copy_pad_cells(w, h, src, rect, dst, dw, dh, None, full) == {("copy", 0 if full else 2, rect is not None)}
+    frames = _frames(w, h, src)
+    planes, ref = _ref(w, h, src, rect, dst, full, dw, dh, None, 4)
+    with _open(w, h, src, rect, dst, dw, dh, full=full, q=4) as enc:
+        assert (enc.scale_path(0), enc.scale_path(1)) == (TILE, COPY) and enc.encode_path() == 0
+        got = enc.encode(frames)
+        check_planes(enc, planes, dst)
+        _check(got, ref)
+        if rect:
+            _check(enc.encode(same_inside(frames, w, h, src, rect, 83)), ref)
+
+
 # ---------------------------------------------------------------- 3f: border only around the stream kernel's picture
 def test_border_only_around_a_picture_written_by_the_stream_kernel():
     """k_pad_plane<.., COPY = false> on a 256x144 canvas (luma 36,864 B: 3 workgroups) around the
@@ -326,6 +348,20 @@ def test_border_only_around_a_picture_written_by_the_stream_kernel():
         got = enc.encode(frames)
         check_planes(enc, planes, c, pad=pad, pic=(dw, dh))
     _check(got, ref)
+
+
+# ---------------------------------------------------------------- 3g: every arm of the scale kernels' selection
+@pytest.mark.parametrize("full", [False, True], ids=["tv", "full"])
+@pytest.mark.parametrize("shape,arm", ARM_SHAPES, ids=["%dx%d_%dx%d" % s for s, _ in ARM_SHAPES])
+def test_every_scale_arm_matches_reference(shape, arm, full):
+    """One plane shape per [tile shape or stream form][d4] arm of build_plan, 4:4:4 in and out (luma
+    and chroma the same size: both planes take the arm), two frames in one host submit: tv range
+    runs the arm's range 1 and range 2 instantiations, full range its range 0 one.  The paths, the
+    planes and then the bytes, as tests/test_gpu_scale_stream.py checks them."""
+    sw, sh, dw, dh = shape
+    assert cg.scale_variant(*shape) == arm
+    path = STREAM if arm[0] == "stream" else TILE
+    scale_stream._run(scale_stream._frames(sw, sh, "444", 2), sw, sh, dw, dh, "444", full=full, paths=(path, path))
 
 
 # ---------------------------------------------------------------- 4: the seeded sweep

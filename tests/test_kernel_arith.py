@@ -221,7 +221,7 @@ def test_screen_thresholds_are_conservative():
 
 
 def _skip_limits(q, col):
-    """Python restatement of open_ctx's k_encode column-skip limits (Rmax, A) for a column."""
+    """Python restatement of build_tabs's k_encode column-skip limits (Rmax, A) for a column."""
     dot = np.array(_int_array("kPass2Dot"), np.int64).reshape(8, 8)
     qm = oracle.matrix(q)[1].astype(np.int64)
     rmax, amax = 65535, 0
