@@ -37,12 +37,12 @@ MJG_NUM_KERNELS = len(KERNEL_NAMES)
 
 # Every symbol include/mjgpu.h declares (checked by tests/test_abi.py).
 EXPORTS = (
-    "mjg_version", "mjg_last_error", "mjg_device_count", "mjg_device_numa_node", "mjg_open", "mjg_open_src", "mjg_open_crop", "mjg_open_pad", "mjg_close",
+    "mjg_version", "mjg_last_error", "mjg_device_count", "mjg_device_numa_node", "mjg_open", "mjg_open_src", "mjg_open_crop", "mjg_open_pad", "mjg_open_orient", "mjg_close",
     "mjg_frame_bytes", "mjg_header", "mjg_submit", "mjg_sync", "mjg_fetch", "mjg_fetch_host",
     "mjg_output_device", "mjg_stream", "mjg_queue_depth", "mjg_ctx_queue_depth", "mjg_submit_segments", "mjg_max_segments", "mjg_host_alloc", "mjg_host_free",
     "mjg_kernel_times", "mjg_build_header", "mjg_sws_filter", "mjg_debug_coefs",
     "mjg_debug_planes", "mjg_debug_filter", "mjg_debug_huff_build", "mjg_debug_scale_path",
-    "mjg_debug_encode_path",
+    "mjg_debug_encode_path", "mjg_debug_oriented", "mjg_debug_orient",
 )
 
 
@@ -89,6 +89,12 @@ def load():
             L.mjg_open_crop.argtypes = [C.c_int, C.POINTER(MjgConfig)] + [C.c_int] * 5 + [C.POINTER(vp)]
         if hasattr(L, "mjg_open_pad"):  # absent from libraries built before 1.4 (A/B builds)
             L.mjg_open_pad.argtypes = [C.c_int, C.POINTER(MjgConfig)] + [C.c_int] * 9 + [C.POINTER(vp)]
+        if hasattr(L, "mjg_open_orient"):  # absent from libraries built before the orientation stage (A/B builds)
+            L.mjg_open_orient.argtypes = [C.c_int, C.POINTER(MjgConfig)] + [C.c_int] * 10 + [C.POINTER(vp)]
+            L.mjg_debug_oriented.argtypes = [vp, C.c_int, u8p, sz]
+            L.mjg_debug_oriented.restype = C.c_int
+            L.mjg_debug_orient.argtypes = [vp]
+            L.mjg_debug_orient.restype = C.c_int
         L.mjg_close.argtypes = [vp]
         L.mjg_close.restype = None
         L.mjg_frame_bytes.argtypes = [vp]
@@ -134,7 +140,7 @@ def load():
         # deep, no merging; and the multi-segment submit, which encoder.submit_segments guards)
         late = (("mjg_queue_depth", "mjg_ctx_queue_depth", "mjg_submit_segments", "mjg_max_segments",
                  "mjg_debug_huff_build", "mjg_open_src", "mjg_open_crop", "mjg_open_pad", "mjg_debug_scale_path",
-                 "mjg_debug_encode_path")
+                 "mjg_debug_encode_path", "mjg_open_orient", "mjg_debug_oriented", "mjg_debug_orient")
                 if os.environ.get("MJG_LIBRARY") else ())
         for name in EXPORTS:
             if name not in late:

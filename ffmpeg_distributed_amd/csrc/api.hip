@@ -211,6 +211,14 @@ struct Pass {
   const PlaneScale *ps = nullptr;  // the filters' device tables and StreamGeom
 };
 
+// One launch of the orientation stage (k_orient_plane; 0 luma, 1 chroma: U and V share it), built
+// at open like the sws stage's: the launcher of the instantiation and the plane's geometry.
+using OrientFn = void (*)(const OrientGeom &g, const SegList &in, uint8_t *dst, int nz, hipStream_t st);
+struct OrientPass {
+  OrientFn launch = nullptr;
+  OrientGeom g{};
+};
+
 struct Slot;
 using EncodeFn = void (*)(const mjg_ctx *c, Slot &S, const SegList &enc_in, int wgs, int ntasks);
 
@@ -249,6 +257,7 @@ struct Slot {
   hipStream_t st = nullptr;        // H2D, scale and k_encode of this slot's submits
   uint8_t *d_stage = nullptr;      // H2D staging for host submits (allocated on first use)
   uint8_t *d_scaled = nullptr;     // -vf scale: k_scale's output planes
+  uint8_t *d_orient = nullptr;     // -vf hflip / vflip / transpose: k_orient_plane's output frames
   uint32_t *d_stage_bits = nullptr;  // k_encode: per wave, lane-major staging of blocks past 128 bits
   int n = 0;  // frames of the launch
   uint32_t *d_scratch = nullptr;
@@ -286,6 +295,10 @@ struct mjg_ctx {
   int enc_grid = 0;             // persistent k_encode workgroups: every CU full (kEmitDefault)
   int enc_grid_cnt = 0;         // the same for the -huffman optimal counting pass (kCount: more LDS)
   bool scale = false;           // the sws stage runs: the sizes or the chroma formats differ
+  // -vf hflip / vflip / transpose (mjg_open_orient): T | FX << 1 | FY << 2, the first filter; every
+  // size and offset below then refers to the oriented frame (src_h x src_w when orient & 1)
+  int orient = 0;
+  OrientPass opass[2];          // its launches: 0 luma, 1 chroma
   size_t in_frame_bytes = 0, enc_frame_bytes = 0;
   // the crop rectangle (mjg_open_crop; the whole frame otherwise): the input of the sws stage,
   // or of k_encode without one
@@ -348,7 +361,7 @@ void free_ctx(mjg_ctx *c) {
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (Slot &S : c->slot) {
-    void *sp[] = {S.d_stage, S.d_scaled, S.d_stage_bits, S.d_scratch, S.d_stream, S.d_work, S.d_chunk_bits, S.d_chunk_off, S.d_group_ff, S.d_ff_off, S.d_frame_bits,
+    void *sp[] = {S.d_stage, S.d_scaled, S.d_orient, S.d_stage_bits, S.d_scratch, S.d_stream, S.d_work, S.d_chunk_bits, S.d_chunk_off, S.d_group_ff, S.d_ff_off, S.d_frame_bits,
                   S.d_status, S.d_frame_size, S.d_frame_offsets, S.d_seg_size, S.d_seg_off, S.d_done, S.d_out,
                   S.d_hist, S.d_ftabs, S.d_dht_nval, S.d_hdr_lens, S.d_dht, S.d_dbg, S.d_syms, S.d_symn};
     for (void *p : sp)
@@ -399,7 +412,8 @@ bool plan_scale_stream(int max_nw, int ht, int npv, StreamGeom *q, bool *hcl, si
 
 // A context's rectangles, resolved by check_config
 struct Layout {
-  int cx, cy, crw, crh;        // the crop rectangle in the source frame: the sws stage's / k_encode's input
+  int orient, ow, oh;          // the orientation and the oriented frame's size (orient 0: the source's)
+  int cx, cy, crw, crh;        // the crop rectangle in the oriented frame: the sws stage's / k_encode's input
   int px, py, pw, ph;          // the picture's place in the canvas and the canvas size (no pad: the picture)
   bool has_pad;                // false for the trivial rectangle
   int s_hsh, s_vsh, hsh, vsh;  // chroma shifts of the source format and of the encoded one
@@ -610,6 +624,7 @@ int alloc_slot(mjg_ctx *c, Slot &S) {
   S.st = slot_stream(c, (int)(&S - c->slot));
   if ((rc = dmalloc(&S.d_stage_bits, c->stage_cols * 64 * kStageWords))) return rc;
   if (c->scale && (rc = dmalloc(&S.d_scaled, B * c->enc_frame_bytes))) return rc;
+  if (c->orient && (rc = dmalloc(&S.d_orient, B * c->in_frame_bytes))) return rc;
   if ((rc = dmalloc(&S.d_scratch, B * NC * (size_t)kSlotWords)) ||
       (rc = dmalloc(&S.d_stream, B * NC * (size_t)kSlotWords)) ||
       (rc = dmalloc(&S.d_chunk_bits, B * NC)) || (rc = dmalloc(&S.d_chunk_off, B * NC)) ||
@@ -644,10 +659,12 @@ int alloc_slot(mjg_ctx *c, Slot &S) {
 }
 
 // open, step 1: the config, the rectangle and the pad (no device, no environment).
-// crop: x, y, w, h in luma samples of the source frame, or nullptr for the whole frame
+// orient: T | FX << 1 | FY << 2 (mjgpu.h), applied first: the crop, dst_w / dst_h and the pad
+// refer to the oriented frame
+// crop: x, y, w, h in luma samples of the oriented frame, or nullptr for the whole frame
 // pad: x, y, w, h in luma samples of the encoded frame (the picture's place and the canvas size),
 // or nullptr for no pad
-int check_config(const mjg_config &k, int src_cf, const int *crop, const int *pad, Layout *lay) {
+int check_config(const mjg_config &k, int src_cf, int orient, const int *crop, const int *pad, Layout *lay) {
   if (std::min({k.src_w, k.src_h, k.dst_w, k.dst_h}) < 1 || std::max({k.src_w, k.src_h, k.dst_w, k.dst_h}) > 16384)
     return set_err(MJG_E_INVALID, "bad frame size %dx%d -> %dx%d", k.src_w, k.src_h, k.dst_w, k.dst_h);
   if (k.qscale < 1 || k.qscale > 31) return set_err(MJG_E_INVALID, "qscale %d not in 1..31", k.qscale);
@@ -658,14 +675,21 @@ int check_config(const mjg_config &k, int src_cf, const int *crop, const int *pa
     return set_err(MJG_E_INVALID, "chroma_format %d", k.chroma_format);
   if (src_cf < MJG_CHROMA_420 || src_cf > MJG_CHROMA_444)
     return set_err(MJG_E_INVALID, "src_chroma_format %d", src_cf);
+  // the orientation: vf_transpose takes only formats whose two chroma shifts are equal
+  if (orient < 0 || orient > 7)
+    return set_err(MJG_E_INVALID, "orient %d not in 0..7 (T | FX << 1 | FY << 2)", orient);
+  if ((orient & 1) && src_cf == MJG_CHROMA_422)
+    return set_err(MJG_E_INVALID, "orient %d transposes a 4:2:2 source (only 4:2:0 and 4:4:4 keep their format)", orient);
+  const int ow = (orient & 1) ? k.src_h : k.src_w, oh = (orient & 1) ? k.src_w : k.src_h;
   // the rectangle (the frame sizes and the source format are valid here)
   const int s_hsh = src_cf == MJG_CHROMA_444 ? 0 : 1, s_vsh = src_cf == MJG_CHROMA_420 ? 1 : 0;
   const int cx = crop ? crop[0] : 0, cy = crop ? crop[1] : 0;
-  const int crw = crop ? crop[2] : k.src_w, crh = crop ? crop[3] : k.src_h;  // the sws stage's / k_encode's input size
+  const int crw = crop ? crop[2] : ow, crh = crop ? crop[3] : oh;  // the sws stage's / k_encode's input size
   if (crw < 1 || crh < 1)
     return set_err(MJG_E_INVALID, "crop %dx%d at (%d,%d): the size is not positive", crw, crh, cx, cy);
-  if (cx < 0 || cy < 0 || cx > k.src_w - crw || cy > k.src_h - crh)
-    return set_err(MJG_E_INVALID, "crop %dx%d at (%d,%d) is outside the %dx%d frame", crw, crh, cx, cy, k.src_w, k.src_h);
+  if (cx < 0 || cy < 0 || cx > ow - crw || cy > oh - crh)
+    return set_err(MJG_E_INVALID, "crop %dx%d at (%d,%d) is outside the %dx%d frame%s", crw, crh, cx, cy, ow, oh,
+                   orient ? " (the oriented one)" : "");
   if ((cx & ((1 << s_hsh) - 1)) || (cy & ((1 << s_vsh) - 1)))
     return set_err(MJG_E_INVALID, "crop %dx%d at (%d,%d): the position is not a multiple of the source's chroma "
                    "sub-sampling (%dx%d)", crw, crh, cx, cy, 1 << s_hsh, 1 << s_vsh);
@@ -697,7 +721,7 @@ int check_config(const mjg_config &k, int src_cf, const int *crop, const int *pa
     return set_err(MJG_E_INVALID, "unknown flags 0x%x", k.flags & ~kKnownFlags);
   if ((k.flags & MJG_F_RST) && (k.flags & MJG_F_HUFFMAN_OPTIMAL))
     return set_err(MJG_E_INVALID, "RST (slice threading) forces -huffman default");
-  *lay = Layout{cx, cy, crw, crh, px, py, pw, ph, has_pad, s_hsh, s_vsh, e_hsh, e_vsh};
+  *lay = Layout{orient, ow, oh, cx, cy, crw, crh, px, py, pw, ph, has_pad, s_hsh, s_vsh, e_hsh, e_vsh};
   return MJG_OK;
 }
 
@@ -707,19 +731,23 @@ int check_config(const mjg_config &k, int src_cf, const int *crop, const int *pa
 int plan_geometry(const mjg_config &k, int src_cf, const Layout &lay, bool unaligned_fetch, mjg_ctx *c) {
   const int cx = lay.cx, cy = lay.cy, crw = lay.crw, crh = lay.crh, px = lay.px, py = lay.py;
   const int s_hsh = lay.s_hsh, s_vsh = lay.s_vsh, hsh = lay.hsh, vsh = lay.vsh;
+  // the frame everything downstream reads: the oriented one (the source itself with orient 0; the
+  // same bytes per frame either way, the formats that transpose have equal chroma shifts)
+  const int fw = lay.ow, fh = lay.oh;
+  c->orient = lay.orient;
   c->has_pad = lay.has_pad;
   // the sws stage: a resize, or a -pix_fmt conversion (source format != encoded format; in
   // FFmpeg one swscale context does both, and tv->pc in the same pass)
   const int cf = k.chroma_format;
   // (a pad always runs it: k_encode then reads the canvas in d_scaled as any other sws output)
   c->scale = (crw != k.dst_w || crh != k.dst_h || src_cf != cf || c->has_pad);
-  const int scw = (k.src_w + s_hsh) >> s_hsh, sch = (k.src_h + s_vsh) >> s_vsh;
+  const int scw = (fw + s_hsh) >> s_hsh, sch = (fh + s_vsh) >> s_vsh;
   // the rectangle's chroma planes: at (cx >> hs, cy >> vs), the chroma size of a crw x crh frame
   // (inside the source's: cx, cy are multiples of the sub-sampling)
   const int ccw = (crw + s_hsh) >> s_hsh, cch = (crh + s_vsh) >> s_vsh;
   c->src_cplane = (long long)scw * sch;
-  c->src_off[0] = (long long)cy * k.src_w + cx;
-  c->src_off[1] = (long long)k.src_w * k.src_h + (long long)(cy >> s_vsh) * scw + (cx >> s_hsh);
+  c->src_off[0] = (long long)cy * fw + cx;
+  c->src_off[1] = (long long)fw * fh + (long long)(cy >> s_vsh) * scw + (cx >> s_hsh);
   c->src_off[2] = c->src_off[1] + c->src_cplane;
   // the encoded frame: the canvas under a pad, else the picture (the sws stage's output, or the
   // source rectangle itself); pcw x pch: the picture's chroma planes
@@ -734,7 +762,7 @@ int plan_geometry(const mjg_config &k, int src_cf, const Layout &lay, bool unali
     q.py = p ? py >> vsh : py;
     q.fill = p ? 128 : 0;
   }
-  c->in_frame_bytes = (size_t)k.src_w * k.src_h + 2 * (size_t)scw * sch;
+  c->in_frame_bytes = (size_t)fw * fh + 2 * (size_t)scw * sch;
   c->enc_frame_bytes = (size_t)w * h + 2 * (size_t)cw * ch;
 
   EncGeom &g = c->geom;
@@ -767,7 +795,7 @@ int plan_geometry(const mjg_config &k, int src_cf, const Layout &lay, bool unali
   // source planes' strides, the block offsets from the rectangle's first luma byte (submit_impl
   // adds src_off[0] to the frame pointers), the planes w x h / cw x ch of it (fetch_rows_edge's
   // clamps).  The whole frame in place: exactly the packed values.
-  g.y_stride = c->scale ? w : k.src_w;
+  g.y_stride = c->scale ? w : fw;
   g.c_stride = c->scale ? cw : scw;
   g.u_off = c->scale ? (long long)w * h : c->src_off[1] - c->src_off[0];
   g.v_off = c->scale ? g.u_off + (long long)cw * ch : c->src_off[2] - c->src_off[0];
@@ -778,7 +806,7 @@ int plan_geometry(const mjg_config &k, int src_cf, const Layout &lay, bool unali
   // the fetch at any alignment: only for a crop read in place, and only when a plane offset, a
   // row stride or the frame stride is no multiple of 8 (else every interior block already
   // passes the alignment test, given an aligned frame pointer, as for uncropped frames)
-  const bool is_crop = cx || cy || crw != k.src_w || crh != k.src_h;
+  const bool is_crop = cx || cy || crw != fw || crh != fh;
   const long long bits = c->src_off[0] | c->src_off[1] | c->src_off[2] | g.y_stride | g.c_stride | g.frame_stride;
   c->enc_ua = is_crop && !c->scale && (bits & 7) != 0 && unaligned_fetch;
   g.range_convert = (!c->scale && !k.in_full_range) ? 1 : 0;
@@ -789,7 +817,7 @@ int plan_geometry(const mjg_config &k, int src_cf, const Layout &lay, bool unali
     sg.sh = p ? cch : crh;
     sg.dw = p ? pcw : k.dst_w;
     sg.dh = p ? pch : k.dst_h;
-    sg.s_stride = p ? scw : k.src_w;  // rows of the source plane (wider than sw under a crop)
+    sg.s_stride = p ? scw : fw;  // rows of the source plane (wider than sw under a crop)
     sg.sw_magic = magic32((uint32_t)sg.sw);
     sg.d_stride = c->pad[p].cw;  // the encoded plane's rows: dw, or the wider canvas under a pad
     sg.s_fstride = (long long)c->in_frame_bytes;
@@ -967,6 +995,38 @@ void build_plan(mjg_ctx *c) {
   }
 }
 
+template <bool T, bool FX>
+void launch_orient(const OrientGeom &g, const SegList &in, uint8_t *dst, int nz, hipStream_t st) {
+  k_orient_plane<T, FX><<<g.gxy * nz, kCopyThreads, 0, st>>>(in, dst, g);
+}
+
+// The orientation stage's launches for luma and chroma (mjg_ctx::opass; no device, no
+// environment): the decoded frame's planes in the source format -> the same planes of the
+// oriented frame, both packed planar and in_frame_bytes apart
+void plan_orient(const mjg_config &k, const Layout &lay, mjg_ctx *c) {
+  if (!lay.orient) return;
+  const bool T = lay.orient & 1, FX = (lay.orient & 2) != 0;
+  for (int p = 0; p < 2; p++) {
+    OrientPass &q = c->opass[p];
+    OrientGeom &g = q.g;
+    g.sw = p ? (k.src_w + lay.s_hsh) >> lay.s_hsh : k.src_w;
+    g.sh = p ? (k.src_h + lay.s_vsh) >> lay.s_vsh : k.src_h;
+    g.s_off = g.d_off = p ? (long long)k.src_w * k.src_h : 0;
+    g.s_fstride = g.d_fstride = (long long)c->in_frame_bytes;
+    g.fy = (lay.orient & 4) ? 1 : 0;
+    g.sw_magic = magic32((uint32_t)g.sw);
+    g.tx = (g.sw + kOrientTile - 1) / kOrientTile;
+    g.ntiles = g.tx * ((g.sh + kOrientTileH - 1) / kOrientTileH);
+    g.tx_magic = magic32((uint32_t)g.tx);
+    const size_t pieces = ((size_t)g.sw * g.sh) >> 4, per = (size_t)kCopyThreads * kCopyVecs;
+    g.gxy = T ? (g.ntiles + kOrientWaves - 1) / kOrientWaves : (int)std::max<size_t>(1, (pieces + per - 1) / per);
+    g.gxy_magic = magic32((uint32_t)g.gxy);
+    q.launch = with_bool(T, [&](auto t) {
+      return with_bool(FX, [](auto fx) -> OrientFn { return launch_orient<decltype(t)::value, decltype(fx)::value>; });
+    });
+  }
+}
+
 // RC, DBG, UA: EncGeom's range_convert and debug_coefs, and the context's enc_ua (a crop read in
 // place at any alignment, fetch_rows<UA>)
 template <bool RC, int MODE, bool DBG, bool UA>
@@ -1010,7 +1070,8 @@ int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
   if (c->merge > 1) {  // slot buffers for merge * max_batch frames: within a share of free memory
     size_t fr = 0, tot = 0;
     HIP_TRY(hipMemGetInfo(&fr, &tot));
-    const double per_frame = 2.0 * (double)c->slot_NC * kSlotWords * 4 + 2.0 * (double)c->enc_frame_bytes;
+    const double per_frame = 2.0 * (double)c->slot_NC * kSlotWords * 4 + 2.0 * (double)c->enc_frame_bytes +
+                             (c->orient ? (double)c->in_frame_bytes : 0.0);
     if (kSlots * (double)c->merge * (double)k.max_batch * per_frame > kMergeMemShare * (double)fr) c->merge = 1;
   }
   if ((unsigned long long)k.max_batch * c->merge * g.nseg * g.nchunks * g.nchunks >= ((unsigned long long)1 << 40))
@@ -1056,14 +1117,15 @@ int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
   return alloc_slot(c, c->slot[0]);
 }
 
-int open_ctx(int device, const mjg_config *cfg, int src_cf, const int *crop, const int *pad, mjg_ctx *c) {
+int open_ctx(int device, const mjg_config *cfg, int src_cf, int orient, const int *crop, const int *pad, mjg_ctx *c) {
   c->device = device;
   c->cfg = *cfg;
   const mjg_config &k = *cfg;
   Layout lay;
   int rc;
-  if ((rc = check_config(k, src_cf, crop, pad, &lay))) return rc;
+  if ((rc = check_config(k, src_cf, orient, crop, pad, &lay))) return rc;
   if ((rc = plan_geometry(k, src_cf, lay, env_int("MJG_UNALIGNED_FETCH", 1) != 0, c))) return rc;
+  plan_orient(k, lay, c);
   quant_matrix(k.qscale, c->mprime, c->qmat);
   c->hdr = build_header(c->geom.w, c->geom.h, c->mprime, k.sar_num, k.sar_den, (k.flags & MJG_F_COM_ITU601) != 0,
                         k.chroma_format, c->rst, &c->dht_pos, &c->dht_end);
@@ -1133,12 +1195,12 @@ int mjg_device_numa_node(int device) {
 }
 
 namespace {
-int open_any(int device, const mjg_config *cfg, int src_chroma_format, const int *crop, const int *pad,
+int open_any(int device, const mjg_config *cfg, int src_chroma_format, int orient, const int *crop, const int *pad,
              mjg_ctx **out) {
   if (!cfg || !out) return set_err(MJG_E_INVALID, "null argument");
   *out = nullptr;
   mjg_ctx *c = new mjg_ctx();
-  const int rc = open_ctx(device, cfg, src_chroma_format, crop, pad, c);
+  const int rc = open_ctx(device, cfg, src_chroma_format, orient, crop, pad, c);
   if (rc) {
     const std::string keep = g_err;
     free_ctx(c);
@@ -1153,17 +1215,23 @@ int open_any(int device, const mjg_config *cfg, int src_chroma_format, const int
 int mjg_open_crop(int device, const mjg_config *cfg, int src_chroma_format, int crop_x, int crop_y, int crop_w,
                   int crop_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h};
-  return open_any(device, cfg, src_chroma_format, crop, nullptr, out);
+  return open_any(device, cfg, src_chroma_format, 0, crop, nullptr, out);
+}
+
+int mjg_open_orient(int device, const mjg_config *cfg, int src_chroma_format, int orient, int crop_x, int crop_y,
+                    int crop_w, int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
+  const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
+  return open_any(device, cfg, src_chroma_format, orient, crop, pad, out);
 }
 
 int mjg_open_pad(int device, const mjg_config *cfg, int src_chroma_format, int crop_x, int crop_y, int crop_w,
                  int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, crop, pad, out);
+  return open_any(device, cfg, src_chroma_format, 0, crop, pad, out);
 }
 
 int mjg_open_src(int device, const mjg_config *cfg, int src_chroma_format, mjg_ctx **out) {
-  return open_any(device, cfg, src_chroma_format, nullptr, nullptr, out);
+  return open_any(device, cfg, src_chroma_format, 0, nullptr, nullptr, out);
 }
 
 int mjg_open(int device, const mjg_config *cfg, mjg_ctx **out) {
@@ -1207,10 +1275,22 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
     HIP_TRY(hipMemcpyAsync(S.d_stage, frames, (size_t)n * c->in_frame_bytes, hipMemcpyHostToDevice, S.st));
     src = S.d_stage;
   }
-  const SegList in_sl = segs ? *segs : one_seg(src);  // the submit's input frames: the caller's segments, or one at src
+  SegList in_sl = segs ? *segs : one_seg(src);  // the submit's input frames: the caller's segments, or one at src
+  if (c->scale || c->orient) tmark(c, S, MJG_K_SCALE, 0);
+  if (c->orient) {  // the first filter: luma, then U and V in one launch as below; the rest reads one buffer
+    const bool uv1 = 2 * n <= 65535;
+    for (int p = 0; p < (uv1 ? 2 : 3); p++) {
+      OrientGeom og = c->opass[p ? 1 : 0].g;
+      og.nf = n;
+      if (p && uv1) og.s_poff = og.d_poff = c->src_cplane;
+      if (p == 2) og.s_off += c->src_cplane, og.d_off += c->src_cplane;
+      c->opass[p ? 1 : 0].launch(og, in_sl, S.d_orient, p && uv1 ? 2 * n : n, S.st);
+    }
+    HIP_TRY(hipGetLastError());
+    in_sl = one_seg(S.d_orient);
+  }
   SegList enc_in = in_sl;
   if (c->scale) {
-    tmark(c, S, MJG_K_SCALE, 0);
     // luma, then U and V in one launch (same filters; blockIdx.z >= n is V) while 2n fits the
     // grid's z range, else one launch each
     const bool uv1 = 2 * n <= 65535;
@@ -1235,6 +1315,7 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
     HIP_TRY(hipGetLastError());
     enc_in = one_seg(S.d_scaled);  // k_encode reads the scaled frames, one buffer
   } else {  // in place: EncGeom's offsets count from the rectangle's first luma byte (0: whole frames)
+    if (c->orient) tmark(c, S, MJG_K_SCALE, 1);  // an orientation alone: the interval holds its passes
     for (int k = 0; k < kMaxSegs; k++) enc_in.p[k] += c->src_off[0];
   }
   const int ntasks = g.nchunks * g.nseg * n;
@@ -1448,7 +1529,7 @@ int mjg_sync(mjg_ctx *c, uint64_t *frame_sizes, uint64_t *total) {
       }
       if (c->timing) {
         for (int k = 0; k < MJG_NUM_KERNELS; k++) {
-          if (k == MJG_K_SCALE && !c->scale) continue;
+          if (k == MJG_K_SCALE && !c->scale && !c->orient) continue;
           if (k == MJG_K_HUFF && !c->optimal) continue;
           const bool tail = is_tail_kernel(k);
           if (tail != c->timing_detail && (tail || k == MJG_K_TAIL)) continue;
@@ -1647,6 +1728,27 @@ int mjg_debug_planes(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
   const size_t f = (size_t)L.jf0[c->last_job] + (size_t)frame;
   HIP_TRY(hipMemcpy(out, L.d_scaled + f * c->enc_frame_bytes, c->enc_frame_bytes, hipMemcpyDeviceToHost));
   return MJG_OK;
+}
+
+int mjg_debug_oriented(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
+  if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
+  if (!c->orient) return set_err(MJG_E_STATE, "context has no orientation (orient 0)");
+  if (pending_jobs(c) > 0) {  // the latest synced submit's frames
+    const int rc = mjg_sync(c, nullptr, nullptr);
+    if (rc) return rc;
+  }
+  if (pending_jobs(c) > 0 || c->last < 0) return set_err(MJG_E_STATE, "sync every queued submit first");
+  const Slot &L = c->slot[c->last];
+  if (frame < 0 || frame >= L.jn[c->last_job]) return set_err(MJG_E_INVALID, "frame %d", frame);
+  if (cap < c->in_frame_bytes) return set_err(MJG_E_CAPACITY, "need %zu bytes", c->in_frame_bytes);
+  const size_t f = (size_t)L.jf0[c->last_job] + (size_t)frame;
+  HIP_TRY(hipMemcpy(out, L.d_orient + f * c->in_frame_bytes, c->in_frame_bytes, hipMemcpyDeviceToHost));
+  return MJG_OK;
+}
+
+int mjg_debug_orient(mjg_ctx *c) {
+  if (!c) return set_err(MJG_E_INVALID, "null context");
+  return c->orient;
 }
 
 int mjg_debug_huff_build(int device, const uint32_t *hist, int nframes, uint8_t *dht, uint32_t *nval) {

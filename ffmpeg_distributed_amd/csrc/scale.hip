@@ -845,4 +845,161 @@ __global__ __launch_bounds__(kCopyThreads) void k_pad_plane(const SegList src, u
   if (wb) d[jb] = (uint8_t)vb;
 }
 
+// k_orient_plane: `-vf hflip / vflip / transpose`, the first filter of the chain.
+// Every plane P (sw x sh) of the decoded frame becomes
+//   out[y][x] = in'[FY ? H - 1 - y : y][FX ? W - 1 - x : x],  in' = T ? transpose(P) : P  (W x H)
+// in a packed planar frame of the same byte count (the slot's d_orient), the bytes unchanged (no
+// range conversion: that stays with the sws stage or k_encode).  The source is the submit's
+// SegList (whole frames at any byte alignment), the destination one buffer; U and V go in one
+// launch (blockIdx >= gxy * nf is V, at s_poff / d_poff).  T and FX are template arguments, FY a
+// run-time flag.
+//   T = 0: a streaming copy as k_plane_copy's: the output plane of a (plane, frame) is one byte
+//   string cut into 16-byte pieces aligned on the destination; piece k covers bytes [head + 16 k,
+//   + 16), byte j is column j % sw of row j / sw (multiply-high, div_magic: j < 2^28).  A piece
+//   inside one output row is one unaligned 16-byte load from source row (FY ? sh - 1 - row : row)
+//   at column col (FX: at sw - 16 - col, the 16 bytes reversed in registers: the dwords swapped
+//   and each byte-swapped); a piece that runs over a row end is gathered byte by byte (16 / sw of
+//   the pieces).  Head and tail bytes go singly in the (plane, frame)'s first workgroup.
+//   T = 1: a tiled byte transpose without LDS.  A wave takes a tile of 128 rows x 64 columns of
+//   the source plane; lane (lr = lane & 15, lc = lane >> 4) loads 16 bytes of each of the source
+//   rows 8 lr .. 8 lr + 7 at tile column 16 lc (every load instruction covers 16 rows x 64
+//   contiguous bytes), transposes its eight 4 x 4 byte blocks with v_perm_b32 and stores 16 dword
+//   pairs: pair m holds source column 16 lc + m of its eight rows, i.e. eight consecutive bytes of
+//   output row (FY ? sw - 1 - col : col) at output column 8 lr (FX: sh - 8 - 8 lr, the eight bytes
+//   reversed: by the selectors inside a dword, and the dwords swapped); every store instruction
+//   covers 4 output rows x 128 contiguous bytes.  (Four rows per lane and 64-byte row pieces
+//   measured 14% slower: half of its write requests were partial lines)  The
+//   stores land at whatever alignment the plane offset and the output width sh leave.  A lane
+//   whose 8 x 16 block is not whole inside the plane (the partial tiles of a plane whose sizes
+//   are no multiples of the tile) moves its bytes one by one and reads nothing past the plane.
+struct OrientGeom {
+  int sw, sh;                      // the source plane (the output plane: sw x sh, T: sh x sw)
+  long long s_off, d_off;          // the plane's offset inside a source / an oriented frame
+  long long s_fstride, d_fstride;  // frame strides
+  long long s_poff, d_poff;        // the next plane's offset from this one (V from U)
+  int nf;                          // frames per plane
+  int fy;                          // FY
+  uint32_t sw_magic;               // T = 0: ceil(2^32 / sw), 0 when sw == 1
+  int tx;                          // T = 1: tile columns, ceil(sw / kOrientTile), and the plane's tiles
+  int ntiles;
+  uint32_t tx_magic;
+  int gxy;                         // workgroups per (plane, frame)
+  uint32_t gxy_magic;
+};
+
+constexpr int kOrientTile = 64;     // T = 1: source columns per tile
+constexpr int kOrientWaves = kCopyThreads / 64;  // T = 1: tiles per workgroup
+constexpr int kOrientTileH = 128;  // T = 1: source rows per tile (the tile: kOrientTileH rows x kOrientTile columns)
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef u32x2 u32x2_a1 __attribute__((aligned(1)));  // output rows start at any byte
+
+__device__ __forceinline__ uint32_t reverse_bytes(uint32_t w) { return __builtin_bswap32(w); }
+
+template <bool T, bool FX>
+__global__ __launch_bounds__(kCopyThreads) void k_orient_plane(const SegList src, uint8_t *__restrict__ dst,
+                                                               OrientGeom g) {
+  const int tid = threadIdx.x;
+  const int t = blockIdx.x;
+  const int z = div_magic(t, g.gxy_magic, g.gxy), blk = t - z * g.gxy;
+  const int pl = z >= g.nf, f = z - (pl ? g.nf : 0);
+  const uint8_t *s = seg_frame(src, f, g.s_fstride) + g.s_off + (pl ? g.s_poff : 0);
+  uint8_t *d = dst + (size_t)f * g.d_fstride + g.d_off + (pl ? g.d_poff : 0);
+  const int sw = g.sw, sh = g.sh;
+  if (!T) {
+    const int nb = sw * sh;  // < 2^28 (16384 x 16384)
+    const int head = min((int)(-(uintptr_t)d & 15), nb);
+    const int nv = (nb - head) >> 4;
+    // the source byte of output byte (row, col)
+    auto byte_at = [&](int j) -> uint8_t {
+      const int row = div_magic(j, g.sw_magic, sw), col = j - row * sw;
+      return s[(size_t)(g.fy ? sh - 1 - row : row) * sw + (FX ? sw - 1 - col : col)];
+    };
+    auto piece = [&](int j) -> u32x4 {
+      const int row = div_magic(j, g.sw_magic, sw), col = j - row * sw;
+      if (col + 16 <= sw) {
+        const uint8_t *rp = s + (size_t)(g.fy ? sh - 1 - row : row) * sw;
+        if (!FX) return *(const u32x4_a1 *)(rp + col);
+        const u32x4 w = *(const u32x4_a1 *)(rp + (sw - 16 - col));
+        return u32x4{reverse_bytes(w[3]), reverse_bytes(w[2]), reverse_bytes(w[1]), reverse_bytes(w[0])};
+      }
+      uint64_t wl = 0, wh = 0;  // (rolled: 16 / sw of the pieces take it)
+#pragma unroll 1
+      for (int b = 0; b < 16; b++) {
+        const uint64_t x = byte_at(j + b);
+        if (b < 8) wl |= x << (8 * b);
+        else wh |= x << (8 * (b - 8));
+      }
+      return u32x4{(uint32_t)wl, (uint32_t)(wl >> 32), (uint32_t)wh, (uint32_t)(wh >> 32)};
+    };
+    const int k0 = blk * (kCopyThreads * kCopyVecs) + tid;
+    u32x4 v[kCopyVecs];
+#pragma unroll
+    for (int i = 0; i < kCopyVecs; i++) {
+      const int k = k0 + i * kCopyThreads;
+      v[i] = k < nv ? piece(head + 16 * k) : u32x4{0, 0, 0, 0};
+    }
+#pragma unroll
+    for (int i = 0; i < kCopyVecs; i++) {
+      const int k = k0 + i * kCopyThreads;
+      if (k < nv) *(u32x4 *)(d + head + 16 * (size_t)k) = v[i];
+    }
+    if (blk == 0 && tid < 16) {
+      const int a = tid, b = head + 16 * nv + tid;
+      if (a < head) d[a] = byte_at(a);
+      if (b < nb) d[b] = byte_at(b);
+    }
+  } else {
+    const int tile = blk * kOrientWaves + (tid >> 6);
+    if (tile >= g.ntiles) return;
+    const int ty = div_magic(tile, g.tx_magic, g.tx), txi = tile - ty * g.tx;
+    const int lane = tid & 63, lr = lane & 15, lc = lane >> 4;
+    const int r0 = ty * kOrientTileH + 8 * lr, c0 = txi * kOrientTile + 16 * lc;  // the lane's 8 x 16 source block
+    if (r0 >= sh || c0 >= sw) return;
+    // output row of source column c, output column of source row r (the output rows are sh wide)
+    auto orow = [&](int c) -> size_t { return (size_t)(g.fy ? sw - 1 - c : c) * sh; };
+    if (r0 + 8 <= sh && c0 + 16 <= sw) {
+      u32x4 w[8];
+#pragma unroll
+      for (int k = 0; k < 8; k++) w[k] = *(const u32x4_a1 *)(s + (size_t)(r0 + k) * sw + c0);
+      const int oc = FX ? sh - 8 - r0 : r0;
+#pragma unroll
+      for (int q = 0; q < 4; q++) {  // the two 4 x 4 blocks at columns 4 q: rows a, b, c, e of each
+        uint32_t o[2][4];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+          const uint32_t a = w[4 * h][q], b = w[4 * h + 1][q], c = w[4 * h + 2][q], e = w[4 * h + 3][q];
+          // (v_perm_b32: selector bytes 0..3 pick from the second operand, 4..7 from the first)
+          const uint32_t ab_lo = __builtin_amdgcn_perm(b, a, FX ? 0x01050004u : 0x05010400u);  // a0 b0 a1 b1 (FX: b0 a0 b1 a1)
+          const uint32_t ab_hi = __builtin_amdgcn_perm(b, a, FX ? 0x03070206u : 0x07030602u);  // a2 b2 a3 b3
+          const uint32_t ce_lo = __builtin_amdgcn_perm(e, c, FX ? 0x01050004u : 0x05010400u);
+          const uint32_t ce_hi = __builtin_amdgcn_perm(e, c, FX ? 0x03070206u : 0x07030602u);
+          // column j of the block: bytes a_j b_j c_j e_j (FX: e_j c_j b_j a_j)
+          if (!FX) {
+            o[h][0] = __builtin_amdgcn_perm(ce_lo, ab_lo, 0x05040100u);
+            o[h][1] = __builtin_amdgcn_perm(ce_lo, ab_lo, 0x07060302u);
+            o[h][2] = __builtin_amdgcn_perm(ce_hi, ab_hi, 0x05040100u);
+            o[h][3] = __builtin_amdgcn_perm(ce_hi, ab_hi, 0x07060302u);
+          } else {
+            o[h][0] = __builtin_amdgcn_perm(ab_lo, ce_lo, 0x05040100u);
+            o[h][1] = __builtin_amdgcn_perm(ab_lo, ce_lo, 0x07060302u);
+            o[h][2] = __builtin_amdgcn_perm(ab_hi, ce_hi, 0x05040100u);
+            o[h][3] = __builtin_amdgcn_perm(ab_hi, ce_hi, 0x07060302u);
+          }
+        }
+        // eight output bytes per source column (FX: the rows 4..7 block first)
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+          *(u32x2_a1 *)(d + orow(c0 + 4 * q + j) + oc) = u32x2{o[FX ? 1 : 0][j], o[FX ? 0 : 1][j]};
+      }
+    } else {  // a partial block at the plane's right or bottom edge: byte by byte, inside the plane
+      const int nr = min(8, sh - r0), nc = min(16, sw - c0);
+#pragma unroll 1
+      for (int k = 0; k < nr; k++)
+#pragma unroll 1
+        for (int j = 0; j < nc; j++)
+          d[orow(c0 + j) + (FX ? sh - 1 - (r0 + k) : r0 + k)] = s[(size_t)(r0 + k) * sw + c0 + j];
+    }
+  }
+}
+
 }  // namespace mjg

@@ -1,7 +1,7 @@
 """GPU MJPEG encoder: the per-segment encode that the reference's worker runs
 (`ffmpeg -f matroska -i pipe: <remote_args> -f matroska pipe:`,
 ffmpeg_distributed.py:131-141), restricted to the profile
-`[-vf [crop=w:h:x:y,][scale=W:H:flags=bicubic][,pad=W:H:x:y]] -c:v mjpeg -q:v N -dct int [-huffman default|optimal] -bitexact`
+`[-vf [vflip|transpose=N,...][crop=w:h:x:y,][scale=W:H:flags=bicubic][,pad=W:H:x:y]] -c:v mjpeg -q:v N -dct int [-huffman default|optimal] -bitexact`
 (+ `-slices N` / `-thread_type slice` for the RST layout).
 
 Host-side wrapper over libmjgpu.so; frames are packed planar YUV (yuv420p / yuvj420p by
@@ -11,7 +11,11 @@ than the input's (`chroma=` is then the encoded format): the chroma planes are r
 the GPU as swscale does it.  `crop=(x, y, w, h)` makes a rectangle of the input frames the
 encoder's (or the scaler's) input; the frames handed over stay whole.  `pad=(x, y, W, H)` puts
 the picture (dst_w x dst_h) at (x, y) of a black W x H canvas, which is what gets encoded
-(`-vf ...,pad=W:H:x:y`).  No CPU fallback.
+(`-vf ...,pad=W:H:x:y`).  `orient=` (0..7: T | FX << 1 | FY << 2, what a run of hflip /
+vflip / transpose filters composes to, profile.compose_orient; the profile itself parses vflip and transpose) turns or mirrors every plane of
+the input frames on the GPU before anything else: the frames handed over stay the decoded ones,
+src_w x src_h, while the crop, dst_w / dst_h and the pad refer to the oriented frame (src_h x
+src_w under a transpose).  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -61,7 +65,7 @@ class MjpegEncoder:
                  sar=(1, 1), max_batch: int = 16, timing: bool = False,
                  debug_coefs: bool = False, sws_bitexact: bool = True, com_itu601: bool = False,
                  huffman: str = "default", chroma: str = "420", rst: bool = False,
-                 merge: bool = False, src_chroma: Optional[str] = None, crop=None, pad=None):
+                 merge: bool = False, src_chroma: Optional[str] = None, crop=None, pad=None, orient: int = 0):
         self._L = _lib.load()
         self.device = int(device)
         self.src_w, self.src_h = int(src_w), int(src_h)
@@ -71,7 +75,11 @@ class MjpegEncoder:
         self.crop = None if crop is None else tuple(int(v) for v in crop)
         if self.crop is not None and len(self.crop) != 4:
             raise ValueError(f"crop {crop!r}: (x, y, w, h)")
-        in_w, in_h = (self.src_w, self.src_h) if self.crop is None else self.crop[2:]
+        # orient: T | FX << 1 | FY << 2, the first filter (mjg_open_orient); or_w x or_h is the oriented
+        # frame, which the crop, the encoded size and the pad refer to
+        self.orient = int(orient)
+        self.or_w, self.or_h = (self.src_h, self.src_w) if self.orient & 1 else (self.src_w, self.src_h)
+        in_w, in_h = (self.or_w, self.or_h) if self.crop is None else self.crop[2:]
         self.dst_w = int(dst_w if dst_w is not None else in_w)
         self.dst_h = int(dst_h if dst_h is not None else in_h)
         # pad: (x, y, W, H) in luma samples of the encoded frames, resolved as profile.resolve_pad
@@ -118,7 +126,14 @@ class MjpegEncoder:
                         int(qscale), int(sar[0]), int(sar[1]), self.max_batch, flags,
                         _lib.CHROMA_FORMATS[self.chroma])
         h = C.c_void_p()
-        if self.pad is not None:
+        if self.orient:
+            if not hasattr(self._L, "mjg_open_orient"):
+                raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_orient")
+            rect = self.crop if self.crop is not None else (0, 0, self.or_w, self.or_h)
+            canvas = self.pad if self.pad is not None else (0, 0, self.dst_w, self.dst_h)
+            check(self._L.mjg_open_orient(self.device, C.byref(cfg), _lib.CHROMA_FORMATS[self.src_chroma],
+                                          self.orient, *rect, *canvas, C.byref(h)))
+        elif self.pad is not None:
             if not hasattr(self._L, "mjg_open_pad"):
                 raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_pad")
             rect = self.crop if self.crop is not None else (0, 0, self.src_w, self.src_h)
@@ -344,6 +359,17 @@ class MjpegEncoder:
         n = i420_frame_bytes(self.enc_w, self.enc_h, self.chroma)
         out = np.zeros(n, np.uint8)
         check(self._L.mjg_debug_planes(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)), n))
+        return out
+
+    def debug_oriented(self, frame: int = 0) -> np.ndarray:
+        """The oriented frame (k_orient_plane's output) of a frame of the last synced submit:
+        packed planar, or_w x or_h in the input format `src_chroma`, frame_bytes bytes.  Only for
+        an encoder opened with a non-zero `orient`."""
+        if not hasattr(self._L, "mjg_debug_oriented"):
+            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_debug_oriented")
+        out = np.zeros(self.frame_bytes, np.uint8)
+        check(self._L.mjg_debug_oriented(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                         out.size))
         return out
 
     def scale_path(self, plane: int) -> int:

@@ -10,7 +10,15 @@ with FILTERS one of
     crop=...,scale=W:H[:flags=bicubic...]   (in this order)
     any of these, or nothing, followed by
     pad=W:H[:x:y[:black]]                   (also width= / w=, height= / h=, x=, y=, color= / c=; last)
-where the crop values are decimal integers (no expressions); `Profile.crop` is the request as
+    and in front of any of these, or alone, a run of any length and order of
+    vflip | transpose=N | transpose=dir=N | transpose=<name>   (N 0..3; cclock_flip, clock, cclock,
+                                            clock_flip; optionally :passthrough=none)
+which is composed here into one of eight plane maps, `Profile.orient` = T | FX << 1 | FY << 2
+(`vflip,vflip` is 0 and costs nothing).  `hflip` is not parsed: the library and the
+encoder take its map (orient 2) and compose_orient composes it, but a graph that names it stays
+outside the profile, as it was (DESIGN §4.12 says why).  An orientation filter after a crop, scale
+or pad, transpose values 4..7, a passthrough other than none and any other option are outside the
+profile.  The crop values are decimal integers (no expressions); `Profile.crop` is the request as
 given and `resolve_crop` turns it into a rectangle of a given input (vf_crop.c's rounding,
 defaults and clamping: DESIGN §4.8).  The pad values are decimal integers too (W / H 0 or absent:
 the input's; a negative x / y centres), plus the two centring expressions x=(ow-iw)/2 and
@@ -53,6 +61,9 @@ class Profile:
     # -vf ...,pad=...: the request as given, {"w", "h", "x", "y"} -> int, None (absent) or, for x / y,
     # the centring expression; unresolved (resolve_pad needs the pad's input size and format); None: no pad
     pad: Optional[dict] = None
+    # a leading run of vflip / transpose filters, composed: T | FX << 1 | FY << 2 (compose_orient);
+    # the crop, the scale and the pad then see the oriented frame.  0: none
+    orient: int = 0
 
 
 class Unsupported(ValueError):
@@ -171,8 +182,91 @@ def resolve_pad(spec: dict, in_w: int, in_h: int, chroma: str) -> Tuple[int, int
     return x, y, W, H
 
 
+ORIENT_FILTERS = ("vflip", "transpose")     # what _parse_vf takes as a leading run (hflip: see the module docstring)
+TRANSPOSE_DIRS = {"cclock_flip": 0, "clock": 1, "cclock": 2, "clock_flip": 3}
+
+
+def orient_after(orient: int, flt: int) -> int:
+    """The orientation (T | FX << 1 | FY << 2: every plane becomes flip_FX,FY(T ? P' : P)) of
+    `orient` followed by the filter with orientation `flt`.  A flip after a flip toggles its bit;
+    transposing a flipped plane transposes it and swaps the two flips (a mirrored column order
+    becomes a mirrored row order), and the filter's own flips follow."""
+    t, fx, fy = orient & 1, (orient >> 1) & 1, (orient >> 2) & 1
+    if flt & 1:
+        t, fx, fy = t ^ 1, fy, fx
+    return t | ((fx ^ ((flt >> 1) & 1)) << 1) | ((fy ^ ((flt >> 2) & 1)) << 2)
+
+
+def _parse_orient(f: str) -> int:
+    """One hflip / vflip / transpose filter -> its orientation.  vf_transpose.c: dir 0 cclock_flip
+    out[y][x] = in[x][y], 1 clock in[h-1-x][y], 2 cclock in[x][w-1-y], 3 clock_flip
+    in[h-1-x][w-1-y]: the transpose, then a flip of the columns (1), the rows (2) or both (3)."""
+    name, _, opts = f.partition("=")
+    if name in ("hflip", "vflip"):
+        if opts or "=" in f:
+            raise Unsupported(f"{name} option {opts!r} (the filter takes none on the GPU path)")
+        return 2 if name == "hflip" else 4
+    d, pos = None, 0
+    for p in opts.split(":") if opts else []:
+        if "=" in p:
+            k, v = p.split("=", 1)
+        else:
+            if pos >= 2:
+                raise Unsupported(f"transpose option {p!r} (positional options are dir:passthrough)")
+            k, v = ("dir", "passthrough")[pos], p
+            pos += 1
+        if k == "passthrough":
+            if v != "none":
+                raise Unsupported(f"transpose passthrough={v} (only passthrough=none is GPU-accelerated)")
+        elif k == "dir":
+            if v in TRANSPOSE_DIRS:
+                d = TRANSPOSE_DIRS[v]
+            elif v.isascii() and v.isdigit() and int(v) <= 3:
+                d = int(v)
+            else:
+                raise Unsupported(f"transpose dir={v} (only 0..3 or cclock_flip, clock, cclock, clock_flip are "
+                                  f"GPU-accelerated; 4..7 are the deprecated passthrough forms)")
+        else:
+            raise Unsupported(f"transpose option {k!r}")
+    d = 0 if d is None else d          # vf_transpose's default dir is cclock_flip
+    return 1 | ((d & 1) << 1) | ((d >> 1) << 2)
+
+
+def compose_orient(filters: Sequence[str]) -> int:
+    """The orientation a run of hflip / vflip / transpose filters composes to (0..7)."""
+    o = 0
+    for f in filters:
+        o = orient_after(o, _parse_orient(f))
+    return o
+
+
 def _parse_vf(vf: str):
-    """-vf value -> (crop request or None, scale size or None, sws flags, pad request or None)."""
+    """-vf value -> (crop request or None, scale size or None, sws flags, pad request or None,
+    orientation).  A leading run of orientation filters is composed and taken off; the limits on
+    the number and order of filters apply to what follows it."""
+    if ";" not in vf:
+        fs = vf.split(",")
+        names = [f.split("=", 1)[0] for f in fs]
+        n = 0
+        while n < len(fs) and names[n] in ORIENT_FILTERS:
+            n += 1
+        late = [nm for nm in names[n:] if nm in ORIENT_FILTERS]
+        if late:
+            raise Unsupported(f"filter graph {vf!r}: {len(fs)} filters, {late[0]} after {names[n]} (vflip and "
+                              f"transpose are GPU-accelerated only in front of [crop,][scale,][pad])")
+        if n and "hflip" in names:
+            raise Unsupported(f"filter graph {vf!r}: hflip is not GPU-accelerated (of the orientation filters only "
+                              f"vflip and transpose are)")
+        if n:
+            orient = compose_orient(fs[:n])
+            if n == len(fs):
+                return None, None, ("bicubic",), None, orient
+            return _parse_chain(",".join(fs[n:])) + (orient,)
+    return _parse_chain(vf) + (0,)
+
+
+def _parse_chain(vf: str):
+    """[crop][,scale][,pad] -> (crop request or None, scale size or None, sws flags, pad request or None)."""
     fs = vf.split(",")
     names = [f.split("=", 1)[0] for f in fs]
     if ";" not in vf and "pad" in names[:-1]:
@@ -294,6 +388,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
     scale = None
     crop = None
     pad = None
+    orient = 0
     flags: Tuple[str, ...] = ("bicubic",)
     i = 0
 
@@ -334,7 +429,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
             if any(name != "bitexact" for _, name in _flag_ops(v)):
                 raise Unsupported(f"-fflags {v}")
         elif o in ("-vf", "-filter:v"):
-            crop, scale, flags, pad = _parse_vf(val())
+            crop, scale, flags, pad, orient = _parse_vf(val())
         elif o in ("-an", "-sn", "-dn", "-y"):
             pass
         elif o in ("-threads", "-threads:v"):
@@ -384,7 +479,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
     if rst:
         huff = "default"  # mjpegenc.c: slice_context_count > 1 forces HUFFMAN_TABLE_DEFAULT
     return Profile(qscale=effective_qscale(q), q_arg=q, scale=scale, sws_flags=flags, huffman=huff,
-                   rst=rst, chroma=chroma, crop=crop, pad=pad)
+                   rst=rst, chroma=chroma, crop=crop, pad=pad, orient=orient)
 
 
 PIX_FMT_CHROMA = {"yuvj420p": "420", "yuvj422p": "422", "yuvj444p": "444"}

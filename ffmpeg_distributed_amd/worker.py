@@ -22,6 +22,11 @@ A `pad=...` at the end of the graph is resolved against the picture it follows (
 output, the crop's rectangle or the input: profile.resolve_pad) and encoded as a black canvas
 around it; a picture whose size is no multiple of the format's chroma sub-sampling, and a pad
 with a -pix_fmt conversion but no scale in front of it, go to the real ffmpeg.
+A leading run of `vflip` / `transpose` filters (profile.Profile.orient) is applied by the
+GPU to the whole decoded frames before anything else; the crop, the scale, the SAR and the pad
+then start from the oriented size (height x width under a transpose, the SAR inverted as
+vf_transpose does).  A transpose of a 4:2:2 input goes to the real ffmpeg, which converts the
+format first.
 """
 from __future__ import annotations
 
@@ -457,15 +462,28 @@ def resample_plan(prof, info):
     return f"-pix_fmt needs {src} -> {dst} chroma resampling"
 
 
-def encoder_key(prof, info, dst_w, dst_h, sar, com_itu601, batch, rect=None, pad=None):
+def encoder_key(prof, info, dst_w, dst_h, sar, com_itu601, batch, rect=None, pad=None, orient=0):
     """What an encoder context kept between segments (serve / resident mode) depends on: the
     input's shape and format and everything of the profile the context is opened with, the
-    encoded chroma format (-pix_fmt), the resolved crop rectangle (x, y, w, h) and the resolved
-    pad (x, y, W, H) included."""
+    encoded chroma format (-pix_fmt), the resolved crop rectangle (x, y, w, h), the resolved
+    pad (x, y, W, H) and the orientation (0..7) included."""
     src_chroma, dst_chroma = resample_plan(prof, info)
     return (info.width, info.height, dst_w, dst_h, info.full_range, prof.qscale, sar,
             com_itu601, prof.huffman, src_chroma, dst_chroma, prof.rst, batch,
-            None if rect is None else tuple(rect), None if pad is None else tuple(pad))
+            None if rect is None else tuple(rect), None if pad is None else tuple(pad), int(orient))
+
+
+def oriented_size(w: int, h: int, orient: int):
+    """The size of a w x h frame after the orientation (T | FX << 1 | FY << 2): h x w under T."""
+    return (h, w) if orient & 1 else (w, h)
+
+
+def oriented_sar(sar, orient: int):
+    """The SAR after the orientation: vf_transpose sets 1 / SAR when the input's is known (its
+    numerator is not 0), the flips keep it; an unknown SAR stays unknown."""
+    if orient & 1 and sar and sar[0] > 0 and sar[1] > 0:
+        return (sar[1], sar[0])
+    return sar
 
 
 def pad_fallthrough_reason(prof, in_size, src_chroma, dst_chroma) -> Optional[str]:
@@ -529,18 +547,27 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
         stderr.flush()
         return ffmpeg_fallthrough(src, args, stdout, stderr)
     src_chroma, dst_chroma = plan
+    # -vf vflip / transpose in front: everything below starts from the oriented frame.
+    # vf_transpose takes only formats whose two chroma shifts are equal
+    orient = prof.orient
+    if orient & 1 and src_chroma == "422":
+        stderr.write(f"gpu:{device}: transpose of a 4:2:2 input: FFmpeg converts the format first; "
+                     f"running ffmpeg on the CPU\n")
+        stderr.flush()
+        return ffmpeg_fallthrough(src, args, stdout, stderr)
+    or_w, or_h = oriented_size(info.width, info.height, orient)
     # -vf crop: the rectangle of this input (the filter sees the decoded format); the scale
     # filter, the SAR and the encoded size then start from its size
     rect = None
     if prof.crop is not None:
         try:
-            rect = profile.resolve_crop(prof.crop, info.width, info.height, src_chroma)
+            rect = profile.resolve_crop(prof.crop, or_w, or_h, src_chroma)
         except profile.CropError as e:  # ffmpeg fails to configure the filter: no pass-through
             stderr.write(f"gpu:{device}: crop: {e}\n")
             stderr.flush()
             src.close(kill=True)
             return 1
-    in_size = (info.width, info.height) if rect is None else (rect[2], rect[3])
+    in_size = (or_w, or_h) if rect is None else (rect[2], rect[3])
     dst_w, dst_h = prof.scale or in_size
     # -vf ...,pad: the canvas around the picture (dst_w x dst_h).  With a scale in front the pad
     # sees the encoded format (the scale converts), else the input's, which is then the encoded one
@@ -573,8 +600,10 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
 
     # (a crop leaves the SAR as it is: keep_aspect=0; scaled_sar of equal sizes only reduces it;
     # a pad leaves it alone too: the scale's SAR, from the picture's size, not the canvas's)
-    sar = profile.scaled_sar(info.sar, in_size, (dst_w, dst_h))
-    key = encoder_key(prof, info, dst_w, dst_h, sar, opts.com_itu601 and not info.full_range, batch, rect, pad)
+    # (a transpose hands on 1 / SAR when the SAR is known: vf_transpose config_props_output)
+    sar = profile.scaled_sar(oriented_sar(info.sar, orient), in_size, (dst_w, dst_h))
+    key = encoder_key(prof, info, dst_w, dst_h, sar, opts.com_itu601 and not info.full_range, batch, rect, pad,
+                      orient)
     nbuf = NBUF
     if cache is not None and cache.get("key") == key:
         enc, bufs, obufs = cache["enc"], cache["bufs"], cache["obufs"]
@@ -584,7 +613,8 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
         enc = MjpegEncoder(device, info.width, info.height, dst_w, dst_h, full_range=info.full_range,
                            qscale=prof.qscale, sar=sar, max_batch=batch,
                            com_itu601=opts.com_itu601 and not info.full_range, huffman=prof.huffman,
-                           chroma=dst_chroma, src_chroma=src_chroma, rst=prof.rst, crop=rect, pad=pad)
+                           chroma=dst_chroma, src_chroma=src_chroma, rst=prof.rst, crop=rect, pad=pad,
+                           orient=orient)
         bufs = [PinnedBuffer(batch * enc.frame_bytes) for _ in range(nbuf)]
         # page-locked output buffers: the packets are DMA'd into one (enc.fetch_into) and the
         # muxer writes them from it; regrown when a submit's JPEGs do not fit

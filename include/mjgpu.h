@@ -6,8 +6,8 @@
  *     nice -n10 ionice -c3 ffmpeg -f matroska -i pipe: <remote_args> -f matroska pipe:
  * and launched/supervised at ffmpeg_distributed.py:139-141 (FFMPEGProc.run,
  * ffmpeg_distributed.py:59-91).  For the north-star profile
- *     [-vf [crop=w:h:x:y,][scale=W:H:flags=bicubic][,pad=W:H:x:y]] -c:v mjpeg -q:v N -dct int -huffman default -bitexact
- * (and `-pix_fmt yuvj420p|yuvj422p` from a 4:4:4 or 4:2:2 input: the chroma down-sampling
+ *     [-vf [vflip|transpose=N,...][crop=w:h:x:y,][scale=W:H:flags=bicubic][,pad=W:H:x:y]] -c:v mjpeg -q:v N -dct int -huffman default -bitexact
+ * (a leading run of vflip / transpose: one of eight plane maps, mjg_open_orient; and `-pix_fmt yuvj420p|yuvj422p` from a 4:4:4 or 4:2:2 input: the chroma down-sampling
  * FFmpeg's auto-inserted scaler does, taken to be its default bicubic; `-vf crop=...` alone or
  * before the scale: a rectangle of the decoded frames, mjg_open_crop; `pad=...` as the last
  * filter: the picture on a black canvas, mjg_open_pad)
@@ -159,6 +159,27 @@ int mjg_open_crop(int device, const mjg_config *cfg, int src_chroma_format,
 int mjg_open_pad(int device, const mjg_config *cfg, int src_chroma_format,
                  int crop_x, int crop_y, int crop_w, int crop_h,
                  int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
+/* mjg_open_pad behind an orientation (`-vf hflip`, `vflip`, `transpose=N`, any run of them at the
+ * front of the graph): orient = (T ? 1 : 0) | (FX ? 2 : 0) | (FY ? 4 : 0) maps every plane P
+ * (w x h) of the decoded frame, the chroma planes as planes of their own, to
+ *     out[y][x] = in'[FY ? H-1-y : y][FX ? W-1-x : x],   in' = T ? transpose(P) : P   (W x H),
+ * so hflip is 2, vflip 4, the half turn 6, transpose=0 (cclock_flip) 1, transpose=1 (clock) 3,
+ * transpose=2 (cclock) 5 and transpose=3 (clock_flip) 7.  The orientation is the first filter:
+ * cfg->src_w / src_h stay the decoded frame's size (mjg_frame_bytes and every submit carry whole
+ * decoded frames), while the crop rectangle, dst_w / dst_h and the pad refer to the oriented frame,
+ * src_h x src_w when orient & 1; without a crop the caller passes that frame's full rectangle.
+ * k_orient_plane writes the oriented frames (same format, same bytes per frame, no range
+ * conversion) into a buffer of the launch slot, from the submit's segments; the sws stage, or
+ * without one k_encode in place, reads that buffer.  Its launches are part of the MJG_K_SCALE
+ * interval, which an orientation alone opens too.  orient 0 is exactly mjg_open_pad: no buffer,
+ * the same launches.  MJG_E_INVALID (before any HIP call, with a message that names the
+ * orientation) for an orient outside 0..7 and for orient & 1 with a 4:2:2 source (vf_transpose
+ * converts such a format first); then mjg_open_pad's checks against the oriented size.
+ * (Added without a version step: mjg_version() stays 105, which tests/test_abi.py pins; a caller
+ * that may meet an older library looks for the symbol, as _lib.py does.) */
+int mjg_open_orient(int device, const mjg_config *cfg, int src_chroma_format, int orient,
+                    int crop_x, int crop_y, int crop_w, int crop_h,
+                    int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
 void mjg_close(mjg_ctx *ctx);
 
 /* Bytes of one packed planar input frame (src_w x src_h in the source chroma format). */
@@ -265,6 +286,13 @@ int mjg_debug_scale_path(mjg_ctx *ctx, int plane);
  * a row stride or the frame stride that is no multiple of 8, unless MJG_UNALIGNED_FETCH=0 at
  * open).  A negative MJG_E_* code for a null context.  Host state only.  (mjg_version() >= 105.) */
 int mjg_debug_encode_path(mjg_ctx *ctx);
+/* The oriented frame (k_orient_plane's output: packed planar, mjg_frame_bytes bytes, the oriented
+ * size in the source format) of frame `frame` of the last synced submit.  MJG_E_STATE for a
+ * context without orientation.  (With mjg_open_orient.) */
+int mjg_debug_oriented(mjg_ctx *ctx, int frame, uint8_t *out, size_t cap);
+/* The orientation of the context (0..7; mjg_open_orient), or a negative MJG_E_* code for a null
+ * context.  Host state only.  (With mjg_open_orient.) */
+int mjg_debug_orient(mjg_ctx *ctx);
 /* Filter tables the context generated: plane 0 = luma, 1 = chroma; dir 0 = horizontal,
  * 1 = vertical.  taps/len may be queried with coeff == NULL.  As mjg_debug_planes: only when
  * the sws stage runs. */
