@@ -7,12 +7,14 @@ shape reaches the path it means to check.
     chunk) at which each work unit of kBatch tasks starts (a unit that starts at chunk != 0
     recomputes its DC predictors from pixel rows: carry_row);
   - copy_span: workgroups and vector slots a plane of n bytes takes in k_plane_copy / k_pad_plane;
+  - orient_span / orient_cells: the tiles and workgroups k_orient_plane takes for a source plane, and
+    its instantiation (plan_orient), for tests/test_gpu_orient_chain.py;
   - scale_variant / copy_pad_cells: the kernel instantiation build_plan picks for a plane;
-  - predict_paths: what mjg_debug_encode_path and mjg_debug_scale_path will report for a
-    crop / -pix_fmt / scale / pad configuration (the rules of plan_geometry and plan_plane_scale; the
-    filters come from the library's own device-free mjg_sws_filter).
+  - predict_paths: what mjg_debug_encode_path and mjg_debug_scale_path will report for an
+    orient / crop / -pix_fmt / scale / pad configuration (the rules of plan_geometry and
+    plan_plane_scale; the filters come from the library's own device-free mjg_sws_filter).
 
-kBatch, kCopyThreads, kCopyVecs and the tile kernel's constants are parsed from the kernel
+kBatch, kCopyThreads, kCopyVecs, the orientation's tile and the tile kernel's constants are parsed from the kernel
 sources, so a change there moves these values and a hollowed-out test fails its precondition."""
 import os
 import re
@@ -40,6 +42,9 @@ SCALE_ALIAS_WORDS = _const("scale.hip", "kScaleAliasWords")
 STREAM_THREADS = _const("scale.hip", "kStreamThreads")
 STREAM_MAX_PIECES = _const("scale.hip", "kStreamMaxPieces")
 STREAM_BAND = _const("scale.hip", "kStreamBand")
+ORIENT_TILE = _const("scale.hip", "kOrientTile")
+ORIENT_TILE_H = _const("scale.hip", "kOrientTileH")
+ORIENT_WAVES = COPY_THREADS // 64  # scale.hip: kCopyThreads / 64 (tests/test_chain_geom.py checks that it still says so)
 
 EncGeom = namedtuple("EncGeom", "mbw mbh nseg seg_blocks nchunks ntasks")
 
@@ -136,6 +141,32 @@ def copy_span(nbytes):
     return wgs, slots
 
 
+OrientSpan = namedtuple("OrientSpan", "tx ty ntiles wgs idle right bottom partial_past_first")
+
+
+def orient_cells(orient):
+    """(T, FX, fy) of k_orient_plane<T, FX> with OrientGeom::fy for orient = T | FX << 1 | FY << 2."""
+    return bool(orient & 1), bool(orient & 2), (orient >> 2) & 1
+
+
+def orient_span(sw, sh, transposing):
+    """What plan_orient and k_orient_plane derive for one source plane of sw x sh.
+    T = 0: copy_span(sw sh), the mirrored streaming copy's (workgroups, vector slots in use).
+    T = 1: tile columns and rows (kOrientTile columns x kOrientTileH rows a tile, one wave each),
+    tiles, workgroups of kOrientWaves tiles and the idle waves of the last one (tile >= ntiles);
+    whether some lane's 16-column x 8-row block is cut by the plane's right edge (sw % 16) / its
+    bottom edge (sh % 8) and so moves byte by byte, and whether a tile past the first workgroup
+    holds such a lane."""
+    if not transposing:
+        return copy_span(sw * sh)
+    tx, ty = (sw + ORIENT_TILE - 1) // ORIENT_TILE, (sh + ORIENT_TILE_H - 1) // ORIENT_TILE_H
+    ntiles = tx * ty
+    wgs = (ntiles + ORIENT_WAVES - 1) // ORIENT_WAVES
+    right, bottom = sw % 16 != 0, sh % 8 != 0
+    past = any((right and t % tx == tx - 1) or (bottom and t // tx == ty - 1) for t in range(ORIENT_WAVES, ntiles))
+    return OrientSpan(tx, ty, ntiles, wgs, wgs * ORIENT_WAVES - ntiles, right, bottom, past)
+
+
 # mjg_debug_scale_path's values
 NONE, COPY, TILE, STREAM, PADCOPY = 0, 1, 2, 3, 4
 IN_PLACE, UA = 1, 2  # mjg_debug_encode_path's bits
@@ -223,12 +254,17 @@ def plane_path(sw, sh, dw, dh, has_pad, plane_copy=True):
     return STREAM if tile_lds(sw, sh, dw, dh) > 64 * 1024 else TILE
 
 
-def predict_paths(w, h, src, rect, dst, dw, dh, pad, unaligned_fetch=True, plane_copy=True):
+def predict_paths(w, h, src, rect, dst, dw, dh, pad, unaligned_fetch=True, plane_copy=True, orient=0):
     """(encode_path, (luma scale_path, chroma scale_path), RECT) of a context on w x h frames in
     `src`, cropped to rect (None: whole frames), encoded in `dst` at dw x dh (None: the
     rectangle's size) on the canvas pad = (x, y, W, H) (None: no pad).  RECT: the luma copy is
     k_plane_copy's rectangle form.  unaligned_fetch / plane_copy: MJG_UNALIGNED_FETCH /
-    MJG_PLANE_COPY not 0 at open."""
+    MJG_PLANE_COPY not 0 at open.  orient (T | FX << 1 | FY << 2): everything after the
+    orientation is derived from the oriented frame as if it were the source (plan_geometry: fw =
+    lay.ow), h x w under T, and the rectangle lies in it; an orientation alone is no crop."""
+    if orient & 1:
+        assert src != "422"
+        w, h = h, w
     x, y, rw, rh = rect or (0, 0, w, h)
     dw, dh = dw or rw, dh or rh
     has_pad = pad is not None and tuple(pad) != (0, 0, dw, dh)
@@ -379,3 +415,78 @@ SWEEP_FLOORS = [
     {"crop_in_place_ua": 3, "crop_in_place_aligned": 2, "rect_copy": 1, "pad_copy": 3, "pad_with_scale": 9, "stream": 1,
      "host": 6, "dev_odd": 11, "segments": 7, "merged": 6},
 ]
+
+
+# ------------------------------------------------------------------ the seeded sweep with an orientation
+ORIENT_FEATURES = (tuple("map%d" % o for o in range(1, 8))
+                   + ("luma_t0_past_one_wg", "luma_t1_past_one_wg", "orient_alone_in_place", "crop_in_place_ua",
+                      "crop_in_place_aligned", "sws_reads_orient") + SUBMITS)
+
+OrientConfig = namedtuple("OrientConfig", Config._fields + ("orient",))
+
+
+def orient_sweep_configs(seed, count):
+    """sweep_configs(seed, count), each with an orientation from a generator of its own: 1..7, or
+    one of 2, 4, 6 where the source is 4:2:2 (no transpose of it).  The drawn w x h is the
+    oriented frame, which the rectangle, the size and the pad refer to: the source frames are
+    source_size(cfg), h x w under a transposing map."""
+    import numpy as np
+    rng = np.random.default_rng([seed, 0x6f72])
+    out = []
+    for c in sweep_configs(seed, count):
+        o = (2, 4, 6)[int(rng.integers(3))] if c.src == "422" else 1 + int(rng.integers(7))
+        out.append(OrientConfig(*c, o))
+    return out
+
+
+def source_size(cfg):
+    return (cfg.h, cfg.w) if cfg.orient & 1 else (cfg.w, cfg.h)
+
+
+def orient_predict(cfg):
+    """predict_paths of an OrientConfig (from its source size, as a context is opened)."""
+    sw, sh = source_size(cfg)
+    return predict_paths(sw, sh, cfg.src, cfg.rect, cfg.dst, cfg.dw, cfg.dh, cfg.pad, orient=cfg.orient)
+
+
+def orient_features(cfg, enc_path, paths):
+    """The ORIENT_FEATURES an OrientConfig carries, from its encode path and scale paths (predicted,
+    or as the context reports them) and orient_span of its source's luma plane."""
+    crop = cfg.rect is not None and tuple(cfg.rect) != (0, 0, cfg.w, cfg.h)
+    sw, sh = source_size(cfg)
+    t = bool(cfg.orient & 1)
+    f = {cfg.submit, "map%d" % cfg.orient}
+    if orient_span(sw, sh, t)[3 if t else 0] > 1:
+        f.add("luma_t1_past_one_wg" if t else "luma_t0_past_one_wg")
+    if enc_path & IN_PLACE:
+        f.add("orient_alone_in_place" if not crop else
+              "crop_in_place_ua" if enc_path & UA else "crop_in_place_aligned")
+    else:
+        assert paths[0] != NONE
+        f.add("sws_reads_orient")
+    return f
+
+
+def orient_predicted_counts(cfgs):
+    sets = []
+    for c in cfgs:
+        enc_path, paths, _ = orient_predict(c)
+        sets.append(orient_features(c, enc_path, paths))
+    return count_orient_features(sets)
+
+
+def count_orient_features(sets):
+    return {k: sum(k in s for s in sets) for k in ORIENT_FEATURES}
+
+
+# The sweep of tests/test_gpu_orient_chain.py: the seed, and per part of 30 configurations the
+# number that carry each feature, counted by orient_predicted_counts (tests/test_chain_geom.py
+# checks that).  Of seeds 1..3000 the one whose sorted counts (68: 17 features x 4 parts) are
+# largest, compared from the smallest up; every count is at least 1 at 30 per part.
+ORIENT_SWEEP_SEED = 2901
+ORIENT_SWEEP_FLOORS = [dict(zip(ORIENT_FEATURES, v)) for v in (
+    (4, 5, 4, 4, 6, 6, 1, 11, 10, 2, 2, 2, 24, 8, 8, 4, 10),
+    (3, 5, 4, 6, 2, 4, 6, 13, 10, 2, 3, 2, 23, 8, 7, 5, 10),
+    (2, 4, 4, 7, 3, 8, 2, 14, 7, 3, 4, 2, 21, 8, 14, 5, 3),
+    (3, 8, 3, 3, 4, 5, 4, 13, 10, 2, 2, 5, 21, 7, 7, 11, 5),
+)]

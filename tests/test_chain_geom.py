@@ -1,10 +1,16 @@
 """tests/chain_geom.py against values computed by hand for the shapes of tests/test_gpu_chain.py
 (no GPU).  The hand values assume kBatch = 12 and 256 x 4 pieces per copy workgroup; the first
 test says so, so that a change of those constants points here before it fails a sum below."""
+import os
+import re
+
+import numpy as np
 import pytest
 
 import chain_geom as cg
 from chain_geom import COPY, NONE, PADCOPY, STREAM, TILE, IN_PLACE, UA
+from orient_ref import orient_frame, orient_plane, oriented_size
+from ffmpeg_distributed_amd.encoder import chroma_size, i420_frame_bytes
 
 
 def test_constants_parsed_from_the_kernel_sources():
@@ -93,6 +99,97 @@ def test_copy_span(nbytes, want):
     assert cg.copy_span(nbytes) == want
 
 
+def test_orient_constants_parsed_from_the_kernel_source():
+    """The hand values below assume tiles of 64 columns x 128 rows, 4 to a workgroup; kOrientWaves
+    is an expression in scale.hip, so chain_geom restates it and this checks that it still reads so."""
+    assert (cg.ORIENT_TILE, cg.ORIENT_TILE_H, cg.ORIENT_WAVES) == (64, 128, 4)
+    with open(os.path.join(cg._CSRC, "scale.hip")) as f:
+        assert re.search(r"constexpr\s+int\s+kOrientWaves\s*=\s*kCopyThreads\s*/\s*64\s*;", f.read())
+
+
+# The shapes of tests/test_gpu_orient_chain.py: (source, format) -> luma T = 0 (workgroups, slots),
+# luma T = 1 (tx, ty, tiles, workgroups), the chroma plane, and the same two for it; None: 4:2:2
+# is not transposed.  Workgroups of 16,384 bytes (T = 0) and of 4 tiles (T = 1).
+ORIENT_SHAPES = {
+    (300, 200, "444"): ((4, 4), (5, 2, 10, 3), (300, 200), (4, 4), (5, 2, 10, 3)),
+    (301, 203, "420"): ((4, 4), (5, 2, 10, 3), (151, 102), (1, 4), (3, 1, 3, 1)),
+    (301, 203, "444"): ((4, 4), (5, 2, 10, 3), (301, 203), (4, 4), (5, 2, 10, 3)),
+    (300, 200, "422"): ((4, 4), None, (150, 200), (2, 4), None),
+    (40, 600, "420"): ((2, 4), (1, 5, 5, 2), (20, 300), (1, 2), (1, 3, 3, 1)),
+    (600, 40, "444"): ((2, 4), (10, 1, 10, 3), (600, 40), (2, 4), (10, 1, 10, 3)),
+    (200, 300, "420"): ((4, 4), (4, 3, 12, 3), (100, 150), (1, 4), (2, 2, 4, 1)),
+    (160, 256, "420"): ((3, 4), (3, 2, 6, 2), (80, 128), (1, 3), (2, 1, 2, 1)),
+}
+
+
+@pytest.mark.parametrize("shape", list(ORIENT_SHAPES), ids=lambda s: "%dx%d_%s" % s)
+def test_orient_span(shape):
+    w, h, c = shape
+    l0, l1, csize, c0, c1 = ORIENT_SHAPES[shape]
+    assert chroma_size(w, h, c) == csize
+    assert cg.orient_span(w, h, False) == l0 == cg.copy_span(w * h)
+    assert cg.orient_span(*csize, False) == c0
+    if l1 is not None:
+        assert tuple(cg.orient_span(w, h, True)[:4]) == l1
+        assert tuple(cg.orient_span(*csize, True)[:4]) == c1
+
+
+def test_orient_span_edges():
+    """The idle waves and the partial blocks of the shapes above, by hand.  300 = 4 x 64 + 44: the
+    last tile column has two whole lane columns, a 12-wide partial one and one outside; 200 = 128 +
+    72 = 9 x 8: no partial rows; tiles 4 and 9 (the last column) lie past the first workgroup.
+    301 x 203: 13-wide and 3-row partial blocks.  40 x 600: one tile column (its tx_magic is 0: the
+    shortcut), 40 = 2 x 16 + 8.  600 x 40: 600 = 9 x 64 + 24, one tile row of 40 rows, 5 lane rows."""
+    assert cg.orient_span(300, 200, True) == (5, 2, 10, 3, 2, True, False, True)
+    assert cg.orient_span(301, 203, True) == (5, 2, 10, 3, 2, True, True, True)
+    assert cg.orient_span(151, 102, True) == (3, 1, 3, 1, 1, True, True, False)
+    assert cg.orient_span(40, 600, True) == (1, 5, 5, 2, 3, True, False, True)
+    assert cg.orient_span(600, 40, True) == (10, 1, 10, 3, 2, True, False, True)
+    assert cg.orient_span(200, 300, True) == (4, 3, 12, 3, 0, True, True, True)
+    assert cg.orient_span(160, 256, True) == (3, 2, 6, 2, 2, False, False, False)
+    assert cg.orient_span(64, 128, True) == (1, 1, 1, 1, 3, False, False, False)
+    assert cg.orient_span(130, 66, True)[:4] == (3, 1, 3, 1)   # the largest planes of tests/test_gpu_orient.py:
+    assert cg.orient_span(70, 150, True)[:4] == (2, 2, 4, 1)   # one workgroup
+    assert cg.orient_span(130, 66, False) == (1, 3) and cg.orient_span(70, 150, False) == (1, 3)
+    # 301 x 203: an odd frame size, so frames 1 and 2 start at an odd byte of the oriented buffer
+    assert (301 * 203 + 2 * 151 * 102) % 2 == 1 and (301 * 203 * 3) % 2 == 1
+
+
+def test_orient_cells_are_reached_by_the_gpu_tests():
+    """k_orient_plane<T, FX> with fy 0 and 1: the seven maps are every cell but <0, 0> with fy 0,
+    which is orient 0 and launches nothing.  tests/test_gpu_orient_chain.py runs all seven on
+    300x200 4:4:4, whose luma plane and whose chroma planes (the U + V launch) take more than one
+    workgroup in both forms; the 4:2:2 case adds the non-transposing maps on a chroma plane half
+    as wide."""
+    cells = {cg.orient_cells(o) for o in range(1, 8)}
+    assert cells == {(t, fx, fy) for t in (False, True) for fx in (False, True) for fy in (0, 1)} - {(False, False, 0)}
+    assert cg.orient_cells(0) == (False, False, 0)
+    assert [cg.orient_cells(o) for o in (1, 2, 4)] == [(True, False, 0), (False, True, 0), (False, False, 1)]
+    w, h, c = 300, 200, "444"
+    for o in range(1, 8):
+        t = cg.orient_cells(o)[0]
+        for plane in ((w, h), chroma_size(w, h, c)):
+            assert cg.orient_span(*plane, t)[3 if t else 0] > 1
+    assert all(cg.orient_span(*chroma_size(300, 200, "422"), False)[0] > 1 for o in (2, 4, 6))
+
+
+def test_the_inverse_of_every_orientation():
+    """orient o undoes itself, except the two quarter turns 3 and 5, which undo each other: what
+    tests/test_gpu_orient_chain.py uses to build a source whose oriented frame is a given one."""
+    p = (np.arange(5 * 7, dtype=np.int64) * 37 % 251).astype(np.uint8).reshape(5, 7)
+    for o, inv in ORIENT_INVERSE.items():
+        assert (orient_plane(orient_plane(p, o), inv) == p).all()
+        assert (orient_plane(orient_plane(p, inv), o) == p).all()
+    assert not (orient_plane(orient_plane(p, 3), 3).shape == p.shape and (orient_plane(orient_plane(p, 3), 3) == p).all())
+    f = (np.arange(i420_frame_bytes(7, 5, "420"), dtype=np.int64) * 41 % 253).astype(np.uint8)
+    for o, inv in ORIENT_INVERSE.items():
+        ow, oh = oriented_size(7, 5, o)
+        assert (orient_frame(orient_frame(f, 7, 5, "420", o), ow, oh, "420", inv) == f).all()
+
+
+ORIENT_INVERSE = {1: 1, 2: 2, 3: 5, 4: 4, 5: 3, 6: 6, 7: 7}
+
+
 @pytest.mark.parametrize("args,want", [
     # crop in place from 300-byte rows: UA; MJG_UNALIGNED_FETCH=0: the plain kernel
     ((300, 200, "420", (2, 6, 250, 150), "420", None, None, None), (IN_PLACE | UA, (NONE, NONE), False)),
@@ -128,6 +225,63 @@ def test_predict_paths_switches():
     assert cg.predict_paths(*a, unaligned_fetch=False) == (IN_PLACE, (NONE, NONE), False)
     b = (300, 200, "444", (3, 5, 251, 151), "420", None, None, None)
     assert cg.predict_paths(*b, plane_copy=False) == (0, (TILE, TILE), False)
+
+
+PREDICT_ROWS = test_predict_paths.pytestmark[0].args[1]
+
+
+@pytest.mark.parametrize("args,want", PREDICT_ROWS)
+def test_predict_paths_with_an_orientation(args, want):
+    """orient = 0 is the function as it was; a mirroring map changes nothing downstream; under a
+    transposing map the same oriented frame comes from an h x w source (4:2:2 is not transposed)."""
+    w, h, src = args[:3]
+    for o in (0, 2, 4, 6):
+        assert cg.predict_paths(*args, orient=o) == want
+    if src != "422":
+        for o in (1, 3, 5, 7):
+            assert cg.predict_paths(h, w, *args[2:], orient=o) == want
+
+
+def test_predict_paths_of_the_oriented_shapes():
+    """tests/test_gpu_orient_chain.py: an orientation alone is read in place and is no crop (never
+    UA, whatever the sizes); the crops out of the oriented 300x200, 400x64 and 256x160."""
+    for (w, h, c) in ORIENT_SHAPES:
+        for o in ((2, 4, 6) if c == "422" else range(1, 8)):
+            assert cg.predict_paths(w, h, c, None, c, None, None, None, orient=o) == (IN_PLACE, (NONE, NONE), False)
+    for o in (3, 5):
+        for rect in ((2, 6, 250, 150), (2, 6, 234, 150)):
+            a = (200, 300, "420", rect, "420", None, None, None)
+            assert cg.predict_paths(*a, orient=o) == (IN_PLACE | UA, (NONE, NONE), False)
+            assert cg.predict_paths(*a, unaligned_fetch=False, orient=o) == (IN_PLACE, (NONE, NONE), False)
+    assert cg.predict_paths(300, 200, "444", (3, 5, 250, 150), "444", None, None, None, orient=6)[0] == IN_PLACE | UA
+    assert cg.predict_paths(64, 400, "444", (3, 5, 350, 40), "444", None, None, None, orient=1)[0] == IN_PLACE | UA
+    assert cg.predict_paths(160, 256, "420", (16, 16, 224, 128), "420", None, None, None, orient=7)[0] == IN_PLACE
+    assert cg.predict_paths(160, 256, "420", (8, 16, 224, 128), "420", None, None, None, orient=7)[0] == IN_PLACE | UA
+    # the sws stage behind an orientation: the source is the oriented frame turned back
+    assert cg.predict_paths(200, 300, "444", (3, 5, 251, 151), "420", None, None, None, orient=5) == (0, (COPY, TILE), True)
+    assert cg.predict_paths(84, 200, "420", None, "420", None, None, (26, 28, 250, 140), orient=1)[1] == (PADCOPY, PADCOPY)
+    assert cg.predict_paths(700, 1100, "420", None, "420", 200, 100, (28, 22, 256, 144), orient=7)[1] == (STREAM, STREAM)
+
+
+def test_orient_sweep_draw_and_its_floors():
+    """The sweep of tests/test_gpu_orient_chain.py, counted without a GPU: the configurations of
+    sweep_configs for its seed, each with a map (a mirroring one on 4:2:2), and per part of 30
+    exactly the feature counts the GPU test uses as floors, every one at least 1."""
+    seed = cg.ORIENT_SWEEP_SEED
+    cfgs = cg.orient_sweep_configs(seed, 120)
+    assert len(cfgs) == 120 and cfgs == cg.orient_sweep_configs(seed, 120)
+    assert [tuple(c[:-1]) for c in cfgs] == [tuple(c) for c in cg.sweep_configs(seed, 120)]
+    for c in cfgs:
+        assert 1 <= c.orient <= 7 and not (c.src == "422" and c.orient & 1)
+        assert cg.source_size(c) == ((c.h, c.w) if c.orient & 1 else (c.w, c.h))
+    parts = [cg.orient_predicted_counts(cfgs[i * 30:(i + 1) * 30]) for i in range(4)]
+    assert parts == cg.ORIENT_SWEEP_FLOORS
+    assert all(set(p) == set(cg.ORIENT_FEATURES) and min(p.values()) >= 1 for p in parts)
+    total = {k: sum(p[k] for p in parts) for k in cg.ORIENT_FEATURES}
+    assert total == {"map1": 12, "map2": 22, "map3": 15, "map4": 20, "map5": 15, "map6": 23, "map7": 13,
+                     "luma_t0_past_one_wg": 51, "luma_t1_past_one_wg": 37, "orient_alone_in_place": 9,
+                     "crop_in_place_ua": 11, "crop_in_place_aligned": 11, "sws_reads_orient": 89,
+                     "host": 31, "dev_odd": 36, "segments": 25, "merged": 28}
 
 
 def test_tile_lds_of_a_shape_the_suite_names():
