@@ -43,7 +43,13 @@ EXPORTS = (
     "mjg_kernel_times", "mjg_build_header", "mjg_sws_filter", "mjg_debug_coefs",
     "mjg_debug_planes", "mjg_debug_filter", "mjg_debug_huff_build", "mjg_debug_scale_path",
     "mjg_debug_encode_path", "mjg_debug_oriented", "mjg_debug_orient",
+    "mjg_open_deint", "mjg_submit_halo", "mjg_debug_deint", "mjg_debug_deint_flags",
 )
+
+# mjg_open_deint's `deint`
+MJG_DEINT_YADIF = 1
+MJG_DEINT_NOSPATIAL = 2
+MJG_DEINT_BFF = 4
 
 
 class MjgError(RuntimeError):
@@ -95,6 +101,14 @@ def load():
             L.mjg_debug_oriented.restype = C.c_int
             L.mjg_debug_orient.argtypes = [vp]
             L.mjg_debug_orient.restype = C.c_int
+        if hasattr(L, "mjg_open_deint"):  # absent from libraries built before the deinterlacer (A/B builds)
+            L.mjg_open_deint.argtypes = [C.c_int, C.POINTER(MjgConfig)] + [C.c_int] * 11 + [C.POINTER(vp)]
+            L.mjg_submit_halo.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
+            L.mjg_submit_halo.restype = C.c_int
+            L.mjg_debug_deint.argtypes = [vp, C.c_int, u8p, sz]
+            L.mjg_debug_deint.restype = C.c_int
+            L.mjg_debug_deint_flags.argtypes = [vp]
+            L.mjg_debug_deint_flags.restype = C.c_int
         L.mjg_close.argtypes = [vp]
         L.mjg_close.restype = None
         L.mjg_frame_bytes.argtypes = [vp]
@@ -140,7 +154,8 @@ def load():
         # deep, no merging; and the multi-segment submit, which encoder.submit_segments guards)
         late = (("mjg_queue_depth", "mjg_ctx_queue_depth", "mjg_submit_segments", "mjg_max_segments",
                  "mjg_debug_huff_build", "mjg_open_src", "mjg_open_crop", "mjg_open_pad", "mjg_debug_scale_path",
-                 "mjg_debug_encode_path", "mjg_open_orient", "mjg_debug_oriented", "mjg_debug_orient")
+                 "mjg_debug_encode_path", "mjg_open_orient", "mjg_debug_oriented", "mjg_debug_orient",
+                 "mjg_open_deint", "mjg_submit_halo", "mjg_debug_deint", "mjg_debug_deint_flags")
                 if os.environ.get("MJG_LIBRARY") else ())
         for name in EXPORTS:
             if name not in late:

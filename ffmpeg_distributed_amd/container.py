@@ -95,6 +95,9 @@ class StreamInfo:
     codec: str = "rawvideo"
     frame_bytes: int = 0
     chroma: str = "420"                 # planar sampling: "420", "422", "444"
+    # field order, as a YUV4MPEG2 'I' tag: "p" progressive (or unflagged), "t" top field first, "b"
+    # bottom field first, "m" mixed / anything else the stream declares (yadif's parity=auto reads it)
+    field: str = "p"
 
     def __post_init__(self):
         if not self.frame_bytes:
@@ -121,7 +124,7 @@ def y4m_header(info: "StreamInfo") -> bytes:
     a = f"A{info.sar[0]}:{info.sar[1]}" if info.sar != (0, 0) else "A0:0"
     x = " XCOLORRANGE=FULL" if info.full_range else ""
     fps = info.fps
-    return (f"YUV4MPEG2 W{info.width} H{info.height} F{fps.numerator}:{fps.denominator} Ip {a} "
+    return (f"YUV4MPEG2 W{info.width} H{info.height} F{fps.numerator}:{fps.denominator} I{info.field} {a} "
             f"C{c}{x}\n").encode()
 
 
@@ -134,7 +137,7 @@ class Y4MReader:
         if not line.startswith(b"YUV4MPEG2"):
             raise ValueError("not a YUV4MPEG2 stream")
         w = h = None
-        fps, sar, full, chroma = Fraction(25), (0, 0), False, "420"
+        fps, sar, full, chroma, fld = Fraction(25), (0, 0), False, "420", "p"
         for tok in line.split()[1:]:
             t, v = tok[:1], tok[1:].decode()
             if t == b"W":
@@ -149,11 +152,13 @@ class Y4MReader:
                 sar = (int(n), int(d))
             elif t == b"C":
                 chroma = y4m_chroma(v)
+            elif t == b"I":
+                fld = v if v in ("p", "t", "b", "m") else "p"    # ('?': unknown, taken as unflagged)
             elif t == b"X" and v.upper().startswith("COLORRANGE="):
                 full = v.split("=", 1)[1].upper() == "FULL"
         if not w or not h:
             raise ValueError("y4m header without W/H")
-        self.info = StreamInfo(w, h, fps, sar, full, chroma=chroma)
+        self.info = StreamInfo(w, h, fps, sar, full, chroma=chroma, field=fld)
 
     def _readline(self) -> bytes:
         out = bytearray()
@@ -196,6 +201,8 @@ class MkvTrack:
     colour_space: bytes = b""
     display: Tuple[int, int] = (0, 0)
     colour_range: int = 0              # Colour/Range: 1 broadcast, 2 full
+    flag_interlaced: int = 0           # Video/FlagInterlaced (0x9A): 0 undetermined, 1 interlaced, 2 progressive
+    field_order: Optional[int] = None  # Video/FieldOrder (0x9D): 1 tff, 6 bff, ...; None: absent
 
 
 class MkvReader:
@@ -279,6 +286,10 @@ class MkvReader:
             self.duration = struct.unpack(">d" if size == 8 else ">f", data)[0]
         elif eid == 0x55B9 and tr:
             tr.colour_range = int.from_bytes(data, "big")
+        elif eid == 0x9A and tr:
+            tr.flag_interlaced = int.from_bytes(data, "big")
+        elif eid == 0x9D and tr:
+            tr.field_order = int.from_bytes(data, "big")
         return True
 
     def read_frame_into(self, track: int, dest) -> Optional[int]:
@@ -424,8 +435,11 @@ class MkvReader:
             s = Fraction(tr.display[0] * tr.height, tr.display[1] * tr.width)
             sar = (s.numerator, s.denominator)
         chroma = MKV_FOURCC_CHROMA.get(tr.colour_space, "420") if tr.codec == "V_UNCOMPRESSED" else "420"
+        # FlagInterlaced other than 1: unflagged; 1 with FieldOrder 1 / 6: tff / bff; any other order,
+        # or none: "m" (nothing the GPU deinterlacer takes one parity from)
+        fld = "p" if tr.flag_interlaced != 1 else {1: "t", 6: "b"}.get(tr.field_order, "m")
         return StreamInfo(tr.width, tr.height, fps.limit_denominator(1001), sar,
-                          full_range=tr.colour_range == 2, codec=tr.codec, chroma=chroma)
+                          full_range=tr.colour_range == 2, codec=tr.codec, chroma=chroma, field=fld)
 
     def duration_seconds(self) -> Optional[float]:
         return None if self.duration is None else self.duration * self.timescale / 1e9

@@ -219,6 +219,14 @@ struct OrientPass {
   OrientGeom g{};
 };
 
+// One launch of the deinterlacer (k_yadif_plane; 0 luma, 1 chroma: U and V share it), built at open
+// like the orientation stage's.
+using DeintFn = void (*)(const DeintGeom &g, const SegList &in, uint8_t *dst, int nz, hipStream_t st);
+struct DeintPass {
+  DeintFn launch = nullptr;
+  DeintGeom g{};
+};
+
 struct Slot;
 using EncodeFn = void (*)(const mjg_ctx *c, Slot &S, const SegList &enc_in, int wgs, int ntasks);
 
@@ -258,6 +266,7 @@ struct Slot {
   uint8_t *d_stage = nullptr;      // H2D staging for host submits (allocated on first use)
   uint8_t *d_scaled = nullptr;     // -vf scale: k_scale's output planes
   uint8_t *d_orient = nullptr;     // -vf hflip / vflip / transpose: k_orient_plane's output frames
+  uint8_t *d_deint = nullptr;      // -vf yadif: k_yadif_plane's output frames
   uint32_t *d_stage_bits = nullptr;  // k_encode: per wave, lane-major staging of blocks past 128 bits
   int n = 0;  // frames of the launch
   uint32_t *d_scratch = nullptr;
@@ -299,6 +308,10 @@ struct mjg_ctx {
   // size and offset below then refers to the oriented frame (src_h x src_w when orient & 1)
   int orient = 0;
   OrientPass opass[2];          // its launches: 0 luma, 1 chroma
+  // -vf yadif (mjg_open_deint): MJG_DEINT_* bits, 0 none; in front of the orientation, on the decoded
+  // frames.  Every submit (every segment of one) is a sequence of its own: no merging
+  int deint = 0;
+  DeintPass dpass[2];           // its launches: 0 luma, 1 chroma
   size_t in_frame_bytes = 0, enc_frame_bytes = 0;
   // the crop rectangle (mjg_open_crop; the whole frame otherwise): the input of the sws stage,
   // or of k_encode without one
@@ -361,7 +374,7 @@ void free_ctx(mjg_ctx *c) {
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (Slot &S : c->slot) {
-    void *sp[] = {S.d_stage, S.d_scaled, S.d_orient, S.d_stage_bits, S.d_scratch, S.d_stream, S.d_work, S.d_chunk_bits, S.d_chunk_off, S.d_group_ff, S.d_ff_off, S.d_frame_bits,
+    void *sp[] = {S.d_stage, S.d_scaled, S.d_orient, S.d_deint, S.d_stage_bits, S.d_scratch, S.d_stream, S.d_work, S.d_chunk_bits, S.d_chunk_off, S.d_group_ff, S.d_ff_off, S.d_frame_bits,
                   S.d_status, S.d_frame_size, S.d_frame_offsets, S.d_seg_size, S.d_seg_off, S.d_done, S.d_out,
                   S.d_hist, S.d_ftabs, S.d_dht_nval, S.d_hdr_lens, S.d_dht, S.d_dbg, S.d_syms, S.d_symn};
     for (void *p : sp)
@@ -412,6 +425,7 @@ bool plan_scale_stream(int max_nw, int ht, int npv, StreamGeom *q, bool *hcl, si
 
 // A context's rectangles, resolved by check_config
 struct Layout {
+  int deint;                   // MJG_DEINT_* bits (0: no deinterlacer)
   int orient, ow, oh;          // the orientation and the oriented frame's size (orient 0: the source's)
   int cx, cy, crw, crh;        // the crop rectangle in the oriented frame: the sws stage's / k_encode's input
   int px, py, pw, ph;          // the picture's place in the canvas and the canvas size (no pad: the picture)
@@ -625,6 +639,7 @@ int alloc_slot(mjg_ctx *c, Slot &S) {
   if ((rc = dmalloc(&S.d_stage_bits, c->stage_cols * 64 * kStageWords))) return rc;
   if (c->scale && (rc = dmalloc(&S.d_scaled, B * c->enc_frame_bytes))) return rc;
   if (c->orient && (rc = dmalloc(&S.d_orient, B * c->in_frame_bytes))) return rc;
+  if (c->deint && (rc = dmalloc(&S.d_deint, B * c->in_frame_bytes))) return rc;
   if ((rc = dmalloc(&S.d_scratch, B * NC * (size_t)kSlotWords)) ||
       (rc = dmalloc(&S.d_stream, B * NC * (size_t)kSlotWords)) ||
       (rc = dmalloc(&S.d_chunk_bits, B * NC)) || (rc = dmalloc(&S.d_chunk_off, B * NC)) ||
@@ -659,12 +674,13 @@ int alloc_slot(mjg_ctx *c, Slot &S) {
 }
 
 // open, step 1: the config, the rectangle and the pad (no device, no environment).
-// orient: T | FX << 1 | FY << 2 (mjgpu.h), applied first: the crop, dst_w / dst_h and the pad
+// deint: MJG_DEINT_* bits (mjgpu.h), the deinterlacer in front of everything, on the decoded frames
+// orient: T | FX << 1 | FY << 2 (mjgpu.h), applied next: the crop, dst_w / dst_h and the pad
 // refer to the oriented frame
 // crop: x, y, w, h in luma samples of the oriented frame, or nullptr for the whole frame
 // pad: x, y, w, h in luma samples of the encoded frame (the picture's place and the canvas size),
 // or nullptr for no pad
-int check_config(const mjg_config &k, int src_cf, int orient, const int *crop, const int *pad, Layout *lay) {
+int check_config(const mjg_config &k, int src_cf, int deint, int orient, const int *crop, const int *pad, Layout *lay) {
   if (std::min({k.src_w, k.src_h, k.dst_w, k.dst_h}) < 1 || std::max({k.src_w, k.src_h, k.dst_w, k.dst_h}) > 16384)
     return set_err(MJG_E_INVALID, "bad frame size %dx%d -> %dx%d", k.src_w, k.src_h, k.dst_w, k.dst_h);
   if (k.qscale < 1 || k.qscale > 31) return set_err(MJG_E_INVALID, "qscale %d not in 1..31", k.qscale);
@@ -675,6 +691,17 @@ int check_config(const mjg_config &k, int src_cf, int orient, const int *crop, c
     return set_err(MJG_E_INVALID, "chroma_format %d", k.chroma_format);
   if (src_cf < MJG_CHROMA_420 || src_cf > MJG_CHROMA_444)
     return set_err(MJG_E_INVALID, "src_chroma_format %d", src_cf);
+  const int s_hsh = src_cf == MJG_CHROMA_444 ? 0 : 1, s_vsh = src_cf == MJG_CHROMA_420 ? 1 : 0;
+  // the deinterlacer: yadif with the two option bits; its row and column clamps need 3 x 3 planes
+  if (deint) {
+    if ((deint & ~(MJG_DEINT_YADIF | MJG_DEINT_NOSPATIAL | MJG_DEINT_BFF)) || !(deint & MJG_DEINT_YADIF))
+      return set_err(MJG_E_INVALID, "deint %d: not 0 or MJG_DEINT_YADIF (1) | MJG_DEINT_NOSPATIAL (2) | MJG_DEINT_BFF (4)",
+                     deint);
+    const int scw = (k.src_w + s_hsh) >> s_hsh, sch = (k.src_h + s_vsh) >> s_vsh;
+    if (std::min({k.src_w, k.src_h, scw, sch}) < 3)
+      return set_err(MJG_E_INVALID, "deint %d (yadif): a %dx%d frame has a plane smaller than 3x3 (chroma %dx%d)", deint,
+                     k.src_w, k.src_h, scw, sch);
+  }
   // the orientation: vf_transpose takes only formats whose two chroma shifts are equal
   if (orient < 0 || orient > 7)
     return set_err(MJG_E_INVALID, "orient %d not in 0..7 (T | FX << 1 | FY << 2)", orient);
@@ -682,7 +709,6 @@ int check_config(const mjg_config &k, int src_cf, int orient, const int *crop, c
     return set_err(MJG_E_INVALID, "orient %d transposes a 4:2:2 source (only 4:2:0 and 4:4:4 keep their format)", orient);
   const int ow = (orient & 1) ? k.src_h : k.src_w, oh = (orient & 1) ? k.src_w : k.src_h;
   // the rectangle (the frame sizes and the source format are valid here)
-  const int s_hsh = src_cf == MJG_CHROMA_444 ? 0 : 1, s_vsh = src_cf == MJG_CHROMA_420 ? 1 : 0;
   const int cx = crop ? crop[0] : 0, cy = crop ? crop[1] : 0;
   const int crw = crop ? crop[2] : ow, crh = crop ? crop[3] : oh;  // the sws stage's / k_encode's input size
   if (crw < 1 || crh < 1)
@@ -721,7 +747,7 @@ int check_config(const mjg_config &k, int src_cf, int orient, const int *crop, c
     return set_err(MJG_E_INVALID, "unknown flags 0x%x", k.flags & ~kKnownFlags);
   if ((k.flags & MJG_F_RST) && (k.flags & MJG_F_HUFFMAN_OPTIMAL))
     return set_err(MJG_E_INVALID, "RST (slice threading) forces -huffman default");
-  *lay = Layout{orient, ow, oh, cx, cy, crw, crh, px, py, pw, ph, has_pad, s_hsh, s_vsh, e_hsh, e_vsh};
+  *lay = Layout{deint, orient, ow, oh, cx, cy, crw, crh, px, py, pw, ph, has_pad, s_hsh, s_vsh, e_hsh, e_vsh};
   return MJG_OK;
 }
 
@@ -735,6 +761,7 @@ int plan_geometry(const mjg_config &k, int src_cf, const Layout &lay, bool unali
   // same bytes per frame either way, the formats that transpose have equal chroma shifts)
   const int fw = lay.ow, fh = lay.oh;
   c->orient = lay.orient;
+  c->deint = lay.deint;
   c->has_pad = lay.has_pad;
   // the sws stage: a resize, or a -pix_fmt conversion (source format != encoded format; in
   // FFmpeg one swscale context does both, and tv->pc in the same pass)
@@ -1027,6 +1054,34 @@ void plan_orient(const mjg_config &k, const Layout &lay, mjg_ctx *c) {
   }
 }
 
+template <bool NOSPATIAL>
+void launch_deint(const DeintGeom &g, const SegList &in, uint8_t *dst, int nz, hipStream_t st) {
+  k_yadif_plane<NOSPATIAL><<<g.gxy * nz, kDeintThreads, 0, st>>>(in, dst, g);
+}
+
+// The deinterlacer's launches for luma and chroma (mjg_ctx::dpass; no device, no environment): the
+// decoded frame's planes in the source format -> the same planes of the deinterlaced frame, both
+// packed planar and in_frame_bytes apart.  submit_impl adds nf, the U+V pairing and the segments'
+// readable frames.
+void plan_deint(const mjg_config &k, const Layout &lay, mjg_ctx *c) {
+  if (!lay.deint) return;
+  for (int p = 0; p < 2; p++) {
+    DeintPass &q = c->dpass[p];
+    DeintGeom &g = q.g;
+    g.w = p ? (k.src_w + lay.s_hsh) >> lay.s_hsh : k.src_w;
+    g.h = p ? (k.src_h + lay.s_vsh) >> lay.s_vsh : k.src_h;
+    g.off = p ? (long long)k.src_w * k.src_h : 0;
+    g.fstride = (long long)c->in_frame_bytes;
+    g.parity = (lay.deint & MJG_DEINT_BFF) ? 1 : 0;  // parity = tff ^ 1
+    g.w_magic = magic32((uint32_t)g.w);
+    const size_t pieces = ((size_t)g.w * g.h) >> 4;
+    g.gxy = (int)std::max<size_t>(1, (pieces + kDeintThreads - 1) / kDeintThreads);
+    g.gxy_magic = magic32((uint32_t)g.gxy);
+    q.launch = with_bool((lay.deint & MJG_DEINT_NOSPATIAL) != 0,
+                         [](auto ns) -> DeintFn { return launch_deint<decltype(ns)::value>; });
+  }
+}
+
 // RC, DBG, UA: EncGeom's range_convert and debug_coefs, and the context's enc_ua (a crop read in
 // place at any alignment, fetch_rows<UA>)
 template <bool RC, int MODE, bool DBG, bool UA>
@@ -1066,12 +1121,13 @@ int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
   // merging (kMerge): opt-in with MJG_F_MERGE (a held submit's frames are read after mjg_submit
   // returns); MJG_MERGE=1 turns it off for a process (A/B), =2..4 sets the jobs per launch
   c->merge = (k.flags & MJG_F_MERGE) ? std::max(1, std::min(kMaxSegs, env_int("MJG_MERGE", kMerge))) : 1;
+  if (c->deint) c->merge = 1;  // a deint context neither holds nor merges submits (mjgpu.h)
   c->hold_idle = env_int("MJG_MERGE_HOLD", 1) != 0;
   if (c->merge > 1) {  // slot buffers for merge * max_batch frames: within a share of free memory
     size_t fr = 0, tot = 0;
     HIP_TRY(hipMemGetInfo(&fr, &tot));
     const double per_frame = 2.0 * (double)c->slot_NC * kSlotWords * 4 + 2.0 * (double)c->enc_frame_bytes +
-                             (c->orient ? (double)c->in_frame_bytes : 0.0);
+                             (c->orient ? (double)c->in_frame_bytes : 0.0);  // (a deinterlacer never merges)
     if (kSlots * (double)c->merge * (double)k.max_batch * per_frame > kMergeMemShare * (double)fr) c->merge = 1;
   }
   if ((unsigned long long)k.max_batch * c->merge * g.nseg * g.nchunks * g.nchunks >= ((unsigned long long)1 << 40))
@@ -1117,15 +1173,17 @@ int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
   return alloc_slot(c, c->slot[0]);
 }
 
-int open_ctx(int device, const mjg_config *cfg, int src_cf, int orient, const int *crop, const int *pad, mjg_ctx *c) {
+int open_ctx(int device, const mjg_config *cfg, int src_cf, int deint, int orient, const int *crop, const int *pad,
+             mjg_ctx *c) {
   c->device = device;
   c->cfg = *cfg;
   const mjg_config &k = *cfg;
   Layout lay;
   int rc;
-  if ((rc = check_config(k, src_cf, orient, crop, pad, &lay))) return rc;
+  if ((rc = check_config(k, src_cf, deint, orient, crop, pad, &lay))) return rc;
   if ((rc = plan_geometry(k, src_cf, lay, env_int("MJG_UNALIGNED_FETCH", 1) != 0, c))) return rc;
   plan_orient(k, lay, c);
+  plan_deint(k, lay, c);
   quant_matrix(k.qscale, c->mprime, c->qmat);
   c->hdr = build_header(c->geom.w, c->geom.h, c->mprime, k.sar_num, k.sar_den, (k.flags & MJG_F_COM_ITU601) != 0,
                         k.chroma_format, c->rst, &c->dht_pos, &c->dht_end);
@@ -1195,12 +1253,12 @@ int mjg_device_numa_node(int device) {
 }
 
 namespace {
-int open_any(int device, const mjg_config *cfg, int src_chroma_format, int orient, const int *crop, const int *pad,
-             mjg_ctx **out) {
+int open_any(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, const int *crop,
+             const int *pad, mjg_ctx **out) {
   if (!cfg || !out) return set_err(MJG_E_INVALID, "null argument");
   *out = nullptr;
   mjg_ctx *c = new mjg_ctx();
-  const int rc = open_ctx(device, cfg, src_chroma_format, orient, crop, pad, c);
+  const int rc = open_ctx(device, cfg, src_chroma_format, deint, orient, crop, pad, c);
   if (rc) {
     const std::string keep = g_err;
     free_ctx(c);
@@ -1215,23 +1273,29 @@ int open_any(int device, const mjg_config *cfg, int src_chroma_format, int orien
 int mjg_open_crop(int device, const mjg_config *cfg, int src_chroma_format, int crop_x, int crop_y, int crop_w,
                   int crop_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h};
-  return open_any(device, cfg, src_chroma_format, 0, crop, nullptr, out);
+  return open_any(device, cfg, src_chroma_format, 0, 0, crop, nullptr, out);
 }
 
 int mjg_open_orient(int device, const mjg_config *cfg, int src_chroma_format, int orient, int crop_x, int crop_y,
                     int crop_w, int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, orient, crop, pad, out);
+  return open_any(device, cfg, src_chroma_format, 0, orient, crop, pad, out);
+}
+
+int mjg_open_deint(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, int crop_x,
+                   int crop_y, int crop_w, int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
+  const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
+  return open_any(device, cfg, src_chroma_format, deint, orient, crop, pad, out);
 }
 
 int mjg_open_pad(int device, const mjg_config *cfg, int src_chroma_format, int crop_x, int crop_y, int crop_w,
                  int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, 0, crop, pad, out);
+  return open_any(device, cfg, src_chroma_format, 0, 0, crop, pad, out);
 }
 
 int mjg_open_src(int device, const mjg_config *cfg, int src_chroma_format, mjg_ctx **out) {
-  return open_any(device, cfg, src_chroma_format, 0, nullptr, nullptr, out);
+  return open_any(device, cfg, src_chroma_format, 0, 0, nullptr, nullptr, out);
 }
 
 int mjg_open(int device, const mjg_config *cfg, mjg_ctx **out) {
@@ -1254,8 +1318,10 @@ int mjg_header(const mjg_ctx *ctx, uint8_t *out, size_t cap, size_t *len) {
 
 namespace {
 // mjg_submit's body; segs (mjg_submit_segments: device frames) replaces the one segment at
-// `frames` as the input of the sws stage, or of k_encode without one
-int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, const SegList *segs) {
+// `frames` as the input of the sws stage, or of k_encode without one.  halo (a deint context's
+// single-segment submit, mjg_submit_halo): bit 1, `frames` starts with one frame that is only
+// read; bit 2, one such frame follows the n encoded ones
+int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, const SegList *segs, int halo = 0) {
   if (n < 1 || (size_t)n > c->slot_B || (!src_is_device && n > c->cfg.max_batch))
     return set_err(MJG_E_INVALID, "nframes %d not in 1..%d", n, c->cfg.max_batch);
   if (c->nout == kSlots) return set_err(MJG_E_STATE, "%d submits queued: sync one first", kSlots);
@@ -1267,16 +1333,36 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
     if (rc) return rc;
   }
   const uint8_t *src = frames;
+  const int hp = halo & 1, hn = (halo >> 1) & 1;  // halo frames in front of and behind the encoded ones
   if (!src_is_device) {
-    if (!S.d_stage) {  // staging for host submits, allocated on first use
-      const int rc = dmalloc(&S.d_stage, (size_t)c->cfg.max_batch * c->in_frame_bytes);
+    if (!S.d_stage) {  // staging for host submits, allocated on first use (a deinterlacer: room for the two halo frames)
+      const int rc = dmalloc(&S.d_stage, (size_t)(c->cfg.max_batch + (c->deint ? 2 : 0)) * c->in_frame_bytes);
       if (rc) return rc;
     }
-    HIP_TRY(hipMemcpyAsync(S.d_stage, frames, (size_t)n * c->in_frame_bytes, hipMemcpyHostToDevice, S.st));
+    HIP_TRY(hipMemcpyAsync(S.d_stage, frames, (size_t)(n + hp + hn) * c->in_frame_bytes, hipMemcpyHostToDevice, S.st));
     src = S.d_stage;
   }
+  src += (size_t)hp * c->in_frame_bytes;  // the first encoded frame
   SegList in_sl = segs ? *segs : one_seg(src);  // the submit's input frames: the caller's segments, or one at src
-  if (c->scale || c->orient) tmark(c, S, MJG_K_SCALE, 0);
+  if (c->scale || c->orient || c->deint) tmark(c, S, MJG_K_SCALE, 0);
+  if (c->deint) {  // in front of everything: luma, then U and V in one launch; the rest reads one buffer
+    const bool uv1 = 2 * n <= 65535;
+    for (int p = 0; p < (uv1 ? 2 : 3); p++) {
+      DeintGeom dg = c->dpass[p ? 1 : 0].g;
+      dg.nf = n;
+      // each segment is a sequence of its own: its frames [0, count), widened by the halo frames
+      for (int k = 0; k < kMaxSegs; k++) {
+        const int end = k + 1 < kMaxSegs && in_sl.f0[k + 1] != INT_MAX ? in_sl.f0[k + 1] : n;
+        dg.lo[k] = -hp;
+        dg.hi[k] = in_sl.f0[k] == INT_MAX ? 0 : end - in_sl.f0[k] - 1 + hn;
+      }
+      if (p && uv1) dg.poff = c->src_cplane;
+      if (p == 2) dg.off += c->src_cplane;
+      c->dpass[p ? 1 : 0].launch(dg, in_sl, S.d_deint, p && uv1 ? 2 * n : n, S.st);
+    }
+    HIP_TRY(hipGetLastError());
+    in_sl = one_seg(S.d_deint);
+  }
   if (c->orient) {  // the first filter: luma, then U and V in one launch as below; the rest reads one buffer
     const bool uv1 = 2 * n <= 65535;
     for (int p = 0; p < (uv1 ? 2 : 3); p++) {
@@ -1315,7 +1401,7 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
     HIP_TRY(hipGetLastError());
     enc_in = one_seg(S.d_scaled);  // k_encode reads the scaled frames, one buffer
   } else {  // in place: EncGeom's offsets count from the rectangle's first luma byte (0: whole frames)
-    if (c->orient) tmark(c, S, MJG_K_SCALE, 1);  // an orientation alone: the interval holds its passes
+    if (c->orient || c->deint) tmark(c, S, MJG_K_SCALE, 1);  // an orientation / a deinterlacer alone: the interval holds its passes
     for (int k = 0; k < kMaxSegs; k++) enc_in.p[k] += c->src_off[0];
   }
   const int ntasks = g.nchunks * g.nseg * n;
@@ -1467,6 +1553,18 @@ int mjg_submit(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device) {
   return submit_impl(c, frames, n, src_is_device, nullptr);
 }
 
+int mjg_submit_halo(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, int halo) {
+  if (!halo) return mjg_submit(c, frames, n, src_is_device);
+  if (!c || !frames) return set_err(MJG_E_INVALID, "null argument");
+  if (!c->deint) return set_err(MJG_E_INVALID, "halo %d on a context without a deinterlacer (deint 0)", halo);
+  if (halo & ~3) return set_err(MJG_E_INVALID, "halo %d: not 0..3 (1: a frame in front, 2: a frame behind)", halo);
+  if (n < 1 || n > c->cfg.max_batch)
+    return set_err(MJG_E_INVALID, "nframes %d not in 1..%d", n, c->cfg.max_batch);
+  // (a deint context holds nothing: merge is 1)
+  if (c->nout >= kSlots) return set_err(MJG_E_STATE, "%d launches queued: sync one first", kSlots);
+  return submit_impl(c, frames, n, src_is_device, nullptr, halo);
+}
+
 int mjg_max_segments(void) { return kMaxSegs; }
 
 int mjg_submit_segments(mjg_ctx *c, const uint8_t *const *seg_frames, const int *seg_nframes, int nsegs) {
@@ -1529,7 +1627,7 @@ int mjg_sync(mjg_ctx *c, uint64_t *frame_sizes, uint64_t *total) {
       }
       if (c->timing) {
         for (int k = 0; k < MJG_NUM_KERNELS; k++) {
-          if (k == MJG_K_SCALE && !c->scale && !c->orient) continue;
+          if (k == MJG_K_SCALE && !c->scale && !c->orient && !c->deint) continue;
           if (k == MJG_K_HUFF && !c->optimal) continue;
           const bool tail = is_tail_kernel(k);
           if (tail != c->timing_detail && (tail || k == MJG_K_TAIL)) continue;
@@ -1749,6 +1847,27 @@ int mjg_debug_oriented(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
 int mjg_debug_orient(mjg_ctx *c) {
   if (!c) return set_err(MJG_E_INVALID, "null context");
   return c->orient;
+}
+
+int mjg_debug_deint(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
+  if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
+  if (!c->deint) return set_err(MJG_E_STATE, "context has no deinterlacer (deint 0)");
+  if (pending_jobs(c) > 0) {  // the latest synced submit's frames
+    const int rc = mjg_sync(c, nullptr, nullptr);
+    if (rc) return rc;
+  }
+  if (pending_jobs(c) > 0 || c->last < 0) return set_err(MJG_E_STATE, "sync every queued submit first");
+  const Slot &L = c->slot[c->last];
+  if (frame < 0 || frame >= L.jn[c->last_job]) return set_err(MJG_E_INVALID, "frame %d", frame);
+  if (cap < c->in_frame_bytes) return set_err(MJG_E_CAPACITY, "need %zu bytes", c->in_frame_bytes);
+  const size_t f = (size_t)L.jf0[c->last_job] + (size_t)frame;
+  HIP_TRY(hipMemcpy(out, L.d_deint + f * c->in_frame_bytes, c->in_frame_bytes, hipMemcpyDeviceToHost));
+  return MJG_OK;
+}
+
+int mjg_debug_deint_flags(mjg_ctx *c) {
+  if (!c) return set_err(MJG_E_INVALID, "null context");
+  return c->deint;
 }
 
 int mjg_debug_huff_build(int device, const uint32_t *hist, int nframes, uint8_t *dht, uint32_t *nval) {

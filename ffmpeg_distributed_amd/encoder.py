@@ -1,7 +1,7 @@
 """GPU MJPEG encoder: the per-segment encode that the reference's worker runs
 (`ffmpeg -f matroska -i pipe: <remote_args> -f matroska pipe:`,
 ffmpeg_distributed.py:131-141), restricted to the profile
-`[-vf [vflip|transpose=N,...][crop=w:h:x:y,][scale=W:H:flags=bicubic][,pad=W:H:x:y]] -c:v mjpeg -q:v N -dct int [-huffman default|optimal] -bitexact`
+`[-vf [yadif,][vflip|transpose=N,...][crop=w:h:x:y,][scale=W:H:flags=bicubic][,pad=W:H:x:y]] -c:v mjpeg -q:v N -dct int [-huffman default|optimal] -bitexact`
 (+ `-slices N` / `-thread_type slice` for the RST layout).
 
 Host-side wrapper over libmjgpu.so; frames are packed planar YUV (yuv420p / yuvj420p by
@@ -15,7 +15,11 @@ the picture (dst_w x dst_h) at (x, y) of a black W x H canvas, which is what get
 vflip / transpose filters composes to, profile.compose_orient; the profile itself parses vflip and transpose) turns or mirrors every plane of
 the input frames on the GPU before anything else: the frames handed over stay the decoded ones,
 src_w x src_h, while the crop, dst_w / dst_h and the pad refer to the oriented frame (src_h x
-src_w under a transpose).  No CPU fallback.
+src_w under a transpose).  `deint=` (MJG_DEINT_YADIF | MJG_DEINT_NOSPATIAL | MJG_DEINT_BFF of
+_lib: `-vf yadif` modes 0 / 2, tff / bff) deinterlaces the decoded frames on the GPU in front of
+the orientation: every output frame is made from the frames before and after it, a submit (and
+each segment of a submit_segments) is a whole sequence, and `submit(..., halo=)` hands over a
+piece of a longer one with its neighbour frames.  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -65,7 +69,8 @@ class MjpegEncoder:
                  sar=(1, 1), max_batch: int = 16, timing: bool = False,
                  debug_coefs: bool = False, sws_bitexact: bool = True, com_itu601: bool = False,
                  huffman: str = "default", chroma: str = "420", rst: bool = False,
-                 merge: bool = False, src_chroma: Optional[str] = None, crop=None, pad=None, orient: int = 0):
+                 merge: bool = False, src_chroma: Optional[str] = None, crop=None, pad=None, orient: int = 0,
+                 deint: Optional[int] = None):
         self._L = _lib.load()
         self.device = int(device)
         self.src_w, self.src_h = int(src_w), int(src_h)
@@ -126,7 +131,19 @@ class MjpegEncoder:
                         int(qscale), int(sar[0]), int(sar[1]), self.max_batch, flags,
                         _lib.CHROMA_FORMATS[self.chroma])
         h = C.c_void_p()
-        if self.orient:
+        # deint: 0, or MJG_DEINT_YADIF | MJG_DEINT_NOSPATIAL | MJG_DEINT_BFF (mjg_open_deint): yadif on
+        # the decoded frames, in front of the orientation.  Every submit is then a whole sequence
+        # (or a piece of one: submit(..., halo=)).  deint=0 opens through mjg_open_deint all the same
+        # (exactly mjg_open_orient); None, the default, through the entry points below
+        self.deint = int(deint or 0)
+        if deint is not None:
+            if not hasattr(self._L, "mjg_open_deint"):
+                raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_deint")
+            rect = self.crop if self.crop is not None else (0, 0, self.or_w, self.or_h)
+            canvas = self.pad if self.pad is not None else (0, 0, self.dst_w, self.dst_h)
+            check(self._L.mjg_open_deint(self.device, C.byref(cfg), _lib.CHROMA_FORMATS[self.src_chroma],
+                                         self.deint, self.orient, *rect, *canvas, C.byref(h)))
+        elif self.orient:
             if not hasattr(self._L, "mjg_open_orient"):
                 raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_orient")
             rect = self.crop if self.crop is not None else (0, 0, self.or_w, self.or_h)
@@ -208,16 +225,31 @@ class MjpegEncoder:
         synced: each takes a launch of its own (mjg_queue_depth)."""
         return int(self._L.mjg_queue_depth()) if hasattr(self._L, "mjg_queue_depth") else 2
 
-    def submit(self, frames=None, nframes: Optional[int] = None, device_ptr: Optional[int] = None):
+    def submit(self, frames=None, nframes: Optional[int] = None, device_ptr: Optional[int] = None, halo: int = 0):
         """Queue `nframes` packed frames: a host buffer (numpy / bytes) or a device pointer
         (`device_ptr`, e.g. torch_tensor.data_ptr() on this GPU, kept alive until its sync).
         Up to `host_depth` host submits may be queued (each one's k_encode runs beside the
         previous one's drain and tail kernels), up to `depth` device submits: with merge=True the
-        library holds a device submit and launches it with the next one."""
+        library holds a device submit and launches it with the next one.
+        `halo` (an encoder with `deint`; mjg_submit_halo): bit 1, the buffer starts with one extra
+        frame that is only read, as the first encoded frame's previous one; bit 2, one such frame
+        follows the last encoded one.  `nframes` counts the encoded frames only (a host buffer's
+        default: its frames less the halo ones)."""
+        halo = int(halo)
+        nhalo = (halo & 1) + ((halo >> 1) & 1)
+        if halo and not hasattr(self._L, "mjg_submit_halo"):
+            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_submit_halo")
+
+        def call(ptr, n, dev):
+            if halo:
+                check(self._L.mjg_submit_halo(self._h, ptr, n, dev, halo))
+            else:
+                check(self._L.mjg_submit(self._h, ptr, n, dev))
+
         if device_ptr is not None:
             if nframes is None:
                 raise ValueError("nframes is required with device_ptr")
-            check(self._L.mjg_submit(self._h, C.c_void_p(int(device_ptr)), int(nframes), 1))
+            call(C.c_void_p(int(device_ptr)), int(nframes), 1)
             self._queued.append((int(nframes), None))
             self._synced_since_submit = False
             return
@@ -227,8 +259,10 @@ class MjpegEncoder:
         if arr.size % self.frame_bytes:
             raise ValueError(f"buffer of {arr.size} bytes is not a whole number of "
                              f"{self.frame_bytes}-byte frames")
-        n = arr.size // self.frame_bytes if nframes is None else int(nframes)
-        check(self._L.mjg_submit(self._h, C.c_void_p(arr.ctypes.data), n, 0))
+        n = arr.size // self.frame_bytes - nhalo if nframes is None else int(nframes)
+        if halo and (n + nhalo) * self.frame_bytes > arr.size:
+            raise ValueError(f"buffer of {arr.size} bytes holds fewer than {n} frames and {nhalo} halo frame(s)")
+        call(C.c_void_p(arr.ctypes.data), n, 0)
         self._queued.append((n, arr))  # the async H2D copy reads arr until its sync
         self._synced_since_submit = False
 
@@ -322,13 +356,19 @@ class MjpegEncoder:
         return int(self._last_sizes.sum())
 
     def encode(self, frames) -> List[bytes]:
-        """Encode host frames (any count; split into max_batch submits)."""
+        """Encode host frames (any count; split into max_batch submits).  With `deint` the frames
+        are one sequence: up to max_batch of them one submit, more of them halo submits that carry
+        each piece's neighbour frames, which gives the same bytes."""
         arr = np.ascontiguousarray(np.asarray(frames, dtype=np.uint8)).reshape(-1)
         n = arr.size // self.frame_bytes
         out: List[bytes] = []
         for i in range(0, n, self.max_batch):
             k = min(self.max_batch, n - i)
-            self.submit(arr[i * self.frame_bytes:(i + k) * self.frame_bytes], k)
+            if self.deint and n > self.max_batch:
+                lo, hi = (1 if i else 0), (1 if i + k < n else 0)
+                self.submit(arr[(i - lo) * self.frame_bytes:(i + k + hi) * self.frame_bytes], k, halo=lo | hi << 1)
+            else:
+                self.submit(arr[i * self.frame_bytes:(i + k) * self.frame_bytes], k)
             out.extend(self.fetch())
         return out
 
@@ -370,6 +410,16 @@ class MjpegEncoder:
         out = np.zeros(self.frame_bytes, np.uint8)
         check(self._L.mjg_debug_oriented(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)),
                                          out.size))
+        return out
+
+    def debug_deint(self, frame: int = 0) -> np.ndarray:
+        """The deinterlaced frame (k_yadif_plane's output) of a frame of the last synced submit:
+        packed planar, src_w x src_h in the input format `src_chroma`, frame_bytes bytes.  Only for
+        an encoder opened with a non-zero `deint`."""
+        if not hasattr(self._L, "mjg_debug_deint"):
+            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_debug_deint")
+        out = np.zeros(self.frame_bytes, np.uint8)
+        check(self._L.mjg_debug_deint(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size))
         return out
 
     def scale_path(self, plane: int) -> int:

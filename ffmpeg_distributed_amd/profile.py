@@ -16,7 +16,14 @@ with FILTERS one of
 which is composed here into one of eight plane maps, `Profile.orient` = T | FX << 1 | FY << 2
 (`vflip,vflip` is 0 and costs nothing).  `hflip` is not parsed: the library and the
 encoder take its map (orient 2) and compose_orient composes it, but a graph that names it stays
-outside the profile, as it was (DESIGN §4.12 says why).  An orientation filter after a crop, scale
+outside the profile, as it was (DESIGN §4.12 says why).  In front of all of that, as the very
+first filter of the graph or alone,
+    yadif[=mode[:parity[:deint]]]           (also mode=, parity=, deint=; send_frame / 0, send_frame_nospatial / 2;
+                                            tff / 0, bff / 1, auto / -1; all / 0)
+is `Profile.deint` = {"mode": 0 | 2, "parity": -1 | 0 | 1} (parity auto is resolved by
+the worker from the container's field order).  The field-rate modes 1 and 3, deint=interlaced, a
+yadif anywhere else in the graph, and bwdif, w3fdif, estdif and the other deinterlacers are outside
+the profile, each with a reason that names it.  An orientation filter after a crop, scale
 or pad, transpose values 4..7, a passthrough other than none and any other option are outside the
 profile.  The crop values are decimal integers (no expressions); `Profile.crop` is the request as
 given and `resolve_crop` turns it into a rectangle of a given input (vf_crop.c's rounding,
@@ -64,6 +71,9 @@ class Profile:
     # a leading run of vflip / transpose filters, composed: T | FX << 1 | FY << 2 (compose_orient);
     # the crop, the scale and the pad then see the oriented frame.  0: none
     orient: int = 0
+    # -vf yadif as the very first filter: {"mode": 0 | 2, "parity": -1 (auto: the container's field
+    # order, worker.resolve_parity) | 0 (tff) | 1 (bff)}; None: no deinterlacer
+    deint: Optional[dict] = None
 
 
 class Unsupported(ValueError):
@@ -240,10 +250,75 @@ def compose_orient(filters: Sequence[str]) -> int:
     return o
 
 
+YADIF_MODES = {"send_frame": 0, "send_field": 1, "send_frame_nospatial": 2, "send_field_nospatial": 3}
+YADIF_PARITIES = {"tff": 0, "bff": 1, "auto": -1}
+YADIF_DEINTS = {"all": 0, "interlaced": 1}
+# the deinterlacers that are named only to say that they run on the CPU
+OTHER_DEINTERLACERS = ("bwdif", "w3fdif", "estdif", "kerndeint", "nnedi", "mcdeint", "fieldmatch", "pullup",
+                       "yadif_cuda", "bwdif_cuda", "bwdif_vulkan", "deinterlace_vaapi", "deinterlace_qsv")
+
+
+def _parse_yadif(f: str) -> dict:
+    """`yadif[=mode[:parity[:deint]]]` -> {"mode": 0 | 2, "parity": -1 | 0 | 1}.  The field-rate
+    modes and deint=interlaced are outside the profile."""
+    name, _, opts = f.partition("=")
+    vals = {"mode": 0, "parity": -1, "deint": 0}
+    tables = {"mode": YADIF_MODES, "parity": YADIF_PARITIES, "deint": YADIF_DEINTS}
+    order, pos = ("mode", "parity", "deint"), 0
+    if "=" in f and not opts:
+        raise Unsupported("yadif= without options")
+    for p in opts.split(":") if opts else []:
+        if "=" in p:
+            k, v = p.split("=", 1)
+        else:
+            if pos >= len(order):
+                raise Unsupported(f"yadif option {p!r} (positional options are mode:parity:deint)")
+            k, v = order[pos], p
+            pos += 1
+        if k not in tables:
+            raise Unsupported(f"yadif option {k!r}")
+        if v in tables[k]:
+            vals[k] = tables[k][v]
+        elif v.lstrip("-").isascii() and v.lstrip("-").isdigit() and int(v) in tables[k].values():
+            vals[k] = int(v)
+        else:
+            raise Unsupported(f"yadif {k}={v}")
+    if vals["mode"] in (1, 3):
+        raise Unsupported(f"yadif mode={vals['mode']} (field rate: one frame per field doubles the frame count and "
+                          f"the rate; only modes 0 and 2 are GPU-accelerated)")
+    if vals["deint"] != 0:
+        raise Unsupported("yadif deint=interlaced (per-frame field flags; only deint=all is GPU-accelerated)")
+    return {"mode": vals["mode"], "parity": vals["parity"]}
+
+
 def _parse_vf(vf: str):
     """-vf value -> (crop request or None, scale size or None, sws flags, pad request or None,
-    orientation).  A leading run of orientation filters is composed and taken off; the limits on
-    the number and order of filters apply to what follows it."""
+    orientation, yadif request or None).  A `yadif` at the very front is taken off first; then a
+    leading run of orientation filters is composed and taken off; the limits on the number and
+    order of filters apply to what follows."""
+    deint = None
+    if ";" not in vf:
+        fs = vf.split(",")
+        names = [f.split("=", 1)[0] for f in fs]
+        other = [nm for nm in names if nm in OTHER_DEINTERLACERS]
+        if other:
+            raise Unsupported(f"filter graph {vf!r}: {other[0]} is not GPU-accelerated (of the deinterlacers only "
+                              f"yadif is)")
+        if "yadif" in names[1:]:
+            at = 1 + names[1:].index("yadif")
+            raise Unsupported(f"filter graph {vf!r}: yadif after {names[at - 1]} (yadif is GPU-accelerated only as "
+                              f"the first filter)")
+        if names[0] == "yadif":
+            deint = _parse_yadif(fs[0])
+            if len(fs) == 1:
+                return None, None, ("bicubic",), None, 0, deint
+            vf = ",".join(fs[1:])
+    return _parse_vf_rest(vf) + (deint,)
+
+
+def _parse_vf_rest(vf: str):
+    """What follows a yadif: (crop request or None, scale size or None, sws flags, pad request or
+    None, orientation)."""
     if ";" not in vf:
         fs = vf.split(",")
         names = [f.split("=", 1)[0] for f in fs]
@@ -389,6 +464,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
     crop = None
     pad = None
     orient = 0
+    deint = None
     flags: Tuple[str, ...] = ("bicubic",)
     i = 0
 
@@ -429,7 +505,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
             if any(name != "bitexact" for _, name in _flag_ops(v)):
                 raise Unsupported(f"-fflags {v}")
         elif o in ("-vf", "-filter:v"):
-            crop, scale, flags, pad, orient = _parse_vf(val())
+            crop, scale, flags, pad, orient, deint = _parse_vf(val())
         elif o in ("-an", "-sn", "-dn", "-y"):
             pass
         elif o in ("-threads", "-threads:v"):
@@ -479,7 +555,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
     if rst:
         huff = "default"  # mjpegenc.c: slice_context_count > 1 forces HUFFMAN_TABLE_DEFAULT
     return Profile(qscale=effective_qscale(q), q_arg=q, scale=scale, sws_flags=flags, huffman=huff,
-                   rst=rst, chroma=chroma, crop=crop, pad=pad, orient=orient)
+                   rst=rst, chroma=chroma, crop=crop, pad=pad, orient=orient, deint=deint)
 
 
 PIX_FMT_CHROMA = {"yuvj420p": "420", "yuvj422p": "422", "yuvj444p": "444"}

@@ -27,6 +27,14 @@ GPU to the whole decoded frames before anything else; the crop, the scale, the S
 then start from the oriented size (height x width under a transpose, the SAR inverted as
 vf_transpose does).  A transpose of a 4:2:2 input goes to the real ffmpeg, which converts the
 format first.
+A `yadif` as the very first filter (profile.Profile.deint) is run by the GPU on the decoded
+frames before all of that.  Its parity is the one given, or with `auto` the input's field order
+(container.StreamInfo.field; resolve_deint): a stream of mixed or unknown order, and one with a
+plane below 3 x 3, go to the real ffmpeg, which is told the source's field order in the y4m header.
+Every output frame reads the frame before and the frame after it, so with a deinterlacer the
+page-locked batches hold two more frames, the reader keeps one frame of look-ahead and copies the
+previous batch's last frame and its look-ahead frame to the head of the next (deint_step is the
+schedule; run()'s deint_reader follows it), and each batch is a halo submit (encoder.submit(halo=)).
 """
 from __future__ import annotations
 
@@ -462,15 +470,63 @@ def resample_plan(prof, info):
     return f"-pix_fmt needs {src} -> {dst} chroma resampling"
 
 
-def encoder_key(prof, info, dst_w, dst_h, sar, com_itu601, batch, rect=None, pad=None, orient=0):
+def encoder_key(prof, info, dst_w, dst_h, sar, com_itu601, batch, rect=None, pad=None, orient=0, deint=0):
     """What an encoder context kept between segments (serve / resident mode) depends on: the
     input's shape and format and everything of the profile the context is opened with, the
     encoded chroma format (-pix_fmt), the resolved crop rectangle (x, y, w, h), the resolved
-    pad (x, y, W, H) and the orientation (0..7) included."""
+    pad (x, y, W, H), the orientation (0..7) and the deinterlacer (the resolved MJG_DEINT_* bits,
+    resolve_deint: the batch buffers of such a context hold two more frames) included."""
     src_chroma, dst_chroma = resample_plan(prof, info)
     return (info.width, info.height, dst_w, dst_h, info.full_range, prof.qscale, sar,
             com_itu601, prof.huffman, src_chroma, dst_chroma, prof.rst, batch,
-            None if rect is None else tuple(rect), None if pad is None else tuple(pad), int(orient))
+            None if rect is None else tuple(rect), None if pad is None else tuple(pad), int(orient), int(deint))
+
+
+def resolve_deint(spec, info):
+    """The MJG_DEINT_* bits of a yadif request (profile.Profile.deint) for a segment's input, or
+    the reason (a str) it runs on the CPU.  parity=tff / bff is used as given; auto takes the
+    stream's field order (container.StreamInfo.field): unflagged and top-field-first streams are
+    tff, bottom-field-first ones bff, and a stream that declares anything else (y4m `Im`, a
+    Matroska FieldOrder other than 1 and 6) has no single parity.  A plane below 3 x 3 is outside
+    the filter's row and column clamps as the library restates them."""
+    if spec is None:
+        return 0
+    hs, vs = _CHROMA_SHIFTS[str(info.chroma)]
+    if min(info.width, info.height, (info.width + hs) >> hs, (info.height + vs) >> vs) < 3:
+        return f"yadif of a {info.width}x{info.height} {info.chroma} input: a plane smaller than 3x3"
+    parity = spec["parity"]
+    if parity < 0:
+        if info.field not in ("p", "t", "b"):
+            return (f"yadif parity=auto on a stream of mixed or unknown field order (I{info.field}): per-frame field "
+                    f"flags are not GPU-accelerated")
+        parity = 1 if info.field == "b" else 0
+    return 1 | (2 if spec["mode"] == 2 else 0) | (4 if parity else 0)
+
+
+def deint_step(done: int, read: int, batch: int, eof: bool):
+    """One submit of a deinterlaced segment: `done` frames are encoded, `read` frames have been
+    read (the reader keeps one frame of look-ahead: read == done + batch + 1 unless the input
+    ended, `eof`).  Returns (first, n, has_prev, has_next): frames [first, first + n) are encoded,
+    with frame first - 1 in front of them and frame first + n behind them in the buffer when the
+    flags say so.  n may be 0 at the end of the input."""
+    n = max(0, min(batch, read - done - (0 if eof else 1)))
+    return done, n, done > 0, done + n < read
+
+
+def deint_schedule(nframes: int, batch: int):
+    """Every submit of a segment of `nframes` frames, as run()'s reader makes them (deint_step on
+    what it has read): the last one has no next frame, a segment of one frame neither neighbour."""
+    out, done, read = [], 0, 0
+    while True:
+        want = done + batch + 1
+        read = min(nframes, want)
+        eof = read < want
+        first, n, hp, hn = deint_step(done, read, batch, eof)
+        if n:
+            out.append((first, n, hp, hn))
+        done += n
+        if eof:
+            return out
 
 
 def oriented_size(w: int, h: int, orient: int):
@@ -547,6 +603,12 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
         stderr.flush()
         return ffmpeg_fallthrough(src, args, stdout, stderr)
     src_chroma, dst_chroma = plan
+    # -vf yadif in front of everything: the parity from the request or the stream's field order
+    deint = resolve_deint(prof.deint, info)
+    if isinstance(deint, str):
+        stderr.write(f"gpu:{device}: {deint}; running ffmpeg on the CPU\n")
+        stderr.flush()
+        return ffmpeg_fallthrough(src, args, stdout, stderr)
     # -vf vflip / transpose in front: everything below starts from the oriented frame.
     # vf_transpose takes only formats whose two chroma shifts are equal
     orient = prof.orient
@@ -603,7 +665,7 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
     # (a transpose hands on 1 / SAR when the SAR is known: vf_transpose config_props_output)
     sar = profile.scaled_sar(oriented_sar(info.sar, orient), in_size, (dst_w, dst_h))
     key = encoder_key(prof, info, dst_w, dst_h, sar, opts.com_itu601 and not info.full_range, batch, rect, pad,
-                      orient)
+                      orient, deint)
     nbuf = NBUF
     if cache is not None and cache.get("key") == key:
         enc, bufs, obufs = cache["enc"], cache["bufs"], cache["obufs"]
@@ -614,8 +676,9 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
                            qscale=prof.qscale, sar=sar, max_batch=batch,
                            com_itu601=opts.com_itu601 and not info.full_range, huffman=prof.huffman,
                            chroma=dst_chroma, src_chroma=src_chroma, rst=prof.rst, crop=rect, pad=pad,
-                           orient=orient)
-        bufs = [PinnedBuffer(batch * enc.frame_bytes) for _ in range(nbuf)]
+                           orient=orient, deint=deint or None)
+        # (a deinterlacer: room for the frame in front of a batch and the one behind it)
+        bufs = [PinnedBuffer((batch + (2 if deint else 0)) * enc.frame_bytes) for _ in range(nbuf)]
         # page-locked output buffers: the packets are DMA'd into one (enc.fetch_into) and the
         # muxer writes them from it; regrown when a submit's JPEGs do not fit
         obufs = [None] * NOUT
@@ -655,7 +718,44 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
         except BaseException as e:   # surfaced by the main loop
             full.put(e)
 
-    th = threading.Thread(target=reader, daemon=True)
+    def deint_reader():
+        """The reader of a deinterlaced segment: a batch needs the frame in front of it and the
+        one behind it, so the reader keeps one frame of look-ahead and every buffer but the first
+        starts with the previous buffer's last encoded frame and its look-ahead frame (two host
+        frame copies per batch; the previous buffer is only read, this thread is the only writer).
+        Posts (buffer, encoded frames, halo) with the encoded frames after the halo frame in front."""
+        try:
+            done = read = 0
+            prev = None  # the previous buffer and the slot of its last encoded frame
+            while True:
+                i = free.get()
+                if i < 0 or abort.is_set():
+                    return
+                t0 = time.monotonic()
+                arr = bufs[i].array
+                base = 0
+                if prev is not None:
+                    pi, slot = prev
+                    if pi == i:
+                        raise RuntimeError("deinterlacer: the previous batch buffer came back before the next was filled")
+                    arr[:2 * fb] = bufs[pi].array[slot * fb:(slot + 2) * fb]
+                    base = 2
+                want = done + batch + 1 - read
+                got = src.read_into(arr[base * fb:(base + want) * fb], want)
+                read += got
+                eof = got < want
+                _, n, hp, hn = deint_step(done, read, batch, eof)
+                tr["read"] += time.monotonic() - t0
+                full.put((i, n, int(hp) | int(hn) << 1))
+                prev = (i, int(hp) + n - 1)
+                done += n
+                if eof:
+                    full.put(None)
+                    return
+        except BaseException as e:   # surfaced by the main loop
+            full.put(e)
+
+    th = threading.Thread(target=deint_reader if deint else reader, daemon=True)
     th.start()
     frames = 0
     queued: "list" = []  # buffer index and frame count per submit, oldest first
@@ -732,12 +832,16 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
                 break
             if isinstance(item, BaseException):
                 raise item
-            i, n = item
+            i, n, *halo = item  # (a deinterlacer's reader adds the halo bits)
             if n:
                 if len(queued) == enc.host_depth:  # host submits: one launch each
                     drain_one()
                 t0 = time.monotonic()
-                enc.submit(bufs[i].array[: n * fb], n)
+                if halo:
+                    nh = (halo[0] & 1) + (halo[0] >> 1)
+                    enc.submit(bufs[i].array[: (n + nh) * fb], n, halo=halo[0])
+                else:
+                    enc.submit(bufs[i].array[: n * fb], n)
                 tr["submit"] += time.monotonic() - t0
                 queued.append((i, n))
             else:

@@ -6,8 +6,9 @@
  *     nice -n10 ionice -c3 ffmpeg -f matroska -i pipe: <remote_args> -f matroska pipe:
  * and launched/supervised at ffmpeg_distributed.py:139-141 (FFMPEGProc.run,
  * ffmpeg_distributed.py:59-91).  For the north-star profile
- *     [-vf [vflip|transpose=N,...][crop=w:h:x:y,][scale=W:H:flags=bicubic][,pad=W:H:x:y]] -c:v mjpeg -q:v N -dct int -huffman default -bitexact
- * (a leading run of vflip / transpose: one of eight plane maps, mjg_open_orient; and `-pix_fmt yuvj420p|yuvj422p` from a 4:4:4 or 4:2:2 input: the chroma down-sampling
+ *     [-vf [yadif[=0|2],][vflip|transpose=N,...][crop=w:h:x:y,][scale=W:H:flags=bicubic][,pad=W:H:x:y]] -c:v mjpeg -q:v N -dct int -huffman default -bitexact
+ * (`yadif` as the very first filter, frame-rate modes 0 and 2: the deinterlacer, mjg_open_deint,
+ * a restatement of the filter's C path that no FFmpeg build has been compared with yet; a leading run of vflip / transpose: one of eight plane maps, mjg_open_orient; and `-pix_fmt yuvj420p|yuvj422p` from a 4:4:4 or 4:2:2 input: the chroma down-sampling
  * FFmpeg's auto-inserted scaler does, taken to be its default bicubic; `-vf crop=...` alone or
  * before the scale: a rectangle of the decoded frames, mjg_open_crop; `pad=...` as the last
  * filter: the picture on a black canvas, mjg_open_pad)
@@ -180,6 +181,33 @@ int mjg_open_pad(int device, const mjg_config *cfg, int src_chroma_format,
 int mjg_open_orient(int device, const mjg_config *cfg, int src_chroma_format, int orient,
                     int crop_x, int crop_y, int crop_w, int crop_h,
                     int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
+
+/* mjg_open_deint's `deint` */
+#define MJG_DEINT_YADIF 1      /* -vf yadif, mode 0 (send_frame), deint=all */
+#define MJG_DEINT_NOSPATIAL 2  /* ... mode 2 (send_frame_nospatial): no spatial interlacing check */
+#define MJG_DEINT_BFF 4        /* bottom field first (parity=bff): the even rows are interpolated; without
+                                  it top field first, the odd rows */
+/* mjg_open_orient behind a deinterlacer (`-vf yadif[=0|2]` as the first filter of the graph):
+ * deint = 0 (none) or MJG_DEINT_YADIF | MJG_DEINT_NOSPATIAL | MJG_DEINT_BFF.  k_yadif_plane
+ * (scale.hip, which restates the filter: the C path of FFmpeg's vf_yadif.c / yadif_common.c as this
+ * project's issue text gives it, not checked against an FFmpeg build here) writes the
+ * deinterlaced frames -- same format, same bytes per frame, no range conversion, every plane
+ * filtered alike -- into a buffer of the launch slot; the orientation stage, the sws stage, or
+ * without either k_encode in place, reads that buffer.  Frame i of a sequence of n is made from
+ * frames max(i - 1, 0), i and min(i + 1, n - 1): n outputs for n inputs.  On such a context every
+ * mjg_submit is a whole sequence and every segment of a mjg_submit_segments is one (the bytes of
+ * one mjg_submit per segment, as ever); a sequence longer than a submit is handed over with
+ * mjg_submit_halo.  The context neither holds nor merges submits: MJG_F_MERGE is accepted and has
+ * no effect, mjg_ctx_queue_depth is mjg_queue_depth().  The deinterlacer's launches are part of
+ * the MJG_K_SCALE interval, which a deinterlacer alone opens too.  cfg->src_w / src_h, orient, the
+ * crop and the pad mean what they mean for mjg_open_orient.  deint 0 is exactly mjg_open_orient:
+ * no buffer, the same launches.  MJG_E_INVALID (before any HIP call, with a message that names
+ * the deinterlacer: "deint ...") for unknown bits, option bits without MJG_DEINT_YADIF, and a
+ * source whose luma or chroma plane is smaller than 3 x 3.  (Added without a version step, as
+ * mjg_open_orient.) */
+int mjg_open_deint(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient,
+                   int crop_x, int crop_y, int crop_w, int crop_h,
+                   int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
 void mjg_close(mjg_ctx *ctx);
 
 /* Bytes of one packed planar input frame (src_w x src_h in the source chroma format). */
@@ -207,6 +235,14 @@ int mjg_header(const mjg_ctx *ctx, uint8_t *out, size_t cap, size_t *len);
  * past that (or when no launch slot is free for a host submit).
  * Replaces the per-segment encode the reference runs at ffmpeg_distributed.py:139-141. */
 int mjg_submit(mjg_ctx *ctx, const uint8_t *frames, int nframes, int src_is_device);
+/* mjg_submit for a piece of a longer sequence, on a context with a deinterlacer: halo bit 1,
+ * `frames` starts with one extra frame that is only read (the first encoded frame's `prev`); bit
+ * 2, one extra frame follows the last encoded one (its `next`).  nframes counts the encoded frames
+ * only (<= max_batch); a host submit copies nframes plus the halo frames (its staging holds
+ * max_batch + 2).  The kernel reads no frame outside [first encoded - (halo & 1), last encoded +
+ * (halo >> 1)].  halo 0 is mjg_submit; a non-zero halo on a context without a deinterlacer, or one
+ * outside 0..3, is MJG_E_INVALID.  (With mjg_open_deint.) */
+int mjg_submit_halo(mjg_ctx *ctx, const uint8_t *frames, int nframes, int src_is_device, int halo);
 /* Several segments in one submit: segment k's seg_nframes[k] packed I420 frames at device
  * pointer seg_frames[k] (on ctx's device), nsegs in 1..mjg_max_segments(), the total within
  * max_batch.  One launch of each kernel (the sws stage's, k_encode, the tail) covers all
@@ -293,6 +329,13 @@ int mjg_debug_oriented(mjg_ctx *ctx, int frame, uint8_t *out, size_t cap);
 /* The orientation of the context (0..7; mjg_open_orient), or a negative MJG_E_* code for a null
  * context.  Host state only.  (With mjg_open_orient.) */
 int mjg_debug_orient(mjg_ctx *ctx);
+/* The deinterlaced frame (k_yadif_plane's output: packed planar, mjg_frame_bytes bytes, the decoded
+ * size in the source format) of frame `frame` of the last synced submit.  MJG_E_STATE for a
+ * context without a deinterlacer.  (With mjg_open_deint.) */
+int mjg_debug_deint(mjg_ctx *ctx, int frame, uint8_t *out, size_t cap);
+/* The context's `deint` value (mjg_open_deint; 0 without a deinterlacer), or a negative MJG_E_*
+ * code for a null context.  Host state only.  (With mjg_open_deint.) */
+int mjg_debug_deint_flags(mjg_ctx *ctx);
 /* Filter tables the context generated: plane 0 = luma, 1 = chroma; dir 0 = horizontal,
  * 1 = vertical.  taps/len may be queried with coeff == NULL.  As mjg_debug_planes: only when
  * the sws stage runs. */

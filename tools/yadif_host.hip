@@ -1,0 +1,73 @@
+// k_yadif_plane's body (scale.hip yadif_work, __host__ __device__) on the CPU: every (workgroup, thread) of
+// the luma and the U + V launch of one submit, on source and destination buffers allocated at exactly
+// their sizes, so that AddressSanitizer sees any access outside a readable frame.  Built and driven by
+// tools/yadif_host_check.py (hipcc -Xarch_host -fsanitize=address,undefined); makes no HIP call.
+//   yadif_host IN OUT w h hshift vshift nospatial parity nframes halo split
+// IN: nframes + halo frames, packed planar; split > 0: frames [0, split) and [split, nframes) are two
+// segments in allocations of their own (mjg_submit_segments' SegList).
+#include <climits>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+#include "kernels.hip"
+#include "scale.hip"
+using namespace mjg;
+
+static uint32_t magic32(uint32_t d) { return d > 1 ? (uint32_t)((((uint64_t)1 << 32) + d - 1) / d) : 0u; }
+
+int main(int argc, char **argv) {
+  if (argc < 12) return 2;
+  const char *in = argv[1], *outp = argv[2];
+  const int w = atoi(argv[3]), h = atoi(argv[4]), hs = atoi(argv[5]), vs = atoi(argv[6]);
+  const int nosp = atoi(argv[7]), parity = atoi(argv[8]), n = atoi(argv[9]), halo = atoi(argv[10]), split = atoi(argv[11]);
+  const int hp = halo & 1, hn = (halo >> 1) & 1;
+  const int cw = (w + hs) >> hs, ch = (h + vs) >> vs;
+  const size_t fb = (size_t)w * h + 2 * (size_t)cw * ch;
+  const size_t tot = (size_t)(n + hp + hn) * fb;
+  FILE *f = fopen(in, "rb");
+  // exact-size buffers: segment 0 and (split) segment 1 in separate allocations
+  const int n0 = split ? split : n;
+  uint8_t *b0 = (uint8_t *)malloc(split ? n0 * fb : tot);
+  uint8_t *b1 = split ? (uint8_t *)malloc((n - n0) * fb) : nullptr;
+  if (fread(b0, 1, split ? n0 * fb : tot, f) != (split ? n0 * fb : tot)) return 3;
+  if (split && fread(b1, 1, (n - n0) * fb, f) != (n - n0) * fb) return 3;
+  fclose(f);
+  // destination at an odd alignment inside an exact allocation: d + 1
+  uint8_t *dbase = (uint8_t *)malloc(n * fb);
+  SegList sl;
+  for (int k = 0; k < kMaxSegs; k++) sl.p[k] = b0 + hp * fb, sl.f0[k] = k ? INT_MAX : 0;
+  if (split) sl.p[1] = b1, sl.f0[1] = n0;
+  for (int p = 0; p < 2; p++) {
+    DeintGeom g{};
+    g.w = p ? cw : w;
+    g.h = p ? ch : h;
+    g.off = p ? (long long)w * h : 0;
+    g.fstride = (long long)fb;
+    g.parity = parity;
+    g.w_magic = magic32(g.w);
+    const size_t pieces = ((size_t)g.w * g.h) >> 4;
+    g.gxy = (int)std::max<size_t>(1, (pieces + kDeintThreads - 1) / kDeintThreads);
+    g.gxy_magic = magic32(g.gxy);
+    g.nf = n;
+    for (int k = 0; k < kMaxSegs; k++) {
+      const int end = k + 1 < kMaxSegs && sl.f0[k + 1] != INT_MAX ? sl.f0[k + 1] : n;
+      g.lo[k] = -hp;
+      g.hi[k] = sl.f0[k] == INT_MAX ? 0 : end - sl.f0[k] - 1 + hn;
+    }
+    if (p) g.poff = (long long)cw * ch;
+    const int nz = p ? 2 * n : n;
+    for (int t = 0; t < g.gxy * nz; t++)
+      for (int tid = 0; tid < kDeintThreads; tid++) {
+        if (nosp) yadif_work<true>(sl, dbase, g, t, tid);
+        else yadif_work<false>(sl, dbase, g, t, tid);
+      }
+  }
+  f = fopen(outp, "wb");
+  fwrite(dbase, 1, n * fb, f);
+  fclose(f);
+  free(b0);
+  free(b1);
+  free(dbase);
+  return 0;
+}
