@@ -44,6 +44,7 @@ EXPORTS = (
     "mjg_debug_planes", "mjg_debug_filter", "mjg_debug_huff_build", "mjg_debug_scale_path",
     "mjg_debug_encode_path", "mjg_debug_oriented", "mjg_debug_orient",
     "mjg_open_deint", "mjg_submit_halo", "mjg_debug_deint", "mjg_debug_deint_flags",
+    "mjg_open_sharp", "mjg_debug_presharp", "mjg_debug_unsharp",
 )
 
 # mjg_open_deint's `deint`
@@ -67,6 +68,12 @@ class MjgConfig(C.Structure):
         ("max_batch", C.c_int32), ("flags", C.c_uint32),
         ("chroma_format", C.c_int32),
     ]
+
+
+class MjgUnsharp(C.Structure):
+    """mjg_unsharp: -vf unsharp's sizes and amounts, the amounts as int(amount * 65536.0)."""
+    _fields_ = [("lx", C.c_int32), ("ly", C.c_int32), ("la", C.c_int32),
+                ("cx", C.c_int32), ("cy", C.c_int32), ("ca", C.c_int32)]
 
 
 _lib = None
@@ -109,6 +116,13 @@ def load():
             L.mjg_debug_deint.restype = C.c_int
             L.mjg_debug_deint_flags.argtypes = [vp]
             L.mjg_debug_deint_flags.restype = C.c_int
+        if hasattr(L, "mjg_open_sharp"):  # absent from libraries built before the sharpen (A/B builds)
+            L.mjg_open_sharp.argtypes = ([C.c_int, C.POINTER(MjgConfig)] + [C.c_int] * 7 + [C.POINTER(MjgUnsharp)]
+                                         + [C.c_int] * 4 + [C.POINTER(vp)])
+            L.mjg_debug_presharp.argtypes = [vp, C.c_int, u8p, sz]
+            L.mjg_debug_presharp.restype = C.c_int
+            L.mjg_debug_unsharp.argtypes = [vp, C.POINTER(MjgUnsharp)]
+            L.mjg_debug_unsharp.restype = C.c_int
         L.mjg_close.argtypes = [vp]
         L.mjg_close.restype = None
         L.mjg_frame_bytes.argtypes = [vp]
@@ -155,7 +169,8 @@ def load():
         late = (("mjg_queue_depth", "mjg_ctx_queue_depth", "mjg_submit_segments", "mjg_max_segments",
                  "mjg_debug_huff_build", "mjg_open_src", "mjg_open_crop", "mjg_open_pad", "mjg_debug_scale_path",
                  "mjg_debug_encode_path", "mjg_open_orient", "mjg_debug_oriented", "mjg_debug_orient",
-                 "mjg_open_deint", "mjg_submit_halo", "mjg_debug_deint", "mjg_debug_deint_flags")
+                 "mjg_open_deint", "mjg_submit_halo", "mjg_debug_deint", "mjg_debug_deint_flags",
+                 "mjg_open_sharp", "mjg_debug_presharp", "mjg_debug_unsharp")
                 if os.environ.get("MJG_LIBRARY") else ())
         for name in EXPORTS:
             if name not in late:

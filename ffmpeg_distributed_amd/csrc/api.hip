@@ -227,6 +227,14 @@ struct DeintPass {
   DeintGeom g{};
 };
 
+// One launch of the sharpen (k_unsharp_plane; 0 luma, 1 chroma: U and V share it), built at open like
+// the orientation stage's: the sws stage's output buffer -> the slot's d_sharp.
+using SharpFn = void (*)(const SharpGeom &g, const uint8_t *src, uint8_t *dst, int nz, hipStream_t st);
+struct SharpPass {
+  SharpFn launch = nullptr;
+  SharpGeom g{};
+};
+
 struct Slot;
 using EncodeFn = void (*)(const mjg_ctx *c, Slot &S, const SegList &enc_in, int wgs, int ntasks);
 
@@ -267,6 +275,7 @@ struct Slot {
   uint8_t *d_scaled = nullptr;     // -vf scale: k_scale's output planes
   uint8_t *d_orient = nullptr;     // -vf hflip / vflip / transpose: k_orient_plane's output frames
   uint8_t *d_deint = nullptr;      // -vf yadif: k_yadif_plane's output frames
+  uint8_t *d_sharp = nullptr;      // -vf unsharp: k_unsharp_plane's output, the encoder's input
   uint32_t *d_stage_bits = nullptr;  // k_encode: per wave, lane-major staging of blocks past 128 bits
   int n = 0;  // frames of the launch
   uint32_t *d_scratch = nullptr;
@@ -312,6 +321,11 @@ struct mjg_ctx {
   // frames.  Every submit (every segment of one) is a sequence of its own: no merging
   int deint = 0;
   DeintPass dpass[2];           // its launches: 0 luma, 1 chroma
+  // -vf unsharp (mjg_open_sharp): behind the sws stage (which then always runs) and in front of
+  // the pad's border; k_encode reads its buffer
+  bool sharp = false;
+  mjg_unsharp us{};
+  SharpPass shpass[2];          // its launches: 0 luma, 1 chroma
   size_t in_frame_bytes = 0, enc_frame_bytes = 0;
   // the crop rectangle (mjg_open_crop; the whole frame otherwise): the input of the sws stage,
   // or of k_encode without one
@@ -374,7 +388,7 @@ void free_ctx(mjg_ctx *c) {
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (Slot &S : c->slot) {
-    void *sp[] = {S.d_stage, S.d_scaled, S.d_orient, S.d_deint, S.d_stage_bits, S.d_scratch, S.d_stream, S.d_work, S.d_chunk_bits, S.d_chunk_off, S.d_group_ff, S.d_ff_off, S.d_frame_bits,
+    void *sp[] = {S.d_stage, S.d_scaled, S.d_orient, S.d_deint, S.d_sharp, S.d_stage_bits, S.d_scratch, S.d_stream, S.d_work, S.d_chunk_bits, S.d_chunk_off, S.d_group_ff, S.d_ff_off, S.d_frame_bits,
                   S.d_status, S.d_frame_size, S.d_frame_offsets, S.d_seg_size, S.d_seg_off, S.d_done, S.d_out,
                   S.d_hist, S.d_ftabs, S.d_dht_nval, S.d_hdr_lens, S.d_dht, S.d_dbg, S.d_syms, S.d_symn};
     for (void *p : sp)
@@ -426,6 +440,8 @@ bool plan_scale_stream(int max_nw, int ht, int npv, StreamGeom *q, bool *hcl, si
 // A context's rectangles, resolved by check_config
 struct Layout {
   int deint;                   // MJG_DEINT_* bits (0: no deinterlacer)
+  bool sharp;                  // -vf unsharp with a non-zero amount
+  mjg_unsharp us;              // ... its sizes and amounts
   int orient, ow, oh;          // the orientation and the oriented frame's size (orient 0: the source's)
   int cx, cy, crw, crh;        // the crop rectangle in the oriented frame: the sws stage's / k_encode's input
   int px, py, pw, ph;          // the picture's place in the canvas and the canvas size (no pad: the picture)
@@ -640,6 +656,7 @@ int alloc_slot(mjg_ctx *c, Slot &S) {
   if (c->scale && (rc = dmalloc(&S.d_scaled, B * c->enc_frame_bytes))) return rc;
   if (c->orient && (rc = dmalloc(&S.d_orient, B * c->in_frame_bytes))) return rc;
   if (c->deint && (rc = dmalloc(&S.d_deint, B * c->in_frame_bytes))) return rc;
+  if (c->sharp && (rc = dmalloc(&S.d_sharp, B * c->enc_frame_bytes))) return rc;
   if ((rc = dmalloc(&S.d_scratch, B * NC * (size_t)kSlotWords)) ||
       (rc = dmalloc(&S.d_stream, B * NC * (size_t)kSlotWords)) ||
       (rc = dmalloc(&S.d_chunk_bits, B * NC)) || (rc = dmalloc(&S.d_chunk_off, B * NC)) ||
@@ -680,7 +697,9 @@ int alloc_slot(mjg_ctx *c, Slot &S) {
 // crop: x, y, w, h in luma samples of the oriented frame, or nullptr for the whole frame
 // pad: x, y, w, h in luma samples of the encoded frame (the picture's place and the canvas size),
 // or nullptr for no pad
-int check_config(const mjg_config &k, int src_cf, int deint, int orient, const int *crop, const int *pad, Layout *lay) {
+// us: -vf unsharp between the sws stage and the pad, or nullptr (both amounts 0: no filter either)
+int check_config(const mjg_config &k, int src_cf, int deint, int orient, const int *crop, const mjg_unsharp *us,
+                 const int *pad, Layout *lay) {
   if (std::min({k.src_w, k.src_h, k.dst_w, k.dst_h}) < 1 || std::max({k.src_w, k.src_h, k.dst_w, k.dst_h}) > 16384)
     return set_err(MJG_E_INVALID, "bad frame size %dx%d -> %dx%d", k.src_w, k.src_h, k.dst_w, k.dst_h);
   if (k.qscale < 1 || k.qscale > 31) return set_err(MJG_E_INVALID, "qscale %d not in 1..31", k.qscale);
@@ -747,7 +766,29 @@ int check_config(const mjg_config &k, int src_cf, int deint, int orient, const i
     return set_err(MJG_E_INVALID, "unknown flags 0x%x", k.flags & ~kKnownFlags);
   if ((k.flags & MJG_F_RST) && (k.flags & MJG_F_HUFFMAN_OPTIMAL))
     return set_err(MJG_E_INVALID, "RST (slice threading) forces -huffman default");
-  *lay = Layout{deint, orient, ow, oh, cx, cy, crw, crh, px, py, pw, ph, has_pad, s_hsh, s_vsh, e_hsh, e_vsh};
+  // the sharpen: odd sizes 3..23, amounts within the filter's option range, and for a plane that is
+  // filtered a sum that fits the filter's 32-bit accumulator
+  mjg_unsharp u{};
+  const bool sharp = us && (us->la != 0 || us->ca != 0);
+  if (us) {
+    u = *us;
+    const int sz[4] = {u.lx, u.ly, u.cx, u.cy};
+    const char *nm[4] = {"lx", "ly", "cx", "cy"};
+    for (int i = 0; i < 4; i++) {
+      if (sz[i] < 3 || sz[i] > 23) return set_err(MJG_E_INVALID, "unsharp %s %d: size not in 3..23", nm[i], sz[i]);
+      if (!(sz[i] & 1)) return set_err(MJG_E_INVALID, "unsharp %s %d: size is even (odd sizes only)", nm[i], sz[i]);
+    }
+    const int am[2] = {u.la, u.ca};
+    for (int i = 0; i < 2; i++) {
+      if (am[i] < -2 * 65536 || am[i] > 5 * 65536)
+        return set_err(MJG_E_INVALID, "unsharp %s %d: amount outside [-2, 5] * 65536", i ? "ca" : "la", am[i]);
+      const int hs = sz[2 * i] / 2 + sz[2 * i + 1] / 2;
+      if (am[i] && hs > kSharpMaxHalfSum)
+        return set_err(MJG_E_INVALID, "unsharp %s %dx%d: sx + sy = %d > %d, the 32-bit sum of the filter wraps",
+                       i ? "chroma" : "luma", sz[2 * i], sz[2 * i + 1], hs, kSharpMaxHalfSum);
+    }
+  }
+  *lay = Layout{deint, sharp, u, orient, ow, oh, cx, cy, crw, crh, px, py, pw, ph, has_pad, s_hsh, s_vsh, e_hsh, e_vsh};
   return MJG_OK;
 }
 
@@ -767,7 +808,10 @@ int plan_geometry(const mjg_config &k, int src_cf, const Layout &lay, bool unali
   // FFmpeg one swscale context does both, and tv->pc in the same pass)
   const int cf = k.chroma_format;
   // (a pad always runs it: k_encode then reads the canvas in d_scaled as any other sws output)
-  c->scale = (crw != k.dst_w || crh != k.dst_h || src_cf != cf || c->has_pad);
+  // (so does a sharpen: k_unsharp_plane reads full-range encoder-input samples from d_scaled)
+  c->sharp = lay.sharp;
+  c->us = lay.us;
+  c->scale = (crw != k.dst_w || crh != k.dst_h || src_cf != cf || c->has_pad || c->sharp);
   const int scw = (fw + s_hsh) >> s_hsh, sch = (fh + s_vsh) >> s_vsh;
   // the rectangle's chroma planes: at (cx >> hs, cy >> vs), the chroma size of a crw x crh frame
   // (inside the source's: cx, cy are multiples of the sub-sampling)
@@ -1082,6 +1126,29 @@ void plan_deint(const mjg_config &k, const Layout &lay, mjg_ctx *c) {
   }
 }
 
+template <int MX, int MY>
+void launch_sharp(const SharpGeom &g, const uint8_t *src, uint8_t *dst, int nz, hipStream_t st) {
+  k_unsharp_plane<MX, MY><<<g.gxy * nz, kSharpThreads, 0, st>>>(src, dst, g);
+}
+
+// The sharpen's launches for luma and chroma (mjg_ctx::shpass; no device, no environment): the
+// encoded frame's planes (the canvas planes under a pad, the picture at the pad's place) of the
+// sws stage's buffer -> the same planes of d_sharp.  A plane whose amount is 0 is copied by the
+// same kernel.  submit_impl adds nf and the U + V pairing.
+void plan_sharp(const mjg_config &k, const Layout &lay, mjg_ctx *c) {
+  if (!lay.sharp) return;
+  const EncGeom &e = c->geom;
+  for (int p = 0; p < 2; p++) {
+    const PadGeom &q = c->pad[p];
+    const int w = p ? (k.dst_w + lay.hsh) >> lay.hsh : k.dst_w, h = p ? (k.dst_h + lay.vsh) >> lay.vsh : k.dst_h;
+    const int mx = p ? lay.us.cx : lay.us.lx, my = p ? lay.us.cy : lay.us.ly;
+    SharpPass &s = c->shpass[p];
+    s.g = sharp_geom(q.cw, q.ch, q.px, q.py, w, h, p ? e.u_off : 0, (long long)c->enc_frame_bytes, mx, my,
+                     p ? lay.us.ca : lay.us.la);
+    s.launch = mx == 5 && my == 5 ? launch_sharp<5, 5> : launch_sharp<0, 0>;
+  }
+}
+
 // RC, DBG, UA: EncGeom's range_convert and debug_coefs, and the context's enc_ua (a crop read in
 // place at any alignment, fetch_rows<UA>)
 template <bool RC, int MODE, bool DBG, bool UA>
@@ -1127,7 +1194,8 @@ int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
     size_t fr = 0, tot = 0;
     HIP_TRY(hipMemGetInfo(&fr, &tot));
     const double per_frame = 2.0 * (double)c->slot_NC * kSlotWords * 4 + 2.0 * (double)c->enc_frame_bytes +
-                             (c->orient ? (double)c->in_frame_bytes : 0.0);  // (a deinterlacer never merges)
+                             (c->orient ? (double)c->in_frame_bytes : 0.0) +  // (a deinterlacer never merges)
+                             (c->sharp ? (double)c->enc_frame_bytes : 0.0);
     if (kSlots * (double)c->merge * (double)k.max_batch * per_frame > kMergeMemShare * (double)fr) c->merge = 1;
   }
   if ((unsigned long long)k.max_batch * c->merge * g.nseg * g.nchunks * g.nchunks >= ((unsigned long long)1 << 40))
@@ -1173,17 +1241,18 @@ int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
   return alloc_slot(c, c->slot[0]);
 }
 
-int open_ctx(int device, const mjg_config *cfg, int src_cf, int deint, int orient, const int *crop, const int *pad,
-             mjg_ctx *c) {
+int open_ctx(int device, const mjg_config *cfg, int src_cf, int deint, int orient, const int *crop,
+             const mjg_unsharp *us, const int *pad, mjg_ctx *c) {
   c->device = device;
   c->cfg = *cfg;
   const mjg_config &k = *cfg;
   Layout lay;
   int rc;
-  if ((rc = check_config(k, src_cf, deint, orient, crop, pad, &lay))) return rc;
+  if ((rc = check_config(k, src_cf, deint, orient, crop, us, pad, &lay))) return rc;
   if ((rc = plan_geometry(k, src_cf, lay, env_int("MJG_UNALIGNED_FETCH", 1) != 0, c))) return rc;
   plan_orient(k, lay, c);
   plan_deint(k, lay, c);
+  plan_sharp(k, lay, c);
   quant_matrix(k.qscale, c->mprime, c->qmat);
   c->hdr = build_header(c->geom.w, c->geom.h, c->mprime, k.sar_num, k.sar_den, (k.flags & MJG_F_COM_ITU601) != 0,
                         k.chroma_format, c->rst, &c->dht_pos, &c->dht_end);
@@ -1254,11 +1323,11 @@ int mjg_device_numa_node(int device) {
 
 namespace {
 int open_any(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, const int *crop,
-             const int *pad, mjg_ctx **out) {
+             const mjg_unsharp *us, const int *pad, mjg_ctx **out) {
   if (!cfg || !out) return set_err(MJG_E_INVALID, "null argument");
   *out = nullptr;
   mjg_ctx *c = new mjg_ctx();
-  const int rc = open_ctx(device, cfg, src_chroma_format, deint, orient, crop, pad, c);
+  const int rc = open_ctx(device, cfg, src_chroma_format, deint, orient, crop, us, pad, c);
   if (rc) {
     const std::string keep = g_err;
     free_ctx(c);
@@ -1273,29 +1342,36 @@ int open_any(int device, const mjg_config *cfg, int src_chroma_format, int deint
 int mjg_open_crop(int device, const mjg_config *cfg, int src_chroma_format, int crop_x, int crop_y, int crop_w,
                   int crop_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h};
-  return open_any(device, cfg, src_chroma_format, 0, 0, crop, nullptr, out);
+  return open_any(device, cfg, src_chroma_format, 0, 0, crop, nullptr, nullptr, out);
 }
 
 int mjg_open_orient(int device, const mjg_config *cfg, int src_chroma_format, int orient, int crop_x, int crop_y,
                     int crop_w, int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, 0, orient, crop, pad, out);
+  return open_any(device, cfg, src_chroma_format, 0, orient, crop, nullptr, pad, out);
 }
 
 int mjg_open_deint(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, int crop_x,
                    int crop_y, int crop_w, int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, deint, orient, crop, pad, out);
+  return open_any(device, cfg, src_chroma_format, deint, orient, crop, nullptr, pad, out);
+}
+
+int mjg_open_sharp(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, int crop_x,
+                   int crop_y, int crop_w, int crop_h, const mjg_unsharp *us, int pad_x, int pad_y, int pad_w,
+                   int pad_h, mjg_ctx **out) {
+  const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
+  return open_any(device, cfg, src_chroma_format, deint, orient, crop, us, pad, out);
 }
 
 int mjg_open_pad(int device, const mjg_config *cfg, int src_chroma_format, int crop_x, int crop_y, int crop_w,
                  int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, 0, 0, crop, pad, out);
+  return open_any(device, cfg, src_chroma_format, 0, 0, crop, nullptr, pad, out);
 }
 
 int mjg_open_src(int device, const mjg_config *cfg, int src_chroma_format, mjg_ctx **out) {
-  return open_any(device, cfg, src_chroma_format, 0, 0, nullptr, nullptr, out);
+  return open_any(device, cfg, src_chroma_format, 0, 0, nullptr, nullptr, nullptr, out);
 }
 
 int mjg_open(int device, const mjg_config *cfg, mjg_ctx **out) {
@@ -1397,9 +1473,20 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
         ps.launch(ps, sg, in_sl, S.d_scaled, p && uv1 ? 2 * n : n, S.st);
       }
     }
+    const uint8_t *enc_buf = S.d_scaled;
+    if (c->sharp) {  // behind the sws stage's passes (the pad's border among them): luma, then U and V as above
+      for (int p = 0; p < (uv1 ? 2 : 3); p++) {
+        SharpGeom hg = c->shpass[p ? 1 : 0].g;
+        hg.nf = n;
+        if (p && uv1) hg.poff = d_cplane;
+        if (p == 2) hg.off += d_cplane;
+        c->shpass[p ? 1 : 0].launch(hg, S.d_scaled, S.d_sharp, p && uv1 ? 2 * n : n, S.st);
+      }
+      enc_buf = S.d_sharp;
+    }
     tmark(c, S, MJG_K_SCALE, 1);
     HIP_TRY(hipGetLastError());
-    enc_in = one_seg(S.d_scaled);  // k_encode reads the scaled frames, one buffer
+    enc_in = one_seg(enc_buf);  // k_encode reads the scaled (the sharpened) frames, one buffer
   } else {  // in place: EncGeom's offsets count from the rectangle's first luma byte (0: whole frames)
     if (c->orient || c->deint) tmark(c, S, MJG_K_SCALE, 1);  // an orientation / a deinterlacer alone: the interval holds its passes
     for (int k = 0; k < kMaxSegs; k++) enc_in.p[k] += c->src_off[0];
@@ -1824,8 +1911,32 @@ int mjg_debug_planes(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
   if (frame < 0 || frame >= L.jn[c->last_job]) return set_err(MJG_E_INVALID, "frame %d", frame);
   if (cap < c->enc_frame_bytes) return set_err(MJG_E_CAPACITY, "need %zu bytes", c->enc_frame_bytes);
   const size_t f = (size_t)L.jf0[c->last_job] + (size_t)frame;
+  // the encoder's input: under a sharpen its output
+  const uint8_t *buf = c->sharp ? L.d_sharp : L.d_scaled;
+  HIP_TRY(hipMemcpy(out, buf + f * c->enc_frame_bytes, c->enc_frame_bytes, hipMemcpyDeviceToHost));
+  return MJG_OK;
+}
+
+int mjg_debug_presharp(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
+  if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
+  if (!c->sharp) return set_err(MJG_E_STATE, "context has no sharpen (no unsharp, or both amounts 0)");
+  if (pending_jobs(c) > 0) {  // the latest synced submit's planes
+    const int rc = mjg_sync(c, nullptr, nullptr);
+    if (rc) return rc;
+  }
+  if (pending_jobs(c) > 0 || c->last < 0) return set_err(MJG_E_STATE, "sync every queued submit first");
+  const Slot &L = c->slot[c->last];
+  if (frame < 0 || frame >= L.jn[c->last_job]) return set_err(MJG_E_INVALID, "frame %d", frame);
+  if (cap < c->enc_frame_bytes) return set_err(MJG_E_CAPACITY, "need %zu bytes", c->enc_frame_bytes);
+  const size_t f = (size_t)L.jf0[c->last_job] + (size_t)frame;
   HIP_TRY(hipMemcpy(out, L.d_scaled + f * c->enc_frame_bytes, c->enc_frame_bytes, hipMemcpyDeviceToHost));
   return MJG_OK;
+}
+
+int mjg_debug_unsharp(mjg_ctx *c, mjg_unsharp *out) {
+  if (!c) return set_err(MJG_E_INVALID, "null context");
+  if (c->sharp && out) *out = c->us;
+  return c->sharp ? 1 : 0;
 }
 
 int mjg_debug_oriented(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {

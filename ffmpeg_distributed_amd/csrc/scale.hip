@@ -1248,4 +1248,301 @@ __global__ __launch_bounds__(kDeintThreads) void k_yadif_plane(const SegList src
   yadif_work<NOSPATIAL>(src, dst, g, (int)blockIdx.x, (int)threadIdx.x);
 }
 
+// k_unsharp_plane: `-vf unsharp`, behind the sws stage and in front of the pad's
+// border: one plane of the sws stage's output (full-range encoder-input samples) -> the same plane
+// of a second buffer of the same layout (the slot's d_sharp), which k_encode then reads.  With
+// sx = mx / 2, sy = my / 2, scalebits = 2 (sx + sy), half = 1 << (scalebits - 1), amount =
+// (int)(amount * 65536.0), C(n, k) the binomial coefficient, P the w x h picture plane and its
+// indices clamped into it (edge replication):
+//   blur[y][x] = (sum_j sum_i C(2sy, j) C(2sx, i) P[clamp(y + j - sy)][clamp(x + i - sx)] + half) >> scalebits
+//   out[y][x]  = clip_uint8(P[y][x] + (((P[y][x] - blur[y][x]) * amount) >> 16))     (C int, arithmetic >>)
+// which is what vf_unsharp.c's running pair sums come to while 8 + scalebits <= 32 (the host refuses
+// anything else for a plane whose amount is not 0).  A plane with amount == 0 is copied.
+// The launch covers the whole plane of the encoded frame: cw x ch, rows cw apart; under a pad that
+// is the canvas and the picture sits at (px, py) in it, else the picture is the plane.  Samples
+// outside the picture are copied (the border k_pad_plane wrote); samples inside clamp at the
+// picture's edges, so no border byte enters a sum.
+// One workgroup makes one kSharpTileW x kSharpTileH tile of the plane, four samples of a row (a
+// quad) per thread and step:
+//   1. the tile and its sx / sy apron, (64 + 2sx) x (32 + 2sy) bytes, go into LDS rows of a
+//      multiple of four bytes, a quad at a time; the coordinates are clamped into the picture before
+//      an address is formed (sharp_fetch), and a quad that no clamp touches is one unaligned dword
+//      load, any other four byte loads;
+//   2. the horizontal pass: for each of the 32 + 2sy staged rows and each quad of the tile's 64
+//      columns the four sums over i of C(2sx, i) * byte, each a uint32 (<= 255 * 2^22), from the
+//      row's aligned dwords into LDS rows of 64 dwords as one 16-byte write;
+//   3. the vertical pass: per quad the four sums over j of C(2sy, j) * row sum (<= 255 * 2^24 <
+//      2^32) from 16-byte reads, the rounding shift, the centre bytes from the staged tile, the
+//      sharpen and one unaligned dword store (sharp_store); a quad that leaves the plane or the
+//      picture goes byte by byte, its samples outside the picture loaded from their own place.
+// In 2 a wave reads 16 quads of each of four rows: rows a multiple of four bytes apart, eight-byte
+// reads at consecutive dwords of a row, no conflict beyond the row change; its writes and the reads
+// of 3 are consecutive 16-byte pieces of 256-byte rows.  A tile that misses the picture, and every
+// tile of a plane with amount 0, is a copy by quads and skips 1 and 2.  The binomials come with the
+// geometry (scalar loads at a uniform index; the horizontal products are 24-bit multiplies); <5, 5>,
+// the filter's default and the commonest size, has them as constants and its loops unrolled, <0, 0>
+// is every other size.  LDS: at most 3,672 bytes of samples and 54 x 64 dwords of row sums, 17.5 KB
+// (<5, 5>: 11.7 KB), so eight workgroups fit a CU.  U and V share a launch (blockIdx >= gxy * nf is
+// V).  The address arithmetic and the three steps are __host__ __device__ functions:
+// tools/unsharp_host.hip walks every (workgroup, thread, iteration) of a launch on the CPU.
+constexpr int kSharpTileW = 64;
+constexpr int kSharpTileH = 32;
+constexpr int kSharpThreads = 256;
+constexpr int kSharpMaxTaps = 23;     // sizes 3..23
+constexpr int kSharpMaxHalfSum = 12;  // sx + sy of a filtered plane: 8 + 2 (sx + sy) <= 32
+constexpr int kSharpQuads = kSharpTileW * kSharpTileH / 4;  // output quads per tile
+struct SharpGeom {
+  int cw, ch;              // the plane of the encoded frame (the canvas plane under a pad): rows cw apart
+  int px, py, w, h;        // the picture inside it (no pad: 0, 0, cw, ch)
+  long long off;           // the plane's offset inside a frame (source and destination alike)
+  long long fstride;       // frame stride (both sides)
+  long long poff;          // the next plane's offset from this one (V from U)
+  int nf;                  // frames per plane
+  int sx, sy;              // half sizes
+  int amount;              // (int)(amount * 65536.0); 0: the plane is copied
+  int tx;                  // tiles per tile row
+  uint32_t tx_magic;
+  int gxy;                 // workgroups (tiles) per (plane, frame)
+  uint32_t gxy_magic;
+  uint32_t nq_magic;       // ceil(2^32 / (sharp_pitch(sx) / 4)): staged quads per row
+  uint32_t bx[kSharpMaxTaps], by[kSharpMaxTaps];  // C(2sx, i), C(2sy, j)
+};
+
+__host__ __device__ constexpr int sharp_pitch(int sx) { return (kSharpTileW + 2 * sx + 3) & ~3; }
+__host__ __device__ constexpr int sharp_rows(int sy) { return kSharpTileH + 2 * sy; }
+// bytes of staged samples: the most over the sizes a filtered plane can have
+__host__ __device__ constexpr int sharp_lds_bytes(int mx, int my) {
+  if (mx) return sharp_pitch(mx / 2) * sharp_rows(my / 2);
+  int m = 0;
+  for (int sx = 1; sx <= kSharpMaxTaps / 2; sx++)
+    for (int sy = 1; sy <= kSharpMaxTaps / 2 && sx + sy <= kSharpMaxHalfSum; sy++)
+      m = sharp_pitch(sx) * sharp_rows(sy) > m ? sharp_pitch(sx) * sharp_rows(sy) : m;
+  return m;
+}
+__host__ __device__ constexpr int sharp_lds_sums(int my) {
+  return sharp_rows(my ? my / 2 : kSharpMaxTaps / 2) * kSharpTileW;
+}
+
+// The geometry of one plane's launch (host; submit adds nf and the U + V pairing)
+inline SharpGeom sharp_geom(int cw, int ch, int px, int py, int w, int h, long long off, long long fstride, int mx,
+                            int my, int amount) {
+  auto magic = [](uint32_t d) { return d > 1 ? (uint32_t)((((uint64_t)1 << 32) + d - 1) / d) : 0u; };
+  SharpGeom g{};
+  g.cw = cw, g.ch = ch, g.px = px, g.py = py, g.w = w, g.h = h;
+  g.off = off, g.fstride = fstride;
+  g.sx = mx / 2, g.sy = my / 2, g.amount = amount;
+  g.tx = (cw + kSharpTileW - 1) / kSharpTileW;
+  g.gxy = g.tx * ((ch + kSharpTileH - 1) / kSharpTileH);
+  g.tx_magic = magic((uint32_t)g.tx);
+  g.gxy_magic = magic((uint32_t)g.gxy);
+  g.nq_magic = magic((uint32_t)(sharp_pitch(g.sx) / 4));
+  for (int d = 0; d < 2; d++) {  // a row of Pascal's triangle by pair sums, as the filter's own cascade
+    uint32_t *b = d ? g.by : g.bx;
+    const int n = 2 * (d ? g.sy : g.sx);
+    b[0] = 1;
+    for (int k = 1; k <= n; k++) {
+      b[k] = 1;
+      for (int i = k - 1; i > 0; i--) b[i] += b[i - 1];
+    }
+  }
+  return g;
+}
+
+struct SharpTile {
+  int x0, y0;  // the tile's first column and row in the plane
+  bool filt;   // it holds picture samples of a plane with a non-zero amount
+};
+
+__host__ __device__ __forceinline__ SharpTile sharp_tile(const SharpGeom &g, int blk) {
+  const int ty = deint_div(blk, g.tx_magic, g.tx);
+  SharpTile T;
+  T.x0 = (blk - ty * g.tx) * kSharpTileW;
+  T.y0 = ty * kSharpTileH;
+  T.filt = g.amount != 0 && T.x0 < g.px + g.w && T.x0 + kSharpTileW > g.px && T.y0 < g.py + g.h &&
+           T.y0 + kSharpTileH > g.py;
+  return T;
+}
+
+// Staged quad `it * kSharpThreads + tid` of a tile: false past the window; else its index in the
+// LDS byte tile and the offsets of its four samples in the plane, each clamped into the picture.
+// whole: no clamp moved a column, the four are consecutive bytes
+__host__ __device__ __forceinline__ bool sharp_fetch(const SharpGeom &g, const SharpTile &T, int sx, int sy, int tid,
+                                                     int it, int *lds_at, long long at[4], bool *whole) {
+  const int nq = sharp_pitch(sx) / 4, idx = it * kSharpThreads + tid;
+  if (idx >= nq * sharp_rows(sy)) return false;
+  const int r = deint_div(idx, g.nq_magic, nq), q = idx - r * nq;
+  const int y = imin(imax(T.y0 - sy + r, g.py), g.py + g.h - 1);
+  const int x = T.x0 - sx + 4 * q;
+  *lds_at = r * sharp_pitch(sx) + 4 * q;
+#pragma unroll
+  for (int k = 0; k < 4; k++) at[k] = (long long)y * g.cw + imin(imax(x + k, g.px), g.px + g.w - 1);
+  *whole = x >= g.px && x + 3 < g.px + g.w;
+  return true;
+}
+
+// Output quad `it * kSharpThreads + tid` of a tile (it < kSharpQuads / kSharpThreads): false outside
+// the plane; else its first column and its row in the tile, its first sample's offset in the plane,
+// how many of its samples lie inside the plane (n, 1..4) and which of those inside the picture (bit
+// k of pic: sample k)
+__host__ __device__ __forceinline__ bool sharp_store(const SharpGeom &g, const SharpTile &T, int tid, int it, int *col,
+                                                     int *row, long long *at, int *n, int *pic) {
+  const int idx = it * kSharpThreads + tid;
+  *col = 4 * (idx & (kSharpTileW / 4 - 1));
+  *row = idx / (kSharpTileW / 4);
+  const int x = T.x0 + *col, y = T.y0 + *row;
+  if (x >= g.cw || y >= g.ch) return false;
+  *at = (long long)y * g.cw + x;
+  *n = imin(4, g.cw - x);
+  const bool yin = y >= g.py && y < g.py + g.h;
+  int m = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++)
+    if (k < *n && yin && x + k >= g.px && x + k < g.px + g.w) m |= 1 << k;
+  *pic = m;
+  return true;
+}
+
+template <int M>
+__host__ __device__ __forceinline__ uint32_t sharp_coef(const uint32_t *b, int i) {
+  if (M == 5) return i == 2 ? 6u : (i == 1 || i == 3) ? 4u : 1u;
+  return b[i];
+}
+
+// bytes s..s + 3 (s in 0..3) of the eight bytes hi:lo
+__host__ __device__ __forceinline__ uint32_t sharp_win(uint32_t lo, uint32_t hi, int s) {
+  return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * s));
+}
+
+// step 1 for one thread: the window into the LDS byte tile
+template <int MX, int MY>
+__host__ __device__ __forceinline__ void sharp_stage(const uint8_t *s, const SharpGeom &g, const SharpTile &T, int tid,
+                                                     uint8_t *lb) {
+  const int sx = MX ? MX / 2 : g.sx, sy = MY ? MY / 2 : g.sy;
+  const int n = sharp_pitch(sx) / 4 * sharp_rows(sy);
+  for (int it = 0; it * kSharpThreads < n; it++) {
+    int lat;
+    long long at[4];
+    bool whole;
+    if (!sharp_fetch(g, T, sx, sy, tid, it, &lat, at, &whole)) continue;
+    uint32_t v;
+    if (whole) v = *(const u32_unaligned *)(s + at[0]);
+    else v = (uint32_t)s[at[0]] | ((uint32_t)s[at[1]] << 8) | ((uint32_t)s[at[2]] << 16) | ((uint32_t)s[at[3]] << 24);
+    *(uint32_t *)(lb + lat) = v;
+  }
+}
+
+// step 2 for one thread: the row sums, a quad at a time
+template <int MX, int MY>
+__host__ __device__ __forceinline__ void sharp_hpass(const SharpGeom &g, int tid, const uint8_t *lb, uint32_t *ls) {
+  const int sx = MX ? MX / 2 : g.sx, sy = MY ? MY / 2 : g.sy;
+  const int pitch = sharp_pitch(sx), n = sharp_rows(sy) * (kSharpTileW / 4);
+  for (int idx = tid; idx < n; idx += kSharpThreads) {
+    const int r = idx / (kSharpTileW / 4), col = 4 * (idx & (kSharpTileW / 4 - 1));
+    const uint32_t *p = (const uint32_t *)(lb + r * pitch + col);  // the quad's window: bytes [0, 4 + 2sx)
+    uint32_t a[4] = {0, 0, 0, 0};
+    uint32_t lo = p[0], hi = 0;
+    if (MX) {
+#pragma unroll
+      for (int t = 0; t < (MX ? MX : 1); t++) {
+        if ((t & 3) == 0 && t) lo = hi;
+        if ((t & 3) == 0 && t + 1 < MX) hi = p[t / 4 + 1];
+        if ((t & 3) == 0 && t + 1 >= MX) hi = 0;
+        const uint32_t wd = sharp_win(lo, hi, t & 3), c = sharp_coef<MX>(g.bx, t);
+#pragma unroll
+        for (int o = 0; o < 4; o++) a[o] += c * ((wd >> (8 * o)) & 255u);
+      }
+    } else {
+      for (int t = 0; t <= 2 * sx; t++) {
+        if ((t & 3) == 0) {  // the next aligned dword, while a later tap needs it (it lies inside the row)
+          if (t) lo = hi;
+          hi = t < 2 * sx ? p[t / 4 + 1] : 0u;
+        }
+        const uint32_t wd = sharp_win(lo, hi, t & 3), c = g.bx[t] & 0xffffffu;  // (24-bit factors: one multiply-add)
+#pragma unroll
+        for (int o = 0; o < 4; o++) a[o] += c * ((wd >> (8 * o)) & 255u);
+      }
+    }
+    *(u32x4 *)(ls + r * kSharpTileW + col) = u32x4{a[0], a[1], a[2], a[3]};
+  }
+}
+
+// step 3 for one thread: the column sums, the sharpen and the stores; without a filter the copy
+template <int MX, int MY>
+__host__ __device__ __forceinline__ void sharp_vpass(const uint8_t *s, uint8_t *d, const SharpGeom &g, const SharpTile &T,
+                                                     int tid, const uint8_t *lb, const uint32_t *ls) {
+  const int sx = MX ? MX / 2 : g.sx, sy = MY ? MY / 2 : g.sy;
+  const int pitch = sharp_pitch(sx), scalebits = 2 * (sx + sy);
+#pragma unroll
+  for (int it = 0; it < kSharpQuads / kSharpThreads; it++) {
+    int col, row, n, pic;
+    long long at;
+    if (!sharp_store(g, T, tid, it, &col, &row, &at, &n, &pic)) continue;
+    if (!T.filt || !pic) {  // a copy
+      if (n == 4) {
+        *(u32_unaligned *)(d + at) = *(const u32_unaligned *)(s + at);
+      } else {
+        for (int k = 0; k < n; k++) d[at + k] = s[at + k];
+      }
+      continue;
+    }
+    const uint32_t *q = ls + row * kSharpTileW + col;
+    uint32_t a[4] = {0, 0, 0, 0};
+    if (MY) {
+#pragma unroll
+      for (int j = 0; j < (MY ? MY : 1); j++) {
+        const u32x4 v = *(const u32x4 *)(q + j * kSharpTileW);
+        const uint32_t c = sharp_coef<MY>(g.by, j);
+#pragma unroll
+        for (int o = 0; o < 4; o++) a[o] += c * v[o];
+      }
+    } else {
+      for (int j = 0; j <= 2 * sy; j++) {
+        const u32x4 v = *(const u32x4 *)(q + j * kSharpTileW);
+        const uint32_t c = g.by[j];
+#pragma unroll
+        for (int o = 0; o < 4; o++) a[o] += c * v[o];
+      }
+    }
+    const uint8_t *ctr = lb + (row + sy) * pitch + col + sx;
+    uint32_t out = 0;
+#pragma unroll
+    for (int o = 0; o < 4; o++) {
+      const int blur = (int)((a[o] + (1u << (scalebits - 1))) >> scalebits);
+      const int p = ctr[o];
+      const int r = p + (((p - blur) * g.amount) >> 16);
+      out |= (uint32_t)imin(imax(r, 0), 255) << (8 * o);
+    }
+    if (n == 4 && pic == 15) {
+      *(u32_unaligned *)(d + at) = out;
+    } else {
+      for (int k = 0; k < n; k++) d[at + k] = (pic >> k) & 1 ? (uint8_t)(out >> (8 * k)) : s[at + k];
+    }
+  }
+}
+
+// workgroup t of a launch: its tile, and the plane of its (plane, frame) in the source and the destination
+__host__ __device__ __forceinline__ SharpTile sharp_block(const SharpGeom &g, int t, long long *plane_at) {
+  const int z = deint_div(t, g.gxy_magic, g.gxy), blk = t - z * g.gxy;
+  const int pl = z >= g.nf, f = z - (pl ? g.nf : 0);
+  *plane_at = (long long)f * g.fstride + g.off + (pl ? g.poff : 0);
+  return sharp_tile(g, blk);
+}
+
+template <int MX, int MY>  // 0, 0: the sizes at run time
+__global__ __launch_bounds__(kSharpThreads) void k_unsharp_plane(const uint8_t *__restrict__ src,
+                                                                 uint8_t *__restrict__ dst, SharpGeom g) {
+  __shared__ __attribute__((aligned(16))) uint8_t lb[sharp_lds_bytes(MX, MY)];
+  __shared__ __attribute__((aligned(16))) uint32_t ls[sharp_lds_sums(MY)];
+  const int tid = threadIdx.x;
+  long long pa;
+  const SharpTile T = sharp_block(g, (int)blockIdx.x, &pa);
+  if (T.filt) {  // (uniform over the workgroup)
+    sharp_stage<MX, MY>(src + pa, g, T, tid, lb);
+    __syncthreads();
+    sharp_hpass<MX, MY>(g, tid, lb, ls);
+    __syncthreads();
+  }
+  sharp_vpass<MX, MY>(src + pa, dst + pa, g, T, tid, lb, ls);
+}
+
 }  // namespace mjg

@@ -1,7 +1,7 @@
 """GPU MJPEG encoder: the per-segment encode that the reference's worker runs
 (`ffmpeg -f matroska -i pipe: <remote_args> -f matroska pipe:`,
 ffmpeg_distributed.py:131-141), restricted to the profile
-`[-vf [yadif,][vflip|transpose=N,...][crop=w:h:x:y,][scale=W:H:flags=bicubic][,pad=W:H:x:y]] -c:v mjpeg -q:v N -dct int [-huffman default|optimal] -bitexact`
+`[-vf [yadif,][vflip|transpose=N,...][crop=w:h:x:y,][scale=W:H:flags=bicubic][,unsharp[=lx:ly:la:cx:cy:ca]][,pad=W:H:x:y]] -c:v mjpeg -q:v N -dct int [-huffman default|optimal] -bitexact`
 (+ `-slices N` / `-thread_type slice` for the RST layout).
 
 Host-side wrapper over libmjgpu.so; frames are packed planar YUV (yuv420p / yuvj420p by
@@ -19,7 +19,10 @@ src_w under a transpose).  `deint=` (MJG_DEINT_YADIF | MJG_DEINT_NOSPATIAL | MJG
 _lib: `-vf yadif` modes 0 / 2, tff / bff) deinterlaces the decoded frames on the GPU in front of
 the orientation: every output frame is made from the frames before and after it, a submit (and
 each segment of a submit_segments) is a whole sequence, and `submit(..., halo=)` hands over a
-piece of a longer one with its neighbour frames.  No CPU fallback.
+piece of a longer one with its neighbour frames.  `unsharp=` (lx, ly, la, cx, cy, ca: `-vf unsharp`
+behind the scale and in front of the pad, the amounts as floats) sharpens or blurs the sws stage's
+output planes on the GPU (mjg_open_sharp); the encoder then reads the sharpened planes.  No CPU
+fallback.
 """
 from __future__ import annotations
 
@@ -70,7 +73,7 @@ class MjpegEncoder:
                  debug_coefs: bool = False, sws_bitexact: bool = True, com_itu601: bool = False,
                  huffman: str = "default", chroma: str = "420", rst: bool = False,
                  merge: bool = False, src_chroma: Optional[str] = None, crop=None, pad=None, orient: int = 0,
-                 deint: Optional[int] = None):
+                 deint: Optional[int] = None, unsharp=None):
         self._L = _lib.load()
         self.device = int(device)
         self.src_w, self.src_h = int(src_w), int(src_h)
@@ -136,7 +139,23 @@ class MjpegEncoder:
         # (or a piece of one: submit(..., halo=)).  deint=0 opens through mjg_open_deint all the same
         # (exactly mjg_open_orient); None, the default, through the entry points below
         self.deint = int(deint or 0)
-        if deint is not None:
+        # unsharp: (lx, ly, la, cx, cy, ca), `-vf unsharp` between the sws stage and the pad
+        # (mjg_open_sharp); the amounts are floats and become the filter's integers here, (int)(amount
+        # * 65536.0).  None, the default, opens as without it
+        self.unsharp = None
+        if unsharp is not None:
+            if len(unsharp) != 6:
+                raise ValueError(f"unsharp {unsharp!r}: (lx, ly, la, cx, cy, ca)")
+            lx, ly, la, cx, cy, ca = unsharp
+            self.unsharp = (int(lx), int(ly), int(float(la) * 65536.0), int(cx), int(cy), int(float(ca) * 65536.0))
+            if not hasattr(self._L, "mjg_open_sharp"):
+                raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_sharp")
+            rect = self.crop if self.crop is not None else (0, 0, self.or_w, self.or_h)
+            canvas = self.pad if self.pad is not None else (0, 0, self.dst_w, self.dst_h)
+            us = _lib.MjgUnsharp(*self.unsharp)
+            check(self._L.mjg_open_sharp(self.device, C.byref(cfg), _lib.CHROMA_FORMATS[self.src_chroma],
+                                         self.deint, self.orient, *rect, C.byref(us), *canvas, C.byref(h)))
+        elif deint is not None:
             if not hasattr(self._L, "mjg_open_deint"):
                 raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_deint")
             rect = self.crop if self.crop is not None else (0, 0, self.or_w, self.or_h)
@@ -411,6 +430,27 @@ class MjpegEncoder:
         check(self._L.mjg_debug_oriented(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)),
                                          out.size))
         return out
+
+    def debug_presharp(self, frame: int = 0) -> np.ndarray:
+        """The sws stage's output (k_unsharp_plane's input) of a frame of the last synced submit, laid
+        out as debug_planes(), which under a sharpen returns the sharpened planes.  Only for an
+        encoder opened with an `unsharp` whose amounts are not both 0."""
+        if not hasattr(self._L, "mjg_debug_presharp"):
+            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_debug_presharp")
+        out = np.zeros(i420_frame_bytes(self.enc_w, self.enc_h, self.chroma), np.uint8)
+        check(self._L.mjg_debug_presharp(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size))
+        return out
+
+    def debug_unsharp(self):
+        """(lx, ly, la, cx, cy, ca) as the context holds them (la, ca the filter's integers), or None
+        for a context without a sharpen.  Host state only."""
+        if not hasattr(self._L, "mjg_debug_unsharp"):
+            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_debug_unsharp")
+        us = _lib.MjgUnsharp()
+        rc = self._L.mjg_debug_unsharp(self._h, C.byref(us))
+        if rc < 0:
+            check(rc)
+        return (us.lx, us.ly, us.la, us.cx, us.cy, us.ca) if rc else None
 
     def debug_deint(self, frame: int = 0) -> np.ndarray:
         """The deinterlaced frame (k_yadif_plane's output) of a frame of the last synced submit:

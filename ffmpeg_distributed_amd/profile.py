@@ -9,6 +9,9 @@ with FILTERS one of
     crop=w:h[:x:y]                          (also w= / out_w=, h= / out_h=, x=, y=; keep_aspect=0, exact=0)
     crop=...,scale=W:H[:flags=bicubic...]   (in this order)
     any of these, or nothing, followed by
+    unsharp[=lx:ly:la:cx:cy:ca]             (also luma_msize_x= / lx=, luma_msize_y= / ly=, luma_amount= / la=,
+                                            chroma_msize_x= / cx=, chroma_msize_y= / cy=, chroma_amount= / ca=)
+    any of these, or nothing, followed by
     pad=W:H[:x:y[:black]]                   (also width= / w=, height= / h=, x=, y=, color= / c=; last)
     and in front of any of these, or alone, a run of any length and order of
     vflip | transpose=N | transpose=dir=N | transpose=<name>   (N 0..3; cclock_flip, clock, cclock,
@@ -23,7 +26,11 @@ first filter of the graph or alone,
 is `Profile.deint` = {"mode": 0 | 2, "parity": -1 | 0 | 1} (parity auto is resolved by
 the worker from the container's field order).  The field-rate modes 1 and 3, deint=interlaced, a
 yadif anywhere else in the graph, and bwdif, w3fdif, estdif and the other deinterlacers are outside
-the profile, each with a reason that names it.  An orientation filter after a crop, scale
+the profile, each with a reason that names it.  `unsharp` is `Profile.unsharp` = (lx, ly, la, cx, cy,
+ca), the filter's defaults 5:5:1.0:5:5:0.0 filled in: plain numbers only, odd sizes
+3..23, amounts -2..5, and lx // 2 + ly // 2 <= 12 for a plane whose amount is not 0 (past that the
+filter's 32-bit sum wraps).  Its alpha and opencl options, an expression, a second unsharp and an
+unsharp anywhere but directly in front of the pad or the end are outside the profile.  An orientation filter after a crop, scale
 or pad, transpose values 4..7, a passthrough other than none and any other option are outside the
 profile.  The crop values are decimal integers (no expressions); `Profile.crop` is the request as
 given and `resolve_crop` turns it into a rectangle of a given input (vf_crop.c's rounding,
@@ -47,6 +54,7 @@ which the GPU path does not: the worker finds that out before it touches the GPU
 """
 from __future__ import annotations
 
+import re
 import shlex
 from math import gcd
 from dataclasses import dataclass
@@ -74,6 +82,9 @@ class Profile:
     # -vf yadif as the very first filter: {"mode": 0 | 2, "parity": -1 (auto: the container's field
     # order, worker.resolve_parity) | 0 (tff) | 1 (bff)}; None: no deinterlacer
     deint: Optional[dict] = None
+    # -vf ...,unsharp[,pad]: (lx, ly, la, cx, cy, ca), sizes as ints and amounts as floats, the
+    # filter's defaults filled in; None: no unsharp
+    unsharp: Optional[tuple] = None
 
 
 class Unsupported(ValueError):
@@ -291,9 +302,62 @@ def _parse_yadif(f: str) -> dict:
     return {"mode": vals["mode"], "parity": vals["parity"]}
 
 
+UNSHARP_KEYS = {"luma_msize_x": 0, "lx": 0, "luma_msize_y": 1, "ly": 1, "luma_amount": 2, "la": 2,
+                "chroma_msize_x": 3, "cx": 3, "chroma_msize_y": 4, "cy": 4, "chroma_amount": 5, "ca": 5}
+UNSHARP_NAMES = ("lx", "ly", "la", "cx", "cy", "ca")
+UNSHARP_DEFAULT = (5, 5, 1.0, 5, 5, 0.0)
+UNSHARP_MAX_HALF_SUM = 12   # 8 + 2 (sx + sy) <= 32: the filter's uint32_t sum
+_INT_RE = re.compile(r"[+-]?\d+\Z")
+_NUM_RE = re.compile(r"[+-]?(\d+\.?\d*|\.\d+)([eE][+-]?\d+)?\Z")
+
+
+def unsharp_amount_i(amount: float) -> int:
+    """The filter's integer amount: (int)(amount * 65536.0), C truncation."""
+    return int(float(amount) * 65536.0)
+
+
+def _parse_unsharp(f: str) -> tuple:
+    """`unsharp[=lx:ly:la:cx:cy:ca]` -> (lx, ly, la, cx, cy, ca) with the defaults filled in."""
+    name, _, opts = f.partition("=")
+    vals = list(UNSHARP_DEFAULT)
+    pos = 0
+    if "=" in f and not opts:
+        raise Unsupported("unsharp= without options")
+    for p in opts.split(":") if opts else []:
+        if "=" in p:
+            k, v = p.split("=", 1)
+            if k not in UNSHARP_KEYS:
+                raise Unsupported(f"unsharp option {k!r} (only the luma and chroma sizes and amounts are "
+                                  f"GPU-accelerated)")
+            at = UNSHARP_KEYS[k]
+        else:
+            if pos >= len(UNSHARP_NAMES):
+                raise Unsupported(f"unsharp option {p!r} (positional options are lx:ly:la:cx:cy:ca; the alpha "
+                                  f"plane's are not GPU-accelerated)")
+            at, v = pos, p
+            pos += 1
+        nm = UNSHARP_NAMES[at]
+        if not (_NUM_RE if at in (2, 5) else _INT_RE).match(v):
+            raise Unsupported(f"unsharp {nm}={v}: an expression or not a plain number (plain numbers only)")
+        vals[at] = float(v) if at in (2, 5) else int(v)
+    for at in (0, 1, 3, 4):
+        if not 3 <= vals[at] <= 23:
+            raise Unsupported(f"unsharp {UNSHARP_NAMES[at]}={vals[at]}: size outside 3..23")
+        if not vals[at] & 1:
+            raise Unsupported(f"unsharp {UNSHARP_NAMES[at]}={vals[at]}: even size (the filter takes odd sizes)")
+    for at in (2, 5):
+        if not -2.0 <= vals[at] <= 5.0:
+            raise Unsupported(f"unsharp {UNSHARP_NAMES[at]}={vals[at]}: amount outside -2..5")
+        hs = vals[at - 2] // 2 + vals[at - 1] // 2
+        if unsharp_amount_i(vals[at]) and hs > UNSHARP_MAX_HALF_SUM:
+            raise Unsupported(f"unsharp {'luma' if at == 2 else 'chroma'} {vals[at - 2]}x{vals[at - 1]}: sx + sy = {hs} > "
+                              f"{UNSHARP_MAX_HALF_SUM}, the filter's 32-bit sum wraps (not GPU-accelerated)")
+    return tuple(vals)
+
+
 def _parse_vf(vf: str):
     """-vf value -> (crop request or None, scale size or None, sws flags, pad request or None,
-    orientation, yadif request or None).  A `yadif` at the very front is taken off first; then a
+    unsharp request or None, orientation, yadif request or None).  A `yadif` at the very front is taken off first; then a
     leading run of orientation filters is composed and taken off; the limits on the number and
     order of filters apply to what follows."""
     deint = None
@@ -311,14 +375,14 @@ def _parse_vf(vf: str):
         if names[0] == "yadif":
             deint = _parse_yadif(fs[0])
             if len(fs) == 1:
-                return None, None, ("bicubic",), None, 0, deint
+                return None, None, ("bicubic",), None, None, 0, deint
             vf = ",".join(fs[1:])
     return _parse_vf_rest(vf) + (deint,)
 
 
 def _parse_vf_rest(vf: str):
     """What follows a yadif: (crop request or None, scale size or None, sws flags, pad request or
-    None, orientation)."""
+    None, unsharp request or None, orientation)."""
     if ";" not in vf:
         fs = vf.split(",")
         names = [f.split("=", 1)[0] for f in fs]
@@ -335,15 +399,48 @@ def _parse_vf_rest(vf: str):
         if n:
             orient = compose_orient(fs[:n])
             if n == len(fs):
-                return None, None, ("bicubic",), None, orient
+                return None, None, ("bicubic",), None, None, orient
             return _parse_chain(",".join(fs[n:])) + (orient,)
     return _parse_chain(vf) + (0,)
 
 
 def _parse_chain(vf: str):
-    """[crop][,scale][,pad] -> (crop request or None, scale size or None, sws flags, pad request or None)."""
+    """[crop][,scale][,unsharp][,pad] -> (crop request or None, scale size or None, sws flags, pad
+    request or None, unsharp request or None)."""
     fs = vf.split(",")
     names = [f.split("=", 1)[0] for f in fs]
+    if ";" not in vf and "unsharp" in names:
+        return _parse_chain_unsharp(vf, fs, names)
+    return _parse_chain_plain(vf, fs, names) + (None,)
+
+
+def _parse_chain_unsharp(vf: str, fs, names):
+    """A chain that names unsharp: the pad is taken off, then the unsharp, which must be the last
+    of what is left; the rest is [crop][,scale] as without it."""
+    if names.count("unsharp") > 1:
+        raise Unsupported(f"filter graph {vf!r}: a second unsharp (one unsharp, directly in front of the pad or the "
+                          f"end, is GPU-accelerated)")
+    if "pad" in names[:-1]:
+        raise Unsupported(f"filter graph {vf!r}: pad is not the last filter (only [crop,][scale,][unsharp,]pad in "
+                          f"this order is GPU-accelerated)")
+    pad = None
+    if names[-1] == "pad":
+        if "=" not in fs[-1]:
+            raise Unsupported(f"filter graph {vf!r}: pad without options")
+        pad = _parse_pad(fs[-1])
+        fs, names = fs[:-1], names[:-1]
+    if names[-1] != "unsharp":
+        at = names.index("unsharp")
+        raise Unsupported(f"filter graph {vf!r}: unsharp before {names[at + 1]} (unsharp is GPU-accelerated only "
+                          f"behind [crop,][scale] and directly in front of the pad or the end)")
+    us = _parse_unsharp(fs[-1])
+    if len(fs) == 1:
+        return None, None, ("bicubic",), pad, us
+    return _parse_crop_scale(",".join(fs[:-1])) + (pad, us)
+
+
+def _parse_chain_plain(vf: str, fs, names):
+    """[crop][,scale][,pad] -> (crop request or None, scale size or None, sws flags, pad request or None)."""
     if ";" not in vf and "pad" in names[:-1]:
         raise Unsupported(f"filter graph {vf!r}: pad is not the last filter (only [crop,][scale,]pad in this "
                           f"order is GPU-accelerated)")
@@ -465,6 +562,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
     pad = None
     orient = 0
     deint = None
+    unsharp = None
     flags: Tuple[str, ...] = ("bicubic",)
     i = 0
 
@@ -505,7 +603,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
             if any(name != "bitexact" for _, name in _flag_ops(v)):
                 raise Unsupported(f"-fflags {v}")
         elif o in ("-vf", "-filter:v"):
-            crop, scale, flags, pad, orient, deint = _parse_vf(val())
+            crop, scale, flags, pad, unsharp, orient, deint = _parse_vf(val())
         elif o in ("-an", "-sn", "-dn", "-y"):
             pass
         elif o in ("-threads", "-threads:v"):
@@ -555,7 +653,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
     if rst:
         huff = "default"  # mjpegenc.c: slice_context_count > 1 forces HUFFMAN_TABLE_DEFAULT
     return Profile(qscale=effective_qscale(q), q_arg=q, scale=scale, sws_flags=flags, huffman=huff,
-                   rst=rst, chroma=chroma, crop=crop, pad=pad, orient=orient, deint=deint)
+                   rst=rst, chroma=chroma, crop=crop, pad=pad, orient=orient, deint=deint, unsharp=unsharp)
 
 
 PIX_FMT_CHROMA = {"yuvj420p": "420", "yuvj422p": "422", "yuvj444p": "444"}

@@ -35,6 +35,10 @@ Every output frame reads the frame before and the frame after it, so with a dein
 page-locked batches hold two more frames, the reader keeps one frame of look-ahead and copies the
 previous batch's last frame and its look-ahead frame to the head of the next (deint_step is the
 schedule; run()'s deint_reader follows it), and each batch is a halo submit (encoder.submit(halo=)).
+An `unsharp` behind the crop and the scale (profile.Profile.unsharp) is run by the GPU on the sws
+stage's output.  Without a scale in the graph FFmpeg sharpens the decoded frames and converts them
+afterwards, so a tv-range or to-be-converted input then goes to the real ffmpeg
+(unsharp_fallthrough_reason).
 """
 from __future__ import annotations
 
@@ -470,16 +474,19 @@ def resample_plan(prof, info):
     return f"-pix_fmt needs {src} -> {dst} chroma resampling"
 
 
-def encoder_key(prof, info, dst_w, dst_h, sar, com_itu601, batch, rect=None, pad=None, orient=0, deint=0):
+def encoder_key(prof, info, dst_w, dst_h, sar, com_itu601, batch, rect=None, pad=None, orient=0, deint=0,
+                unsharp=None):
     """What an encoder context kept between segments (serve / resident mode) depends on: the
     input's shape and format and everything of the profile the context is opened with, the
     encoded chroma format (-pix_fmt), the resolved crop rectangle (x, y, w, h), the resolved
     pad (x, y, W, H), the orientation (0..7) and the deinterlacer (the resolved MJG_DEINT_* bits,
-    resolve_deint: the batch buffers of such a context hold two more frames) included."""
+    resolve_deint: the batch buffers of such a context hold two more frames) included, and the
+    six values of an unsharp (profile.Profile.unsharp; None without one)."""
     src_chroma, dst_chroma = resample_plan(prof, info)
     return (info.width, info.height, dst_w, dst_h, info.full_range, prof.qscale, sar,
             com_itu601, prof.huffman, src_chroma, dst_chroma, prof.rst, batch,
-            None if rect is None else tuple(rect), None if pad is None else tuple(pad), int(orient), int(deint))
+            None if rect is None else tuple(rect), None if pad is None else tuple(pad), int(orient), int(deint),
+            None if unsharp is None else tuple(unsharp))
 
 
 def resolve_deint(spec, info):
@@ -556,6 +563,19 @@ def pad_fallthrough_reason(prof, in_size, src_chroma, dst_chroma) -> Optional[st
     if w & ((1 << hs) - 1) or h & ((1 << vs) - 1):
         return (f"pad of a {w}x{h} picture in {dst_chroma}: the size is no multiple of the chroma "
                 f"sub-sampling ({1 << hs}x{1 << vs})")
+    return None
+
+
+def unsharp_fallthrough_reason(prof, full_range, src_chroma, dst_chroma) -> Optional[str]:
+    """Why a graph with an `unsharp` runs on the CPU for this input, or None.  With a scale directly
+    in front of it, format negotiation lets that scaler deliver the encoder's full-range format (as
+    the pad assumes), so the filter sees what the sws stage produces.  Without a scale
+    FFmpeg sharpens the decoded frames and converts afterwards, which equals the GPU path (sharpen
+    behind the sws stage) only when nothing is converted: a full-range source in the encoded format."""
+    if prof.unsharp is None or prof.scale is not None:
+        return None
+    if not full_range or src_chroma != dst_chroma:
+        return "unsharp without a scale on a tv-range / converted input: FFmpeg sharpens before its converter"
     return None
 
 
@@ -648,6 +668,12 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
             src.close(kill=True)
             return 1
     enc_w, enc_h = (dst_w, dst_h) if pad is None else pad[2:]
+    # -vf ...,unsharp: behind the sws stage; without a scale only when nothing is converted
+    why = unsharp_fallthrough_reason(prof, info.full_range, src_chroma, dst_chroma)
+    if why is not None:
+        stderr.write(f"gpu:{device}: {why}; running ffmpeg on the CPU\n")
+        stderr.flush()
+        return ffmpeg_fallthrough(src, args, stdout, stderr)
     # the one scale the library refuses (a filter of 256 taps or more, about 64:1), decided here
     # without a device: as the up-sampling -pix_fmt pairs, the segment goes to ffmpeg
     why = scale_cascade_reason(in_size, (dst_w, dst_h), src_chroma, dst_chroma)
@@ -665,7 +691,7 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
     # (a transpose hands on 1 / SAR when the SAR is known: vf_transpose config_props_output)
     sar = profile.scaled_sar(oriented_sar(info.sar, orient), in_size, (dst_w, dst_h))
     key = encoder_key(prof, info, dst_w, dst_h, sar, opts.com_itu601 and not info.full_range, batch, rect, pad,
-                      orient, deint)
+                      orient, deint, prof.unsharp)
     nbuf = NBUF
     if cache is not None and cache.get("key") == key:
         enc, bufs, obufs = cache["enc"], cache["bufs"], cache["obufs"]
@@ -676,7 +702,7 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
                            qscale=prof.qscale, sar=sar, max_batch=batch,
                            com_itu601=opts.com_itu601 and not info.full_range, huffman=prof.huffman,
                            chroma=dst_chroma, src_chroma=src_chroma, rst=prof.rst, crop=rect, pad=pad,
-                           orient=orient, deint=deint or None)
+                           orient=orient, deint=deint or None, unsharp=prof.unsharp)
         # (a deinterlacer: room for the frame in front of a batch and the one behind it)
         bufs = [PinnedBuffer((batch + (2 if deint else 0)) * enc.frame_bytes) for _ in range(nbuf)]
         # page-locked output buffers: the packets are DMA'd into one (enc.fetch_into) and the

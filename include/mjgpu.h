@@ -6,8 +6,9 @@
  *     nice -n10 ionice -c3 ffmpeg -f matroska -i pipe: <remote_args> -f matroska pipe:
  * and launched/supervised at ffmpeg_distributed.py:139-141 (FFMPEGProc.run,
  * ffmpeg_distributed.py:59-91).  For the north-star profile
- *     [-vf [yadif[=0|2],][vflip|transpose=N,...][crop=w:h:x:y,][scale=W:H:flags=bicubic][,pad=W:H:x:y]] -c:v mjpeg -q:v N -dct int -huffman default -bitexact
- * (`yadif` as the very first filter, frame-rate modes 0 and 2: the deinterlacer, mjg_open_deint,
+ *     [-vf [yadif[=0|2],][vflip|transpose=N,...][crop=w:h:x:y,][scale=W:H:flags=bicubic][,unsharp[=lx:ly:la:cx:cy:ca]][,pad=W:H:x:y]] -c:v mjpeg -q:v N -dct int -huffman default -bitexact
+ * (`unsharp` behind the scale and in front of the pad: the sharpen, mjg_open_sharp, a restatement of
+ * vf_unsharp.c's 8-bit path that no FFmpeg build has been compared with yet; `yadif` as the very first filter, frame-rate modes 0 and 2: the deinterlacer, mjg_open_deint,
  * a restatement of the filter's C path that no FFmpeg build has been compared with yet; a leading run of vflip / transpose: one of eight plane maps, mjg_open_orient; and `-pix_fmt yuvj420p|yuvj422p` from a 4:4:4 or 4:2:2 input: the chroma down-sampling
  * FFmpeg's auto-inserted scaler does, taken to be its default bicubic; `-vf crop=...` alone or
  * before the scale: a rectangle of the decoded frames, mjg_open_crop; `pad=...` as the last
@@ -208,6 +209,31 @@ int mjg_open_orient(int device, const mjg_config *cfg, int src_chroma_format, in
 int mjg_open_deint(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient,
                    int crop_x, int crop_y, int crop_w, int crop_h,
                    int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
+
+/* -vf unsharp: luma and chroma matrix sizes (odd, 3..23) and amounts as the filter holds them,
+ * (int)(amount * 65536.0) with C truncation; the filter's defaults are {5, 5, 65536, 5, 5, 0}. */
+typedef struct mjg_unsharp { int32_t lx, ly, la, cx, cy, ca; } mjg_unsharp;
+/* mjg_open_deint with a sharpen (`unsharp[=lx:ly:la:cx:cy:ca]` behind the scale, in front of the
+ * pad).  us == NULL, or la == 0 and ca == 0, is exactly mjg_open_deint: no buffer, the same
+ * launches (the sizes of a given us are checked all the same).  Otherwise the sws stage always runs, as it does with a pad (a plane that keeps its
+ * size goes through k_plane_copy / k_pad_plane with the tv->pc table), and k_unsharp_plane
+ * (scale.hip, which restates the filter: the 8-bit planar path of FFmpeg's vf_unsharp.c as this
+ * project's issue text gives it, not checked against an FFmpeg build) makes from every
+ * plane of its output the same plane of a second buffer of the launch slot, which k_encode reads:
+ *   blur = (sum_j sum_i C(2sy, j) C(2sx, i) P[clamp(y + j - sy)][clamp(x + i - sx)] + half) >> scalebits
+ *   out  = clip_uint8(P[y][x] + (((P[y][x] - blur) * amount) >> 16))
+ * with sx = size_x / 2, sy = size_y / 2, scalebits = 2 (sx + sy), half = 1 << (scalebits - 1), the
+ * indices clamped into the picture (dst_w x dst_h; its chroma planes at their own size with cx, cy,
+ * ca) and C int arithmetic.  A plane whose amount is 0 (the default chroma) is copied by the same
+ * launch.  Under a pad the launch covers the canvas: the border is copied and never enters a sum.
+ * Works per frame: MJG_F_MERGE, mjg_submit_segments and mjg_submit_halo are unchanged.  Its
+ * launches are part of the MJG_K_SCALE interval.  MJG_E_INVALID (before any HIP call, with a
+ * message that starts "unsharp") for an even size, a size outside 3..23, an amount outside
+ * [-2 * 65536, 5 * 65536], and size_x / 2 + size_y / 2 > 12 for a plane whose amount is not 0: the
+ * filter's 32-bit sum would wrap.  (Added without a version step, as mjg_open_orient.) */
+int mjg_open_sharp(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient,
+                   int crop_x, int crop_y, int crop_w, int crop_h, const mjg_unsharp *us,
+                   int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
 void mjg_close(mjg_ctx *ctx);
 
 /* Bytes of one packed planar input frame (src_w x src_h in the source chroma format). */
@@ -307,8 +333,16 @@ int mjg_sws_filter(int src_len, int dst_len, int one, int align, int bitexact, i
 int mjg_debug_coefs(mjg_ctx *ctx, int frame, int16_t *out, size_t nblocks);
 /* The full-range encoder-input planes (after scale/range stage) of frame `frame`,
  * packed planar at dst size (under a pad: the canvas size) in the encoded chroma format.  Only for a config whose sws stage
- * runs (src size != dst size, or source chroma format != encoded one). */
+ * runs (src size != dst size, or source chroma format != encoded one).  Under a sharpen
+ * (mjg_open_sharp) these are the sharpened planes, k_unsharp_plane's output. */
 int mjg_debug_planes(mjg_ctx *ctx, int frame, uint8_t *out, size_t cap);
+/* The sws stage's output under a sharpen (k_unsharp_plane's input; layout as mjg_debug_planes).
+ * MJG_E_STATE for a context without a sharpen.  (With mjg_open_sharp.) */
+int mjg_debug_presharp(mjg_ctx *ctx, int frame, uint8_t *out, size_t cap);
+/* 1 and the context's sizes and amounts in *out (which may be NULL) when it has a sharpen, 0
+ * without one, or a negative MJG_E_* code for a null context.  Host state only.  (With
+ * mjg_open_sharp.) */
+int mjg_debug_unsharp(mjg_ctx *ctx, mjg_unsharp *out);
 /* Which kernel the sws stage runs for a plane (0 = luma, 1 = chroma): 0 no sws stage for it (the
  * context has none), 1 k_plane_copy (the plane keeps its size), 2 k_scale (one LDS tile per 64-column
  * tile: down to about 4:1), 3 k_scale_stream (any ratio whose filters stay below 256 taps, about
