@@ -10,11 +10,14 @@ shape reaches the path it means to check.
   - orient_span / orient_cells: the tiles and workgroups k_orient_plane takes for a source plane, and
     its instantiation (plan_orient), for tests/test_gpu_orient_chain.py;
   - scale_variant / copy_pad_cells: the kernel instantiation build_plan picks for a plane;
+  - deint_span / sharp_cells: the workgroups, pieces and head / tail bytes k_yadif_plane takes for a
+    plane, and the tiles, `pic` masks and short quads of k_unsharp_plane's launch, for
+    tests/test_gpu_filter_chain.py; filter_sweep_configs and its family: that file's seeded sweep;
   - predict_paths: what mjg_debug_encode_path and mjg_debug_scale_path will report for an
     orient / crop / -pix_fmt / scale / pad configuration (the rules of plan_geometry and
     plan_plane_scale; the filters come from the library's own device-free mjg_sws_filter).
 
-kBatch, kCopyThreads, kCopyVecs, the orientation's tile and the tile kernel's constants are parsed from the kernel
+kBatch, kCopyThreads, kCopyVecs, kDeintThreads, the orientation's and the sharpen's tile and the tile kernel's constants are parsed from the kernel
 sources, so a change there moves these values and a hollowed-out test fails its precondition."""
 import os
 import re
@@ -489,4 +492,237 @@ ORIENT_SWEEP_FLOORS = [dict(zip(ORIENT_FEATURES, v)) for v in (
     (3, 5, 4, 6, 2, 4, 6, 13, 10, 2, 3, 2, 23, 8, 7, 5, 10),
     (2, 4, 4, 7, 3, 8, 2, 14, 7, 3, 4, 2, 21, 8, 14, 5, 3),
     (3, 8, 3, 3, 4, 5, 4, 13, 10, 2, 2, 5, 21, 7, 7, 11, 5),
+)]
+
+
+# ------------------------------------------------------------------ the deinterlacer's and the sharpen's launches
+DEINT_THREADS = _const("scale.hip", "kDeintThreads")
+SHARP_TILE_W = _const("scale.hip", "kSharpTileW")
+SHARP_TILE_H = _const("scale.hip", "kSharpTileH")
+
+DeintSpan = namedtuple("DeintSpan", "wgs pieces over_row_end head tail")
+
+
+def deint_span(w, h, head=0):
+    """What plan_deint and yadif_work derive for one (plane, frame) of w x h whose first output
+    byte lies `head` bytes in front of a 16-byte boundary: the workgroups of kDeintThreads pieces
+    (the launch sizes its grid from w h >> 4), the whole 16-byte pieces nv = (w h - head) >> 4, how
+    many of them run over a row end (col + 16 > w: gathered byte by byte), and the bytes in front
+    of the first and behind the last piece, which the first workgroup's threads 0..15 make."""
+    nb = w * h
+    wgs = max(1, ((nb >> 4) + DEINT_THREADS - 1) // DEINT_THREADS)
+    head = min(head, nb)
+    nv = (nb - head) >> 4
+    over = sum(1 for k in range(nv) if (head + 16 * k) % w + 16 > w)
+    return DeintSpan(wgs, nv, over, head, nb - head - 16 * nv)
+
+
+SharpCells = namedtuple("SharpCells", "tx ty filt copy masks short")
+
+
+def _row_quads(cw, px, w):
+    """[(x, n, pic)] of the output quads of one picture row of a cw-wide plane (sharp_store: quads
+    start at multiples of 4 of the plane, a tile is a multiple of 4 wide): n samples inside the
+    plane, bit k of pic: sample k inside the picture columns [px, px + w)."""
+    out = []
+    for x in range(0, cw, 4):
+        n = min(4, cw - x)
+        out.append((x, n, sum(1 << k for k in range(n) if px <= x + k < px + w)))
+    return out
+
+
+def sharp_cells(cw, ch, px, py, w, h, amount):
+    """What sharp_geom, sharp_tile and sharp_store derive for one cw x ch plane with the w x h
+    picture at (px, py) and the plane's amount: tile columns and rows, the tiles that filter
+    (amount != 0 and the tile holds a picture sample) and those that only copy, the histogram of
+    `pic` over the output quads of the filtering tiles (0: a quad of such a tile outside the
+    picture, copied; 15: one dword store; anything else byte by byte), and the quads of the whole
+    plane with fewer than four samples inside it (n < 4, at the plane's right edge)."""
+    tw, th = SHARP_TILE_W, SHARP_TILE_H
+    tx, ty = (cw + tw - 1) // tw, (ch + th - 1) // th
+    quads = _row_quads(cw, px, w)
+    filt = copy = 0
+    masks = {}
+    for r in range(ty):
+        y0 = r * th
+        rows = min(th, ch - y0)
+        rows_in = max(0, min(y0 + rows, py + h) - max(y0, py))
+        for c in range(tx):
+            x0 = c * tw
+            if not (amount != 0 and x0 < px + w and x0 + tw > px and y0 < py + h and y0 + th > py):
+                copy += 1
+                continue
+            filt += 1
+            for x, n, pic in quads:
+                if x0 <= x < x0 + tw:
+                    if rows_in:
+                        masks[pic] = masks.get(pic, 0) + rows_in
+                    if rows - rows_in:
+                        masks[0] = masks.get(0, 0) + rows - rows_in
+    short = ch * sum(1 for _, n, _ in quads if n < 4)
+    return SharpCells(tx, ty, filt, copy, dict(sorted(masks.items())), short)
+
+
+def sharp_plane_geoms(W, H, c, px, py, w, h, us):
+    """The two launches' (cw, ch, px, py, w, h, amount_i) of an encoded W x H frame in `c` whose
+    w x h picture sits at (px, py) (plan_sharp: luma, then the chroma planes), for sharp_cells."""
+    hs, vs = CHROMA_SHIFTS[c]
+    la, ca = int(float(us[2]) * 65536.0), int(float(us[5]) * 65536.0)
+    return ((W, H, px, py, w, h, la),
+            ((W + hs) >> hs, (H + vs) >> vs, px >> hs, py >> vs, (w + hs) >> hs, (h + vs) >> vs, ca))
+
+
+# ------------------------------------------------------------------ the seeded sweep with a filter
+DEINTS = (None, "tff", "bff", "tff_nospatial", "bff_nospatial")
+DEINT_FLAGS = {None: 0, "tff": 1, "bff": 1 | 4, "tff_nospatial": 1 | 2, "bff_nospatial": 1 | 2 | 4}  # MJG_DEINT_*
+SHARPS = (None, (5, 5, 1.0, 5, 5, 0.0), (5, 5, 1.0, 5, 5, 1.0), (3, 7, 1.5, 7, 3, -0.5), (9, 15, -1.0, 3, 3, 0.8),
+          (5, 5, 0.0, 3, 5, 0.7))
+SHARP_KINDS = {SHARPS[1]: "sharp55_luma_only", SHARPS[2]: "sharp55_all_planes", SHARPS[3]: "sharp_runtime_sizes",
+               SHARPS[4]: "sharp_runtime_sizes", SHARPS[5]: "sharp_luma_copied"}
+FILTER_FEATURES = (tuple("deint_" + str(d) for d in DEINTS)
+                   + ("sharp55_luma_only", "sharp55_all_planes", "sharp_runtime_sizes", "sharp_luma_copied")
+                   + ("deint_to_in_place_ua", "deint_to_in_place_aligned", "deint_to_rect_copy", "deint_to_pad_copy",
+                      "deint_to_tile_scale", "deint_to_stream", "deint_to_orient_t0", "deint_to_orient_t1")
+                   + ("sharp_from_tile_scale", "sharp_from_stream", "sharp_from_plane_copy", "sharp_from_pad_copy",
+                      "sharp_from_pad_with_scale")
+                   + ("sharp_three_tile_columns", "sharp_copy_tile_beside_filter", "sharp_left_partial_mask",
+                      "sharp_right_partial_mask")
+                   + SUBMITS + ("default", "optimal", "rst"))
+
+FilterConfig = namedtuple("FilterConfig", Config._fields + ("orient", "deint", "unsharp"))
+
+def filter_sweep_configs(seed, count):
+    """sweep_configs(seed, count), each with values from a generator of its own (seeded [seed,
+    tag]): a deinterlacer out of DEINTS, a sharpen out of SHARPS, in one draw of three an
+    orientation (1..7; 2, 4 or 6 where the source is 4:2:2), and a submit mode for the case below.
+    Every value is drawn before the rules are tested; a draw with neither a deinterlacer nor a
+    sharpen is drawn again.  As in orient_sweep_configs the drawn w x h is the oriented frame and
+    the source frames are source_size(cfg).  A deinterlaced configuration has three frames (the
+    middle one has two distinct neighbours) and, a deint context never merging, one of the other
+    three submit modes in place of "merged"; its segments are 2 + 1 frames.
+    The odds are not those of a uniform draw.  sweep_configs gives a part of 30 about one
+    configuration on the stream kernel, one or two crops read in place of either kind and two
+    rectangle copies (of seeds 1..800, 13% have a stream kernel in every part, 64% each kind of
+    crop in place, 80% a rectangle copy, 4% all of them), so with uniform odds no seed of 1..3000
+    gave every feature in every part.  Hence: "no deinterlacer" counts twice among six
+    deinterlacer values (merged submits are for sharpen-only draws), and a base draw on one of
+    those rare paths always gets one of the four deinterlacers; one that is read in place gets no
+    sharpen (a sharpen runs the sws stage: nothing would read d_deint in place) and no
+    orientation; one with a plane on the stream kernel always gets a sharpen and no orientation
+    (so the one configuration has d_deint in front of the stream kernel and d_sharp behind it)."""
+    import numpy as np
+    rng = np.random.default_rng([seed, 0x6669])
+    out = []
+    for c in sweep_configs(seed, count):
+        enc_path, paths, rect_form = predict_paths(c.w, c.h, c.src, c.rect, c.dst, c.dw, c.dh, c.pad)
+        in_place, stream = bool(enc_path & IN_PLACE), STREAM in paths
+        while True:
+            d6, d4 = int(rng.integers(6)), 1 + int(rng.integers(4))
+            s6, s5 = int(rng.integers(6)), 1 + int(rng.integers(5))
+            turned = int(rng.integers(3)) == 0
+            o, om = 1 + int(rng.integers(7)), (2, 4, 6)[int(rng.integers(3))]
+            sub = SUBMITS[int(rng.integers(3))]
+            d = d4 if in_place or stream or rect_form else max(0, d6 - 1)
+            s = 0 if in_place else s5 if stream else s6
+            if d or s:
+                break
+        orient = 0 if not turned or in_place or stream else om if c.src == "422" else o
+        submit, nframes = c.submit, c.nframes
+        if d:
+            submit, nframes = (sub if submit == "merged" else submit), 3
+        out.append(FilterConfig(*c._replace(submit=submit, nframes=nframes), orient, DEINTS[d], SHARPS[s]))
+    return out
+
+
+def filter_predict(cfg):
+    """(encode_path, (luma, chroma) scale_path, RECT) of a FilterConfig: predict_paths from its
+    source size; a sharpen always runs the sws stage (plan_geometry: scale |= sharp), so what
+    would be read in place goes through the plane copy first."""
+    sw, sh = source_size(cfg)
+    enc_path, paths, rect_form = predict_paths(sw, sh, cfg.src, cfg.rect, cfg.dst, cfg.dw, cfg.dh, cfg.pad,
+                                               orient=cfg.orient)
+    if cfg.unsharp is not None and enc_path & IN_PLACE:
+        assert paths == (NONE, NONE)
+        return 0, (COPY, COPY), cfg.rect is not None and cfg.rect[2] != cfg.w
+    return enc_path, paths, rect_form
+
+
+def encoded_geometry(cfg):
+    """(canvas W, H, picture x, y, w, h) of the frames a configuration encodes."""
+    pw = cfg.dw or (cfg.rect[2] if cfg.rect else cfg.w)
+    ph = cfg.dh or (cfg.rect[3] if cfg.rect else cfg.h)
+    return (cfg.pad[2], cfg.pad[3], cfg.pad[0], cfg.pad[1], pw, ph) if cfg.pad is not None else (pw, ph, 0, 0, pw, ph)
+
+
+def filter_features(cfg, enc_path, paths):
+    """The FILTER_FEATURES a FilterConfig carries, from its encode path and scale paths (predicted
+    by filter_predict, or as the context reports them), its own values and sharp_cells of its
+    encoded planes."""
+    crop = cfg.rect is not None and tuple(cfg.rect) != (0, 0, cfg.w, cfg.h)
+    f = {cfg.submit, "deint_" + str(cfg.deint),
+         "optimal" if cfg.kw.get("huffman") == "optimal" else "rst" if cfg.kw.get("rst") else "default"}
+    if cfg.deint is not None:  # who reads d_deint
+        if cfg.orient:
+            f.add("deint_to_orient_t1" if cfg.orient & 1 else "deint_to_orient_t0")
+        elif enc_path & IN_PLACE:
+            if crop:
+                f.add("deint_to_in_place_ua" if enc_path & UA else "deint_to_in_place_aligned")
+        else:
+            if paths[0] == COPY and crop and cfg.rect[2] != cfg.w:
+                f.add("deint_to_rect_copy")
+            if PADCOPY in paths:
+                f.add("deint_to_pad_copy")
+            if TILE in paths:
+                f.add("deint_to_tile_scale")
+            if STREAM in paths:
+                f.add("deint_to_stream")
+    if cfg.unsharp is not None:
+        assert not enc_path & IN_PLACE
+        f.add(SHARP_KINDS[cfg.unsharp])
+        if cfg.pad is not None and (TILE in paths or STREAM in paths):
+            f.add("sharp_from_pad_with_scale")
+        if PADCOPY in paths:
+            f.add("sharp_from_pad_copy")
+        if COPY in paths:
+            f.add("sharp_from_plane_copy")
+        if TILE in paths and cfg.pad is None:
+            f.add("sharp_from_tile_scale")
+        if STREAM in paths:
+            f.add("sharp_from_stream")
+        for cw, ch, px, py, w, h, amount in sharp_plane_geoms(*encoded_geometry(cfg)[:2], cfg.dst,
+                                                              *encoded_geometry(cfg)[2:], cfg.unsharp):
+            if not amount:
+                continue
+            cells = sharp_cells(cw, ch, px, py, w, h, amount)
+            if cells.tx >= 3:
+                f.add("sharp_three_tile_columns")
+            if cells.filt and cells.copy:
+                f.add("sharp_copy_tile_beside_filter")
+            for x, n, pic in _row_quads(cw, px, w):
+                if pic and not pic & 1:
+                    f.add("sharp_left_partial_mask")
+                if n == 4 and pic & 1 and pic != 15:
+                    f.add("sharp_right_partial_mask")  # (the picture's right edge cuts a whole quad of the canvas)
+    return f
+
+
+def count_filter_features(sets):
+    return {k: sum(k in s for s in sets) for k in FILTER_FEATURES}
+
+
+def filter_predicted_counts(cfgs):
+    return count_filter_features([filter_features(c, *filter_predict(c)[:2]) for c in cfgs])
+
+
+# The sweep of tests/test_gpu_filter_chain.py: the seed, and per part of 30 configurations the
+# number that carry each feature, counted by filter_predicted_counts (tests/test_chain_geom.py
+# checks that).  Of seeds 1..3000 the one whose sorted counts (132: 33 features x 4 parts) are
+# largest, compared from the smallest up; five seeds have every count at least 1, which the GPU
+# test requires of every feature in every part.
+FILTER_SWEEP_SEED = 2451
+FILTER_SWEEP_FLOORS = [dict(zip(FILTER_FEATURES, v)) for v in (
+    (6, 7, 6, 6, 5, 4, 6, 6, 6, 1, 4, 2, 3, 12, 1, 3, 1, 16, 1, 3, 2, 4, 4, 4, 2, 3, 12, 9, 8, 1, 9, 11, 10),
+    (6, 6, 8, 6, 4, 1, 4, 11, 4, 3, 1, 2, 2, 8, 2, 4, 3, 13, 2, 5, 2, 5, 2, 4, 6, 4, 6, 10, 12, 2, 7, 11, 12),
+    (3, 5, 6, 8, 8, 3, 3, 9, 6, 1, 2, 1, 2, 12, 4, 5, 2, 10, 4, 3, 4, 8, 5, 8, 9, 8, 14, 8, 7, 1, 10, 14, 6),
+    (4, 5, 5, 6, 10, 4, 3, 8, 6, 1, 5, 2, 2, 13, 1, 3, 3, 15, 1, 3, 1, 6, 3, 4, 6, 6, 11, 9, 9, 1, 9, 14, 7),
 )]

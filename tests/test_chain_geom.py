@@ -1,5 +1,5 @@
-"""tests/chain_geom.py against values computed by hand for the shapes of tests/test_gpu_chain.py
-(no GPU).  The hand values assume kBatch = 12 and 256 x 4 pieces per copy workgroup; the first
+"""tests/chain_geom.py against values computed by hand for the shapes of tests/test_gpu_chain.py,
+tests/test_gpu_orient_chain.py and tests/test_gpu_filter_chain.py (no GPU).  The hand values assume kBatch = 12 and 256 x 4 pieces per copy workgroup; the first
 test says so, so that a change of those constants points here before it fails a sum below."""
 import os
 import re
@@ -390,3 +390,172 @@ def test_copy_and_pad_cells_are_reached_by_the_gpu_tests():
 # frames) and the 4:4:4 size at which the chroma planes keep theirs
 CHROMA_COPY_RECTS = (None, (2, 6, 250, 150))
 CHROMA_COPY_SIZE = {None: (150, 100), (2, 6, 250, 150): (125, 75)}
+
+
+# ------------------------------------------------------------------ the deinterlacer's and the sharpen's launches
+def test_filter_constants_parsed_from_the_kernel_source():
+    """The hand values below assume 256 pieces of 16 bytes a deinterlacer workgroup and 64 x 32 tiles."""
+    assert (cg.DEINT_THREADS, cg.SHARP_TILE_W, cg.SHARP_TILE_H) == (256, 64, 32)
+
+
+@pytest.mark.parametrize("args,want", [
+    # 130 x 66 = 8580 B: 536 pieces and 4 bytes, 3 workgroups (256 + 256 + 24).  16 and 130 share the factor 2: over 65
+    # pieces (8 rows) the piece's column takes every even value once, and it runs over the row end from column 116 on
+    # (116..128: 7 of 65); 536 = 8 * 65 + 16, and of the last 16 pieces (from row 64, column 0) the one at column 128
+    ((130, 66), (3, 536, 8 * 7 + 1, 0, 4)),
+    # 4100 x 5 = 20500 B: 1281 pieces and 4 bytes, 6 workgroups (the sixth holds one piece); 4100 = 16 * 256 + 4, so the
+    # ends of rows 0, 1 and 2 (4100, 8200, 12300) fall inside a piece and the end of row 3 (16400 = 16 * 1025) between two
+    ((4100, 5), (6, 1281, 3, 0, 4)),
+    # 33 x 17 = 561 B at an odd address (15 bytes to the boundary, as frame 1 of a 4:4:4 sequence has): 34 pieces after
+    # the head and 2 bytes; a piece at column c of a 33-byte row runs over its end from c = 18 on.  16 and 33 are coprime,
+    # so pieces 0..32 (columns (15 + 16 k) % 33) take every column once, 15 of them in 18..32; piece 33 is at column 15 again
+    ((33, 17, 15), (1, 34, 15, 15, 2)),
+    ((33, 17), (1, 35, 15, 0, 1)),
+    ((3, 3, 7), (1, 0, 0, 7, 2)),       # smaller than a piece: threads 0..15 of the one workgroup make every byte
+])
+def test_deint_span(args, want):
+    span = cg.deint_span(*args)
+    assert tuple(span) == want
+    # the same by walking every byte of the plane's string once (yadif_work: head, nv pieces of 16, the rest)
+    w, h, head = args[0], args[1], (args[2] if len(args) > 2 else 0)
+    head = min(head, w * h)
+    over = sum(1 for j in range(head, w * h - 15, 16) if j // w != (j + 15) // w)
+    assert span.over_row_end == over and span.head + 16 * span.pieces + span.tail == w * h and 0 <= span.tail < 16
+    assert (span.wgs - 1) * cg.DEINT_THREADS < max(1, (w * h) >> 4) <= span.wgs * cg.DEINT_THREADS
+
+
+def _cells_by_sharp_store(cw, ch, px, py, w, h, amount):
+    """sharp_cells again, quad by quad as k_unsharp_plane's threads see them (sharp_tile and sharp_store)."""
+    tw, th = cg.SHARP_TILE_W, cg.SHARP_TILE_H
+    tx, ty = -(-cw // tw), -(-ch // th)
+    filt = copy = short = 0
+    masks = {}
+    for blk in range(tx * ty):
+        x0, y0 = blk % tx * tw, blk // tx * th
+        f = amount != 0 and x0 < px + w and x0 + tw > px and y0 < py + h and y0 + th > py
+        filt, copy = filt + f, copy + (not f)
+        for idx in range(tw * th // 4):
+            x, y = x0 + 4 * (idx % (tw // 4)), y0 + idx // (tw // 4)
+            if x >= cw or y >= ch:
+                continue
+            n = min(4, cw - x)
+            pic = sum(1 << k for k in range(n) if py <= y < py + h and px <= x + k < px + w)
+            short += n < 4
+            if f:
+                masks[pic] = masks.get(pic, 0) + 1
+    return cg.SharpCells(tx, ty, filt, copy, dict(sorted(masks.items())), short)
+
+
+# (plane, picture, amount) -> (tx, ty, filtering tiles, copying tiles, pic masks of the filtering tiles' quads)
+SHARP_CELLS = [
+    # 197 = 3 * 64 + 5 columns: 49 whole quads and one of a single sample per row, 70 rows over three tile rows
+    ((197, 70, 0, 0, 197, 70, 65536), (4, 3, 12, 0, {1: 70, 15: 49 * 70})),
+    # the picture's columns 67..136 and rows 33..66 touch tile columns 1, 2 and tile rows 1, 2; those tiles hold
+    # 128 x 64 samples = 32 quads x 64 rows = 2048 quads; per picture row (34 of them): 67 = 4 * 16 + 3 starts with the
+    # last sample of a quad (8), 137 = 4 * 34 + 1 ends with the first of one (1), 17 whole quads between (68..135)
+    ((201, 99, 67, 33, 70, 34, 65536), (4, 4, 4, 12, {0: 2048 - 19 * 34, 1: 34, 8: 34, 15: 17 * 34})),
+    # columns 69..134 (69 = 4 * 17 + 1: samples 1..3 of a quad, 14; 135 = 4 * 33 + 3: samples 0..2, 7; 15 whole quads
+    # 72..131), rows 35..67 (33 rows) in the same four tiles
+    ((203, 101, 69, 35, 66, 33, 98304), (4, 4, 4, 12, {0: 2048 - 17 * 33, 7: 33, 14: 33, 15: 15 * 33})),
+    # the chroma plane of 134 x 70 4:2:2: 67 = 64 + 3 columns, 16 whole quads and one of three samples per row
+    ((67, 70, 0, 0, 67, 70, 32768), (2, 3, 6, 0, {7: 70, 15: 16 * 70})),
+    # the chroma of the next: columns 35..99 and rows 19..51 touch tile columns 0, 1 and tile rows 0, 1 (2048 quads);
+    # 35 = 4 * 8 + 3 (8), 100 = 4 * 25: the right edge falls between quads, 16 whole quads 36..99; five more tiles copy
+    ((132, 68, 35, 19, 65, 33, 65536), (3, 3, 4, 5, {0: 2048 - 17 * 33, 8: 33, 15: 16 * 33})),
+    # columns 70..199, rows 38..103: tile columns 1..3, tile rows 1..3, nine tiles of 512 quads; 70 = 4 * 17 + 2 (12),
+    # 200 = 4 * 50, 32 whole quads 72..199, 66 rows
+    ((264, 136, 70, 38, 130, 66, 65536), (5, 5, 9, 16, {0: 9 * 512 - 33 * 66, 12: 66, 15: 32 * 66})),
+]
+
+
+@pytest.mark.parametrize("geom,want", SHARP_CELLS, ids=["%dx%d_%dx%d+%d+%d" % (g[0], g[1], g[4], g[5], g[2], g[3])
+                                                       for g, _ in SHARP_CELLS])
+def test_sharp_cells(geom, want):
+    """The six planes of tests/test_gpu_filter_chain.py, by hand and by walking every thread's quads."""
+    cells = cg.sharp_cells(*geom)
+    assert tuple(cells[:5]) == want
+    assert cells == _cells_by_sharp_store(*geom)
+    assert cg.sharp_cells(*geom[:6], 0)[2:5] == (0, cells.tx * cells.ty, {})      # amount 0: every tile copies
+
+
+def test_sharp_cells_of_the_geometries_the_gpu_tests_encode():
+    """Every plane of unsharp_ref.GPU_GEOMETRY_CHAIN is one of the table above (or the 134 x 70 luma);
+    and the claim the new cases rest on: no geometry of unsharp_ref.GPU_GEOMETRY (tests/test_gpu_unsharp.py)
+    has a picture edge that cuts a quad on its left (pic masks are 0, 15, or 1, 3, 7 on the right) or three
+    tile columns, and one alone has a copying tile in a launch that also filters: the luma of 50 x 38 with
+    the picture's rows 10..27, whose second tile row (rows 32..37) lies under the picture in a single tile
+    column.  None has a copying tile to the left or right of a filtering one."""
+    import unsharp_ref
+    table = {g[:6] for g, _ in SHARP_CELLS} | {(134, 70, 0, 0, 134, 70)}
+    for (W, H, c, px, py, w, h, us) in unsharp_ref.GPU_GEOMETRY_CHAIN:
+        for g in cg.sharp_plane_geoms(W, H, c, px, py, w, h, us):
+            assert g[:6] in table, g
+    assert unsharp_ref.WIDE == (197, 70)
+    seen = set()
+    for (W, H, c, px, py, w, h, us) in unsharp_ref.GPU_GEOMETRY:
+        for g in cg.sharp_plane_geoms(W, H, c, px, py, w, h, us):
+            cells = cg.sharp_cells(*g)
+            assert cells == _cells_by_sharp_store(*g)
+            assert cells.tx <= 2
+            assert not (cells.filt and cells.copy) or (g[:6] == (50, 38, 8, 10, 34, 18) and cells[:4] == (1, 2, 1, 1)), g
+            assert all(m == 0 or m & 1 for m in cells.masks), (g, cells.masks)
+            seen |= set(cells.masks)
+    assert seen <= {0, 1, 3, 7, 15}
+    new = set()
+    for g, _ in SHARP_CELLS:
+        new |= set(cg.sharp_cells(*g).masks)
+    assert {8, 12, 14} <= new
+
+
+# ------------------------------------------------------------------ the seeded sweep with a filter
+def test_filter_predict_and_features():
+    base = cg.Config(300, 200, "420", (6, 16, 224, 128), "420", None, None, None, False, 5, {}, "host", 3, 1)
+    cfg = cg.FilterConfig(*base, 0, "bff", None)
+    assert cg.filter_predict(cfg)[:2] == (IN_PLACE | UA, (NONE, NONE))
+    assert cg.filter_features(cfg, *cg.filter_predict(cfg)[:2]) == {"host", "default", "deint_bff", "deint_to_in_place_ua"}
+    # a sharpen runs the sws stage: the rectangle goes through k_plane_copy's RECT form, 224 = 3.5 tile columns
+    cfg = cfg._replace(unsharp=cg.SHARPS[1])
+    assert cg.filter_predict(cfg) == (0, (COPY, COPY), True)
+    assert cg.filter_features(cfg, 0, (COPY, COPY)) == {"host", "default", "deint_bff", "deint_to_rect_copy", "sharp55_luma_only",
+                                                        "sharp_from_plane_copy", "sharp_three_tile_columns"}
+    # the 4:2:0 pad case of tests/test_gpu_filter_chain.py behind an orientation
+    cfg = cg.FilterConfig(260, 132, "420", None, "420", 130, 66, (70, 38, 264, 136), False, 5, {"rst": True}, "segments", 3, 1,
+                          5, "tff_nospatial", cg.SHARPS[2])
+    assert cg.source_size(cfg) == (132, 260) and cg.encoded_geometry(cfg) == (264, 136, 70, 38, 130, 66)
+    assert cg.filter_features(cfg, *cg.filter_predict(cfg)[:2]) == {
+        "segments", "rst", "deint_tff_nospatial", "deint_to_orient_t1", "sharp55_all_planes", "sharp_from_pad_with_scale",
+        "sharp_three_tile_columns", "sharp_copy_tile_beside_filter", "sharp_left_partial_mask"}
+
+
+def test_filter_sweep_draw_and_its_floors():
+    """The sweep of tests/test_gpu_filter_chain.py, counted without a GPU: the configurations of
+    sweep_configs for its seed, each with a deinterlacer, a sharpen or both, and per part of 30
+    exactly the feature counts the GPU test uses as floors, every one at least 1."""
+    seed = cg.FILTER_SWEEP_SEED
+    assert seed == 2451
+    cfgs = cg.filter_sweep_configs(seed, 120)
+    assert len(cfgs) == 120 and cfgs == cg.filter_sweep_configs(seed, 120)
+    for c, b in zip(cfgs, cg.sweep_configs(seed, 120)):
+        assert tuple(c[:11]) == tuple(b[:11]) and c.fseed == b.fseed
+        assert c.deint in cg.DEINTS and c.unsharp in cg.SHARPS and (c.deint or c.unsharp)
+        assert 0 <= c.orient <= 7 and not (c.src == "422" and c.orient & 1)
+        if c.deint:
+            assert c.nframes == 3 and c.submit in ("host", "dev_odd", "segments")
+            assert c.submit == b.submit or b.submit == "merged"
+        else:
+            assert (c.submit, c.nframes) == (b.submit, b.nframes)
+        sw, sh = cg.source_size(c)
+        assert min(chroma_size(sw, sh, c.src)) >= 24      # every plane far above the deinterlacer's 3 x 3
+    assert sum(1 for c in cfgs if c.orient) == 31          # about one in three of those not on a rare path
+    parts = [cg.filter_predicted_counts(cfgs[i * 30:(i + 1) * 30]) for i in range(4)]
+    assert parts == cg.FILTER_SWEEP_FLOORS
+    assert all(set(p) == set(cg.FILTER_FEATURES) and min(p.values()) >= 1 for p in parts)
+    total = {k: sum(p[k] for p in parts) for k in cg.FILTER_FEATURES}
+    assert total == {"deint_None": 19, "deint_tff": 23, "deint_bff": 25, "deint_tff_nospatial": 26, "deint_bff_nospatial": 27,
+                     "sharp55_luma_only": 12, "sharp55_all_planes": 16, "sharp_runtime_sizes": 34, "sharp_luma_copied": 22,
+                     "deint_to_in_place_ua": 6, "deint_to_in_place_aligned": 12, "deint_to_rect_copy": 7, "deint_to_pad_copy": 9,
+                     "deint_to_tile_scale": 45, "deint_to_stream": 8, "deint_to_orient_t0": 15, "deint_to_orient_t1": 9,
+                     "sharp_from_tile_scale": 54, "sharp_from_stream": 8, "sharp_from_plane_copy": 14, "sharp_from_pad_copy": 9,
+                     "sharp_from_pad_with_scale": 23, "sharp_three_tile_columns": 14, "sharp_copy_tile_beside_filter": 20,
+                     "sharp_left_partial_mask": 23, "sharp_right_partial_mask": 21, "host": 43, "dev_odd": 36, "segments": 36,
+                     "merged": 5, "default": 35, "optimal": 50, "rst": 35}

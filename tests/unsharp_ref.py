@@ -159,3 +159,25 @@ GPU_GEOMETRY = [
     (50, 38, "420", 8, 10, 34, 18, US2),
     (64, 32, "420", 0, 0, 64, 32, DEFAULT),
 ]
+
+# The encoded geometry of tests/test_gpu_filter_chain.py, in the same form and walked by the same
+# tool: planes of three and more tile columns (aprons of 11 across tile seams, the staging loop's
+# third iteration), <5, 5> on all three planes, pictures whose left edge cuts a quad (pic masks 8,
+# 12, 14) inside canvases whose outer tiles only copy, a 4:2:2 frame, and a copied luma of 12 tiles.
+US_23 = (23, 3, 1.0, 3, 23, 0.7)
+US_13 = (13, 13, 1.0, 9, 15, -1.0)
+US_55 = (5, 5, 1.0, 5, 5, 1.0)
+US_73 = (7, 3, 1.5, 3, 7, 0.5)
+US_422 = (7, 5, 1.5, 5, 5, 0.5)
+US_LUMA0 = (5, 5, 0.0, 3, 3, 1.0)
+WIDE = (3 * kernel_constant("kSharpTileW") + 5, 2 * kernel_constant("kSharpTileH") + 6)      # 197 x 70
+GPU_GEOMETRY_CHAIN = [
+    (*WIDE, "444", 0, 0, *WIDE, US_23),
+    (*WIDE, "444", 0, 0, *WIDE, US_13),
+    (*WIDE, "444", 0, 0, *WIDE, US_55),
+    (201, 99, "444", 67, 33, 70, 34, US_55),
+    (203, 101, "444", 69, 35, 66, 33, US_73),
+    (264, 136, "420", 70, 38, 130, 66, US_55),
+    (134, 70, "422", 0, 0, 134, 70, US_422),
+    (*WIDE, "444", 0, 0, *WIDE, US_LUMA0),
+]

@@ -2,12 +2,14 @@
 """k_unsharp_plane's body on the CPU: builds tools/unsharp_host.hip (the kernel's __host__ __device__
 steps and address arithmetic run over every (workgroup, thread, iteration) of its launches) with
 AddressSanitizer and UBSan on the host side, for the encoded geometry of every GPU test
-(tests/unsharp_ref.py GPU_GEOMETRY) and a few smaller ones: two frames, U and V in one launch and in
+(tests/unsharp_ref.py GPU_GEOMETRY and GPU_GEOMETRY_CHAIN) and a few smaller ones: two frames, U and V in one launch and in
 one each.  The program itself asserts that every staged load lies inside the picture rectangle and
 that every byte of every plane is stored exactly once, on buffers allocated at exactly the frames'
-size; this script compares its output with tests/unsharp_ref.py.  No GPU.
+size; this script compares its output with tests/unsharp_ref.py.  --sweep walks instead the encoded
+geometry of every sharpened configuration of the seeded sweep (tests/chain_geom.py
+filter_sweep_configs, tests/test_gpu_filter_chain.py).  No GPU.
 
-usage: python3 tools/unsharp_host_check.py [--keep]"""
+usage: python3 tools/unsharp_host_check.py [--keep] [--sweep]"""
 import os
 import subprocess
 import sys
@@ -18,7 +20,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from unsharp_ref import GPU_GEOMETRY, amount_i, unsharp_planes  # noqa: E402
+from unsharp_ref import GPU_GEOMETRY, GPU_GEOMETRY_CHAIN, amount_i, unsharp_planes  # noqa: E402
 from pad_ref import pad_planes  # noqa: E402
 from ffmpeg_distributed_amd.encoder import chroma_size, pack_i420  # noqa: E402
 
@@ -38,7 +40,12 @@ def main():
                     os.path.join(ROOT, "tools", "unsharp_host.hip")], check=True)
     rng = np.random.default_rng(7)
     bad = 0
-    for (PW, PH, c, px, py, w, h, us) in GPU_GEOMETRY + EXTRA:
+    geoms = GPU_GEOMETRY + GPU_GEOMETRY_CHAIN + EXTRA
+    if "--sweep" in sys.argv:
+        import chain_geom as cg
+        cfgs = cg.filter_sweep_configs(cg.FILTER_SWEEP_SEED, 120)
+        geoms = [(*cg.encoded_geometry(k)[:2], k.dst, *cg.encoded_geometry(k)[2:], k.unsharp) for k in cfgs if k.unsharp]
+    for (PW, PH, c, px, py, w, h, us) in geoms:
         hs, vs = SHIFTS[c]
         cw, ch = chroma_size(w, h, c)
         pics = []

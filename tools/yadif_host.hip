@@ -3,8 +3,8 @@
 // their sizes, so that AddressSanitizer sees any access outside a readable frame.  Built and driven by
 // tools/yadif_host_check.py (hipcc -Xarch_host -fsanitize=address,undefined); makes no HIP call.
 //   yadif_host IN OUT w h hshift vshift nospatial parity nframes halo split
-// IN: nframes + halo frames, packed planar; split > 0: frames [0, split) and [split, nframes) are two
-// segments in allocations of their own (mjg_submit_segments' SegList).
+// IN: nframes + halo frames, packed planar; split: 0, or the lengths of up to kMaxSegs segments as a,b,...
+// (their sum nframes, no halo): each segment in an allocation of its own (mjg_submit_segments' SegList).
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
@@ -20,24 +20,42 @@ int main(int argc, char **argv) {
   if (argc < 12) return 2;
   const char *in = argv[1], *outp = argv[2];
   const int w = atoi(argv[3]), h = atoi(argv[4]), hs = atoi(argv[5]), vs = atoi(argv[6]);
-  const int nosp = atoi(argv[7]), parity = atoi(argv[8]), n = atoi(argv[9]), halo = atoi(argv[10]), split = atoi(argv[11]);
+  const int nosp = atoi(argv[7]), parity = atoi(argv[8]), n = atoi(argv[9]), halo = atoi(argv[10]);
+  std::vector<int> lens;  // the segments' lengths; empty: one segment of n frames and its halo
+  for (const char *p = argv[11]; *p;) {
+    char *e;
+    const int v = (int)strtol(p, &e, 10);
+    if (v > 0) lens.push_back(v);
+    p = *e ? e + 1 : e;
+  }
+  const int nsegs = (int)lens.size();
+  if (nsegs > kMaxSegs || (nsegs && halo)) return 2;
   const int hp = halo & 1, hn = (halo >> 1) & 1;
   const int cw = (w + hs) >> hs, ch = (h + vs) >> vs;
   const size_t fb = (size_t)w * h + 2 * (size_t)cw * ch;
   const size_t tot = (size_t)(n + hp + hn) * fb;
   FILE *f = fopen(in, "rb");
-  // exact-size buffers: segment 0 and (split) segment 1 in separate allocations
-  const int n0 = split ? split : n;
-  uint8_t *b0 = (uint8_t *)malloc(split ? n0 * fb : tot);
-  uint8_t *b1 = split ? (uint8_t *)malloc((n - n0) * fb) : nullptr;
-  if (fread(b0, 1, split ? n0 * fb : tot, f) != (split ? n0 * fb : tot)) return 3;
-  if (split && fread(b1, 1, (n - n0) * fb, f) != (n - n0) * fb) return 3;
+  // exact-size buffers: one for the submit and its halo, or one per segment
+  std::vector<uint8_t *> bufs;
+  SegList sl;
+  if (!nsegs) {
+    bufs.push_back((uint8_t *)malloc(tot));
+    if (fread(bufs[0], 1, tot, f) != tot) return 3;
+    for (int k = 0; k < kMaxSegs; k++) sl.p[k] = bufs[0] + hp * fb, sl.f0[k] = k ? INT_MAX : 0;
+  } else {
+    int at = 0;
+    for (int k = 0; k < nsegs; k++) {
+      bufs.push_back((uint8_t *)malloc(lens[k] * fb));
+      if (fread(bufs[k], 1, lens[k] * fb, f) != lens[k] * fb) return 3;
+      sl.p[k] = bufs[k], sl.f0[k] = at;
+      at += lens[k];
+    }
+    if (at != n) return 2;
+    for (int k = nsegs; k < kMaxSegs; k++) sl.p[k] = bufs[0], sl.f0[k] = INT_MAX;  // as mjg_submit_segments fills them
+  }
   fclose(f);
   // destination at an odd alignment inside an exact allocation: d + 1
   uint8_t *dbase = (uint8_t *)malloc(n * fb);
-  SegList sl;
-  for (int k = 0; k < kMaxSegs; k++) sl.p[k] = b0 + hp * fb, sl.f0[k] = k ? INT_MAX : 0;
-  if (split) sl.p[1] = b1, sl.f0[1] = n0;
   for (int p = 0; p < 2; p++) {
     DeintGeom g{};
     g.w = p ? cw : w;
@@ -66,8 +84,7 @@ int main(int argc, char **argv) {
   f = fopen(outp, "wb");
   fwrite(dbase, 1, n * fb, f);
   fclose(f);
-  free(b0);
-  free(b1);
+  for (uint8_t *b : bufs) free(b);
   free(dbase);
   return 0;
 }

@@ -3,10 +3,15 @@
 run over every (workgroup, thread) of its launches) with AddressSanitizer and UBSan on the host
 side, and compares its output with tests/yadif_ref.py for every shape of the GPU tests and a few
 smaller ones, both parities, both modes: one submit of 5 frames, the same frames as halo submits of
-2 + 2 + 1, and as two segments of 3 + 2.  The source and destination buffers are allocated at
-exactly their sizes, so a load or store outside a readable frame stops the program.  No GPU.
+2 + 2 + 1, and as segments of their own in one launch: 3 + 2, 1 + 3 + 1 (a one-frame segment
+between others) and 1 + 1 + 2 + 1 (kMaxSegs segments), the splits of tests/test_gpu_yadif.py and
+tests/test_gpu_filter_chain.py; the shapes of the latter's cases are in the list too.  The source and destination buffers are allocated at
+exactly their sizes, so a load or store outside a readable frame stops the program.  --sweep walks
+instead every deinterlaced configuration of the seeded sweep (tests/chain_geom.py
+filter_sweep_configs): its source shape, mode and parity, three frames in one submit and as
+segments of 2 + 1.  No GPU.
 
-usage: python3 tools/yadif_host_check.py [--keep]"""
+usage: python3 tools/yadif_host_check.py [--keep] [--sweep]"""
 import os
 import subprocess
 import sys
@@ -22,7 +27,9 @@ from ffmpeg_distributed_amd.encoder import i420_frame_bytes  # noqa: E402
 
 SHIFTS = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}
 SHAPES = [(130, 66, "420"), (131, 67, "420"), (130, 66, "422"), (33, 17, "444"), (6, 6, "420"), (20, 8, "444"),
-          (4100, 5, "444"), (3, 3, "444"), (16, 3, "444"), (19, 4, "444"), (40, 7, "420")]
+          (4100, 5, "444"), (3, 3, "444"), (16, 3, "444"), (19, 4, "444"), (40, 7, "420"),
+          (256, 160, "420"), (256, 160, "444"), (130, 66, "444"), (301, 203, "420")]      # tests/test_gpu_filter_chain.py
+SPLITS = [(3, 2), (1, 3, 1), (1, 1, 2, 1)]
 
 
 def main():
@@ -39,7 +46,7 @@ def main():
         fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
         frames.tofile(fin)
         r = subprocess.run([exe, fin, fout, str(w), str(h), str(hs), str(vs), str(1 if mode == 2 else 0), str(tff ^ 1),
-                            str(n), str(halo), str(split)], capture_output=True, text=True)
+                            str(n), str(halo), ",".join(str(v) for v in split) if split else "0"], capture_output=True, text=True)
         if r.returncode:
             sys.exit(f"yadif_host failed ({r.returncode}) at {w}x{h} {c} mode {mode} tff {tff} halo {halo} split {split}:\n"
                      + r.stderr[-4000:])
@@ -47,7 +54,24 @@ def main():
 
     rng = np.random.default_rng(5)
     bad = 0
-    for (w, h, c) in SHAPES:
+    if "--sweep" in sys.argv:
+        import chain_geom as cg
+        seen = set()
+        for k in cg.filter_sweep_configs(cg.FILTER_SWEEP_SEED, 120):
+            key = (*cg.source_size(k), k.src, k.deint)
+            if not k.deint or key in seen:
+                continue
+            seen.add(key)
+            (w, h), c = cg.source_size(k), k.src
+            mode, tff = (2 if "nospatial" in k.deint else 0), int(k.deint.startswith("tff"))
+            frames = rng.integers(0, 256, (3, i420_frame_bytes(w, h, c)), dtype=np.uint8)
+            one = run(frames, w, h, c, mode, tff, 3, 0, 0)
+            segs = run(frames, w, h, c, mode, tff, 3, 0, (2, 1))
+            want_segs = np.concatenate([deint_frames(frames[:2], w, h, c, mode, tff), deint_frames(frames[2:], w, h, c, mode, tff)])
+            ok = [(one == deint_frames(frames, w, h, c, mode, tff)).all(), (segs == want_segs).all()]
+            print(f"{w}x{h} {c} {k.deint}: one submit {ok[0]}, segments 2+1 {ok[1]}")
+            bad += ok.count(False)
+    for (w, h, c) in ([] if "--sweep" in sys.argv else SHAPES):
         fb = i420_frame_bytes(w, h, c)
         frames = rng.integers(0, 256, (5, fb), dtype=np.uint8)
         frames[3] = (np.arange(fb) * 3 % 256).astype(np.uint8)
@@ -57,12 +81,14 @@ def main():
                 one = run(frames, w, h, c, mode, tff, 5, 0, 0)
                 halo = np.concatenate([run(frames[0:3], w, h, c, mode, tff, 2, 2, 0), run(frames[1:5], w, h, c, mode, tff, 2, 3, 0),
                                        run(frames[3:5], w, h, c, mode, tff, 1, 1, 0)])
-                segs = run(frames, w, h, c, mode, tff, 5, 0, 3)
-                want_segs = np.concatenate([deint_frames(frames[:3], w, h, c, mode, tff),
-                                            deint_frames(frames[3:], w, h, c, mode, tff)])
-                ok = [(one == want).all(), (halo == want).all(), (segs == want_segs).all()]
+                ok = [(one == want).all(), (halo == want).all()]
+                for split in SPLITS:      # each segment is a sequence of its own
+                    segs = run(frames, w, h, c, mode, tff, 5, 0, split)
+                    cuts = np.cumsum((0,) + split)
+                    want_segs = np.concatenate([deint_frames(frames[a:b], w, h, c, mode, tff) for a, b in zip(cuts, cuts[1:])])
+                    ok.append((segs == want_segs).all())
                 print(f"{w}x{h} {c} {'tff' if tff else 'bff'} mode {mode}: one submit {ok[0]}, halo 2+2+1 {ok[1]}, "
-                      f"segments 3+2 {ok[2]}")
+                      + ", ".join(f"segments {'+'.join(map(str, sp))} {o}" for sp, o in zip(SPLITS, ok[2:])))
                 bad += ok.count(False)
     if "--keep" not in sys.argv:
         for f in os.listdir(tmp):
