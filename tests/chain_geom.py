@@ -13,6 +13,9 @@ shape reaches the path it means to check.
   - deint_span / sharp_cells: the workgroups, pieces and head / tail bytes k_yadif_plane takes for a
     plane, and the tiles, `pic` masks and short quads of k_unsharp_plane's launch, for
     tests/test_gpu_filter_chain.py; filter_sweep_configs and its family: that file's seeded sweep;
+  - plane_launches / merged_frames: the launches submit_impl makes per plane stage for a launch of
+    n frames (U and V apart past 2 n <= 65535) and the frames a merged launch may carry;
+    LONG_CASES and its family: the shapes of tests/test_gpu_long_submit.py;
   - predict_paths: what mjg_debug_encode_path and mjg_debug_scale_path will report for an
     orient / crop / -pix_fmt / scale / pad configuration (the rules of plan_geometry and
     plan_plane_scale; the filters come from the library's own device-free mjg_sws_filter).
@@ -726,3 +729,128 @@ FILTER_SWEEP_FLOORS = [dict(zip(FILTER_FEATURES, v)) for v in (
     (3, 5, 6, 8, 8, 3, 3, 9, 6, 1, 2, 1, 2, 12, 4, 5, 2, 10, 4, 3, 4, 8, 5, 8, 9, 8, 14, 8, 7, 1, 10, 14, 6),
     (4, 5, 5, 6, 10, 4, 3, 8, 6, 1, 5, 2, 2, 13, 1, 3, 3, 15, 1, 3, 1, 6, 3, 4, 6, 6, 11, 9, 9, 1, 9, 14, 7),
 )]
+
+
+# ------------------------------------------------------------------ the plane stages' launches of a long submit
+def _uv_limit():
+    """The largest grid z submit_impl gives a plane stage: every `uv1 = 2 * n <= LIMIT` of api.hip (the
+    deinterlacer, the orientation, the sws stage with the sharpen) must state the same one."""
+    with open(os.path.join(_CSRC, "api.hip")) as f:
+        found = re.findall(r"const bool uv1 = 2 \* n <= (\d+);", f.read())
+    assert len(found) == 3 and len(set(found)) == 1, found
+    return int(found[0])
+
+
+def _api_const(name):
+    with open(os.path.join(_CSRC, "api.hip")) as f:
+        m = re.search(r"constexpr\s+int\s+" + name + r"\s*=\s*(\d+)\s*;", f.read())
+    assert m, name
+    return int(m.group(1))
+
+
+UV_LIMIT = _uv_limit()
+MAX_BATCH = 65535      # check_config: max_batch in 1..65535
+MAX_SEGS = _const("kernels.hip", "kMaxSegs")
+MERGE = _api_const("kMerge")
+SLOTS = _api_const("kSlots")
+SLOT_WORDS = (64 * _const("kernels.hip", "kMaxBlockBits") + 31) // 32      # kSlotWords: one chunk's scratch / stream words
+LONG = UV_LIMIT // 2 + 1      # the fewest frames of one launch whose V plane gets a launch of its own
+
+
+def plane_launches(n):
+    """[(planes, grid z)] of the launches submit_impl makes per plane stage (deinterlacer, orientation,
+    every pass of the sws stage, sharpen) for a launch of n frames: luma, then U and V together
+    (blockIdx.z >= n is V, through poff) while 2 n fits the grid's z range; past that U alone (poff
+    0, nz = n) and V alone (`p == 2`: the plane offset added on the host)."""
+    if 2 * n <= UV_LIMIT:
+        return [("Y", n), ("UV", 2 * n)]
+    return [("Y", n), ("U", n), ("V", n)]
+
+
+def merged_frames(max_batch, merge=True, deint=False, nseg=1, nchunks=1, per_frame_bytes=0, free_bytes=None):
+    """The frames one launch may carry (open_device: slot_B = max_batch * merge) on a context opened
+    with max_batch and MJG_F_MERGE (`merge`), capped as open caps it: kMerge jobs a launch (at most
+    kMaxSegs; MJG_MERGE unset), none with a deinterlacer, none when kSlots slots of merge x max_batch
+    frames of per_frame_bytes would take more than a quarter of free_bytes (given: the device's
+    free memory; None: not tested), none when max_batch merge nseg nchunks^2 reaches 2^40
+    (k_encode's task magic)."""
+    assert 1 <= max_batch <= MAX_BATCH
+    m = max(1, min(MAX_SEGS, MERGE)) if merge else 1
+    if deint:
+        m = 1
+    if m > 1 and free_bytes is not None and SLOTS * m * max_batch * per_frame_bytes > 0.25 * free_bytes:
+        m = 1
+    if max_batch * m * nseg * nchunks * nchunks >= 1 << 40:
+        m = 1
+    return m * max_batch
+
+
+def slot_frame_bytes(nchunks, nseg, enc_frame_bytes, in_frame_bytes=0, orient=False, sharp=False):
+    """open_device's per_frame: scratch and stream words of a frame's chunks, the scaled frame twice
+    (d_scaled, d_out's share), the oriented and the sharpened frame where those stages run."""
+    return (2 * nchunks * nseg * SLOT_WORDS * 4 + 2 * enc_frame_bytes + (in_frame_bytes if orient else 0)
+            + (enc_frame_bytes if sharp else 0))
+
+
+LONG_K = 61      # distinct base frames of tests/test_gpu_long_submit.py: prime, so no period lines up with 64, 256 or a grid
+
+
+def long_frame_index(n):
+    """Base frame of every frame of a long submit: frame i is base[(7 i + i // 1000) % 61]."""
+    import numpy as np
+    i = np.arange(n, dtype=np.int64)
+    return ((i * 7 + i // 1000) % LONG_K).astype(np.int64)
+
+
+LongCase = namedtuple("LongCase", "w h src dst rect dw dh pad full orient deint unsharp kw stream")
+
+
+def _lc(w, h, src="420", dst=None, rect=None, dw=None, dh=None, pad=None, full=False, orient=0, deint=None, unsharp=None,
+        kw=None, stream=False):
+    return LongCase(w, h, src, dst or src, rect, dw, dh, pad, full, orient, deint, unsharp, kw or {}, stream)
+
+
+# The configurations of tests/test_gpu_long_submit.py: per plane stage the smallest frames on which it
+# exists (w x h source frames; the rectangle, the size and the pad refer to the oriented frame; deint
+# out of DEINTS; stream: MJG_SCALE_STREAM=1).  The pads sit at (4, 6): py >> 1 = 3, so the V launch's
+# d_off is no plane start.  tests/test_chain_geom.py pins the paths of each.
+LONG_CASES = {
+    "in_place": _lc(8, 8),
+    "optimal": _lc(8, 8, kw={"huffman": "optimal"}),
+    "rst": _lc(8, 32, kw={"rst": True}),
+    "scale_tv": _lc(16, 16, dw=8, dh=8),
+    "scale_pc": _lc(16, 16, dw=8, dh=8, full=True),
+    "scale_up_444": _lc(8, 8, "444", dw=12, dh=12),
+    "scale_stream": _lc(16, 16, dw=8, dh=8, stream=True),
+    "pix_fmt_copy": _lc(8, 8, "444", "420"),
+    "rect_copy": _lc(16, 8, "444", "420", rect=(4, 0, 8, 8)),
+    "pad_copy": _lc(8, 8, pad=(4, 6, 16, 16)),
+    "pad_scale": _lc(16, 16, dw=8, dh=8, pad=(4, 6, 16, 16)),
+    "hflip": _lc(24, 8, orient=2),
+    "transpose": _lc(24, 8, orient=1),
+    "yadif": _lc(8, 8, deint="tff"),
+    "yadif_nospatial": _lc(8, 8, deint="tff_nospatial"),
+    "unsharp55": _lc(8, 8, full=True, unsharp=SHARPS[2]),
+    "unsharp_chroma": _lc(8, 8, full=True, unsharp=SHARPS[5]),
+    "chain": _lc(24, 16, deint="tff", orient=1, rect=(2, 2, 12, 20), dw=8, dh=12, unsharp=SHARPS[2], pad=(4, 6, 16, 24)),
+    "scale_sharp": _lc(16, 16, dw=8, dh=8, unsharp=SHARPS[2]),
+}
+
+
+def long_predict(c):
+    """(encode_path, (luma, chroma) scale_path, RECT) of a LongCase: predict_paths from its source
+    size; a sharpen always runs the sws stage (filter_predict)."""
+    enc_path, paths, rect_form = predict_paths(c.w, c.h, c.src, c.rect, c.dst, c.dw, c.dh, c.pad, orient=c.orient)
+    if c.unsharp is not None and enc_path & IN_PLACE:
+        assert paths == (NONE, NONE)
+        ow = c.h if c.orient & 1 else c.w
+        return 0, (COPY, COPY), c.rect is not None and c.rect[2] != ow
+    return enc_path, paths, rect_form
+
+
+def long_plane_sizes(c):
+    """((source w, h), (encoded w, h)) of the luma and of a chroma plane of the sws stage of a LongCase."""
+    ow, oh = (c.h, c.w) if c.orient & 1 else (c.w, c.h)
+    rw, rh = c.rect[2:] if c.rect else (ow, oh)
+    dw, dh = c.dw or rw, c.dh or rh
+    return (((rw, rh), (dw, dh)), (chroma_size(rw, rh, c.src), chroma_size(dw, dh, c.dst)))

@@ -559,3 +559,97 @@ def test_filter_sweep_draw_and_its_floors():
                      "sharp_from_pad_with_scale": 23, "sharp_three_tile_columns": 14, "sharp_copy_tile_beside_filter": 20,
                      "sharp_left_partial_mask": 23, "sharp_right_partial_mask": 21, "host": 43, "dev_odd": 36, "segments": 36,
                      "merged": 5, "default": 35, "optimal": 50, "rst": 35}
+
+
+# ------------------------------------------------------------------ long submits: V in a launch of its own
+def test_plane_launches_at_the_grid_limit():
+    """submit_impl's launches per plane stage, by hand: U and V share a grid while 2 n <= 65535
+    (n <= 32767); from 32768 frames on U and V get a launch each, of n in z."""
+    assert (cg.UV_LIMIT, cg.LONG, cg.MAX_BATCH) == (65535, 32768, 65535)
+    assert cg.plane_launches(1) == [("Y", 1), ("UV", 2)]
+    assert cg.plane_launches(32767) == [("Y", 32767), ("UV", 65534)]
+    assert cg.plane_launches(32768) == [("Y", 32768), ("U", 32768), ("V", 32768)]
+    assert cg.plane_launches(65535) == [("Y", 65535), ("U", 65535), ("V", 65535)]
+    assert cg.plane_launches(39999) == [("Y", 39999), ("U", 39999), ("V", 39999)]
+    assert all(nz <= cg.UV_LIMIT for n in (1, 32767, 32768, 39999, 65535) for _, nz in cg.plane_launches(n))
+
+
+def test_merged_frames_is_capped_as_open_caps_it():
+    """slot_B = max_batch * merge: two jobs a launch (kMerge = 2 of kMaxSegs = 4), so two submits
+    below the limit make one launch above it; never with a deinterlacer, without MJG_F_MERGE, past a
+    quarter of free memory or where k_encode's task magic would overflow."""
+    assert (cg.MERGE, cg.MAX_SEGS, cg.SLOTS, cg.SLOT_WORDS) == (2, 4, 2, 3328)
+    assert cg.merged_frames(20000) == 40000 and len(cg.plane_launches(20000)) == 2 and len(cg.plane_launches(39999)) == 3
+    assert cg.merged_frames(20000, merge=False) == 20000
+    assert cg.merged_frames(20000, deint=True) == 20000
+    assert cg.merged_frames(65535) == 131070
+    assert cg.merged_frames(65535, nseg=2, nchunks=2048) == 131070       # 65535 * 2 * 2 * 2048^2 = 2^40 - 2^24
+    assert cg.merged_frames(65535, nseg=2, nchunks=2049) == 65535
+    # the 16 x 16 -> 8 x 8 4:2:0 context with a sharpen: one chunk a frame, 96-byte encoded frames
+    per = cg.slot_frame_bytes(1, 1, 96, 384, sharp=True)
+    assert per == 2 * 3328 * 4 + 3 * 96
+    assert cg.merged_frames(20000, per_frame_bytes=per, free_bytes=16 << 30) == 40000      # 2.2 GB of 4 GB
+    assert cg.merged_frames(20000, per_frame_bytes=per, free_bytes=8 << 30) == 20000
+
+
+def test_long_frame_index_tells_the_frames_at_the_limit_apart():
+    """Frame i of a long submit is base (7 i + i // 1000) % 61: frames 0, 32767, 32768 and the last
+    frame are four different base frames at every frame count the GPU file uses, neighbours always
+    differ, and all 61 occur on both sides of frame 32768."""
+    assert cg.LONG_K == 61
+    idx = cg.long_frame_index(65535)
+    assert [int(idx[i]) for i in (0, 1, 999, 1000, 32767, 32768)] == [0, 7, 39, 47, 41, 48]      # 7001 = 114 * 61 + 47
+    for n in (32770, 38000, 39999, 65535):
+        assert len({int(idx[i]) for i in (0, 32767, 32768, n - 1)}) == 4, n
+    assert int(idx[0]) != int(idx[32766]) != int(idx[32767])       # the n = 32768 and 32767 submits' ends
+    assert (idx[1:] != idx[:-1]).all() and (idx[2:] != idx[:-2]).all()
+    assert set(idx[:32768].tolist()) == set(idx[32768:39999].tolist()) == set(range(61))
+
+
+LONG_PATHS = {
+    "in_place": (IN_PLACE, (NONE, NONE)), "optimal": (IN_PLACE, (NONE, NONE)), "rst": (IN_PLACE, (NONE, NONE)),
+    "scale_tv": (0, (TILE, TILE)), "scale_pc": (0, (TILE, TILE)), "scale_up_444": (0, (TILE, TILE)),
+    "scale_stream": (0, (TILE, TILE)),      # (without MJG_SCALE_STREAM; with it both planes stream)
+    "pix_fmt_copy": (0, (COPY, TILE)), "rect_copy": (0, (COPY, TILE)),
+    "pad_copy": (0, (PADCOPY, PADCOPY)), "pad_scale": (0, (TILE, TILE)),
+    "hflip": (IN_PLACE, (NONE, NONE)), "transpose": (IN_PLACE, (NONE, NONE)),
+    "yadif": (IN_PLACE, (NONE, NONE)), "yadif_nospatial": (IN_PLACE, (NONE, NONE)),
+    "unsharp55": (0, (COPY, COPY)), "unsharp_chroma": (0, (COPY, COPY)),
+    "chain": (0, (TILE, TILE)), "scale_sharp": (0, (TILE, TILE)),
+}
+
+
+def test_long_cases_reach_the_paths_they_are_listed_for():
+    """The shapes of tests/test_gpu_long_submit.py, each the smallest on which its stage exists: the
+    kernel family of either plane, the three tile instantiations, the stream form, the rectangle
+    form of the copy, both forms of the pad with a V offset that is no plane start, the
+    deinterlacer's 3 x 3 floor, and the sharpen's two cells."""
+    assert set(cg.LONG_CASES) == set(LONG_PATHS)
+    for name, c in cg.LONG_CASES.items():
+        enc_path, paths, rect_form = cg.long_predict(c)
+        assert (enc_path, paths) == LONG_PATHS[name], name
+        assert rect_form == (name == "rect_copy"), name
+        if c.pad:
+            assert c.pad[1] >> 1 != 0 and c.pad[0] >> 1 != 0
+        if c.deint:
+            assert min(chroma_size(c.w, c.h, c.src)) > 3
+    variants = {n: [cg.scale_variant(*s, *d, force_stream=c.stream) for s, d in cg.long_plane_sizes(c)]
+                for n, c in cg.LONG_CASES.items() if not cg.long_predict(c)[0] & IN_PLACE}
+    assert variants["scale_tv"] == variants["scale_pc"] == variants["pad_scale"] == variants["scale_sharp"] \
+        == [("tile", (8, 5, 64), True), ("tile", (0, 0, 32), True)]
+    assert variants["scale_up_444"] == [("tile", (4, 3, 32), False)] * 2
+    assert variants["scale_stream"] == [("stream", True, True)] * 2
+    assert variants["pix_fmt_copy"] == variants["rect_copy"] == [("copy",), ("tile", (0, 0, 32), True)]
+    assert variants["pad_copy"] == variants["unsharp55"] == variants["unsharp_chroma"] == [("copy",), ("copy",)]
+    assert variants["chain"] == [("tile", (8, 5, 32), True), ("tile", (0, 0, 32), True)]
+    assert cg.LONG_CASES["hflip"].orient == 2 and cg.orient_cells(2)[:2] == (False, True)
+    assert cg.LONG_CASES["transpose"].orient == 1 and cg.orient_cells(1)[0] is True
+    assert chroma_size(24, 8, "420") == (12, 4)
+    # the sharpen's cells: <5, 5> filtering every plane; 5:5 at amount 0 copying the luma, 3:5 on U and V
+    for name, want in (("unsharp55", (1, 1)), ("unsharp_chroma", (0, 1))):
+        us = cg.LONG_CASES[name].unsharp
+        luma, chroma = (cg.sharp_cells(*g) for g in cg.sharp_plane_geoms(8, 8, "420", 0, 0, 8, 8, us))
+        assert (luma.filt, luma.copy, chroma.filt, chroma.copy) == (want[0], 1 - want[0], want[1], 1 - want[1]), name
+    assert cg.LONG_CASES["unsharp55"].unsharp[:2] == cg.LONG_CASES["unsharp55"].unsharp[3:5] == (5, 5)
+    assert cg.LONG_CASES["unsharp_chroma"].unsharp == (5, 5, 0.0, 3, 5, 0.7)
+    assert cg.enc_geom(8, 32, "420", True).nseg == 2 and cg.enc_geom(8, 32, "420", True, cg.LONG).ntasks == 65536

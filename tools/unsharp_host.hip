@@ -8,7 +8,8 @@
 // -fsanitize=address,undefined), which compares the output with tests/unsharp_ref.py; makes no HIP call.
 //   unsharp_host IN OUT PW PH hshift vshift PX PY W H lx ly la cx cy ca nframes split
 // IN: nframes frames of the encoded size PW x PH (the canvas under a pad; else PX = PY = 0, W x H = PW x PH), packed
-// planar, the W x H picture at (PX, PY); la / ca are the filter's integers; split: U and V in a launch each.
+// planar, the W x H picture at (PX, PY); la / ca are the filter's integers; split: U and V in a launch each (poff 0, V's
+// off advanced by the chroma plane, nz = nframes), as always past 32,767 frames.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -86,7 +87,7 @@ int main(int argc, char **argv) {
   for (int i = 0; i < 16; i++) a[i] = atoi(argv[3 + i]);
   const int PW = a[0], PH = a[1], hs = a[2], vs = a[3], PX = a[4], PY = a[5], W = a[6], H = a[7];
   const int us[6] = {a[8], a[9], a[10], a[11], a[12], a[13]};
-  const int n = a[14], split = a[15];
+  const int n = a[14], split = a[15] || 2 * n > 65535;  // past 32,767 frames submit_impl launches U and V apart
   const int cw = (PW + hs) >> hs, ch = (PH + vs) >> vs;
   const size_t fb = (size_t)PW * PH + 2 * (size_t)cw * ch;
   uint8_t *src = (uint8_t *)malloc(n * fb), *dst = (uint8_t *)malloc(n * fb);

@@ -7,9 +7,12 @@ one each.  The program itself asserts that every staged load lies inside the pic
 that every byte of every plane is stored exactly once, on buffers allocated at exactly the frames'
 size; this script compares its output with tests/unsharp_ref.py.  --sweep walks instead the encoded
 geometry of every sharpened configuration of the seeded sweep (tests/chain_geom.py
-filter_sweep_configs, tests/test_gpu_filter_chain.py).  No GPU.
+filter_sweep_configs, tests/test_gpu_filter_chain.py).  --long walks the sharpened geometries of
+tests/test_gpu_long_submit.py at 32,770 frames, where U and V get a launch each (poff 0, V's off
+advanced by the chroma plane, frame indices 32,767 and 32,768); the frames cycle through 61 pictures
+as in that file.  No GPU.
 
-usage: python3 tools/unsharp_host_check.py [--keep] [--sweep]"""
+usage: python3 tools/unsharp_host_check.py [--keep] [--sweep | --long]"""
 import os
 import subprocess
 import sys
@@ -45,6 +48,40 @@ def main():
         import chain_geom as cg
         cfgs = cg.filter_sweep_configs(cg.FILTER_SWEEP_SEED, 120)
         geoms = [(*cg.encoded_geometry(k)[:2], k.dst, *cg.encoded_geometry(k)[2:], k.unsharp) for k in cfgs if k.unsharp]
+    if "--long" in sys.argv:
+        import chain_geom as cg
+        geoms = []
+        for name in ("unsharp55", "unsharp_chroma", "chain"):      # (scale_sharp encodes unsharp55's geometry)
+            k = cg.LONG_CASES[name]
+            ow, oh = (k.h, k.w) if k.orient & 1 else (k.w, k.h)
+            pw, ph = k.dw or (k.rect[2] if k.rect else ow), k.dh or (k.rect[3] if k.rect else oh)
+            geoms.append((k.pad[2], k.pad[3], k.dst, k.pad[0], k.pad[1], pw, ph, k.unsharp) if k.pad
+                         else (pw, ph, k.dst, 0, 0, pw, ph, k.unsharp))
+        n = cg.LONG + 2
+        assert len(cg.plane_launches(n)) == 3
+        idx = cg.long_frame_index(n)
+        for (PW, PH, c, px, py, w, h, us) in geoms:
+            hs, vs = SHIFTS[c]
+            cw, ch = chroma_size(w, h, c)
+            pics = [[rng.integers(0, 256, (hh, ww), dtype=np.uint8) for ww, hh in ((w, h), (cw, ch), (cw, ch))]
+                    for _ in range(cg.LONG_K)]
+            padded = (px, py, w, h) != (0, 0, PW, PH)
+            place = (lambda pl: pad_planes(*pl, c, px, py, PW, PH)) if padded else (lambda pl: pl)
+            src = np.stack([pack_i420(*place(pl)) for pl in pics])[idx]
+            want = np.stack([pack_i420(*place(unsharp_planes(*pl, us))) for pl in pics])[idx]
+            ints = (us[0], us[1], amount_i(us[2]), us[3], us[4], amount_i(us[5]))
+            fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
+            src.tofile(fin)
+            r = subprocess.run([exe, fin, fout] + [str(v) for v in (PW, PH, hs, vs, px, py, w, h, *ints, n, 0)],
+                               capture_output=True, text=True)
+            if r.returncode:
+                sys.exit(f"unsharp_host failed ({r.returncode}) at {PW}x{PH} {c} picture {w}x{h}+{px}+{py} {us} {n} frames:\n"
+                         + r.stderr[-4000:])
+            ok = bool((np.fromfile(fout, np.uint8).reshape(n, -1) == want).all())
+            print(f"{PW}x{PH} {c} picture {w}x{h}+{px}+{py} unsharp {':'.join(str(v) for v in us)} {n} frames, U, V apart: "
+                  f"equal {ok}; {r.stdout.strip()}")
+            bad += not ok
+        geoms = []
     for (PW, PH, c, px, py, w, h, us) in geoms:
         hs, vs = SHIFTS[c]
         cw, ch = chroma_size(w, h, c)

@@ -2,9 +2,11 @@
 // the luma and the U + V launch of one submit, on source and destination buffers allocated at exactly
 // their sizes, so that AddressSanitizer sees any access outside a readable frame.  Built and driven by
 // tools/yadif_host_check.py (hipcc -Xarch_host -fsanitize=address,undefined); makes no HIP call.
-//   yadif_host IN OUT w h hshift vshift nospatial parity nframes halo split
+//   yadif_host IN OUT w h hshift vshift nospatial parity nframes halo split [apart]
 // IN: nframes + halo frames, packed planar; split: 0, or the lengths of up to kMaxSegs segments as a,b,...
 // (their sum nframes, no halo): each segment in an allocation of its own (mjg_submit_segments' SegList).
+// apart: 1, U and V in a launch each whatever nframes is (submit_impl's `p == 2`: poff 0, off advanced by the
+// chroma plane, nz = nframes); without it they are apart from 32,768 frames on, as submit_impl launches them.
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
@@ -31,6 +33,7 @@ int main(int argc, char **argv) {
   const int nsegs = (int)lens.size();
   if (nsegs > kMaxSegs || (nsegs && halo)) return 2;
   const int hp = halo & 1, hn = (halo >> 1) & 1;
+  const bool uv1 = 2 * n <= 65535 && !(argc > 12 && atoi(argv[12]));  // U and V in one launch
   const int cw = (w + hs) >> hs, ch = (h + vs) >> vs;
   const size_t fb = (size_t)w * h + 2 * (size_t)cw * ch;
   const size_t tot = (size_t)(n + hp + hn) * fb;
@@ -56,7 +59,7 @@ int main(int argc, char **argv) {
   fclose(f);
   // destination at an odd alignment inside an exact allocation: d + 1
   uint8_t *dbase = (uint8_t *)malloc(n * fb);
-  for (int p = 0; p < 2; p++) {
+  for (int p = 0; p < (uv1 ? 2 : 3); p++) {
     DeintGeom g{};
     g.w = p ? cw : w;
     g.h = p ? ch : h;
@@ -73,8 +76,9 @@ int main(int argc, char **argv) {
       g.lo[k] = -hp;
       g.hi[k] = sl.f0[k] == INT_MAX ? 0 : end - sl.f0[k] - 1 + hn;
     }
-    if (p) g.poff = (long long)cw * ch;
-    const int nz = p ? 2 * n : n;
+    if (p && uv1) g.poff = (long long)cw * ch;
+    if (p == 2) g.off += (long long)cw * ch;
+    const int nz = p && uv1 ? 2 * n : n;
     for (int t = 0; t < g.gxy * nz; t++)
       for (int tid = 0; tid < kDeintThreads; tid++) {
         if (nosp) yadif_work<true>(sl, dbase, g, t, tid);

@@ -9,9 +9,13 @@ tests/test_gpu_filter_chain.py; the shapes of the latter's cases are in the list
 exactly their sizes, so a load or store outside a readable frame stops the program.  --sweep walks
 instead every deinterlaced configuration of the seeded sweep (tests/chain_geom.py
 filter_sweep_configs): its source shape, mode and parity, three frames in one submit and as
-segments of 2 + 1.  No GPU.
+segments of 2 + 1.  --long walks the deinterlaced shapes of tests/test_gpu_long_submit.py past 32,767
+frames, where U and V get a launch each (poff 0, off advanced by the chroma plane, frame indices
+32,767 and 32,768): one submit of 32,770 frames, a halo submit of 32,770 out of 32,772, and four
+segments of 38,000 with a boundary at frame 32,767; the frames cycle through 61 base frames as in
+that file, so the reference is made once per distinct (prev, cur, next).  No GPU.
 
-usage: python3 tools/yadif_host_check.py [--keep] [--sweep]"""
+usage: python3 tools/yadif_host_check.py [--keep] [--sweep | --long]"""
 import os
 import subprocess
 import sys
@@ -22,7 +26,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from yadif_ref import deint_frames  # noqa: E402
+from yadif_ref import deint_frame, deint_frames  # noqa: E402
 from ffmpeg_distributed_amd.encoder import i420_frame_bytes  # noqa: E402
 
 SHIFTS = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}
@@ -41,12 +45,13 @@ def main():
                     "-I", os.path.join(ROOT, "ffmpeg_distributed_amd", "csrc"), "-o", exe,
                     os.path.join(ROOT, "tools", "yadif_host.hip")], check=True)
 
-    def run(frames, w, h, c, mode, tff, n, halo, split):
+    def run(frames, w, h, c, mode, tff, n, halo, split, apart=0):
         hs, vs = SHIFTS[c]
         fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
         frames.tofile(fin)
         r = subprocess.run([exe, fin, fout, str(w), str(h), str(hs), str(vs), str(1 if mode == 2 else 0), str(tff ^ 1),
-                            str(n), str(halo), ",".join(str(v) for v in split) if split else "0"], capture_output=True, text=True)
+                            str(n), str(halo), ",".join(str(v) for v in split) if split else "0", str(apart)],
+                           capture_output=True, text=True)
         if r.returncode:
             sys.exit(f"yadif_host failed ({r.returncode}) at {w}x{h} {c} mode {mode} tff {tff} halo {halo} split {split}:\n"
                      + r.stderr[-4000:])
@@ -54,6 +59,40 @@ def main():
 
     rng = np.random.default_rng(5)
     bad = 0
+    if "--long" in sys.argv:
+        import chain_geom as cg
+
+        def want_of(base, idx, seqs, w, h, c, mode, tff):      # seqs: (first, count) of each sequence in the buffer
+            made, out = {}, np.empty((len(idx), base.shape[1]), np.uint8)
+            for first, count in seqs:
+                for j in range(first, first + count):
+                    key = (idx[max(j - 1, first)], idx[j], idx[min(j + 1, first + count - 1)])
+                    if key not in made:
+                        made[key] = deint_frame(base[key[0]], base[key[1]], base[key[2]], w, h, c, mode, tff)
+                    out[j] = made[key]
+            return out
+
+        lens = (12345, 20422, 3000, 2233)
+        cuts = np.cumsum((0,) + lens)
+        assert cuts[2] == cg.LONG - 1
+        for name in ("yadif", "chain"):
+            k = cg.LONG_CASES[name]
+            w, h, c = k.w, k.h, k.src
+            base = rng.integers(0, 256, (cg.LONG_K, i420_frame_bytes(w, h, c)), dtype=np.uint8)
+            n = cg.LONG + 2
+            assert len(cg.plane_launches(n)) == 3
+            idx = cg.long_frame_index(sum(lens)).tolist()
+            one = run(base[idx[:n]], w, h, c, 0, 1, n, 0, 0)
+            ok = [(one == want_of(base, idx[:n], [(0, n)], w, h, c, 0, 1)).all()]
+            halo = run(base[idx[:n + 2]], w, h, c, 2, 1, n, 3, 0)
+            ok.append((halo == want_of(base, idx[:n + 2], [(0, n + 2)], w, h, c, 2, 1)[1:n + 1]).all())
+            segs = run(base[idx], w, h, c, 0, 1, sum(lens), 0, lens)
+            ok.append((segs == want_of(base, idx, [(int(a), int(b - a)) for a, b in zip(cuts, cuts[1:])], w, h, c, 0, 1)).all())
+            few = run(base[idx[:5]], w, h, c, 0, 0, 5, 0, 0, apart=1)      # five frames, U and V apart all the same
+            ok.append((few == deint_frames(base[idx[:5]], w, h, c, 0, 0)).all())
+            print(f"{w}x{h} {c} U, V apart: one submit of {n} (mode 0 tff) {ok[0]}, halo 3 of {n} out of {n + 2} (mode 2 tff) {ok[1]}, "
+                  f"segments {'+'.join(map(str, lens))} {ok[2]}, 5 frames bff forced apart {ok[3]}")
+            bad += ok.count(False)
     if "--sweep" in sys.argv:
         import chain_geom as cg
         seen = set()
@@ -71,7 +110,7 @@ def main():
             ok = [(one == deint_frames(frames, w, h, c, mode, tff)).all(), (segs == want_segs).all()]
             print(f"{w}x{h} {c} {k.deint}: one submit {ok[0]}, segments 2+1 {ok[1]}")
             bad += ok.count(False)
-    for (w, h, c) in ([] if "--sweep" in sys.argv else SHAPES):
+    for (w, h, c) in ([] if "--sweep" in sys.argv or "--long" in sys.argv else SHAPES):
         fb = i420_frame_bytes(w, h, c)
         frames = rng.integers(0, 256, (5, fb), dtype=np.uint8)
         frames[3] = (np.arange(fb) * 3 % 256).astype(np.uint8)
