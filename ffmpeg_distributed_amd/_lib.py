@@ -45,6 +45,7 @@ EXPORTS = (
     "mjg_debug_encode_path", "mjg_debug_oriented", "mjg_debug_orient",
     "mjg_open_deint", "mjg_submit_halo", "mjg_debug_deint", "mjg_debug_deint_flags",
     "mjg_open_sharp", "mjg_debug_presharp", "mjg_debug_unsharp",
+    "mjg_open_lut", "mjg_debug_lut", "mjg_debug_lut_in",
 )
 
 # mjg_open_deint's `deint`
@@ -74,6 +75,11 @@ class MjgUnsharp(C.Structure):
     """mjg_unsharp: -vf unsharp's sizes and amounts, the amounts as int(amount * 65536.0)."""
     _fields_ = [("lx", C.c_int32), ("ly", C.c_int32), ("la", C.c_int32),
                 ("cx", C.c_int32), ("cy", C.c_int32), ("ca", C.c_int32)]
+
+
+class MjgLut(C.Structure):
+    """mjg_lut: a 256-entry table per plane, out = t[in]."""
+    _fields_ = [("y", C.c_uint8 * 256), ("u", C.c_uint8 * 256), ("v", C.c_uint8 * 256)]
 
 
 _lib = None
@@ -123,6 +129,13 @@ def load():
             L.mjg_debug_presharp.restype = C.c_int
             L.mjg_debug_unsharp.argtypes = [vp, C.POINTER(MjgUnsharp)]
             L.mjg_debug_unsharp.restype = C.c_int
+        if hasattr(L, "mjg_open_lut"):  # absent from libraries built before the table stage (A/B builds)
+            L.mjg_open_lut.argtypes = ([C.c_int, C.POINTER(MjgConfig)] + [C.c_int] * 7 + [C.POINTER(MjgLut)] * 2
+                                       + [C.POINTER(MjgUnsharp)] + [C.c_int] * 4 + [C.POINTER(vp)])
+            L.mjg_debug_lut.argtypes = [vp, C.c_int, C.POINTER(MjgLut)]
+            L.mjg_debug_lut.restype = C.c_int
+            L.mjg_debug_lut_in.argtypes = [vp, C.c_int, u8p, sz]
+            L.mjg_debug_lut_in.restype = C.c_int
         L.mjg_close.argtypes = [vp]
         L.mjg_close.restype = None
         L.mjg_frame_bytes.argtypes = [vp]
@@ -170,7 +183,8 @@ def load():
                  "mjg_debug_huff_build", "mjg_open_src", "mjg_open_crop", "mjg_open_pad", "mjg_debug_scale_path",
                  "mjg_debug_encode_path", "mjg_open_orient", "mjg_debug_oriented", "mjg_debug_orient",
                  "mjg_open_deint", "mjg_submit_halo", "mjg_debug_deint", "mjg_debug_deint_flags",
-                 "mjg_open_sharp", "mjg_debug_presharp", "mjg_debug_unsharp")
+                 "mjg_open_sharp", "mjg_debug_presharp", "mjg_debug_unsharp",
+                 "mjg_open_lut", "mjg_debug_lut", "mjg_debug_lut_in")
                 if os.environ.get("MJG_LIBRARY") else ())
         for name in EXPORTS:
             if name not in late:

@@ -276,6 +276,7 @@ struct Slot {
   uint8_t *d_orient = nullptr;     // -vf hflip / vflip / transpose: k_orient_plane's output frames
   uint8_t *d_deint = nullptr;      // -vf yadif: k_yadif_plane's output frames
   uint8_t *d_sharp = nullptr;      // -vf unsharp: k_unsharp_plane's output, the encoder's input
+  uint8_t *d_lut = nullptr;        // a table in front of the sws stage on a caller's frames: k_lut_plane's output frames
   uint32_t *d_stage_bits = nullptr;  // k_encode: per wave, lane-major staging of blocks past 128 bits
   int n = 0;  // frames of the launch
   uint32_t *d_scratch = nullptr;
@@ -326,6 +327,14 @@ struct mjg_ctx {
   bool sharp = false;
   mjg_unsharp us{};
   SharpPass shpass[2];          // its launches: 0 luma, 1 chroma
+  // the tables (mjg_open_lut): [0] slot "in", behind the deinterlacer and the orientation, on whole
+  // frames in the source format (in place in d_deint / d_orient, else into the slot's d_lut, which
+  // the sws stage or k_encode then reads); [1] slot "out", in place on the picture in d_scaled
+  // (the sws stage then always runs), in front of the sharpen.  Identity tables are no table
+  bool has_lut[2] = {false, false};
+  mjg_lut lut[2];
+  LutGeom lpass[2][2];          // their launches: [slot][0 luma, 1 chroma]
+  uint8_t *d_luts = nullptr;    // both slots' tables, 768 bytes each
   size_t in_frame_bytes = 0, enc_frame_bytes = 0;
   // the crop rectangle (mjg_open_crop; the whole frame otherwise): the input of the sws stage,
   // or of k_encode without one
@@ -382,13 +391,13 @@ void free_ctx(mjg_ctx *c) {
   for (hipStream_t st : c->more)
     if (st) (void)hipStreamSynchronize(st);
   if (c->tail) (void)hipStreamSynchronize(c->tail);
-  void *ptrs[] = {c->d_tabs, c->d_hdr, c->ps[0].hcp,
+  void *ptrs[] = {c->d_tabs, c->d_hdr, c->d_luts, c->ps[0].hcp,
                   c->ps[0].vcp, c->ps[0].hp, c->ps[0].vps, c->ps[1].hcp, c->ps[1].vcp, c->ps[1].hp,
                   c->ps[0].hsum, c->ps[1].hsum, c->ps[1].vps, c->ps[0].mfb, c->ps[1].mfb};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (Slot &S : c->slot) {
-    void *sp[] = {S.d_stage, S.d_scaled, S.d_orient, S.d_deint, S.d_sharp, S.d_stage_bits, S.d_scratch, S.d_stream, S.d_work, S.d_chunk_bits, S.d_chunk_off, S.d_group_ff, S.d_ff_off, S.d_frame_bits,
+    void *sp[] = {S.d_stage, S.d_scaled, S.d_orient, S.d_deint, S.d_sharp, S.d_lut, S.d_stage_bits, S.d_scratch, S.d_stream, S.d_work, S.d_chunk_bits, S.d_chunk_off, S.d_group_ff, S.d_ff_off, S.d_frame_bits,
                   S.d_status, S.d_frame_size, S.d_frame_offsets, S.d_seg_size, S.d_seg_off, S.d_done, S.d_out,
                   S.d_hist, S.d_ftabs, S.d_dht_nval, S.d_hdr_lens, S.d_dht, S.d_dbg, S.d_syms, S.d_symn};
     for (void *p : sp)
@@ -442,6 +451,7 @@ struct Layout {
   int deint;                   // MJG_DEINT_* bits (0: no deinterlacer)
   bool sharp;                  // -vf unsharp with a non-zero amount
   mjg_unsharp us;              // ... its sizes and amounts
+  const mjg_lut *lut[2];       // the tables of slot "in" and slot "out" (null: none, or three identity tables)
   int orient, ow, oh;          // the orientation and the oriented frame's size (orient 0: the source's)
   int cx, cy, crw, crh;        // the crop rectangle in the oriented frame: the sws stage's / k_encode's input
   int px, py, pw, ph;          // the picture's place in the canvas and the canvas size (no pad: the picture)
@@ -657,6 +667,7 @@ int alloc_slot(mjg_ctx *c, Slot &S) {
   if (c->orient && (rc = dmalloc(&S.d_orient, B * c->in_frame_bytes))) return rc;
   if (c->deint && (rc = dmalloc(&S.d_deint, B * c->in_frame_bytes))) return rc;
   if (c->sharp && (rc = dmalloc(&S.d_sharp, B * c->enc_frame_bytes))) return rc;
+  if (c->has_lut[0] && !c->orient && !c->deint && (rc = dmalloc(&S.d_lut, B * c->in_frame_bytes))) return rc;
   if ((rc = dmalloc(&S.d_scratch, B * NC * (size_t)kSlotWords)) ||
       (rc = dmalloc(&S.d_stream, B * NC * (size_t)kSlotWords)) ||
       (rc = dmalloc(&S.d_chunk_bits, B * NC)) || (rc = dmalloc(&S.d_chunk_off, B * NC)) ||
@@ -698,8 +709,9 @@ int alloc_slot(mjg_ctx *c, Slot &S) {
 // pad: x, y, w, h in luma samples of the encoded frame (the picture's place and the canvas size),
 // or nullptr for no pad
 // us: -vf unsharp between the sws stage and the pad, or nullptr (both amounts 0: no filter either)
-int check_config(const mjg_config &k, int src_cf, int deint, int orient, const int *crop, const mjg_unsharp *us,
-                 const int *pad, Layout *lay) {
+// lut_in, lut_out: the tables in front of and behind the sws stage, or nullptr (three identity tables: none either)
+int check_config(const mjg_config &k, int src_cf, int deint, int orient, const int *crop, const mjg_lut *lut_in,
+                 const mjg_lut *lut_out, const mjg_unsharp *us, const int *pad, Layout *lay) {
   if (std::min({k.src_w, k.src_h, k.dst_w, k.dst_h}) < 1 || std::max({k.src_w, k.src_h, k.dst_w, k.dst_h}) > 16384)
     return set_err(MJG_E_INVALID, "bad frame size %dx%d -> %dx%d", k.src_w, k.src_h, k.dst_w, k.dst_h);
   if (k.qscale < 1 || k.qscale > 31) return set_err(MJG_E_INVALID, "qscale %d not in 1..31", k.qscale);
@@ -788,7 +800,13 @@ int check_config(const mjg_config &k, int src_cf, int deint, int orient, const i
                        i ? "chroma" : "luma", sz[2 * i], sz[2 * i + 1], hs, kSharpMaxHalfSum);
     }
   }
-  *lay = Layout{deint, sharp, u, orient, ow, oh, cx, cy, crw, crh, px, py, pw, ph, has_pad, s_hsh, s_vsh, e_hsh, e_vsh};
+  const mjg_lut *luts[2] = {lut_in, lut_out};
+  for (const mjg_lut *&l : luts) {
+    bool id = true;
+    for (int i = 0; l && i < 256; i++) id = id && l->y[i] == i && l->u[i] == i && l->v[i] == i;
+    if (id) l = nullptr;
+  }
+  *lay = Layout{deint, sharp, u, {luts[0], luts[1]}, orient, ow, oh, cx, cy, crw, crh, px, py, pw, ph, has_pad, s_hsh, s_vsh, e_hsh, e_vsh};
   return MJG_OK;
 }
 
@@ -811,7 +829,12 @@ int plan_geometry(const mjg_config &k, int src_cf, const Layout &lay, bool unali
   // (so does a sharpen: k_unsharp_plane reads full-range encoder-input samples from d_scaled)
   c->sharp = lay.sharp;
   c->us = lay.us;
-  c->scale = (crw != k.dst_w || crh != k.dst_h || src_cf != cf || c->has_pad || c->sharp);
+  // (and a table behind it: k_lut_plane maps the picture in d_scaled)
+  for (int i = 0; i < 2; i++) {
+    c->has_lut[i] = lay.lut[i] != nullptr;
+    if (lay.lut[i]) c->lut[i] = *lay.lut[i];
+  }
+  c->scale = (crw != k.dst_w || crh != k.dst_h || src_cf != cf || c->has_pad || c->sharp || c->has_lut[1]);
   const int scw = (fw + s_hsh) >> s_hsh, sch = (fh + s_vsh) >> s_vsh;
   // the rectangle's chroma planes: at (cx >> hs, cy >> vs), the chroma size of a crw x crh frame
   // (inside the source's: cx, cy are multiples of the sub-sampling)
@@ -1149,6 +1172,45 @@ void plan_sharp(const mjg_config &k, const Layout &lay, mjg_ctx *c) {
   }
 }
 
+// The table stages' launches for luma and chroma (mjg_ctx::lpass; no device, no environment).  Slot
+// "in": the whole planes of the frame behind the orientation, source format, frames in_frame_bytes
+// apart on both sides.  Slot "out": the picture's planes in d_scaled, at the canvas stride and the
+// picture's place under a pad, in place.  submit_impl adds nf, the U + V pairing and, for slot
+// "in", whether the stage runs in place.
+void plan_lut(const mjg_config &k, const Layout &lay, mjg_ctx *c) {
+  for (int slot = 0; slot < 2; slot++) {
+    if (!c->has_lut[slot]) continue;
+    const mjg_lut &L = c->lut[slot];
+    int ident = 0;
+    const uint8_t *t[3] = {L.y, L.u, L.v};
+    for (int i = 0; i < 3; i++) {
+      bool id = true;
+      for (int v = 0; v < 256; v++) id = id && t[i][v] == v;
+      ident |= id ? 1 << i : 0;
+    }
+    for (int p = 0; p < 2; p++) {
+      LutGeom &g = c->lpass[slot][p];
+      g = LutGeom{};
+      if (!slot) {
+        const int w = p ? (lay.ow + lay.s_hsh) >> lay.s_hsh : lay.ow, h = p ? (lay.oh + lay.s_vsh) >> lay.s_vsh : lay.oh;
+        lut_geom_rect(g, w, h, w, w);
+        g.s_off = g.d_off = p ? (long long)lay.ow * lay.oh : 0;
+        g.s_fstride = g.d_fstride = (long long)c->in_frame_bytes;
+      } else {
+        const PadGeom &pg = c->pad[p];
+        const int w = p ? (k.dst_w + lay.hsh) >> lay.hsh : k.dst_w, h = p ? (k.dst_h + lay.vsh) >> lay.vsh : k.dst_h;
+        lut_geom_rect(g, w, h, pg.cw, pg.cw);
+        g.s_off = g.d_off = (p ? c->geom.u_off : 0) + (long long)pg.py * pg.cw + pg.px;
+        g.s_fstride = g.d_fstride = (long long)c->enc_frame_bytes;
+      }
+      g.tab = p;
+      g.ident = ident;
+      g.ds_magic = magic32((uint32_t)g.d_stride);
+      g.gxy_magic = magic32((uint32_t)g.gxy);
+    }
+  }
+}
+
 // RC, DBG, UA: EncGeom's range_convert and debug_coefs, and the context's enc_ua (a crop read in
 // place at any alignment, fetch_rows<UA>)
 template <bool RC, int MODE, bool DBG, bool UA>
@@ -1195,7 +1257,8 @@ int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
     HIP_TRY(hipMemGetInfo(&fr, &tot));
     const double per_frame = 2.0 * (double)c->slot_NC * kSlotWords * 4 + 2.0 * (double)c->enc_frame_bytes +
                              (c->orient ? (double)c->in_frame_bytes : 0.0) +  // (a deinterlacer never merges)
-                             (c->sharp ? (double)c->enc_frame_bytes : 0.0);
+                             (c->sharp ? (double)c->enc_frame_bytes : 0.0) +
+                             (c->has_lut[0] && !c->orient ? (double)c->in_frame_bytes : 0.0);
     if (kSlots * (double)c->merge * (double)k.max_batch * per_frame > kMergeMemShare * (double)fr) c->merge = 1;
   }
   if ((unsigned long long)k.max_batch * c->merge * g.nseg * g.nchunks * g.nchunks >= ((unsigned long long)1 << 40))
@@ -1208,6 +1271,10 @@ int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
   c->timing_tail = c->timing && !c->timing_detail && !env_int("MJG_TIMING_NOTAIL", 0);
   HIP_TRY(hipMemcpy(c->d_tabs, tabs, kTabWords * sizeof(uint32_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(c->d_hdr, c->hdr.data(), c->hdr.size(), hipMemcpyHostToDevice));
+  if (c->has_lut[0] || c->has_lut[1]) {
+    if ((rc = dmalloc(&c->d_luts, 2 * sizeof(mjg_lut)))) return rc;
+    HIP_TRY(hipMemcpy(c->d_luts, c->lut, 2 * sizeof(mjg_lut), hipMemcpyHostToDevice));
+  }
 
   if (c->scale) {
     const bool bitexact = !(k.flags & MJG_F_SWS_NO_BITEXACT);
@@ -1242,17 +1309,18 @@ int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
 }
 
 int open_ctx(int device, const mjg_config *cfg, int src_cf, int deint, int orient, const int *crop,
-             const mjg_unsharp *us, const int *pad, mjg_ctx *c) {
+             const mjg_lut *lut_in, const mjg_lut *lut_out, const mjg_unsharp *us, const int *pad, mjg_ctx *c) {
   c->device = device;
   c->cfg = *cfg;
   const mjg_config &k = *cfg;
   Layout lay;
   int rc;
-  if ((rc = check_config(k, src_cf, deint, orient, crop, us, pad, &lay))) return rc;
+  if ((rc = check_config(k, src_cf, deint, orient, crop, lut_in, lut_out, us, pad, &lay))) return rc;
   if ((rc = plan_geometry(k, src_cf, lay, env_int("MJG_UNALIGNED_FETCH", 1) != 0, c))) return rc;
   plan_orient(k, lay, c);
   plan_deint(k, lay, c);
   plan_sharp(k, lay, c);
+  plan_lut(k, lay, c);
   quant_matrix(k.qscale, c->mprime, c->qmat);
   c->hdr = build_header(c->geom.w, c->geom.h, c->mprime, k.sar_num, k.sar_den, (k.flags & MJG_F_COM_ITU601) != 0,
                         k.chroma_format, c->rst, &c->dht_pos, &c->dht_end);
@@ -1323,11 +1391,11 @@ int mjg_device_numa_node(int device) {
 
 namespace {
 int open_any(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, const int *crop,
-             const mjg_unsharp *us, const int *pad, mjg_ctx **out) {
+             const mjg_lut *lut_in, const mjg_lut *lut_out, const mjg_unsharp *us, const int *pad, mjg_ctx **out) {
   if (!cfg || !out) return set_err(MJG_E_INVALID, "null argument");
   *out = nullptr;
   mjg_ctx *c = new mjg_ctx();
-  const int rc = open_ctx(device, cfg, src_chroma_format, deint, orient, crop, us, pad, c);
+  const int rc = open_ctx(device, cfg, src_chroma_format, deint, orient, crop, lut_in, lut_out, us, pad, c);
   if (rc) {
     const std::string keep = g_err;
     free_ctx(c);
@@ -1342,36 +1410,43 @@ int open_any(int device, const mjg_config *cfg, int src_chroma_format, int deint
 int mjg_open_crop(int device, const mjg_config *cfg, int src_chroma_format, int crop_x, int crop_y, int crop_w,
                   int crop_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h};
-  return open_any(device, cfg, src_chroma_format, 0, 0, crop, nullptr, nullptr, out);
+  return open_any(device, cfg, src_chroma_format, 0, 0, crop, nullptr, nullptr, nullptr, nullptr, out);
 }
 
 int mjg_open_orient(int device, const mjg_config *cfg, int src_chroma_format, int orient, int crop_x, int crop_y,
                     int crop_w, int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, 0, orient, crop, nullptr, pad, out);
+  return open_any(device, cfg, src_chroma_format, 0, orient, crop, nullptr, nullptr, nullptr, pad, out);
 }
 
 int mjg_open_deint(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, int crop_x,
                    int crop_y, int crop_w, int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, deint, orient, crop, nullptr, pad, out);
+  return open_any(device, cfg, src_chroma_format, deint, orient, crop, nullptr, nullptr, nullptr, pad, out);
 }
 
 int mjg_open_sharp(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, int crop_x,
                    int crop_y, int crop_w, int crop_h, const mjg_unsharp *us, int pad_x, int pad_y, int pad_w,
                    int pad_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, deint, orient, crop, us, pad, out);
+  return open_any(device, cfg, src_chroma_format, deint, orient, crop, nullptr, nullptr, us, pad, out);
+}
+
+int mjg_open_lut(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, int crop_x,
+                 int crop_y, int crop_w, int crop_h, const mjg_lut *lut_in, const mjg_lut *lut_out,
+                 const mjg_unsharp *us, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
+  const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
+  return open_any(device, cfg, src_chroma_format, deint, orient, crop, lut_in, lut_out, us, pad, out);
 }
 
 int mjg_open_pad(int device, const mjg_config *cfg, int src_chroma_format, int crop_x, int crop_y, int crop_w,
                  int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, 0, 0, crop, nullptr, pad, out);
+  return open_any(device, cfg, src_chroma_format, 0, 0, crop, nullptr, nullptr, nullptr, pad, out);
 }
 
 int mjg_open_src(int device, const mjg_config *cfg, int src_chroma_format, mjg_ctx **out) {
-  return open_any(device, cfg, src_chroma_format, 0, 0, nullptr, nullptr, nullptr, out);
+  return open_any(device, cfg, src_chroma_format, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, out);
 }
 
 int mjg_open(int device, const mjg_config *cfg, mjg_ctx **out) {
@@ -1393,6 +1468,26 @@ int mjg_header(const mjg_ctx *ctx, uint8_t *out, size_t cap, size_t *len) {
 }
 
 namespace {
+// where slot "in"'s table stage leaves its frames: the buffer of the stage in front of it (in place), else d_lut
+uint8_t *lut_in_buf(const mjg_ctx *c, const Slot &S) { return c->orient ? S.d_orient : c->deint ? S.d_deint : S.d_lut; }
+
+// One table stage of a submit: luma, then U and V in one launch (V's blocks behind U's) when uv1 (2n fits
+// the grid, as for the other plane stages), else one launch each.  in_place: dst holds the frames
+// already, so a launch whose planes all have the identity table is left out; otherwise it copies
+// them.  cplane: bytes from the U to the V plane.
+void launch_lut(const mjg_ctx *c, const Slot &S, int slot, const SegList &in, uint8_t *dst, int n, bool uv1,
+                bool in_place, long long cplane) {
+  for (int p = 0; p < (uv1 ? 2 : 3); p++) {
+    LutGeom g = c->lpass[slot][p ? 1 : 0];
+    g.nf = n;
+    if (p && uv1) g.s_poff = g.d_poff = cplane;
+    if (p == 2) g.s_off += cplane, g.d_off += cplane, g.tab = 2;
+    const int tabs = p && uv1 ? 6 : 1 << g.tab;  // the launch's tables, as bits of g.ident
+    if (in_place && (g.ident & tabs) == tabs) continue;
+    k_lut_plane<<<g.gxy * (p && uv1 ? 2 * n : n), kCopyThreads, 0, S.st>>>(in, dst, c->d_luts + slot * sizeof(mjg_lut), g);
+  }
+}
+
 // mjg_submit's body; segs (mjg_submit_segments: device frames) replaces the one segment at
 // `frames` as the input of the sws stage, or of k_encode without one.  halo (a deint context's
 // single-segment submit, mjg_submit_halo): bit 1, `frames` starts with one frame that is only
@@ -1420,7 +1515,7 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
   }
   src += (size_t)hp * c->in_frame_bytes;  // the first encoded frame
   SegList in_sl = segs ? *segs : one_seg(src);  // the submit's input frames: the caller's segments, or one at src
-  if (c->scale || c->orient || c->deint) tmark(c, S, MJG_K_SCALE, 0);
+  if (c->scale || c->orient || c->deint || c->has_lut[0]) tmark(c, S, MJG_K_SCALE, 0);
   if (c->deint) {  // in front of everything: luma, then U and V in one launch; the rest reads one buffer
     const bool uv1 = 2 * n <= 65535;
     for (int p = 0; p < (uv1 ? 2 : 3); p++) {
@@ -1451,6 +1546,12 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
     HIP_TRY(hipGetLastError());
     in_sl = one_seg(S.d_orient);
   }
+  if (c->has_lut[0]) {  // behind the orientation: in place in that stage's buffer, else the caller's frames -> d_lut
+    uint8_t *buf = lut_in_buf(c, S);
+    launch_lut(c, S, 0, in_sl, buf, n, 2 * n <= 65535, buf != S.d_lut, c->src_cplane);
+    HIP_TRY(hipGetLastError());
+    in_sl = one_seg(buf);
+  }
   SegList enc_in = in_sl;
   if (c->scale) {
     // luma, then U and V in one launch (same filters; blockIdx.z >= n is V) while 2n fits the
@@ -1473,6 +1574,8 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
         ps.launch(ps, sg, in_sl, S.d_scaled, p && uv1 ? 2 * n : n, S.st);
       }
     }
+    // a table on the picture, in place: behind every sws pass, in front of the sharpen
+    if (c->has_lut[1]) launch_lut(c, S, 1, one_seg(S.d_scaled), S.d_scaled, n, uv1, true, d_cplane);
     const uint8_t *enc_buf = S.d_scaled;
     if (c->sharp) {  // behind the sws stage's passes (the pad's border among them): luma, then U and V as above
       for (int p = 0; p < (uv1 ? 2 : 3); p++) {
@@ -1488,7 +1591,7 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
     HIP_TRY(hipGetLastError());
     enc_in = one_seg(enc_buf);  // k_encode reads the scaled (the sharpened) frames, one buffer
   } else {  // in place: EncGeom's offsets count from the rectangle's first luma byte (0: whole frames)
-    if (c->orient || c->deint) tmark(c, S, MJG_K_SCALE, 1);  // an orientation / a deinterlacer alone: the interval holds its passes
+    if (c->orient || c->deint || c->has_lut[0]) tmark(c, S, MJG_K_SCALE, 1);  // an orientation / a deinterlacer / a table alone: the interval holds its passes
     for (int k = 0; k < kMaxSegs; k++) enc_in.p[k] += c->src_off[0];
   }
   const int ntasks = g.nchunks * g.nseg * n;
@@ -1714,7 +1817,7 @@ int mjg_sync(mjg_ctx *c, uint64_t *frame_sizes, uint64_t *total) {
       }
       if (c->timing) {
         for (int k = 0; k < MJG_NUM_KERNELS; k++) {
-          if (k == MJG_K_SCALE && !c->scale && !c->orient && !c->deint) continue;
+          if (k == MJG_K_SCALE && !c->scale && !c->orient && !c->deint && !c->has_lut[0]) continue;
           if (k == MJG_K_HUFF && !c->optimal) continue;
           const bool tail = is_tail_kernel(k);
           if (tail != c->timing_detail && (tail || k == MJG_K_TAIL)) continue;
@@ -1937,6 +2040,30 @@ int mjg_debug_unsharp(mjg_ctx *c, mjg_unsharp *out) {
   if (!c) return set_err(MJG_E_INVALID, "null context");
   if (c->sharp && out) *out = c->us;
   return c->sharp ? 1 : 0;
+}
+
+int mjg_debug_lut(mjg_ctx *c, int slot, mjg_lut *out) {
+  if (!c) return set_err(MJG_E_INVALID, "null context");
+  if (slot < 0 || slot > 1) return set_err(MJG_E_INVALID, "slot %d: not 0 (in) or 1 (out)", slot);
+  if (c->has_lut[slot] && out) *out = c->lut[slot];
+  return c->has_lut[slot] ? 1 : 0;
+}
+
+int mjg_debug_lut_in(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
+  if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
+  if (!c->has_lut[0]) return set_err(MJG_E_STATE, "context has no table in front of the sws stage (none, or identity tables)");
+  if (pending_jobs(c) > 0) {  // the latest synced submit's frames
+    const int rc = mjg_sync(c, nullptr, nullptr);
+    if (rc) return rc;
+  }
+  if (pending_jobs(c) > 0 || c->last < 0) return set_err(MJG_E_STATE, "sync every queued submit first");
+  const Slot &L = c->slot[c->last];
+  if (frame < 0 || frame >= L.jn[c->last_job]) return set_err(MJG_E_INVALID, "frame %d", frame);
+  if (cap < c->in_frame_bytes) return set_err(MJG_E_CAPACITY, "need %zu bytes", c->in_frame_bytes);
+  const size_t f = (size_t)L.jf0[c->last_job] + (size_t)frame;
+  // (in place in the buffer of the stage in front of it, else d_lut)
+  HIP_TRY(hipMemcpy(out, lut_in_buf(c, L) + f * c->in_frame_bytes, c->in_frame_bytes, hipMemcpyDeviceToHost));
+  return MJG_OK;
 }
 
 int mjg_debug_oriented(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {

@@ -1545,4 +1545,120 @@ __global__ __launch_bounds__(kSharpThreads) void k_unsharp_plane(const uint8_t *
   sharp_vpass<MX, MY>(src + pa, dst + pa, g, T, tid, lb, ls);
 }
 
+// k_lut_plane: a table per plane, out = T[in] (`-vf eq` is three such tables, and the
+// library knows only the tables).  A w x h rectangle of one plane of every frame of a launch, with row
+// strides, plane and frame offsets of their own on either side; dst may be src (every byte is read and
+// written by the same thread, and no byte outside the rectangle is read or written).  Streamed as
+// k_plane_copy streams: the destination's span of a (plane, frame), the (h - 1) d_stride + w bytes from
+// the rectangle's first to its last, is cut into 16-byte pieces aligned on the destination, piece k at
+// span bytes [head + 16 k, + 16); span byte j is column j % d_stride of row j / d_stride (multiply-high:
+// j < 2^28 + 2^14) and belongs to the rectangle when the column is below w.  A piece inside one row
+// is one unaligned 16-byte load, sixteen LDS byte reads and one aligned store, kCopyVecs pieces per
+// thread with every load issued before the first store; a piece between two rows is skipped; a piece
+// that runs over a row end, and the bytes before the first and after the last whole piece (the (plane,
+// frame)'s first workgroup), go byte by byte.  A rectangle whose rows are contiguous on both sides
+// comes as one row of w h bytes (lut_geom), so whole planes have no row ends at all.
+// The three tables (Y, U, V; 768 bytes at `tabs`) sit in LDS; a launch's first plane uses table
+// g.tab and its second (V behind U: blockIdx >= gxy * nf) the next.  A plane whose table is the
+// identity (g.ident) is copied without the lookups, or left alone when dst is src.  The LDS reads
+// are k_plane_copy<RANGE>'s: byte reads at data-dependent addresses of a 256-byte table, 64 banks of
+// one dword, so a wave's conflicts are those of 64 random draws from 64 banks.
+// The body is a __host__ __device__ function, as yadif_work is, for tools/lut_host.hip.
+struct LutGeom {
+  int w, h;                    // the rectangle
+  int s_stride, d_stride;      // its row strides
+  long long s_off, d_off;      // its first byte inside a frame
+  long long s_fstride, d_fstride;
+  long long s_poff, d_poff;    // the next plane's rectangle from this one's (V from U)
+  int nf;                      // frames per plane
+  int tab;                     // the first plane's table: 0 Y, 1 U, 2 V
+  int ident;                   // bit i: table i is the identity
+  uint32_t ds_magic;           // ceil(2^32 / d_stride)
+  int gxy;                     // workgroups per (plane, frame)
+  uint32_t gxy_magic;
+};
+
+// The geometry of a w x h rectangle (nf, tab, ident, the plane offsets and the magics of the two
+// divisors are the caller's): rows contiguous on both sides fold into one
+inline void lut_geom_rect(LutGeom &g, int w, int h, int s_stride, int d_stride) {
+  const bool flat = s_stride == w && d_stride == w;
+  g.w = flat ? w * h : w;  // (<= 2^28)
+  g.h = flat ? 1 : h;
+  g.s_stride = flat ? g.w : s_stride;
+  g.d_stride = flat ? g.w : d_stride;
+  const size_t pieces = ((size_t)(g.h - 1) * g.d_stride + g.w) >> 4, per = (size_t)kCopyThreads * kCopyVecs;
+  g.gxy = (int)(pieces ? (pieces + per - 1) / per : 1);
+}
+
+__host__ __device__ __forceinline__ void lut_work(const SegList &src, uint8_t *dst, const LutGeom &g,
+                                                  const uint8_t *tabs, int t, int tid) {
+  const int z = deint_div(t, g.gxy_magic, g.gxy), blk = t - z * g.gxy;
+  const int pl = z >= g.nf, f = z - (pl ? g.nf : 0);
+  int k = 0;
+#pragma unroll
+  for (int j = 1; j < kMaxSegs; j++)
+    if (f >= src.f0[j]) k = j;
+  const uint8_t *s = src.p[k] + (long long)(f - (k ? src.f0[k] : 0)) * g.s_fstride + g.s_off + (pl ? g.s_poff : 0);
+  uint8_t *d = dst + (long long)f * g.d_fstride + g.d_off + (pl ? g.d_poff : 0);
+  const int ti = g.tab + pl;
+  const bool id = (g.ident >> ti) & 1;
+  if (id && s == d) return;  // (uniform over the workgroup)
+  const uint8_t *T = tabs + 256 * ti;
+  const int w = g.w, ss = g.s_stride, ds = g.d_stride;
+  const int nb = (g.h - 1) * ds + w;
+  const int head = imin((int)(-(uintptr_t)d & 15), nb);
+  const int nv = (nb - head) >> 4;
+  auto map4 = [&](uint32_t x) -> uint32_t {
+    if (id) return x;
+    return (uint32_t)T[x & 255u] | ((uint32_t)T[(x >> 8) & 255u] << 8) | ((uint32_t)T[(x >> 16) & 255u] << 16) |
+           ((uint32_t)T[x >> 24] << 24);
+  };
+  auto byte_at = [&](int j) {  // span byte j, when it is one of the rectangle's
+    const int row = deint_div(j, g.ds_magic, ds), col = j - row * ds;
+    if (col < w) {
+      const uint8_t x = s[(size_t)row * ss + col];
+      d[j] = id ? x : T[x];
+    }
+  };
+  const int k0 = blk * (kCopyThreads * kCopyVecs) + tid;
+  u32x4 v[kCopyVecs];
+  bool whole[kCopyVecs];
+#pragma unroll
+  for (int i = 0; i < kCopyVecs; i++) {
+    const int kp = k0 + i * kCopyThreads;
+    whole[i] = false;
+    v[i] = u32x4{0, 0, 0, 0};
+    if (kp < nv) {
+      const int j = head + 16 * kp;
+      const int row = deint_div(j, g.ds_magic, ds), col = j - row * ds;
+      if (col + 16 <= w) {
+        whole[i] = true;
+        v[i] = *(const u32x4_a1 *)(s + (size_t)row * ss + col);
+      } else if (col < w || col + 16 > ds) {  // over a row end (rolled: 16 / d_stride of the pieces)
+#pragma unroll 1
+        for (int b = 0; b < 16; b++) byte_at(j + b);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < kCopyVecs; i++) {
+    const int kp = k0 + i * kCopyThreads;
+    if (whole[i]) *(u32x4 *)(d + head + 16 * kp) = u32x4{map4(v[i][0]), map4(v[i][1]), map4(v[i][2]), map4(v[i][3])};
+  }
+  if (blk == 0 && tid < 16) {
+    const int a = tid, b = head + 16 * nv + tid;
+    if (a < head) byte_at(a);
+    if (b < nb) byte_at(b);
+  }
+}
+
+__global__ __launch_bounds__(kCopyThreads) void k_lut_plane(const SegList src, uint8_t *dst,
+                                                            const uint8_t *__restrict__ tabs, LutGeom g) {
+  __shared__ __attribute__((aligned(16))) uint8_t tab[768];
+  const int tid = threadIdx.x;
+  if (tid < 192) ((uint32_t *)tab)[tid] = ((const uint32_t *)tabs)[tid];
+  __syncthreads();
+  lut_work(src, dst, g, tab, (int)blockIdx.x, tid);
+}
+
 }  // namespace mjg

@@ -2,6 +2,7 @@
 (`ffmpeg -f matroska -i pipe: <remote_args> -f matroska pipe:`,
 ffmpeg_distributed.py:131-141), restricted to the profile
 `[-vf [yadif,][vflip|transpose=N,...][crop=w:h:x:y,][scale=W:H:flags=bicubic][,unsharp[=lx:ly:la:cx:cy:ca]][,pad=W:H:x:y]] -c:v mjpeg -q:v N -dct int [-huffman default|optimal] -bitexact`
+(and one `eq=...` in front of the scale or directly behind it)
 (+ `-slices N` / `-thread_type slice` for the RST layout).
 
 Host-side wrapper over libmjgpu.so; frames are packed planar YUV (yuv420p / yuvj420p by
@@ -21,8 +22,10 @@ the orientation: every output frame is made from the frames before and after it,
 each segment of a submit_segments) is a whole sequence, and `submit(..., halo=)` hands over a
 piece of a longer one with its neighbour frames.  `unsharp=` (lx, ly, la, cx, cy, ca: `-vf unsharp`
 behind the scale and in front of the pad, the amounts as floats) sharpens or blurs the sws stage's
-output planes on the GPU (mjg_open_sharp); the encoder then reads the sharpened planes.  No CPU
-fallback.
+output planes on the GPU (mjg_open_sharp); the encoder then reads the sharpened planes.  `lut_in=` /
+`lut_out=` ((3, 256) uint8, rows Y, U, V) map every sample through a table per plane on the GPU
+(mjg_open_lut), in front of the sws stage and directly behind it: `-vf eq=...` in front of the scale or
+directly behind it, with profile.eq_tables.  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -73,7 +76,7 @@ class MjpegEncoder:
                  debug_coefs: bool = False, sws_bitexact: bool = True, com_itu601: bool = False,
                  huffman: str = "default", chroma: str = "420", rst: bool = False,
                  merge: bool = False, src_chroma: Optional[str] = None, crop=None, pad=None, orient: int = 0,
-                 deint: Optional[int] = None, unsharp=None):
+                 deint: Optional[int] = None, unsharp=None, lut_in=None, lut_out=None):
         self._L = _lib.load()
         self.device = int(device)
         self.src_w, self.src_h = int(src_w), int(src_h)
@@ -148,6 +151,27 @@ class MjpegEncoder:
                 raise ValueError(f"unsharp {unsharp!r}: (lx, ly, la, cx, cy, ca)")
             lx, ly, la, cx, cy, ca = unsharp
             self.unsharp = (int(lx), int(ly), int(float(la) * 65536.0), int(cx), int(cy), int(float(ca) * 65536.0))
+        # lut_in / lut_out: a (3, 256) uint8 array each, rows Y, U, V, out = t[in] (mjg_open_lut): in front
+        # of the sws stage on the frames behind the orientation, and on the sws stage's output picture
+        # in front of the unsharp.  `-vf eq` is profile.eq_tables.  None, the default, opens as without them
+        luts = []
+        for name, t in (("lut_in", lut_in), ("lut_out", lut_out)):
+            if t is not None:
+                t = np.ascontiguousarray(t)
+                if t.shape != (3, 256) or t.dtype != np.uint8:
+                    raise ValueError(f"{name}: a (3, 256) uint8 array, not {t.shape} {t.dtype}")
+            luts.append(t)
+        self.lut_in, self.lut_out = luts
+        if lut_in is not None or lut_out is not None:
+            if not hasattr(self._L, "mjg_open_lut"):
+                raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_lut")
+            rect = self.crop if self.crop is not None else (0, 0, self.or_w, self.or_h)
+            canvas = self.pad if self.pad is not None else (0, 0, self.dst_w, self.dst_h)
+            us = None if self.unsharp is None else C.byref(_lib.MjgUnsharp(*self.unsharp))
+            tabs = [None if t is None else C.byref(_lib.MjgLut.from_buffer_copy(t.tobytes())) for t in luts]
+            check(self._L.mjg_open_lut(self.device, C.byref(cfg), _lib.CHROMA_FORMATS[self.src_chroma],
+                                       self.deint, self.orient, *rect, tabs[0], tabs[1], us, *canvas, C.byref(h)))
+        elif unsharp is not None:
             if not hasattr(self._L, "mjg_open_sharp"):
                 raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_sharp")
             rect = self.crop if self.crop is not None else (0, 0, self.or_w, self.or_h)
@@ -451,6 +475,27 @@ class MjpegEncoder:
         if rc < 0:
             check(rc)
         return (us.lx, us.ly, us.la, us.cx, us.cy, us.ca) if rc else None
+
+    def debug_lut_in(self, frame: int = 0) -> np.ndarray:
+        """k_lut_plane's slot-"in" output of a frame of the last synced submit: a whole frame behind the
+        orientation in the input format `src_chroma`, frame_bytes bytes.  Only for an encoder opened
+        with a `lut_in` that is not three identity tables."""
+        if not hasattr(self._L, "mjg_debug_lut_in"):
+            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_debug_lut_in")
+        out = np.zeros(self.frame_bytes, np.uint8)
+        check(self._L.mjg_debug_lut_in(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size))
+        return out
+
+    def debug_lut(self, slot: str = "in"):
+        """The (3, 256) tables the context holds for slot "in" or "out", or None without (none given,
+        or three identity tables).  Host state only."""
+        if not hasattr(self._L, "mjg_debug_lut"):
+            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_debug_lut")
+        t = _lib.MjgLut()
+        rc = self._L.mjg_debug_lut(self._h, {"in": 0, "out": 1}[slot], C.byref(t))
+        if rc < 0:
+            check(rc)
+        return np.frombuffer(bytes(t), np.uint8).reshape(3, 256).copy() if rc else None
 
     def debug_deint(self, frame: int = 0) -> np.ndarray:
         """The deinterlaced frame (k_yadif_plane's output) of a frame of the last synced submit:

@@ -30,7 +30,13 @@ the profile, each with a reason that names it.  `unsharp` is `Profile.unsharp` =
 ca), the filter's defaults 5:5:1.0:5:5:0.0 filled in: plain numbers only, odd sizes
 3..23, amounts -2..5, and lx // 2 + ly // 2 <= 12 for a plane whose amount is not 0 (past that the
 filter's 32-bit sum wraps).  Its alpha and opencl options, an expression, a second unsharp and an
-unsharp anywhere but directly in front of the pad or the end are outside the profile.  An orientation filter after a crop, scale
+unsharp anywhere but directly in front of the pad or the end are outside the profile.  One
+    eq[=contrast:brightness:saturation:gamma:gamma_r:gamma_g:gamma_b:gamma_weight]   (or by these names)
+behind the yadif and the orientation run is `Profile.eq`: anywhere in front of the
+scale (slot "in"; without a scale, in front of the unsharp and the pad) or directly behind it (slot
+"out").  Plain numbers inside the filter's ranges only; `eval=`, an expression, a second eq and an eq
+behind the unsharp or the pad are outside the profile.  `eq_tables` makes the three byte tables, a
+restatement of vf_eq.c's 8-bit path that is unpinned against FFmpeg.  An orientation filter after a crop, scale
 or pad, transpose values 4..7, a passthrough other than none and any other option are outside the
 profile.  The crop values are decimal integers (no expressions); `Profile.crop` is the request as
 given and `resolve_crop` turns it into a rectangle of a given input (vf_crop.c's rounding,
@@ -85,6 +91,10 @@ class Profile:
     # -vf ...,unsharp[,pad]: (lx, ly, la, cx, cy, ca), sizes as ints and amounts as floats, the
     # filter's defaults filled in; None: no unsharp
     unsharp: Optional[tuple] = None
+    # -vf ...,eq=...: {"slot": "in" (in front of the scale, on the decoded samples) | "out" (directly
+    # behind the scale, on its full-range output), and the filter's eight numbers (EQ_NAMES), the
+    # defaults filled in}; eq_tables turns them into the three tables.  None: no eq
+    eq: Optional[dict] = None
 
 
 class Unsupported(ValueError):
@@ -355,6 +365,117 @@ def _parse_unsharp(f: str) -> tuple:
     return tuple(vals)
 
 
+EQ_NAMES = ("contrast", "brightness", "saturation", "gamma", "gamma_r", "gamma_g", "gamma_b", "gamma_weight")
+EQ_DEFAULT = {"contrast": 1.0, "brightness": 0.0, "saturation": 1.0, "gamma": 1.0, "gamma_r": 1.0, "gamma_g": 1.0,
+              "gamma_b": 1.0, "gamma_weight": 1.0}
+EQ_RANGES = {"contrast": (-1000.0, 1000.0), "brightness": (-1.0, 1.0), "saturation": (0.0, 3.0), "gamma": (0.1, 10.0),
+             "gamma_r": (0.1, 10.0), "gamma_g": (0.1, 10.0), "gamma_b": (0.1, 10.0), "gamma_weight": (0.0, 1.0)}
+
+
+def _parse_eq(f: str) -> dict:
+    """`eq=contrast:brightness:saturation:gamma:gamma_r:gamma_g:gamma_b:gamma_weight` -> the eight
+    numbers with the defaults filled in.  Plain numbers inside the filter's ranges only: FFmpeg clips a
+    value outside its range, which is not restated here."""
+    name, _, opts = f.partition("=")
+    vals = dict(EQ_DEFAULT)
+    pos = 0
+    if "=" in f and not opts:
+        raise Unsupported("eq= without options")
+    for p in opts.split(":") if opts else []:
+        if "=" in p:
+            k, v = p.split("=", 1)
+            if k == "eval":
+                raise Unsupported(f"eq eval={v} (per-frame evaluation is not GPU-accelerated)")
+            if k not in EQ_DEFAULT:
+                raise Unsupported(f"eq option {k!r} (only contrast, brightness, saturation and the gammas are "
+                                  f"GPU-accelerated)")
+        else:
+            if pos >= len(EQ_NAMES):
+                raise Unsupported(f"eq option {p!r} (positional options are {':'.join(EQ_NAMES)})")
+            k, v = EQ_NAMES[pos], p
+            pos += 1
+        if not _NUM_RE.match(v):
+            raise Unsupported(f"eq {k}={v}: an expression or not a plain number (plain numbers only)")
+        vals[k] = float(v)
+        lo, hi = EQ_RANGES[k]
+        if not lo <= vals[k] <= hi:
+            raise Unsupported(f"eq {k}={v}: outside {lo:g}..{hi:g} (FFmpeg clips it; the clip is not GPU-accelerated)")
+    return vals
+
+
+def _c_div(a: int, b: int) -> int:
+    """C integer division: truncates toward zero."""
+    q = abs(a) // abs(b)
+    return q if (a < 0) == (b < 0) else -q
+
+
+def eq_plane_table(C: float, B: float, G: float, W: float) -> list:
+    """One plane's 256 bytes for contrast C, brightness B, gamma G and gamma weight W (doubles):
+    vf_eq.c's 8-bit path as DESIGN §4.15 restates it."""
+    import math
+    if C == 1.0 and B == 0.0 and G == 1.0:
+        return list(range(256))                    # the filter copies the plane
+    out = []
+    if G == 1.0 and abs(C) < 7.9:                  # the linear form: C ints, truncating conversions and division
+        ci = int(C * 256 * 16)
+        bi = _c_div(int(100.0 * B + 100.0) * 511, 200) - 128 - _c_div(ci, 32)
+        for v in range(256):
+            pel = ((v * ci) >> 12) + bi
+            out.append(0 if pel < 0 else 255 if pel > 255 else pel)
+        return out
+    for v in range(256):                           # the table form
+        x = C * (v / 255.0 - 0.5) + 0.5 + B
+        if x <= 0.0:
+            out.append(0)
+            continue
+        x = x * (1.0 - W) + math.pow(x, 1.0 / G) * W
+        out.append(255 if x >= 1.0 else int(256.0 * x))
+    return out
+
+
+def eq_tables(spec: dict):
+    """(3, 256) uint8, rows Y, U, V: the tables `-vf eq` with the options `spec` (EQ_NAMES; absent:
+    the default) applies to 8-bit planar frames.  Every option goes through IEEE single first, as the
+    filter's float clip does; the rest is double arithmetic."""
+    import math
+    import numpy as np
+    o = {k: float(np.float32(spec.get(k, EQ_DEFAULT[k]))) for k in EQ_NAMES}
+    W = o["gamma_weight"]
+    planes = ((o["contrast"], o["brightness"], o["gamma"] * o["gamma_g"], W),
+              (o["saturation"], 0.0, math.sqrt(o["gamma_b"] / o["gamma_g"]), W),
+              (o["saturation"], 0.0, math.sqrt(o["gamma_r"] / o["gamma_g"]), W))
+    return np.array([eq_plane_table(*p) for p in planes], np.uint8)
+
+
+def _take_eq(vf: str):
+    """A graph that names eq -> (the graph without it, or None when nothing is left; the eq request with
+    its slot).  One eq, behind the yadif and the orientation run: slot "in" anywhere in front of the
+    scale (without a scale: in front of the unsharp and the pad), slot "out" directly behind the scale."""
+    fs = vf.split(",")
+    names = [f.split("=", 1)[0] for f in fs]
+    if names.count("eq") > 1:
+        raise Unsupported(f"filter graph {vf!r}: a second eq (one eq, in front of the scale or directly behind it, is "
+                          f"GPU-accelerated)")
+    at = names.index("eq")
+    if any(nm == "yadif" or nm in ORIENT_FILTERS or nm in OTHER_DEINTERLACERS or nm == "hflip" for nm in names[at + 1:]):
+        _parse_vf(vf)                              # "yadif after eq", "vflip after eq", ...: the reasons these have
+        raise Unsupported(f"filter graph {vf!r}: eq in front of {names[at + 1]}")
+    for nm in ("unsharp", "pad"):
+        if nm in names[:at]:
+            raise Unsupported(f"filter graph {vf!r}: eq behind the {nm} (eq is GPU-accelerated only in front of the "
+                              f"scale or directly behind it, in front of the unsharp and the pad)")
+    slot = "in"
+    if "scale" in names:
+        si = names.index("scale")
+        if at > si + 1:
+            raise Unsupported(f"filter graph {vf!r}: eq behind {names[at - 1]} (behind the scale, eq is GPU-accelerated "
+                              f"only directly behind it)")
+        slot = "in" if at < si else "out"
+    eq = dict(_parse_eq(fs[at]), slot=slot)
+    rest = fs[:at] + fs[at + 1:]
+    return (",".join(rest) if rest else None), eq
+
+
 def _parse_vf(vf: str):
     """-vf value -> (crop request or None, scale size or None, sws flags, pad request or None,
     unsharp request or None, orientation, yadif request or None).  A `yadif` at the very front is taken off first; then a
@@ -563,6 +684,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
     orient = 0
     deint = None
     unsharp = None
+    eq = None
     flags: Tuple[str, ...] = ("bicubic",)
     i = 0
 
@@ -603,7 +725,12 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
             if any(name != "bitexact" for _, name in _flag_ops(v)):
                 raise Unsupported(f"-fflags {v}")
         elif o in ("-vf", "-filter:v"):
-            crop, scale, flags, pad, unsharp, orient, deint = _parse_vf(val())
+            vf = val()
+            eq = None
+            if ";" not in vf and "eq" in [f.split("=", 1)[0] for f in vf.split(",")]:
+                vf, eq = _take_eq(vf)              # the rest of the graph is parsed as without it
+            if vf is not None:
+                crop, scale, flags, pad, unsharp, orient, deint = _parse_vf(vf)
         elif o in ("-an", "-sn", "-dn", "-y"):
             pass
         elif o in ("-threads", "-threads:v"):
@@ -653,7 +780,8 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
     if rst:
         huff = "default"  # mjpegenc.c: slice_context_count > 1 forces HUFFMAN_TABLE_DEFAULT
     return Profile(qscale=effective_qscale(q), q_arg=q, scale=scale, sws_flags=flags, huffman=huff,
-                   rst=rst, chroma=chroma, crop=crop, pad=pad, orient=orient, deint=deint, unsharp=unsharp)
+                   rst=rst, chroma=chroma, crop=crop, pad=pad, orient=orient, deint=deint, unsharp=unsharp,
+                   eq=eq)
 
 
 PIX_FMT_CHROMA = {"yuvj420p": "420", "yuvj422p": "422", "yuvj444p": "444"}

@@ -39,6 +39,10 @@ An `unsharp` behind the crop and the scale (profile.Profile.unsharp) is run by t
 stage's output.  Without a scale in the graph FFmpeg sharpens the decoded frames and converts them
 afterwards, so a tv-range or to-be-converted input then goes to the real ffmpeg
 (unsharp_fallthrough_reason).
+One `eq` (profile.Profile.eq) becomes three byte tables (profile.eq_tables) that the GPU applies in
+front of the sws stage (slot "in": the decoded samples, before any conversion) or on its output (slot
+"out": directly behind the scale); eq_fallthrough_reason names the inputs that still go to the real
+ffmpeg.
 """
 from __future__ import annotations
 
@@ -475,17 +479,20 @@ def resample_plan(prof, info):
 
 
 def encoder_key(prof, info, dst_w, dst_h, sar, com_itu601, batch, rect=None, pad=None, orient=0, deint=0,
-                unsharp=None):
+                unsharp=None, luts=None):
     """What an encoder context kept between segments (serve / resident mode) depends on: the
     input's shape and format and everything of the profile the context is opened with, the
     encoded chroma format (-pix_fmt), the resolved crop rectangle (x, y, w, h), the resolved
     pad (x, y, W, H), the orientation (0..7) and the deinterlacer (the resolved MJG_DEINT_* bits,
     resolve_deint: the batch buffers of such a context hold two more frames) included, and the
-    six values of an unsharp (profile.Profile.unsharp; None without one)."""
+    six values of an unsharp (profile.Profile.unsharp; None without one), and the bytes of the
+    tables in front of and behind the sws stage (luts: (lut_in, lut_out), each a (3, 256) uint8
+    array or None: two eq filters with different options are different contexts)."""
     src_chroma, dst_chroma = resample_plan(prof, info)
     return (info.width, info.height, dst_w, dst_h, info.full_range, prof.qscale, sar,
             com_itu601, prof.huffman, src_chroma, dst_chroma, prof.rst, batch,
             None if rect is None else tuple(rect), None if pad is None else tuple(pad), int(orient), int(deint),
+            tuple(None if t is None else t.tobytes() for t in (luts or (None, None))),
             None if unsharp is None else tuple(unsharp))
 
 
@@ -577,6 +584,27 @@ def unsharp_fallthrough_reason(prof, full_range, src_chroma, dst_chroma) -> Opti
     if not full_range or src_chroma != dst_chroma:
         return "unsharp without a scale on a tv-range / converted input: FFmpeg sharpens before its converter"
     return None
+
+
+def eq_fallthrough_reason(prof, info) -> Optional[str]:
+    """Why a graph with an `eq` runs on the CPU for this input, or None.  The tables are the filter's
+    8-bit path: samples of more than 8 bits go through another one."""
+    if prof.eq is None:
+        return None
+    # slot "out" is directly behind a scale (profile._take_eq)
+    assert prof.eq["slot"] == "in" or prof.scale is not None, prof
+    bits = int(getattr(info, "bits", 8))
+    if bits != 8:
+        return f"eq on a {bits}-bit input: only the filter's 8-bit path is GPU-accelerated"
+    return None
+
+
+def eq_luts(prof):
+    """(lut_in, lut_out) for MjpegEncoder: the eq's tables in its slot, None elsewhere."""
+    if prof.eq is None:
+        return None, None
+    tabs = profile.eq_tables(prof.eq)
+    return (tabs, None) if prof.eq["slot"] == "in" else (None, tabs)
 
 
 def scale_cascade_reason(in_size, out_size, src_chroma, dst_chroma) -> Optional[str]:
@@ -674,6 +702,13 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
         stderr.write(f"gpu:{device}: {why}; running ffmpeg on the CPU\n")
         stderr.flush()
         return ffmpeg_fallthrough(src, args, stdout, stderr)
+    # -vf ...,eq: tables in front of or behind the sws stage
+    why = eq_fallthrough_reason(prof, info)
+    if why is not None:
+        stderr.write(f"gpu:{device}: {why}; running ffmpeg on the CPU\n")
+        stderr.flush()
+        return ffmpeg_fallthrough(src, args, stdout, stderr)
+    lut_in, lut_out = eq_luts(prof)
     # the one scale the library refuses (a filter of 256 taps or more, about 64:1), decided here
     # without a device: as the up-sampling -pix_fmt pairs, the segment goes to ffmpeg
     why = scale_cascade_reason(in_size, (dst_w, dst_h), src_chroma, dst_chroma)
@@ -691,7 +726,7 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
     # (a transpose hands on 1 / SAR when the SAR is known: vf_transpose config_props_output)
     sar = profile.scaled_sar(oriented_sar(info.sar, orient), in_size, (dst_w, dst_h))
     key = encoder_key(prof, info, dst_w, dst_h, sar, opts.com_itu601 and not info.full_range, batch, rect, pad,
-                      orient, deint, prof.unsharp)
+                      orient, deint, prof.unsharp, (lut_in, lut_out))
     nbuf = NBUF
     if cache is not None and cache.get("key") == key:
         enc, bufs, obufs = cache["enc"], cache["bufs"], cache["obufs"]
@@ -702,7 +737,8 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
                            qscale=prof.qscale, sar=sar, max_batch=batch,
                            com_itu601=opts.com_itu601 and not info.full_range, huffman=prof.huffman,
                            chroma=dst_chroma, src_chroma=src_chroma, rst=prof.rst, crop=rect, pad=pad,
-                           orient=orient, deint=deint or None, unsharp=prof.unsharp)
+                           orient=orient, deint=deint or None, unsharp=prof.unsharp,
+                           lut_in=lut_in, lut_out=lut_out)
         # (a deinterlacer: room for the frame in front of a batch and the one behind it)
         bufs = [PinnedBuffer((batch + (2 if deint else 0)) * enc.frame_bytes) for _ in range(nbuf)]
         # page-locked output buffers: the packets are DMA'd into one (enc.fetch_into) and the

@@ -7,7 +7,8 @@
  * and launched/supervised at ffmpeg_distributed.py:139-141 (FFMPEGProc.run,
  * ffmpeg_distributed.py:59-91).  For the north-star profile
  *     [-vf [yadif[=0|2],][vflip|transpose=N,...][crop=w:h:x:y,][scale=W:H:flags=bicubic][,unsharp[=lx:ly:la:cx:cy:ca]][,pad=W:H:x:y]] -c:v mjpeg -q:v N -dct int -huffman default -bitexact
- * (`unsharp` behind the scale and in front of the pad: the sharpen, mjg_open_sharp, a restatement of
+ * (one `eq=...` in front of the scale, or directly behind it: a table per plane, mjg_open_lut, a
+ * restatement of vf_eq.c's 8-bit path that no FFmpeg build has been compared with yet; `unsharp` behind the scale and in front of the pad: the sharpen, mjg_open_sharp, a restatement of
  * vf_unsharp.c's 8-bit path that no FFmpeg build has been compared with yet; `yadif` as the very first filter, frame-rate modes 0 and 2: the deinterlacer, mjg_open_deint,
  * a restatement of the filter's C path that no FFmpeg build has been compared with yet; a leading run of vflip / transpose: one of eight plane maps, mjg_open_orient; and `-pix_fmt yuvj420p|yuvj422p` from a 4:4:4 or 4:2:2 input: the chroma down-sampling
  * FFmpeg's auto-inserted scaler does, taken to be its default bicubic; `-vf crop=...` alone or
@@ -234,6 +235,30 @@ typedef struct mjg_unsharp { int32_t lx, ly, la, cx, cy, ca; } mjg_unsharp;
 int mjg_open_sharp(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient,
                    int crop_x, int crop_y, int crop_w, int crop_h, const mjg_unsharp *us,
                    int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
+
+/* A table per plane: out = t[in].  `-vf eq` on 8-bit planar frames is three such tables
+ * (profile.eq_tables makes them); the library knows tables, not the filter. */
+typedef struct mjg_lut { uint8_t y[256], u[256], v[256]; } mjg_lut;   /* out = t[in], per plane */
+/* mjg_open_sharp with tables in front of the sws stage (lut_in) and behind it (lut_out).  NULL, or
+ * three identity tables, is no table; with neither the call is exactly mjg_open_sharp: no buffer,
+ * the same launches.
+ * lut_in acts on the frames that enter the sws stage, or k_encode in place: behind the
+ * deinterlacer and the orientation, on whole frames in the source format, before any range
+ * conversion.  k_lut_plane (scale.hip) writes them into a buffer of the launch slot,
+ * which the sws stage or k_encode then reads; the caller's frames are never written.  Behind a
+ * deinterlacer or an orientation the stage runs in place in that stage's buffer instead (so
+ * mjg_debug_oriented, or mjg_debug_deint without an orientation, then return the mapped frames).
+ * lut_out forces the sws stage, as a pad and a sharpen do, and acts in place on the picture
+ * rectangle of its output (dst_w x dst_h and its chroma size, at the canvas stride under a pad),
+ * behind every sws pass, the pad's border among them, and in front of the sharpen; the border is
+ * never mapped.  A plane whose table is the identity is copied by the same launch, or left alone
+ * in place.  Both stages work per frame (MJG_F_MERGE, mjg_submit_segments and mjg_submit_halo are
+ * unchanged) and belong to the MJG_K_SCALE interval, which a lut_in alone opens too.
+ * (Added without a version step, as mjg_open_orient.) */
+int mjg_open_lut(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient,
+                 int crop_x, int crop_y, int crop_w, int crop_h,
+                 const mjg_lut *lut_in, const mjg_lut *lut_out, const mjg_unsharp *us,
+                 int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
 void mjg_close(mjg_ctx *ctx);
 
 /* Bytes of one packed planar input frame (src_w x src_h in the source chroma format). */
@@ -343,6 +368,15 @@ int mjg_debug_presharp(mjg_ctx *ctx, int frame, uint8_t *out, size_t cap);
  * without one, or a negative MJG_E_* code for a null context.  Host state only.  (With
  * mjg_open_sharp.) */
 int mjg_debug_unsharp(mjg_ctx *ctx, mjg_unsharp *out);
+/* 1 and the tables of slot 0 ("in") or 1 ("out") in *out (which may be NULL) when the context has
+ * them, 0 without (none given, or three identity tables), or a negative MJG_E_* code.  Host state
+ * only.  (With mjg_open_lut.) */
+int mjg_debug_lut(mjg_ctx *ctx, int slot, mjg_lut *out);
+/* k_lut_plane's slot-"in" output for frame `frame` of the last synced submit: a whole frame in the
+ * source format (behind the orientation: the oriented one), from wherever the stage left it.
+ * MJG_E_STATE for a context without a lut_in.  Under a lut_out, mjg_debug_planes and
+ * mjg_debug_presharp return the mapped planes.  (With mjg_open_lut.) */
+int mjg_debug_lut_in(mjg_ctx *ctx, int frame, uint8_t *out, size_t cap);
 /* Which kernel the sws stage runs for a plane (0 = luma, 1 = chroma): 0 no sws stage for it (the
  * context has none), 1 k_plane_copy (the plane keeps its size), 2 k_scale (one LDS tile per 64-column
  * tile: down to about 4:1), 3 k_scale_stream (any ratio whose filters stay below 256 taps, about

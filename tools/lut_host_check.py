@@ -1,0 +1,113 @@
+#!/usr/bin/env python3
+"""k_lut_plane's body on the CPU: builds tools/lut_host.hip (the kernel's __host__ __device__ body run
+over every (workgroup, thread) of its launches) with AddressSanitizer and UBSan on the host side, and
+compares its output with tests/eq_ref.py for every shape of tests/test_gpu_eq.py and a few smaller
+ones.  Slot "in": three frames into a second buffer, in place, and as segments of 1 + 3 + 1 and 1 + 1 + 2
++ 1 in allocations of their own, each one byte in; with permutation tables, with an identity Y and
+with an identity U.  Slot "out": the picture of a padded canvas in place, where every byte outside it
+must stay.  Every buffer is allocated at exactly its size, so a load or store outside a frame stops
+the program.  --long walks 8x8 4:2:0 in one submit of 32,768 frames, where U and V get a launch each,
+and five frames forced apart.  No GPU.
+
+usage: python3 tools/lut_host_check.py [--keep] [--long]"""
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import eq_ref  # noqa: E402
+from ffmpeg_distributed_amd.encoder import i420_frame_bytes  # noqa: E402
+
+SHIFTS = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}
+# tests/test_gpu_eq.py's frames (203x301: 301x203 behind a transpose; 36x20, 40x24, 24x16: the worker's), and smaller ones
+SHAPES = [(9, 5, "420"), (33, 17, "444"), (130, 66, "420"), (4100, 5, "444"), (203, 301, "420"), (130, 66, "444"),
+          (130, 66, "422"), (40, 24, "420"), (1, 1, "444"), (2, 2, "420"), (15, 1, "444"), (16, 1, "444"), (17, 3, "422"),
+          (1030, 5, "420")]
+# slot "out": (canvas w, h, format, px, py, picture w, h)
+CANVASES = [(80, 48, "420", 6, 10, 64, 32), (80, 48, "444", 3, 5, 64, 32), (64, 32, "420", 0, 0, 64, 32),
+            (32, 24, "420", 4, 4, 24, 16), (70, 40, "422", 2, 3, 31, 17), (40, 9, "444", 25, 2, 15, 7),
+            (300, 20, "444", 1, 1, 290, 18)]
+SPLITS = [(1, 3, 1), (1, 1, 2, 1)]
+
+
+def main():
+    tmp = tempfile.mkdtemp(prefix="lut_host_")
+    exe = os.path.join(tmp, "lut_host")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
+                    "-Xarch_host", "-fno-omit-frame-pointer", "-Wno-pass-failed", "-I", os.path.join(ROOT, "include"),
+                    "-I", os.path.join(ROOT, "ffmpeg_distributed_amd", "csrc"), "-o", exe,
+                    os.path.join(ROOT, "tools", "lut_host.hip")], check=True)
+
+    def run(frames, tabs, w, h, c, split=0, apart=0, inplace=0, canvas=None):
+        hs, vs = SHIFTS[c]
+        fin, ftab, fout = (os.path.join(tmp, nm) for nm in ("in.bin", "tab.bin", "out.bin"))
+        frames.tofile(fin)
+        np.asarray(tabs, np.uint8).tofile(ftab)
+        n = frames.shape[0]
+        cmd = [exe, fin, ftab, fout, str(w), str(h), str(hs), str(vs), str(n),
+               ",".join(str(v) for v in split) if split else "0", str(apart), str(inplace)]
+        if canvas:
+            cmd += [str(v) for v in canvas]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode:
+            sys.exit(f"lut_host failed ({r.returncode}) at {w}x{h} {c} split {split} inplace {inplace} canvas {canvas}:\n"
+                     + r.stderr[-4000:])
+        return np.fromfile(fout, np.uint8).reshape(n, -1)
+
+    rng = np.random.default_rng(11)
+    perm = eq_ref.perm_tables(3)
+    id_y = perm.copy()
+    id_y[0] = eq_ref.IDENTITY
+    id_u = perm.copy()
+    id_u[1] = eq_ref.IDENTITY
+    bad = 0
+    if "--long" in sys.argv:
+        w, h, c = 8, 8, "420"
+        n = 32768
+        base = rng.integers(0, 256, (61, i420_frame_bytes(w, h, c)), dtype=np.uint8)
+        frames = base[np.arange(n) % 61]
+        ok = [(run(frames, perm, w, h, c) == eq_ref.map_frames(frames, w, h, c, perm)).all(),
+              (run(frames, id_u, w, h, c, inplace=1) == eq_ref.map_frames(frames, w, h, c, id_u)).all(),
+              (run(frames[:5], perm, w, h, c, apart=1) == eq_ref.map_frames(frames[:5], w, h, c, perm)).all()]
+        print(f"{w}x{h} {c} U, V apart: one submit of {n} {ok[0]}, in place with an identity U {ok[1]}, 5 frames forced apart {ok[2]}")
+        bad += ok.count(False)
+    for (w, h, c) in ([] if "--long" in sys.argv else SHAPES):
+        fb = i420_frame_bytes(w, h, c)
+        frames = rng.integers(0, 256, (5, fb), dtype=np.uint8)
+        frames[3] = (np.arange(fb) * 3 % 256).astype(np.uint8)
+        ok = []
+        for tabs in (perm, id_y, id_u):
+            want = eq_ref.map_frames(frames, w, h, c, tabs)
+            ok.append((run(frames[:3], tabs, w, h, c) == want[:3]).all())
+            ok.append((run(frames[:3], tabs, w, h, c, inplace=1) == want[:3]).all())
+            for split in SPLITS:
+                ok.append((run(frames, tabs, w, h, c, split=split) == want).all())
+        print(f"in {w}x{h} {c}: " + ", ".join(
+            f"{nm}: copy {o[0]} in place {o[1]} 1+3+1 {o[2]} 1+1+2+1 {o[3]}"
+            for nm, o in zip(("perm", "identity Y", "identity U"), (ok[0:4], ok[4:8], ok[8:12]))))
+        bad += ok.count(False)
+    for (cw, ch, c, px, py, w, h) in ([] if "--long" in sys.argv else CANVASES):
+        fb = i420_frame_bytes(cw, ch, c)
+        frames = rng.integers(0, 256, (3, fb), dtype=np.uint8)    # (a random border: any byte written there shows)
+        ok = []
+        for tabs in (perm, id_y, id_u):
+            want = eq_ref.map_picture(frames, cw, ch, c, px, py, w, h, tabs)
+            ok.append((run(frames, tabs, w, h, c, canvas=(cw, ch, px, py)) == want).all())
+        print(f"out {w}x{h} at ({px},{py}) of {cw}x{ch} {c}: perm {ok[0]}, identity Y {ok[1]}, identity U {ok[2]}")
+        bad += ok.count(False)
+    if "--keep" not in sys.argv:
+        for f in os.listdir(tmp):
+            os.unlink(os.path.join(tmp, f))
+        os.rmdir(tmp)
+    print("all equal" if not bad else f"{bad} mismatches")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
