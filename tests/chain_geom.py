@@ -13,6 +13,10 @@ shape reaches the path it means to check.
   - deint_span / sharp_cells: the workgroups, pieces and head / tail bytes k_yadif_plane takes for a
     plane, and the tiles, `pic` masks and short quads of k_unsharp_plane's launch, for
     tests/test_gpu_filter_chain.py; filter_sweep_configs and its family: that file's seeded sweep;
+  - lut_span / lut_plane_geoms / lut_out_spans: the workgroups, the whole pieces, those over a row end
+    and those skipped between two rows (and how many of each lie in workgroups blk >= 1), head and
+    tail bytes of one (plane, frame) of k_lut_plane, and slot "out"'s rectangles as plan_lut sets
+    them, for tests/test_gpu_eq_chain.py; eq_sweep_configs and its family: that file's seeded sweep;
   - plane_launches / merged_frames: the launches submit_impl makes per plane stage for a launch of
     n frames (U and V apart past 2 n <= 65535) and the frames a merged launch may carry;
     LONG_CASES and its family: the shapes of tests/test_gpu_long_submit.py;
@@ -854,3 +858,227 @@ def long_plane_sizes(c):
     rw, rh = c.rect[2:] if c.rect else (ow, oh)
     dw, dh = c.dw or rw, c.dh or rh
     return (((rw, rh), (dw, dh)), (chroma_size(rw, rh, c.src), chroma_size(dw, dh, c.dst)))
+
+
+# ------------------------------------------------------------------ the table stage's launches
+LutSpan = namedtuple("LutSpan", "wgs whole over_row_end skipped late_over late_skipped head tail")
+LUT_PER_WG = COPY_THREADS * COPY_VECS      # the 16-byte pieces of one workgroup of k_lut_plane
+
+
+def lut_span(w, h, stride, head=0):
+    """What lut_geom_rect and lut_work derive for one (plane, frame) of a table launch: a w x h
+    rectangle whose rows lie `stride` bytes apart on both sides (slot "in": stride = w; slot "out":
+    the canvas stride) and whose first destination byte lies `head` bytes in front of a 16-byte
+    boundary.  Rows that are contiguous fold into one row of w h bytes.  The span is nb = (h - 1)
+    stride + w bytes; the launch sizes its grid from nb >> 4 pieces, kCopyThreads x kCopyVecs a
+    workgroup; the kernel's own count is nv = (nb - head) >> 4, piece k at span bytes [head + 16 k,
+    + 16), column col = (head + 16 k) % stride: whole (one 16-byte load and store) when col + 16 <=
+    w, over a row end (byte by byte) when col < w or col + 16 > stride, else between two rows and
+    skipped.  late_*: those of pieces k >= kCopyThreads kCopyVecs, which workgroups blk >= 1 hold.
+    head, tail: the bytes in front of the first and behind the last piece (workgroup 0, threads
+    0..15)."""
+    if stride == w:
+        w, h, stride = w * h, 1, w * h
+    nb = (h - 1) * stride + w
+    pieces = nb >> 4
+    wgs = (pieces + LUT_PER_WG - 1) // LUT_PER_WG if pieces else 1
+    head = min(head, nb)
+    nv = (nb - head) >> 4
+    tail = nb - head - 16 * nv
+    if h == 1:
+        return LutSpan(wgs, nv, 0, 0, 0, 0, head, tail)
+    whole = over = skipped = late_over = late_skipped = 0
+    for k in range(nv):
+        col = (head + 16 * k) % stride
+        if col + 16 <= w:
+            whole += 1
+        elif col < w or col + 16 > stride:
+            over += 1
+            late_over += k >= LUT_PER_WG
+        else:
+            skipped += 1
+            late_skipped += k >= LUT_PER_WG
+    return LutSpan(wgs, whole, over, skipped, late_over, late_skipped, head, tail)
+
+
+def lut_plane_geoms(W, H, c, px, py, w, h):
+    """The luma and the chroma (w, h, stride, d_off) of slot "out" as plan_lut sets them for an
+    encoded W x H frame in `c` whose w x h picture sits at (px, py): the picture's planes in
+    d_scaled at the canvas stride, d_off the rectangle's first byte inside a frame (the chroma
+    one is U's; V's lies a chroma plane of the canvas further, lut_plane_heads).  A 16-aligned
+    d_scaled and frame bytes that are a multiple of 16 make head = (-d_off) & 15 in every frame."""
+    hs, vs = CHROMA_SHIFTS[c]
+    cw, ch = (W + hs) >> hs, (H + vs) >> vs
+    return ((w, h, W, py * W + px),
+            ((w + hs) >> hs, (h + vs) >> vs, cw, W * H + (py >> vs) * cw + (px >> hs)))
+
+
+def lut_out_spans(W, H, c, px, py, w, h, nframes=1):
+    """{(plane, frame): LutSpan} of slot "out" for nframes frames of d_scaled (16-aligned; frames
+    enc_frame_bytes apart, so at any address where that is odd)."""
+    hs, vs = CHROMA_SHIFTS[c]
+    cplane = ((W + hs) >> hs) * ((H + vs) >> vs)
+    fb = W * H + 2 * cplane
+    luma, chroma = lut_plane_geoms(W, H, c, px, py, w, h)
+    out = {}
+    for f in range(nframes):
+        for p, (gw, gh, gs, off) in enumerate((luma, chroma, chroma)):
+            out[(p, f)] = lut_span(gw, gh, gs, -(f * fb + off + (cplane if p == 2 else 0)) & 15)
+    return out
+
+
+# ------------------------------------------------------------------ the seeded sweep with a table
+LUT_KINDS = (None, "perm", "perm_id_y", "perm_id_uv")      # a slot's tables: none, eq_ref.perm_tables, with identity planes
+LUT_IDENT = {None: (0, 1, 2), "perm": (), "perm_id_y": (0,), "perm_id_uv": (1, 2)}
+EQ_FEATURES = (tuple("in_" + k for k in LUT_KINDS[1:]) + tuple("out_" + k for k in LUT_KINDS[1:]) + ("both_slots",)
+               + ("in_to_d_lut", "in_place_d_deint", "in_place_d_orient")
+               + tuple("d_lut_" + s for s in SUBMITS) + ("d_lut_identity_copy_three_wgs",)
+               + ("read_in_place_aligned", "read_in_place_ua", "read_rect_copy", "read_pad_copy", "read_plane_copy",
+                  "read_k_scale", "read_k_scale_stream")
+               + ("out_flat", "out_strided", "out_flat_past_one_wg", "out_strided_past_one_wg", "out_late_over",
+                  "out_late_skipped", "out_strided_v_second_slot", "out_sharp_behind", "v_mapped_three_wgs")
+               + SUBMITS + ("default", "optimal", "rst"))
+
+EqConfig = namedtuple("EqConfig", FilterConfig._fields + ("lut_in", "lut_out"))
+
+
+def eq_sweep_configs(seed, count):
+    """sweep_configs(seed, count), each with values from a generator of its own (seeded [seed,
+    tag]): a table kind out of LUT_KINDS per slot, in one draw of four a deinterlacer, in one of
+    four an orientation (1..7; 2, 4 or 6 where the source is 4:2:2), in one of three a sharpen, and
+    a submit mode for a deinterlaced draw.  Every value is drawn before the rules are tested; a
+    draw with no table is drawn again.  The drawn w x h is the oriented frame (source_size); a
+    deinterlaced configuration has three frames, never "merged", segments of 2 + 1.
+    The odds: slot "in" writes d_lut only on a caller's frames (no deinterlacer, no orientation),
+    and that has to meet each of four submit modes in every part of 30, so both are rarer than in
+    filter_sweep_configs.  The rules: a base draw whose crop k_encode reads in place keeps that
+    (the rare path): slot "in" only, no sharpen, no orientation; one on the stream kernel or the
+    rectangle copy always gets slot "in" and no orientation, so those readers see mapped frames.
+    Anything else that would be read in place and draws slot "out" goes through the sws stage
+    (eq_predict).  With these odds 22 seeds of 1..3000 give every feature of EQ_FEATURES in every
+    part of 30; EQ_SWEEP_SEED is the one whose sorted counts are largest, compared from the
+    smallest up."""
+    import numpy as np
+    rng = np.random.default_rng([seed, 0x6571])
+    out = []
+    for c in sweep_configs(seed, count):
+        enc_path, paths, rect_form = predict_paths(c.w, c.h, c.src, c.rect, c.dst, c.dw, c.dh, c.pad)
+        crop = c.rect is not None and tuple(c.rect) != (0, 0, c.w, c.h)
+        keep, rare = bool(enc_path & IN_PLACE) and crop, STREAM in paths or rect_form
+        while True:
+            li, li3, lo = int(rng.integers(4)), 1 + int(rng.integers(3)), int(rng.integers(4))
+            d4, d = int(rng.integers(4)) == 0, 1 + int(rng.integers(4))
+            turned = int(rng.integers(4)) == 0
+            o, om = 1 + int(rng.integers(7)), (2, 4, 6)[int(rng.integers(3))]
+            s3, s5 = int(rng.integers(3)) == 0, 1 + int(rng.integers(5))
+            sub = SUBMITS[int(rng.integers(3))]
+            li = li3 if keep or rare else li
+            lo = 0 if keep else lo
+            if li or lo:
+                break
+        orient = 0 if not turned or keep or rare else om if c.src == "422" else o
+        sharp = SHARPS[s5] if s3 and not keep else None
+        submit, nframes = c.submit, c.nframes
+        if d4:
+            submit, nframes = (sub if submit == "merged" else submit), 3
+        out.append(EqConfig(*c._replace(submit=submit, nframes=nframes), orient, DEINTS[d] if d4 else None, sharp,
+                            LUT_KINDS[li], LUT_KINDS[lo]))
+    return out
+
+
+def eq_predict(cfg):
+    """(encode_path, (luma, chroma) scale_path, RECT) of an EqConfig: filter_predict's rule with
+    slot "out" beside the sharpen (plan_geometry: either runs the sws stage), so what would be
+    read in place goes through the plane copy first."""
+    sw, sh = source_size(cfg)
+    enc_path, paths, rect_form = predict_paths(sw, sh, cfg.src, cfg.rect, cfg.dst, cfg.dw, cfg.dh, cfg.pad,
+                                               orient=cfg.orient)
+    if (cfg.unsharp is not None or cfg.lut_out is not None) and enc_path & IN_PLACE:
+        assert paths == (NONE, NONE)
+        return 0, (COPY, COPY), cfg.rect is not None and cfg.rect[2] != cfg.w
+    return enc_path, paths, rect_form
+
+
+def eq_features(cfg, enc_path, paths):
+    """The EQ_FEATURES an EqConfig carries, from its encode path and scale paths (predicted by
+    eq_predict, or as the context reports them), its own values and lut_span of every mapped
+    (plane, frame) of slot "out" (a plane with the identity table is left alone in d_scaled).  Three
+    features are there because a mutation run showed the need (profiles/eq_chain/mutations.txt):
+    an identity plane copied into d_lut by three workgroups or more, a mapped V plane of three, and
+    a V plane at the canvas stride with pieces past the first kCopyThreads."""
+    crop = cfg.rect is not None and tuple(cfg.rect) != (0, 0, cfg.w, cfg.h)
+    f = {cfg.submit, "optimal" if cfg.kw.get("huffman") == "optimal" else "rst" if cfg.kw.get("rst") else "default"}
+    if cfg.lut_in and cfg.lut_out:
+        f.add("both_slots")
+    if cfg.lut_in:
+        f.add("in_" + cfg.lut_in)
+        iw, ih = chroma_size(cfg.w, cfg.h, cfg.src)      # slot "in": the whole planes of the oriented frame, flat
+        in_planes = ((cfg.w, cfg.h, cfg.w), (iw, ih, iw))
+        if cfg.orient:
+            f.add("in_place_d_orient")
+        elif cfg.deint:
+            f.add("in_place_d_deint")
+        else:
+            f.update(("in_to_d_lut", "d_lut_" + cfg.submit))
+            if any(lut_span(*in_planes[min(p, 1)]).wgs >= 3 for p in LUT_IDENT[cfg.lut_in]):
+                f.add("d_lut_identity_copy_three_wgs")      # (`id && s != d` in workgroups blk >= 2)
+        if 2 not in LUT_IDENT[cfg.lut_in] and lut_span(*in_planes[1]).wgs >= 3:
+            f.add("v_mapped_three_wgs")      # (a V workgroup blk >= 2 of the paired launch, whose blk is not its blockIdx)
+        if enc_path & IN_PLACE:
+            if crop:
+                f.add("read_in_place_ua" if enc_path & UA else "read_in_place_aligned")
+        else:
+            if paths[0] == COPY and crop and cfg.rect[2] != cfg.w:
+                f.add("read_rect_copy")
+            for path, name in ((PADCOPY, "read_pad_copy"), (COPY, "read_plane_copy"), (TILE, "read_k_scale"),
+                               (STREAM, "read_k_scale_stream")):
+                if path in paths:
+                    f.add(name)
+    if cfg.lut_out:
+        assert not enc_path & IN_PLACE
+        f.add("out_" + cfg.lut_out)
+        if cfg.unsharp is not None:
+            f.add("out_sharp_behind")
+        W, H, px, py, w, h = encoded_geometry(cfg)
+        wide = [g[2] != g[0] for g in lut_plane_geoms(W, H, cfg.dst, px, py, w, h)]      # plan_lut: d_stride = pg.cw > w
+        for (p, _), sp in lut_out_spans(W, H, cfg.dst, px, py, w, h, cfg.nframes).items():
+            if p in LUT_IDENT[cfg.lut_out]:
+                continue
+            strided = wide[min(p, 1)]
+            f.add("out_strided" if strided else "out_flat")
+            if sp.wgs > 1:
+                f.add("out_strided_past_one_wg" if strided else "out_flat_past_one_wg")
+            if sp.late_over:
+                f.add("out_late_over")
+            if sp.late_skipped:
+                f.add("out_late_skipped")
+            gw, _, gs, _ = lut_plane_geoms(W, H, cfg.dst, px, py, w, h)[1]
+            if strided and p == 2 and any((sp.head + 16 * k) % gs + 16 <= gw for k in
+                                          range(COPY_THREADS, sp.whole + sp.over_row_end + sp.skipped)):
+                f.add("out_strided_v_second_slot")      # (a whole V piece of loop iteration i >= 1 at the canvas stride)
+            if p == 2 and sp.wgs >= 3:
+                f.add("v_mapped_three_wgs")
+    return f
+
+
+def count_eq_features(sets):
+    return {k: sum(k in s for s in sets) for k in EQ_FEATURES}
+
+
+def eq_predicted_counts(cfgs):
+    return count_eq_features([eq_features(c, *eq_predict(c)[:2]) for c in cfgs])
+
+
+# The sweep of tests/test_gpu_eq_chain.py: the seed, the configurations (in four parts) and per part
+# the number that carry each feature, counted by eq_predicted_counts (tests/test_chain_geom.py
+# checks that).  Of seeds 1..3000 the one whose sorted counts (152: 38 features x 4 parts) are
+# largest, compared from the smallest up; 22 seeds have every count at least 1, which the GPU test
+# requires of every feature in every part.
+EQ_SWEEP_SEED = 168
+EQ_SWEEP_COUNT = 120
+EQ_SWEEP_FLOORS = [dict(zip(EQ_FEATURES, v)) for v in (
+    (8, 5, 13, 8, 6, 6, 16, 18, 5, 3, 6, 6, 4, 2, 5, 6, 1, 2, 3, 5, 15, 1, 13, 7, 4, 3, 3, 3, 3, 7, 5, 10, 11, 7, 2, 17, 8, 5),
+    (9, 9, 8, 5, 6, 8, 15, 17, 6, 3, 4, 4, 4, 5, 6, 3, 2, 6, 2, 8, 19, 1, 13, 6, 4, 2, 2, 2, 2, 6, 3, 7, 9, 8, 6, 13, 9, 8),
+    (9, 6, 5, 4, 9, 12, 15, 13, 5, 2, 4, 2, 3, 4, 4, 3, 1, 2, 3, 5, 12, 1, 15, 10, 3, 2, 2, 2, 3, 12, 4, 8, 7, 8, 7, 10, 13, 7),
+    (10, 6, 10, 8, 8, 4, 16, 13, 5, 8, 3, 4, 5, 1, 2, 3, 2, 1, 4, 4, 14, 1, 10, 10, 3, 4, 4, 4, 2, 6, 5, 10, 7, 10, 3, 11, 11, 8),
+)]

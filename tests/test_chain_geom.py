@@ -653,3 +653,104 @@ def test_long_cases_reach_the_paths_they_are_listed_for():
     assert cg.LONG_CASES["unsharp55"].unsharp[:2] == cg.LONG_CASES["unsharp55"].unsharp[3:5] == (5, 5)
     assert cg.LONG_CASES["unsharp_chroma"].unsharp == (5, 5, 0.0, 3, 5, 0.7)
     assert cg.enc_geom(8, 32, "420", True).nseg == 2 and cg.enc_geom(8, 32, "420", True, cg.LONG).ntasks == 65536
+
+
+# ------------------------------------------------------------------ the table stage's launches
+def test_lut_span_by_hand():
+    """200 x 100 at (5, 7) of a 208 x 120 4:4:4 canvas: rows 208 apart, a gap of 8 between a row's end
+    and the next one's start, so no piece lies between two rows; the span is 99 * 208 + 200 bytes."""
+    luma, chroma = cg.lut_plane_geoms(208, 120, "444", 5, 7, 200, 100)
+    assert luma == (200, 100, 208, 7 * 208 + 5) == (200, 100, 208, 1461)
+    assert chroma == (200, 100, 208, 208 * 120 + 1461)
+    assert (-1461) & 15 == 11 and (208 * 120) % 16 == 0 and (3 * 208 * 120) % 16 == 0
+    nb = 99 * 208 + 200
+    assert nb == 20792 and nb >> 4 == 1299 and (nb - 11) >> 4 == 1298
+    sp = cg.lut_span(200, 100, 208, 11)
+    assert cg.LUT_PER_WG == 1024 and (sp.wgs, sp.head, sp.tail) == (2, 11, nb - 11 - 16 * 1298) == (2, 11, 13)
+    assert sp.whole + sp.over_row_end == 1298 and sp.skipped == sp.late_skipped == 0
+    # 208 = 13 pieces: every row end (span bytes 200..207 of a row) lies inside one piece or on the seam of two,
+    # counted here from the rows instead of from the pieces
+    over = set()
+    for r in range(100):
+        for j in range(r * 208 + 200, r * 208 + 208):      # the gap behind row r; the pieces that hold a byte of it
+            if j - 11 >= 0 and (j - 11) // 16 < 1298:
+                over.add((j - 11) // 16)
+    assert len(over) == sp.over_row_end == 198 and sum(1 for k in over if k >= 1024) == sp.late_over == 42
+    assert sp.whole == 1100
+    # flat: rows fold into one; the kernel's own piece count is one less behind a head
+    assert cg.lut_span(130, 66, 130) == cg.LutSpan(1, 536, 0, 0, 0, 0, 0, 4)
+    assert cg.lut_span(256, 160, 256) == cg.LutSpan(3, 2560, 0, 0, 0, 0, 0, 0)
+    assert cg.lut_span(301, 203, 301, 13) == cg.LutSpan(4, 3818, 0, 0, 0, 0, 13, 2)
+    assert cg.lut_span(3, 3, 3, 15) == cg.LutSpan(1, 0, 0, 0, 0, 0, 9, 0)      # all head
+    # the largest canvas of tests/test_gpu_eq.py: 159 pieces, one workgroup
+    assert (31 * 80 + 64) >> 4 == 159 and cg.lut_span(64, 32, 80).wgs == 1 and cg.lut_span(64, 32, 80).late_over == 0
+
+
+def test_lut_span_of_the_canvases_the_gpu_tests_encode():
+    """Cases 1 to 4 of tests/test_gpu_eq_chain.py."""
+    # the 4:2:0 pad geometry: 130 x 66 at (70, 38) of 264 x 136; chroma 65 x 33 at (35, 19) of 132 x 68
+    luma, chroma = cg.lut_plane_geoms(264, 136, "420", 70, 38, 130, 66)
+    assert luma == (130, 66, 264, 38 * 264 + 70) and chroma == (65, 33, 132, 264 * 136 + 19 * 132 + 35)
+    sp = cg.lut_out_spans(264, 136, "420", 70, 38, 130, 66)
+    assert sp[(0, 0)] == cg.LutSpan(2, 495, 98, 487, 5, 22, 10, 0) and 65 * 264 + 130 == 17290
+    assert sp[(1, 0)] == sp[(2, 0)] == cg.LutSpan(1, 108, 56, 104, 0, 0, 1, 0)
+    # 500 x 280 at (12, 14) of 520 x 300: the chroma gap of 10 skips nothing; at (20, 14) of 540 x 300 it does
+    sp = cg.lut_out_spans(520, 300, "420", 12, 14, 500, 280)
+    assert sp[(0, 0)] == cg.LutSpan(9, 8540, 418, 140, 372, 124, 4, 8)
+    assert sp[(1, 0)] == cg.LutSpan(3, 2065, 208, 0, 114, 0, 14, 8) and sp[(2, 0)] == cg.LutSpan(3, 2065, 209, 0, 114, 0, 6, 0)
+    sp = cg.lut_out_spans(540, 300, "420", 20, 14, 500, 280)
+    assert all(sp[(p, 0)].wgs == 3 and sp[(p, 0)].late_skipped >= 1 and sp[(p, 0)].late_over >= 1 for p in (1, 2))
+    # flat, and flat on odd frame bytes
+    assert set(cg.lut_out_spans(256, 160, "444", 0, 0, 256, 160, 3).values()) == {cg.LutSpan(3, 2560, 0, 0, 0, 0, 0, 0)}
+    sp = cg.lut_out_spans(301, 203, "420", 0, 0, 301, 203, 3)
+    assert [sp[(0, f)][-2:] for f in range(3)] == [(0, 15), (13, 2), (10, 5)] and sp[(1, 1)].whole == 961
+    # a pad with rows as wide as the picture is flat
+    assert cg.lut_plane_geoms(64, 48, "420", 0, 8, 64, 32)[0][:3] == (64, 32, 64) and cg.lut_span(64, 32, 64).over_row_end == 0
+
+
+# ------------------------------------------------------------------ the seeded sweep with a table
+def test_eq_predict_and_features():
+    base = cg.Config(300, 200, "420", (6, 16, 224, 128), "420", None, None, None, False, 5, {}, "host", 3, 1)
+    cfg = cg.EqConfig(*base, 0, "bff", None, "perm", None)
+    assert cg.eq_predict(cfg)[:2] == (IN_PLACE | UA, (NONE, NONE))
+    assert cg.eq_features(cfg, *cg.eq_predict(cfg)[:2]) == {"host", "default", "in_perm", "in_place_d_deint", "read_in_place_ua"}
+    # slot "out" runs the sws stage as a sharpen does: the rectangle goes through k_plane_copy's RECT form
+    cfg = cfg._replace(lut_out="perm_id_y", deint=None)
+    assert cg.eq_predict(cfg) == (0, (COPY, COPY), True)
+    assert cg.eq_features(cfg, 0, (COPY, COPY)) == {"host", "default", "in_perm", "out_perm_id_y", "both_slots", "in_to_d_lut",
+                                                    "d_lut_host", "read_rect_copy", "read_plane_copy", "out_flat"}
+    # the 4:2:0 pad case behind an orientation, a sharpen behind slot "out"; with an identity Y only the chroma counts
+    cfg = cg.EqConfig(260, 132, "420", None, "420", 130, 66, (70, 38, 264, 136), False, 5, {"rst": True}, "segments", 3, 1,
+                      5, "tff_nospatial", cg.SHARPS[2], "perm_id_uv", "perm")
+    assert cg.eq_features(cfg, *cg.eq_predict(cfg)[:2]) == {
+        "segments", "rst", "in_perm_id_uv", "out_perm", "both_slots", "in_place_d_orient", "read_k_scale", "out_strided",
+        "out_strided_past_one_wg", "out_late_over", "out_late_skipped", "out_sharp_behind", "out_strided_v_second_slot"}
+    # (65 x 33 at a stride of 132 behind a head of 1: 268 pieces, piece 256 at column 5 of row 31 is whole)
+    assert (1 + 16 * 256) % 132 == 5 and (33 * 132 - 67 - 1) >> 4 == 268
+    assert "out_strided_past_one_wg" not in cg.eq_features(cfg._replace(lut_out="perm_id_y"), *cg.eq_predict(cfg)[:2])
+
+
+def test_eq_sweep_draw_and_its_floors():
+    """The sweep of tests/test_gpu_eq_chain.py, counted without a GPU: the configurations of sweep_configs
+    for its seed, each with a table in at least one slot, and per part exactly the feature counts the GPU
+    test uses as floors, every one at least 1."""
+    seed, count = cg.EQ_SWEEP_SEED, cg.EQ_SWEEP_COUNT
+    assert seed == 168 and count % 4 == 0
+    cfgs = cg.eq_sweep_configs(seed, count)
+    assert len(cfgs) == count and cfgs == cg.eq_sweep_configs(seed, count)
+    for c, b in zip(cfgs, cg.sweep_configs(seed, count)):
+        assert tuple(c[:11]) == tuple(b[:11]) and c.fseed == b.fseed
+        assert c.lut_in in cg.LUT_KINDS and c.lut_out in cg.LUT_KINDS and (c.lut_in or c.lut_out)
+        assert c.deint in cg.DEINTS and c.unsharp in cg.SHARPS
+        assert 0 <= c.orient <= 7 and not (c.src == "422" and c.orient & 1)
+        if c.deint:
+            assert c.nframes == 3 and c.submit in ("host", "dev_odd", "segments")
+        else:
+            assert (c.submit, c.nframes) == (b.submit, b.nframes)
+        enc_path = cg.eq_predict(c)[0]
+        assert not (enc_path & IN_PLACE and (c.lut_out or c.unsharp))      # what k_encode reads in place has slot "in" only
+    per = count // 4
+    parts = [cg.eq_predicted_counts(cfgs[i * per:(i + 1) * per]) for i in range(4)]
+    assert parts == cg.EQ_SWEEP_FLOORS
+    assert all(set(p) == set(cg.EQ_FEATURES) and min(p.values()) >= 1 for p in parts)
+    assert len(cg.EQ_FEATURES) == 38 and len(set(cg.EQ_FEATURES)) == 38

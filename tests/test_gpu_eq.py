@@ -171,8 +171,9 @@ ALONE = [(9, 5, "420"), (33, 17, "444"), (130, 66, "420"), (4100, 5, "444")]
 @pytest.mark.parametrize("device", [False, True], ids=["host", "device+1"])
 @pytest.mark.parametrize("w,h,c", ALONE, ids=[f"{w}x{h}_{c}" for w, h, c in ALONE])
 def test_lut_in_alone_k_encode_reads_the_mapped_frames_in_place(w, h, c, device):
-    """9x5 4:2:0: chroma planes of 15 bytes, all head and tail; 33x17 4:4:4: odd frame bytes; 130x66: luma
-    past one workgroup; 4100x5: long rows."""
+    """9x5 4:2:0: chroma planes of 15 bytes, all head and tail; 33x17 4:4:4: odd frame bytes; 130x66: 536 luma
+    pieces, so slots i = 0..2 of one workgroup's 1024 (past one workgroup: tests/test_gpu_eq_chain.py); 4100x5:
+    long rows, two workgroups a plane."""
     _run(w, h, c, lut_in=T_IN, device=device, want_paths=(0, 0, 1))
 
 

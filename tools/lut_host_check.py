@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """k_lut_plane's body on the CPU: builds tools/lut_host.hip (the kernel's __host__ __device__ body run
 over every (workgroup, thread) of its launches) with AddressSanitizer and UBSan on the host side, and
-compares its output with tests/eq_ref.py for every shape of tests/test_gpu_eq.py and a few smaller
-ones.  Slot "in": three frames into a second buffer, in place, and as segments of 1 + 3 + 1 and 1 + 1 + 2
+compares its output with tests/eq_ref.py for every shape of tests/test_gpu_eq.py and
+tests/test_gpu_eq_chain.py and a few smaller ones.  Slot "in": three frames into a second buffer, in place, and as segments of 1 + 3 + 1 and 1 + 1 + 2
 + 1 in allocations of their own, each one byte in; with permutation tables, with an identity Y and
 with an identity U.  Slot "out": the picture of a padded canvas in place, where every byte outside it
 must stay.  Every buffer is allocated at exactly its size, so a load or store outside a frame stops
@@ -27,11 +27,19 @@ SHIFTS = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}
 # tests/test_gpu_eq.py's frames (203x301: 301x203 behind a transpose; 36x20, 40x24, 24x16: the worker's), and smaller ones
 SHAPES = [(9, 5, "420"), (33, 17, "444"), (130, 66, "420"), (4100, 5, "444"), (203, 301, "420"), (130, 66, "444"),
           (130, 66, "422"), (40, 24, "420"), (1, 1, "444"), (2, 2, "420"), (15, 1, "444"), (16, 1, "444"), (17, 3, "422"),
-          (1030, 5, "420")]
+          (1030, 5, "420"),
+          # tests/test_gpu_eq_chain.py's: planes past one workgroup (301x203: odd frame bytes; 208x562: eight workgroups)
+          (301, 203, "420"), (256, 160, "420"), (256, 160, "444"), (208, 562, "444"), (197, 70, "444"), (260, 132, "420"),
+          (500, 280, "420"), (200, 100, "444")]
 # slot "out": (canvas w, h, format, px, py, picture w, h)
 CANVASES = [(80, 48, "420", 6, 10, 64, 32), (80, 48, "444", 3, 5, 64, 32), (64, 32, "420", 0, 0, 64, 32),
             (32, 24, "420", 4, 4, 24, 16), (70, 40, "422", 2, 3, 31, 17), (40, 9, "444", 25, 2, 15, 7),
-            (300, 20, "444", 1, 1, 290, 18)]
+            (300, 20, "444", 1, 1, 290, 18),
+            # tests/test_gpu_eq_chain.py's: spans past one workgroup (16 KB), strided (row ends 8 bytes apart; skipped
+            # pieces; the chroma past one workgroup; odd offsets) and flat (301x203: frames at odd addresses)
+            (208, 120, "444", 5, 7, 200, 100), (520, 300, "420", 11, 13, 500, 280), (520, 300, "420", 12, 14, 500, 280), (540, 300, "420", 20, 14, 500, 280),
+            (264, 136, "420", 70, 38, 130, 66), (203, 101, "444", 69, 35, 66, 33), (1040, 40, "422", 3, 1, 1001, 37),
+            (256, 160, "444", 0, 0, 256, 160), (301, 203, "420", 0, 0, 301, 203), (197, 70, "444", 0, 0, 197, 70)]
 SPLITS = [(1, 3, 1), (1, 1, 2, 1)]
 
 
