@@ -46,6 +46,7 @@ EXPORTS = (
     "mjg_open_deint", "mjg_submit_halo", "mjg_debug_deint", "mjg_debug_deint_flags",
     "mjg_open_sharp", "mjg_debug_presharp", "mjg_debug_unsharp",
     "mjg_open_lut", "mjg_debug_lut", "mjg_debug_lut_in",
+    "mjg_debug_tail",
 )
 
 # mjg_open_deint's `deint`
@@ -81,6 +82,18 @@ class MjgLut(C.Structure):
     """mjg_lut: a 256-entry table per plane, out = t[in]."""
     _fields_ = [("y", C.c_uint8 * 256), ("u", C.c_uint8 * 256), ("v", C.c_uint8 * 256)]
 
+
+class MjgTailJob(C.Structure):
+    """mjg_tail_job: chunks for mjg_debug_tail (the stuffing tail alone; tests/test_gpu_tail.py)."""
+    _fields_ = [("nframes", C.c_int32), ("nseg", C.c_int32), ("nchunks", C.c_int32),
+                ("chunk_bits", C.POINTER(C.c_uint32)), ("words", C.POINTER(C.c_uint32)), ("fill", C.c_uint32),
+                ("hdr", C.POINTER(C.c_uint8)), ("hdr_len", C.c_int32),
+                ("dht", C.POINTER(C.c_uint8)), ("nval", C.POINTER(C.c_uint32)),
+                ("dht_pos", C.c_int32), ("dht_end", C.c_int32), ("out_cap", C.c_uint64)]
+
+
+MJG_TAIL_GUARD = 64
+MJG_TAIL_MAX_SLOTS = 8192
 
 _lib = None
 _lock = threading.Lock()
@@ -167,6 +180,10 @@ def load():
                                        C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         if hasattr(L, "mjg_debug_huff_build"):  # absent from libraries built before r05 (A/B builds)
             L.mjg_debug_huff_build.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.c_int, u8p, C.POINTER(C.c_uint32)]
+        if hasattr(L, "mjg_debug_tail"):  # absent from libraries built before the tail hook (A/B builds)
+            L.mjg_debug_tail.argtypes = [C.c_int, C.POINTER(MjgTailJob), u8p, C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+            L.mjg_debug_tail.restype = C.c_int
         if hasattr(L, "mjg_debug_scale_path"):  # absent from libraries built before 1.3 (A/B builds)
             L.mjg_debug_scale_path.argtypes = [vp, C.c_int]
             L.mjg_debug_scale_path.restype = C.c_int
@@ -184,7 +201,7 @@ def load():
                  "mjg_debug_encode_path", "mjg_open_orient", "mjg_debug_oriented", "mjg_debug_orient",
                  "mjg_open_deint", "mjg_submit_halo", "mjg_debug_deint", "mjg_debug_deint_flags",
                  "mjg_open_sharp", "mjg_debug_presharp", "mjg_debug_unsharp",
-                 "mjg_open_lut", "mjg_debug_lut", "mjg_debug_lut_in")
+                 "mjg_open_lut", "mjg_debug_lut", "mjg_debug_lut_in", "mjg_debug_tail")
                 if os.environ.get("MJG_LIBRARY") else ())
         for name in EXPORTS:
             if name not in late:

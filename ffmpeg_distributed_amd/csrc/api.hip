@@ -1340,13 +1340,22 @@ void tmark(mjg_ctx *c, Slot &S, int k, int end) {
   (void)hipEventRecord(S.ev[k][end], tail ? c->tail : S.st);
 }
 
+// The stuffing tail's launch sizes, one place for submit_impl, launch_write and mjg_debug_tail:
+// groups a segment; k_scan_bits_seg's workgroups (a wave per segment, 4 a workgroup); k_count_ff's
+// and k_write's (a wave per group, 4 a workgroup).  k_scan_bits and k_scan_ff take a workgroup a
+// frame (1024 and 256 threads).
+inline int tail_gps(int nchunks) { return (nchunks + kChunksPerWave - 1) / kChunksPerWave; }
+inline int tail_seg_wgs(int nsegs) { return (nsegs + 3) / 4; }
+inline int tail_group_wgs(int ngroups) { return (ngroups + 3) / 4; }
+constexpr int kTailDone = 1;  // k_scan_ff's frame ticket: the `done` words k_scan_bits zeroes
+
 // status: reset the overflow flag first (the regrow path; a submit's scan kernel resets it)
 int launch_write(mjg_ctx *c, Slot &S, int n, bool reset_status) {
   const EncGeom &g = c->geom;
-  const int gps = (g.nchunks + kChunksPerWave - 1) / kChunksPerWave, ngroups = gps * n * g.nseg;
+  const int gps = tail_gps(g.nchunks), ngroups = gps * n * g.nseg;
   if (reset_status) HIP_TRY(hipMemsetAsync(S.d_status, 0, 4, c->tail));
   tmark(c, S, MJG_K_WRITE, 0);
-  k_write<<<(ngroups + 3) / 4, 256, 0, c->tail>>>(
+  k_write<<<tail_group_wgs(ngroups), 256, 0, c->tail>>>(
       S.d_stream, S.d_chunk_bits, S.d_chunk_off, S.d_frame_bits, S.d_ff_off, g.nchunks, gps, g.nseg, n,
       S.d_seg_size, S.d_seg_off, S.d_frame_offsets, c->d_hdr, (int)c->hdr.size(),
       c->optimal ? S.d_hdr_lens : nullptr, (int)c->dht_pos, (int)c->dht_end, S.d_dht,
@@ -1618,9 +1627,9 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
   HIP_TRY(hipStreamWaitEvent(c->tail, S.enc_done, 0));
   if (c->timing_tail) (void)hipEventRecord(S.ev[MJG_K_TAIL][0], c->tail);
   tmark(c, S, MJG_K_SCAN_BITS, 0);
-  const int ndone = 1;  // k_scan_ff's frame ticket
+  const int ndone = kTailDone;
   if (c->rst)
-    k_scan_bits_seg<<<(nsegs + 3) / 4, 256, 0, c->tail>>>(S.d_chunk_bits, S.d_chunk_off, S.d_frame_bits, g.nchunks, nsegs,
+    k_scan_bits_seg<<<tail_seg_wgs(nsegs), 256, 0, c->tail>>>(S.d_chunk_bits, S.d_chunk_off, S.d_frame_bits, g.nchunks, nsegs,
                                                           S.d_work, S.d_status, S.d_done, ndone);
   else
     k_scan_bits<<<n, 1024, 0, c->tail>>>(S.d_chunk_bits, S.d_chunk_off, S.d_frame_bits, g.nchunks,
@@ -1628,8 +1637,8 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
   tmark(c, S, MJG_K_SCAN_BITS, 1);
   HIP_TRY(hipGetLastError());
   tmark(c, S, MJG_K_COUNT_FF, 0);
-  const int gps = (g.nchunks + kChunksPerWave - 1) / kChunksPerWave;
-  k_count_ff<<<(gps * nsegs + 3) / 4, 256, 0, c->tail>>>(S.d_scratch, S.d_chunk_bits, S.d_chunk_off,
+  const int gps = tail_gps(g.nchunks);
+  k_count_ff<<<tail_group_wgs(gps * nsegs), 256, 0, c->tail>>>(S.d_scratch, S.d_chunk_bits, S.d_chunk_off,
                                                            S.d_frame_bits, S.d_group_ff, g.nchunks, gps,
                                                            gps * nsegs, S.d_stream);
   tmark(c, S, MJG_K_COUNT_FF, 1);
@@ -2133,6 +2142,123 @@ int mjg_debug_huff_build(int device, const uint32_t *hist, int nframes, uint8_t 
   (void)hipFree(d_ftabs);
   (void)hipFree(d_dht);
   (void)hipFree(d_nval);
+  return rc;
+}
+
+int mjg_debug_tail(int device, const mjg_tail_job *job, uint8_t *out, uint64_t *frame_offsets, uint32_t *group_ff,
+                   uint32_t *status) {
+  // every check before any HIP call: a host without a GPU answers them
+  if (!job || !out || !frame_offsets || !status) return set_err(MJG_E_INVALID, "null argument");
+  const mjg_tail_job &j = *job;
+  if (!j.chunk_bits || !j.words || !j.hdr) return set_err(MJG_E_INVALID, "null chunk_bits, words or hdr");
+  if (j.nframes < 1 || j.nseg < 1 || j.nchunks < 1 || j.hdr_len < 1 || j.hdr_len > 65536)
+    return set_err(MJG_E_INVALID, "nframes %d, nseg %d, nchunks %d or hdr_len %d: below 1 (hdr_len: or above 65536)",
+                   j.nframes, j.nseg, j.nchunks, j.hdr_len);
+  const uint64_t nslots64 = (uint64_t)j.nframes * (uint64_t)j.nseg * (uint64_t)j.nchunks;
+  if (nslots64 > MJG_TAIL_MAX_SLOTS)
+    return set_err(MJG_E_INVALID, "%d frames x %d segments x %d chunks: more than %d slots", j.nframes, j.nseg,
+                   j.nchunks, MJG_TAIL_MAX_SLOTS);
+  if (j.out_cap > (1ull << 30)) return set_err(MJG_E_INVALID, "out_cap above 2^30");
+  const bool optimal = j.nval != nullptr;
+  if (optimal) {
+    if (!j.dht) return set_err(MJG_E_INVALID, "nval without dht");
+    // frame_hdr_len takes the default DHT for 4 + 4 * 17 + 348 bytes
+    if (j.dht_pos < 0 || j.dht_end != j.dht_pos + 420 || j.dht_end > j.hdr_len)
+      return set_err(MJG_E_INVALID, "dht_pos %d, dht_end %d: not a 420-byte DHT inside the %d header bytes", j.dht_pos,
+                     j.dht_end, j.hdr_len);
+    for (size_t i = 0; i < (size_t)j.nframes * 4; i++)
+      if (j.nval[i] > 256) return set_err(MJG_E_INVALID, "nval[%zu] = %u: above 256", i, j.nval[i]);
+  }
+  const size_t nslots = (size_t)nslots64, nsegs = (size_t)j.nframes * j.nseg;
+  constexpr uint32_t kSlotBits = (uint32_t)kSlotWords * 32u;
+  for (size_t i = 0; i < nslots; i++) {
+    const uint32_t L = j.chunk_bits[i];
+    const bool last = (i + 1) % (size_t)j.nchunks == 0;
+    if (L == 0) return set_err(MJG_E_INVALID, "chunk %zu has 0 bits", i);
+    if (L < 32 && !last)
+      return set_err(MJG_E_INVALID, "chunk %zu has %u bits and is not its segment's last: every other chunk covers "
+                     "a word start (32 bits or more)", i, L);
+  }
+  // the scratch image: every slot word `fill`, then each chunk's words at its slot
+  std::vector<uint32_t> image(nslots * (size_t)kSlotWords, j.fill);
+  {
+    const uint32_t *w = j.words;
+    for (size_t i = 0; i < nslots; i++) {
+      const size_t nw = (std::min(j.chunk_bits[i], kSlotBits) + 31u) / 32u;
+      memcpy(image.data() + i * (size_t)kSlotWords, w, nw * 4);
+      w += nw;
+    }
+  }
+  HIP_TRY(hipSetDevice(device));
+  const int gps = tail_gps(j.nchunks), ngroups = gps * (int)nsegs;
+  const size_t nwork = (size_t)kXcds * kCtrStride, nout = (size_t)j.out_cap + MJG_TAIL_GUARD;
+  uint32_t *d_scratch = nullptr, *d_stream = nullptr, *d_bits = nullptr, *d_off = nullptr, *d_gff = nullptr;
+  uint32_t *d_ffo = nullptr, *d_segb = nullptr, *d_status = nullptr, *d_done = nullptr, *d_work = nullptr;
+  uint32_t *d_segsz = nullptr, *d_segoff = nullptr, *d_hl = nullptr, *d_nval = nullptr;
+  uint64_t *d_fsz = nullptr, *d_fo = nullptr;
+  uint8_t *d_hdr = nullptr, *d_dht = nullptr, *d_out = nullptr;
+  const size_t ndht = (size_t)j.nframes * 4 * kDhtSlot;
+  auto run = [&]() -> int {
+    int rc;
+    if ((rc = dmalloc(&d_scratch, image.size())) || (rc = dmalloc(&d_stream, image.size())) ||
+        (rc = dmalloc(&d_bits, nslots)) || (rc = dmalloc(&d_off, nslots)) || (rc = dmalloc(&d_gff, (size_t)ngroups)) ||
+        (rc = dmalloc(&d_ffo, (size_t)ngroups)) || (rc = dmalloc(&d_segb, nsegs)) || (rc = dmalloc(&d_status, 1)) ||
+        (rc = dmalloc(&d_done, (size_t)kTailDone)) || (rc = dmalloc(&d_work, nwork)) ||
+        (rc = dmalloc(&d_fsz, (size_t)j.nframes)) || (rc = dmalloc(&d_fo, (size_t)j.nframes + 1)) ||
+        (rc = dmalloc(&d_hdr, (size_t)j.hdr_len)) || (rc = dmalloc(&d_out, nout)))
+      return rc;
+    if (j.nseg > 1 && ((rc = dmalloc(&d_segsz, nsegs)) || (rc = dmalloc(&d_segoff, nsegs)))) return rc;
+    if (optimal && ((rc = dmalloc(&d_hl, (size_t)j.nframes)) || (rc = dmalloc(&d_nval, (size_t)j.nframes * 4)) ||
+                    (rc = dmalloc(&d_dht, ndht))))
+      return rc;
+    HIP_TRY(hipMemcpy(d_scratch, image.data(), image.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_bits, j.chunk_bits, nslots * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_hdr, j.hdr, (size_t)j.hdr_len, hipMemcpyHostToDevice));
+    if (optimal) {
+      HIP_TRY(hipMemcpy(d_nval, j.nval, (size_t)j.nframes * 16, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(d_dht, j.dht, ndht, hipMemcpyHostToDevice));
+    }
+    // the counters and the flag non-zero: the scan kernel is what zeroes them.  Offsets and
+    // counts that no kernel wrote come back as 0xFF.., the stream's unwritten words as 0x5A..
+    HIP_TRY(hipMemset(d_work, 0xFF, nwork * 4));
+    HIP_TRY(hipMemset(d_status, 0xFF, 4));
+    HIP_TRY(hipMemset(d_done, 0xFF, (size_t)kTailDone * 4));
+    HIP_TRY(hipMemset(d_fo, 0xFF, ((size_t)j.nframes + 1) * 8));
+    HIP_TRY(hipMemset(d_gff, 0xFF, (size_t)ngroups * 4));
+    HIP_TRY(hipMemset(d_stream, 0x5A, image.size() * 4));
+    HIP_TRY(hipMemset(d_out, 0xA5, nout));
+    if (j.nseg > 1)
+      k_scan_bits_seg<<<tail_seg_wgs((int)nsegs), 256>>>(d_bits, d_off, d_segb, j.nchunks, (int)nsegs, d_work, d_status,
+                                                         d_done, kTailDone);
+    else
+      k_scan_bits<<<j.nframes, 1024>>>(d_bits, d_off, d_segb, j.nchunks, d_work, d_status, d_done, kTailDone);
+    HIP_TRY(hipGetLastError());
+    k_count_ff<<<tail_group_wgs(ngroups), 256>>>(d_scratch, d_bits, d_off, d_segb, d_gff, j.nchunks, gps, ngroups,
+                                                 d_stream);
+    HIP_TRY(hipGetLastError());
+    k_scan_ff<<<j.nframes, 256>>>(d_gff, d_ffo, d_segb, j.nchunks, gps, j.nseg, j.hdr_len, optimal ? d_nval : nullptr,
+                                  d_hl, d_segsz, d_segoff, d_fsz, d_fo, d_done);
+    HIP_TRY(hipGetLastError());
+    k_write<<<tail_group_wgs(ngroups), 256>>>(d_stream, d_bits, d_off, d_segb, d_ffo, j.nchunks, gps, j.nseg, j.nframes,
+                                              d_segsz, d_segoff, d_fo, d_hdr, j.hdr_len, optimal ? d_hl : nullptr,
+                                              j.dht_pos, j.dht_end, d_dht, optimal ? d_nval : nullptr, d_out, j.out_cap,
+                                              d_status);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, d_out, nout, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(frame_offsets, d_fo, ((size_t)j.nframes + 1) * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(status, d_status, 4, hipMemcpyDeviceToHost));
+    if (group_ff) HIP_TRY(hipMemcpy(group_ff, d_gff, (size_t)ngroups * 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> work(nwork);
+    HIP_TRY(hipMemcpy(work.data(), d_work, nwork * 4, hipMemcpyDeviceToHost));
+    for (int x = 0; x < kXcds; x++)
+      if (work[(size_t)x * kCtrStride]) return set_err(MJG_E_STATE, "the scan left work counter %d at %u", x, work[(size_t)x * kCtrStride]);
+    return MJG_OK;
+  };
+  const int rc = run();
+  void *bufs[] = {d_scratch, d_stream, d_bits, d_off, d_gff, d_ffo, d_segb, d_status, d_done, d_work,
+                  d_segsz, d_segoff, d_hl, d_nval, d_fsz, d_fo, d_hdr, d_dht, d_out};
+  for (void *p : bufs) (void)hipFree(p);
   return rc;
 }
 

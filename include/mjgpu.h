@@ -415,6 +415,41 @@ int mjg_debug_filter(mjg_ctx *ctx, int plane, int dir, int16_t *coeff, int32_t *
  * 2 AC luma, 3 AC chroma) and nval[f][t] (HUFFVAL entries).  Replaces the table build of
  * ff_mjpeg_encode_huffman_close (libavcodec/mjpegenc_huffman.c); tests compare it with the oracle. */
 int mjg_debug_huff_build(int device, const uint32_t *hist, int nframes, uint8_t *dht, uint32_t *nval);
+/* The stuffing tail (k_scan_bits or k_scan_bits_seg, k_count_ff, k_scan_ff, k_write: a submit's launches
+ * after k_encode, same blocks and grids) on given chunks, on GPU `device`: no context, buffers of its
+ * own, the default stream.  The scratch image is built on the host: every slot word `fill`, then each
+ * chunk's words at the start of its slot.
+ * Domain, as k_encode leaves its chunks (64 blocks of 2 bits or more): no chunk of 0 bits, and
+ * every chunk but its segment's last has 32 bits or more, so that it covers the start of a word of the
+ * segment (a word belongs to the chunk that holds its first bit).  A length above the slot's bits is
+ * accepted, and clamped by the scan as in a submit; `words` then holds the slot's words.  At most
+ * MJG_TAIL_MAX_SLOTS chunks in all.  What is outside the domain, a null pointer or a size below 1 is
+ * MJG_E_INVALID with a message, before any HIP call (so on a host without a GPU too).
+ * out: out_cap + MJG_TAIL_GUARD bytes, all 0xA5 before k_write and all copied back, so a byte written
+ * past a frame's end, past out_cap or into a frame k_write refused shows.  frame_offsets: nframes + 1.
+ * group_ff: NULL, or k_count_ff's 0xFF count per group of 32 chunks (nframes * nseg *
+ * ceil(nchunks / 32)).  *status: k_write's overflow flag (1: a frame ended past out_cap).  The
+ * counters and the flag the scan kernel zeroes in a submit are non-zero before it here; a unit counter
+ * it leaves non-zero is MJG_E_STATE. */
+typedef struct mjg_tail_job {
+  int32_t nframes, nseg, nchunks; /* nseg entropy-coded segments a frame (1: no RST; above 1:
+                                     k_scan_bits_seg, segment sizes and offsets, RSTn), nchunks
+                                     chunks a segment */
+  const uint32_t *chunk_bits;     /* [nframes * nseg * nchunks] bit lengths (unclamped) */
+  const uint32_t *words;          /* the chunks' slot words, chunk after chunk: ceil(min(L, slot
+                                     bits) / 32) words each, bits MSB first, zero past the last bit */
+  uint32_t fill;                  /* every other word of the scratch image */
+  const uint8_t *hdr;             /* the bytes every frame starts with */
+  int32_t hdr_len;                /* 1..65536 */
+  const uint8_t *dht;             /* NULL, or -huffman optimal's tables a frame, as k_huff_build */
+  const uint32_t *nval;           /* leaves them: dht[f][4][272], nval[f][4] (each <= 256); hdr then */
+  int32_t dht_pos, dht_end;       /* holds the default DHT (420 bytes) at [dht_pos, dht_end) */
+  uint64_t out_cap;               /* k_write's capacity (<= 2^30) */
+} mjg_tail_job;
+#define MJG_TAIL_GUARD 64
+#define MJG_TAIL_MAX_SLOTS 8192
+int mjg_debug_tail(int device, const mjg_tail_job *job, uint8_t *out, uint64_t *frame_offsets,
+                   uint32_t *group_ff, uint32_t *status);
 
 #ifdef __cplusplus
 }

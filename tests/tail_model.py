@@ -21,9 +21,10 @@ def _shfl(x, src):
 
 
 class Seg:
-    """One entropy-coded segment: chunk bit lengths and their slot words (bits MSB first)."""
+    """One entropy-coded segment: chunk bit lengths and their slot words (bits MSB first), the
+    bits drawn from rng or given per chunk."""
 
-    def __init__(self, lengths, rng):
+    def __init__(self, lengths, rng, bits=None):
         self.L = np.asarray(lengths, np.int64)
         self.n = len(self.L)
         self.O = np.concatenate([[0], np.cumsum(self.L)[:-1]]).astype(np.int64)
@@ -31,7 +32,8 @@ class Seg:
         self.slots = np.zeros((self.n + 1) * SLOT, np.uint64)  # one spare slot past the end
         self.bits = []
         for c, L in enumerate(self.L):
-            b = rng.integers(0, 2, int(L), dtype=np.uint8)
+            b = rng.integers(0, 2, int(L), dtype=np.uint8) if bits is None else np.asarray(bits[c], np.uint8)
+            assert len(b) == L
             self.bits.append(b)
             nw = (int(L) + 31) // 32
             pad = np.zeros(nw * 32, np.uint8)

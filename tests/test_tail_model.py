@@ -1,10 +1,13 @@
 """CPU check of the stuffing tail's word fetch (k_count_ff / k_write `group_values`) through its
 lane-level model (tests/tail_model.py): every segment word equals the concatenated chunk bits
 with the 1-bit byte padding, and no slot load leaves the words k_encode wrote (the chunk's
-ceil(L / 32) words, or the next chunk's first word)."""
+ceil(L / 32) words, or the next chunk's first word).  The layouts the GPU runs
+(tests/tail_layouts.py, tests/test_gpu_tail.py) go through the model too, segment by segment: the
+GPU cannot show a load outside those words, the model can."""
 import numpy as np
 import pytest
 
+import tail_layouts
 from tail_model import G, R, Seg, segment_words
 
 
@@ -28,9 +31,7 @@ def _layouts():
     yield "long chunks (many rounds)", [64 * 1664] * 3 + [4]
 
 
-@pytest.mark.parametrize("name,lengths", list(_layouts()))
-def test_group_values_model(name, lengths):
-    seg = Seg(lengths, np.random.default_rng(len(lengths)))
+def _check(seg):
     got = segment_words(seg)
     exp = seg.expected_words()
     assert sorted(got) == list(range(len(exp))), "words missing or extra"
@@ -39,3 +40,21 @@ def test_group_values_model(name, lengths):
     oob = [t for t in seg.touched if not t[2]]
     assert not oob, f"loads outside the written words: {oob[:5]}"
     assert R >= 1
+
+
+@pytest.mark.parametrize("name,lengths", list(_layouts()))
+def test_group_values_model(name, lengths):
+    _check(Seg(lengths, np.random.default_rng(len(lengths))))
+
+
+@pytest.mark.parametrize("name", [n for n, lay in tail_layouts.layouts().items() if lay.model])
+def test_group_values_model_on_the_gpu_layouts(name):
+    """Every segment of the layout, its lengths clamped to the slot as the scan leaves them."""
+    lay = tail_layouts.layouts()[name]
+    L = lay.clamped()
+    for s in range(lay.nframes * lay.nseg):
+        i0 = s * lay.nchunks
+        try:
+            _check(Seg(L[i0:i0 + lay.nchunks], None, bits=lay.bits[i0:i0 + lay.nchunks]))
+        except AssertionError as e:
+            raise AssertionError(f"{name}: segment {s}, lengths {L[i0:i0 + lay.nchunks][:8].tolist()}..: {e}") from None
