@@ -47,6 +47,7 @@ EXPORTS = (
     "mjg_open_sharp", "mjg_debug_presharp", "mjg_debug_unsharp",
     "mjg_open_lut", "mjg_debug_lut", "mjg_debug_lut_in",
     "mjg_debug_tail",
+    "mjg_open_cmat", "mjg_debug_cmat", "mjg_debug_cmat_out",
 )
 
 # mjg_open_deint's `deint`
@@ -94,6 +95,12 @@ class MjgTailJob(C.Structure):
 
 MJG_TAIL_GUARD = 64
 MJG_TAIL_MAX_SLOTS = 8192
+
+class MjgCmatrix(C.Structure):
+    """mjg_cmatrix: the six 16.16 coefficients c2..c7 of a colour matrix."""
+    _fields_ = [("yu", C.c_int32), ("yv", C.c_int32), ("uu", C.c_int32), ("uv", C.c_int32), ("vu", C.c_int32),
+                ("vv", C.c_int32)]
+
 
 _lib = None
 _lock = threading.Lock()
@@ -149,6 +156,14 @@ def load():
             L.mjg_debug_lut.restype = C.c_int
             L.mjg_debug_lut_in.argtypes = [vp, C.c_int, u8p, sz]
             L.mjg_debug_lut_in.restype = C.c_int
+        if hasattr(L, "mjg_open_cmat"):  # absent from libraries built before the colour matrix (A/B builds)
+            L.mjg_open_cmat.argtypes = ([C.c_int, C.POINTER(MjgConfig)] + [C.c_int] * 7 + [C.POINTER(MjgCmatrix)]
+                                        + [C.POINTER(MjgLut)] * 2 + [C.POINTER(MjgUnsharp)] + [C.c_int] * 4
+                                        + [C.POINTER(vp)])
+            L.mjg_debug_cmat.argtypes = [vp, C.POINTER(MjgCmatrix)]
+            L.mjg_debug_cmat.restype = C.c_int
+            L.mjg_debug_cmat_out.argtypes = [vp, C.c_int, u8p, sz]
+            L.mjg_debug_cmat_out.restype = C.c_int
         L.mjg_close.argtypes = [vp]
         L.mjg_close.restype = None
         L.mjg_frame_bytes.argtypes = [vp]
@@ -201,7 +216,8 @@ def load():
                  "mjg_debug_encode_path", "mjg_open_orient", "mjg_debug_oriented", "mjg_debug_orient",
                  "mjg_open_deint", "mjg_submit_halo", "mjg_debug_deint", "mjg_debug_deint_flags",
                  "mjg_open_sharp", "mjg_debug_presharp", "mjg_debug_unsharp",
-                 "mjg_open_lut", "mjg_debug_lut", "mjg_debug_lut_in", "mjg_debug_tail")
+                 "mjg_open_lut", "mjg_debug_lut", "mjg_debug_lut_in", "mjg_debug_tail",
+                 "mjg_open_cmat", "mjg_debug_cmat", "mjg_debug_cmat_out")
                 if os.environ.get("MJG_LIBRARY") else ())
         for name in EXPORTS:
             if name not in late:

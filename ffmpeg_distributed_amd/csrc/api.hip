@@ -335,6 +335,13 @@ struct mjg_ctx {
   mjg_lut lut[2];
   LutGeom lpass[2][2];          // their launches: [slot][0 luma, 1 chroma]
   uint8_t *d_luts = nullptr;    // both slots' tables, 768 bytes each
+  // the colour matrix (mjg_open_cmat): behind the deinterlacer and the orientation and in front of
+  // lut[0], on whole frames in the source format (in place in d_deint / d_orient, else into the
+  // slot's d_lut, where lut[0] then runs in place).  The identity is no matrix
+  bool has_cmat = false;
+  mjg_cmatrix cmat{};
+  CmatGeom cgeom{};             // its launch
+  void (*cmat_launch)(const SegList &, uint8_t *, const CmatGeom &, const CmatCoef &, int, hipStream_t) = nullptr;
   size_t in_frame_bytes = 0, enc_frame_bytes = 0;
   // the crop rectangle (mjg_open_crop; the whole frame otherwise): the input of the sws stage,
   // or of k_encode without one
@@ -452,6 +459,7 @@ struct Layout {
   bool sharp;                  // -vf unsharp with a non-zero amount
   mjg_unsharp us;              // ... its sizes and amounts
   const mjg_lut *lut[2];       // the tables of slot "in" and slot "out" (null: none, or three identity tables)
+  const mjg_cmatrix *cm;       // the colour matrix (null: none, or the identity)
   int orient, ow, oh;          // the orientation and the oriented frame's size (orient 0: the source's)
   int cx, cy, crw, crh;        // the crop rectangle in the oriented frame: the sws stage's / k_encode's input
   int px, py, pw, ph;          // the picture's place in the canvas and the canvas size (no pad: the picture)
@@ -667,7 +675,7 @@ int alloc_slot(mjg_ctx *c, Slot &S) {
   if (c->orient && (rc = dmalloc(&S.d_orient, B * c->in_frame_bytes))) return rc;
   if (c->deint && (rc = dmalloc(&S.d_deint, B * c->in_frame_bytes))) return rc;
   if (c->sharp && (rc = dmalloc(&S.d_sharp, B * c->enc_frame_bytes))) return rc;
-  if (c->has_lut[0] && !c->orient && !c->deint && (rc = dmalloc(&S.d_lut, B * c->in_frame_bytes))) return rc;
+  if ((c->has_lut[0] || c->has_cmat) && !c->orient && !c->deint && (rc = dmalloc(&S.d_lut, B * c->in_frame_bytes))) return rc;
   if ((rc = dmalloc(&S.d_scratch, B * NC * (size_t)kSlotWords)) ||
       (rc = dmalloc(&S.d_stream, B * NC * (size_t)kSlotWords)) ||
       (rc = dmalloc(&S.d_chunk_bits, B * NC)) || (rc = dmalloc(&S.d_chunk_off, B * NC)) ||
@@ -710,8 +718,9 @@ int alloc_slot(mjg_ctx *c, Slot &S) {
 // or nullptr for no pad
 // us: -vf unsharp between the sws stage and the pad, or nullptr (both amounts 0: no filter either)
 // lut_in, lut_out: the tables in front of and behind the sws stage, or nullptr (three identity tables: none either)
-int check_config(const mjg_config &k, int src_cf, int deint, int orient, const int *crop, const mjg_lut *lut_in,
-                 const mjg_lut *lut_out, const mjg_unsharp *us, const int *pad, Layout *lay) {
+// cm: the colour matrix in front of lut_in, or nullptr (the identity: none either)
+int check_config(const mjg_config &k, int src_cf, int deint, int orient, const int *crop, const mjg_cmatrix *cm,
+                 const mjg_lut *lut_in, const mjg_lut *lut_out, const mjg_unsharp *us, const int *pad, Layout *lay) {
   if (std::min({k.src_w, k.src_h, k.dst_w, k.dst_h}) < 1 || std::max({k.src_w, k.src_h, k.dst_w, k.dst_h}) > 16384)
     return set_err(MJG_E_INVALID, "bad frame size %dx%d -> %dx%d", k.src_w, k.src_h, k.dst_w, k.dst_h);
   if (k.qscale < 1 || k.qscale > 31) return set_err(MJG_E_INVALID, "qscale %d not in 1..31", k.qscale);
@@ -806,7 +815,18 @@ int check_config(const mjg_config &k, int src_cf, int deint, int orient, const i
     for (int i = 0; l && i < 256; i++) id = id && l->y[i] == i && l->u[i] == i && l->v[i] == i;
     if (id) l = nullptr;
   }
-  *lay = Layout{deint, sharp, u, {luts[0], luts[1]}, orient, ow, oh, cx, cy, crw, crh, px, py, pw, ph, has_pad, s_hsh, s_vsh, e_hsh, e_vsh};
+  // the colour matrix: |coefficient| <= 2^18, four times unity.  With |U - 128|, |V - 128| <= 128 a sum
+  // of two products is at most 2^26 and, with the rounding term (< 2^24), below 2^27: int32 holds it
+  if (cm) {
+    const int32_t v[6] = {cm->yu, cm->yv, cm->uu, cm->uv, cm->vu, cm->vv};
+    const char *nm[6] = {"yu", "yv", "uu", "uv", "vu", "vv"};
+    for (int i = 0; i < 6; i++)
+      if (v[i] > kCmatMaxCoef || v[i] < -kCmatMaxCoef)
+        return set_err(MJG_E_INVALID, "cmatrix %s %d: outside [-%d, %d] (four times 65536)", nm[i], (int)v[i], kCmatMaxCoef,
+                       kCmatMaxCoef);
+    if (v[0] == 0 && v[1] == 0 && v[2] == 65536 && v[3] == 0 && v[4] == 0 && v[5] == 65536) cm = nullptr;
+  }
+  *lay = Layout{deint, sharp, u, {luts[0], luts[1]}, cm, orient, ow, oh, cx, cy, crw, crh, px, py, pw, ph, has_pad, s_hsh, s_vsh, e_hsh, e_vsh};
   return MJG_OK;
 }
 
@@ -834,6 +854,8 @@ int plan_geometry(const mjg_config &k, int src_cf, const Layout &lay, bool unali
     c->has_lut[i] = lay.lut[i] != nullptr;
     if (lay.lut[i]) c->lut[i] = *lay.lut[i];
   }
+  c->has_cmat = lay.cm != nullptr;
+  if (lay.cm) c->cmat = *lay.cm;
   c->scale = (crw != k.dst_w || crh != k.dst_h || src_cf != cf || c->has_pad || c->sharp || c->has_lut[1]);
   const int scw = (fw + s_hsh) >> s_hsh, sch = (fh + s_vsh) >> s_vsh;
   // the rectangle's chroma planes: at (cx >> hs, cy >> vs), the chroma size of a crw x crh frame
@@ -1211,6 +1233,24 @@ void plan_lut(const mjg_config &k, const Layout &lay, mjg_ctx *c) {
   }
 }
 
+template <int HS, int VS>
+void launch_cmat(const SegList &in, uint8_t *dst, const CmatGeom &g, const CmatCoef &cm, int n, hipStream_t st) {
+  k_cmat_frame<HS, VS><<<g.gxy * n, kCmatThreads, 0, st>>>(in, dst, g, cm);
+}
+
+// The colour matrix's launch (mjg_ctx::cgeom, cmat_launch; no device, no environment): the whole
+// frame behind the orientation, source format, frames in_frame_bytes apart on both sides.
+void plan_cmat(const Layout &lay, mjg_ctx *c) {
+  if (!c->has_cmat) return;
+  CmatGeom &g = c->cgeom;
+  g = CmatGeom{};
+  cmat_geom_frame(g, lay.ow, lay.oh, lay.s_hsh, lay.s_vsh);
+  g.s_fstride = g.d_fstride = (long long)c->in_frame_bytes;
+  g.ppr_magic = magic32((uint32_t)g.ppr);
+  g.gxy_magic = magic32((uint32_t)g.gxy);
+  c->cmat_launch = !lay.s_hsh ? launch_cmat<0, 0> : lay.s_vsh ? launch_cmat<1, 1> : launch_cmat<1, 0>;
+}
+
 // RC, DBG, UA: EncGeom's range_convert and debug_coefs, and the context's enc_ua (a crop read in
 // place at any alignment, fetch_rows<UA>)
 template <bool RC, int MODE, bool DBG, bool UA>
@@ -1258,12 +1298,16 @@ int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
     const double per_frame = 2.0 * (double)c->slot_NC * kSlotWords * 4 + 2.0 * (double)c->enc_frame_bytes +
                              (c->orient ? (double)c->in_frame_bytes : 0.0) +  // (a deinterlacer never merges)
                              (c->sharp ? (double)c->enc_frame_bytes : 0.0) +
-                             (c->has_lut[0] && !c->orient ? (double)c->in_frame_bytes : 0.0);
+                             ((c->has_lut[0] || c->has_cmat) && !c->orient ? (double)c->in_frame_bytes : 0.0);
     if (kSlots * (double)c->merge * (double)k.max_batch * per_frame > kMergeMemShare * (double)fr) c->merge = 1;
   }
   if ((unsigned long long)k.max_batch * c->merge * g.nseg * g.nchunks * g.nchunks >= ((unsigned long long)1 << 40))
     c->merge = 1;  // merged launches would overflow k_encode's task magic (checked for max_batch above)
   c->slot_B = (size_t)k.max_batch * (size_t)c->merge;  // frames one launch may carry
+  // k_cmat_frame's grid is workgroups per frame x frames in x alone
+  if (c->has_cmat && (unsigned long long)c->cgeom.gxy * c->slot_B > (unsigned long long)INT_MAX)
+    return set_err(MJG_E_INVALID, "cmatrix: %d workgroups a frame x %zu frames a launch is past 2^31 - 1", c->cgeom.gxy,
+                   c->slot_B);
   int rc;
   if ((rc = dmalloc(&c->d_tabs, kTabWords)) || (rc = dmalloc(&c->d_hdr, c->hdr.size()))) return rc;
   c->timing = (k.flags & (MJG_F_TIMING | MJG_F_TIMING_DETAIL)) != 0;
@@ -1309,18 +1353,19 @@ int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
 }
 
 int open_ctx(int device, const mjg_config *cfg, int src_cf, int deint, int orient, const int *crop,
-             const mjg_lut *lut_in, const mjg_lut *lut_out, const mjg_unsharp *us, const int *pad, mjg_ctx *c) {
+             const mjg_cmatrix *cm, const mjg_lut *lut_in, const mjg_lut *lut_out, const mjg_unsharp *us, const int *pad, mjg_ctx *c) {
   c->device = device;
   c->cfg = *cfg;
   const mjg_config &k = *cfg;
   Layout lay;
   int rc;
-  if ((rc = check_config(k, src_cf, deint, orient, crop, lut_in, lut_out, us, pad, &lay))) return rc;
+  if ((rc = check_config(k, src_cf, deint, orient, crop, cm, lut_in, lut_out, us, pad, &lay))) return rc;
   if ((rc = plan_geometry(k, src_cf, lay, env_int("MJG_UNALIGNED_FETCH", 1) != 0, c))) return rc;
   plan_orient(k, lay, c);
   plan_deint(k, lay, c);
   plan_sharp(k, lay, c);
   plan_lut(k, lay, c);
+  plan_cmat(lay, c);
   quant_matrix(k.qscale, c->mprime, c->qmat);
   c->hdr = build_header(c->geom.w, c->geom.h, c->mprime, k.sar_num, k.sar_den, (k.flags & MJG_F_COM_ITU601) != 0,
                         k.chroma_format, c->rst, &c->dht_pos, &c->dht_end);
@@ -1400,11 +1445,11 @@ int mjg_device_numa_node(int device) {
 
 namespace {
 int open_any(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, const int *crop,
-             const mjg_lut *lut_in, const mjg_lut *lut_out, const mjg_unsharp *us, const int *pad, mjg_ctx **out) {
+             const mjg_cmatrix *cm, const mjg_lut *lut_in, const mjg_lut *lut_out, const mjg_unsharp *us, const int *pad, mjg_ctx **out) {
   if (!cfg || !out) return set_err(MJG_E_INVALID, "null argument");
   *out = nullptr;
   mjg_ctx *c = new mjg_ctx();
-  const int rc = open_ctx(device, cfg, src_chroma_format, deint, orient, crop, lut_in, lut_out, us, pad, c);
+  const int rc = open_ctx(device, cfg, src_chroma_format, deint, orient, crop, cm, lut_in, lut_out, us, pad, c);
   if (rc) {
     const std::string keep = g_err;
     free_ctx(c);
@@ -1419,43 +1464,51 @@ int open_any(int device, const mjg_config *cfg, int src_chroma_format, int deint
 int mjg_open_crop(int device, const mjg_config *cfg, int src_chroma_format, int crop_x, int crop_y, int crop_w,
                   int crop_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h};
-  return open_any(device, cfg, src_chroma_format, 0, 0, crop, nullptr, nullptr, nullptr, nullptr, out);
+  return open_any(device, cfg, src_chroma_format, 0, 0, crop, nullptr, nullptr, nullptr, nullptr, nullptr, out);
 }
 
 int mjg_open_orient(int device, const mjg_config *cfg, int src_chroma_format, int orient, int crop_x, int crop_y,
                     int crop_w, int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, 0, orient, crop, nullptr, nullptr, nullptr, pad, out);
+  return open_any(device, cfg, src_chroma_format, 0, orient, crop, nullptr, nullptr, nullptr, nullptr, pad, out);
 }
 
 int mjg_open_deint(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, int crop_x,
                    int crop_y, int crop_w, int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, deint, orient, crop, nullptr, nullptr, nullptr, pad, out);
+  return open_any(device, cfg, src_chroma_format, deint, orient, crop, nullptr, nullptr, nullptr, nullptr, pad, out);
 }
 
 int mjg_open_sharp(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, int crop_x,
                    int crop_y, int crop_w, int crop_h, const mjg_unsharp *us, int pad_x, int pad_y, int pad_w,
                    int pad_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, deint, orient, crop, nullptr, nullptr, us, pad, out);
+  return open_any(device, cfg, src_chroma_format, deint, orient, crop, nullptr, nullptr, nullptr, us, pad, out);
 }
 
 int mjg_open_lut(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, int crop_x,
                  int crop_y, int crop_w, int crop_h, const mjg_lut *lut_in, const mjg_lut *lut_out,
                  const mjg_unsharp *us, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, deint, orient, crop, lut_in, lut_out, us, pad, out);
+  return open_any(device, cfg, src_chroma_format, deint, orient, crop, nullptr, lut_in, lut_out, us, pad, out);
+}
+
+int mjg_open_cmat(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, int crop_x,
+                  int crop_y, int crop_w, int crop_h, const mjg_cmatrix *cm, const mjg_lut *lut_in,
+                  const mjg_lut *lut_out, const mjg_unsharp *us, int pad_x, int pad_y, int pad_w, int pad_h,
+                  mjg_ctx **out) {
+  const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
+  return open_any(device, cfg, src_chroma_format, deint, orient, crop, cm, lut_in, lut_out, us, pad, out);
 }
 
 int mjg_open_pad(int device, const mjg_config *cfg, int src_chroma_format, int crop_x, int crop_y, int crop_w,
                  int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
   const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, 0, 0, crop, nullptr, nullptr, nullptr, pad, out);
+  return open_any(device, cfg, src_chroma_format, 0, 0, crop, nullptr, nullptr, nullptr, nullptr, pad, out);
 }
 
 int mjg_open_src(int device, const mjg_config *cfg, int src_chroma_format, mjg_ctx **out) {
-  return open_any(device, cfg, src_chroma_format, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, out);
+  return open_any(device, cfg, src_chroma_format, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out);
 }
 
 int mjg_open(int device, const mjg_config *cfg, mjg_ctx **out) {
@@ -1477,7 +1530,7 @@ int mjg_header(const mjg_ctx *ctx, uint8_t *out, size_t cap, size_t *len) {
 }
 
 namespace {
-// where slot "in"'s table stage leaves its frames: the buffer of the stage in front of it (in place), else d_lut
+// where slot "in"'s table stage and the colour matrix leave their frames: the buffer of the stage in front of them (in place), else d_lut
 uint8_t *lut_in_buf(const mjg_ctx *c, const Slot &S) { return c->orient ? S.d_orient : c->deint ? S.d_deint : S.d_lut; }
 
 // One table stage of a submit: luma, then U and V in one launch (V's blocks behind U's) when uv1 (2n fits
@@ -1524,7 +1577,7 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
   }
   src += (size_t)hp * c->in_frame_bytes;  // the first encoded frame
   SegList in_sl = segs ? *segs : one_seg(src);  // the submit's input frames: the caller's segments, or one at src
-  if (c->scale || c->orient || c->deint || c->has_lut[0]) tmark(c, S, MJG_K_SCALE, 0);
+  if (c->scale || c->orient || c->deint || c->has_lut[0] || c->has_cmat) tmark(c, S, MJG_K_SCALE, 0);
   if (c->deint) {  // in front of everything: luma, then U and V in one launch; the rest reads one buffer
     const bool uv1 = 2 * n <= 65535;
     for (int p = 0; p < (uv1 ? 2 : 3); p++) {
@@ -1555,9 +1608,16 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
     HIP_TRY(hipGetLastError());
     in_sl = one_seg(S.d_orient);
   }
-  if (c->has_lut[0]) {  // behind the orientation: in place in that stage's buffer, else the caller's frames -> d_lut
+  if (c->has_cmat) {  // behind the orientation: in place in that stage's buffer, else the caller's frames -> d_lut
     uint8_t *buf = lut_in_buf(c, S);
-    launch_lut(c, S, 0, in_sl, buf, n, 2 * n <= 65535, buf != S.d_lut, c->src_cplane);
+    const mjg_cmatrix &m = c->cmat;
+    c->cmat_launch(in_sl, buf, c->cgeom, CmatCoef{m.yu, m.yv, m.uu, m.uv, m.vu, m.vv}, n, S.st);
+    HIP_TRY(hipGetLastError());
+    in_sl = one_seg(buf);
+  }
+  if (c->has_lut[0]) {  // behind the colour matrix: in place in the buffer in front, else the caller's frames -> d_lut
+    uint8_t *buf = lut_in_buf(c, S);
+    launch_lut(c, S, 0, in_sl, buf, n, 2 * n <= 65535, buf != S.d_lut || c->has_cmat, c->src_cplane);
     HIP_TRY(hipGetLastError());
     in_sl = one_seg(buf);
   }
@@ -1600,7 +1660,7 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
     HIP_TRY(hipGetLastError());
     enc_in = one_seg(enc_buf);  // k_encode reads the scaled (the sharpened) frames, one buffer
   } else {  // in place: EncGeom's offsets count from the rectangle's first luma byte (0: whole frames)
-    if (c->orient || c->deint || c->has_lut[0]) tmark(c, S, MJG_K_SCALE, 1);  // an orientation / a deinterlacer / a table alone: the interval holds its passes
+    if (c->orient || c->deint || c->has_lut[0] || c->has_cmat) tmark(c, S, MJG_K_SCALE, 1);  // an orientation / a deinterlacer / a table / a matrix alone: the interval holds its passes
     for (int k = 0; k < kMaxSegs; k++) enc_in.p[k] += c->src_off[0];
   }
   const int ntasks = g.nchunks * g.nseg * n;
@@ -1826,7 +1886,7 @@ int mjg_sync(mjg_ctx *c, uint64_t *frame_sizes, uint64_t *total) {
       }
       if (c->timing) {
         for (int k = 0; k < MJG_NUM_KERNELS; k++) {
-          if (k == MJG_K_SCALE && !c->scale && !c->orient && !c->deint && !c->has_lut[0]) continue;
+          if (k == MJG_K_SCALE && !c->scale && !c->orient && !c->deint && !c->has_lut[0] && !c->has_cmat) continue;
           if (k == MJG_K_HUFF && !c->optimal) continue;
           const bool tail = is_tail_kernel(k);
           if (tail != c->timing_detail && (tail || k == MJG_K_TAIL)) continue;
@@ -2071,6 +2131,29 @@ int mjg_debug_lut_in(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
   if (cap < c->in_frame_bytes) return set_err(MJG_E_CAPACITY, "need %zu bytes", c->in_frame_bytes);
   const size_t f = (size_t)L.jf0[c->last_job] + (size_t)frame;
   // (in place in the buffer of the stage in front of it, else d_lut)
+  HIP_TRY(hipMemcpy(out, lut_in_buf(c, L) + f * c->in_frame_bytes, c->in_frame_bytes, hipMemcpyDeviceToHost));
+  return MJG_OK;
+}
+
+int mjg_debug_cmat(mjg_ctx *c, mjg_cmatrix *out) {
+  if (!c) return set_err(MJG_E_INVALID, "null context");
+  if (c->has_cmat && out) *out = c->cmat;
+  return c->has_cmat ? 1 : 0;
+}
+
+int mjg_debug_cmat_out(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
+  if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
+  if (!c->has_cmat) return set_err(MJG_E_STATE, "context has no colour matrix (none, or the identity)");
+  if (pending_jobs(c) > 0) {  // the latest synced submit's frames
+    const int rc = mjg_sync(c, nullptr, nullptr);
+    if (rc) return rc;
+  }
+  if (pending_jobs(c) > 0 || c->last < 0) return set_err(MJG_E_STATE, "sync every queued submit first");
+  const Slot &L = c->slot[c->last];
+  if (frame < 0 || frame >= L.jn[c->last_job]) return set_err(MJG_E_INVALID, "frame %d", frame);
+  if (cap < c->in_frame_bytes) return set_err(MJG_E_CAPACITY, "need %zu bytes", c->in_frame_bytes);
+  const size_t f = (size_t)L.jf0[c->last_job] + (size_t)frame;
+  // (in place in the buffer of the stage in front of it, else d_lut; a lut_in has mapped it there)
   HIP_TRY(hipMemcpy(out, lut_in_buf(c, L) + f * c->in_frame_bytes, c->in_frame_bytes, hipMemcpyDeviceToHost));
   return MJG_OK;
 }

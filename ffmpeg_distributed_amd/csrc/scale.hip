@@ -1661,4 +1661,163 @@ __global__ __launch_bounds__(kCopyThreads) void k_lut_plane(const SegList src, u
   lut_work(src, dst, g, tab, (int)blockIdx.x, tid);
 }
 
+// k_cmat_frame: a 3 x 3 colour matrix on whole frames (`-vf colormatrix` is six 16.16
+// coefficients, and the library knows only the coefficients).  Per sample, C int and arithmetic >>, with
+// (U, V) the chroma pair of the luma sample's cell (x >> HS, y >> VS):
+//   u = U - 128, v = V - 128, k = (yu u + yv v + 1081344) >> 16
+//   Y' = clip8(Y - 16 + k)                        (= clip8((65536 (Y - 16) + yu u + yv v + 1081344) >> 16))
+//   U' = clip8((uu u + uv v + 8421376) >> 16), V' = clip8((vu u + vv v + 8421376) >> 16)
+// so a luma sample depends on the chroma pair above it, and one launch covers all three planes of every
+// frame of a submit.  The work item is a piece: 16 chroma samples of one chroma row (piece p of row r:
+// columns [16 p, 16 p + 16)) with the luma cell rows above them, 16 U bytes, 16 V bytes and 1 << VS rows
+// of 16 << HS luma bytes.  A piece that lies inside the three planes is 2 + (1 << VS) (1 << HS) unaligned
+// 16-byte loads, all issued before the first store, and as many stores; the second luma row that the
+// last cell row of an odd height lacks is left out.  A piece over a chroma row's end (the last of a row whose width is no
+// multiple of 16, every piece of a plane narrower than 16), and one whose last chroma column has a
+// single luma column (odd width), goes sample by sample.  Every byte is read and written by the thread
+// of its piece alone, so dst may be src, and no byte outside the three planes is touched; frames lie at
+// any alignment (33 x 17 4:4:4 has odd frame bytes), with frame strides of their own on either side.
+// The grid's x is workgroups per frame x frames, nothing else: no plane is a grid index, so there is no
+// 2 n <= 65,535 as for the plane kernels and no launch for V alone.  38,000 frames fit because x runs
+// to 2^31 - 1 and a frame of up to 256 pieces is one workgroup (38,000 of them); open refuses a context
+// whose gxy x frames would pass 2^31 - 1.
+// Sums: |coefficient| <= 2^18 (mjg_open_cmat) and |u|, |v| <= 128, so |yu u + yv v| <= 2^26 and every
+// sum is below 2^26 + 2^24 in magnitude: int32 holds it, and k fits an int16.
+// The body is a __host__ __device__ function, as lut_work is, for tools/cmat_host.hip.
+struct CmatCoef { int yu, yv, uu, uv, vu, vv; };
+struct CmatGeom {
+  int w, h;                    // the luma plane
+  int cw, ch;                  // the chroma planes: (w + HS) >> HS, (h + VS) >> VS
+  long long s_fstride, d_fstride;
+  int ppr;                     // pieces per chroma row: ceil(cw / 16)
+  uint32_t ppr_magic;
+  int np;                      // pieces per frame: ppr * ch
+  int gxy;                     // workgroups per frame
+  uint32_t gxy_magic;
+};
+
+constexpr int kCmatThreads = 256;  // one piece per thread
+constexpr int kCmatMaxCoef = 262144;  // |coefficient| <= 2^18, four times unity (mjg_open_cmat refuses more)
+
+// The geometry of w x h frames with chroma shifts hs, vs (the frame strides and the magics of the two
+// divisors are the caller's)
+inline void cmat_geom_frame(CmatGeom &g, int w, int h, int hs, int vs) {
+  g.w = w;
+  g.h = h;
+  g.cw = (w + hs) >> hs;
+  g.ch = (h + vs) >> vs;
+  g.ppr = (g.cw + 15) >> 4;
+  g.np = g.ppr * g.ch;  // (<= 2^10 * 2^14)
+  g.gxy = (g.np + kCmatThreads - 1) / kCmatThreads;
+}
+
+__host__ __device__ __forceinline__ int cmat_clip8(int x) { return x < 0 ? 0 : x > 255 ? 255 : x; }
+
+// clip8(x >> 16), with the clamp in front of the shift: [0, 0xFFFFFF] >> 16 is [0, 255].  Written
+// as clip8(x >> 16), pairs of these become gfx950's v_ashr_pk_u8_i32, which writes 16 bits of its
+// register and keeps the other 16, and hipcc (ROCm 7.x) then ORs bytes 2 and 3 into that register as
+// if they were zero: byte 2 came out OR-ed with the unclipped byte 0 on the MI355X
+__host__ __device__ __forceinline__ int cmat_clip8_16(int x) {
+  x = x < 0 ? 0 : x > 0xFFFFFF ? 0xFFFFFF : x;
+  return (int)((uint32_t)x >> 16);
+}
+
+// A coefficient as the compiler can see it: sign-extended from 24 bits, which changes no value that
+// mjg_open_cmat lets through (|c| <= 2^18).  With |u|, |v| <= 128 both factors are then inside 24 bits
+// and the device takes the full-rate 24-bit multiply-add (a 32-bit multiply is quarter rate)
+__host__ __device__ __forceinline__ int cmat_c24(int c) { return (int)((uint32_t)c << 8) >> 8; }
+
+// One chroma pair: what its cell's luma samples gain (k - 16), and U', V'
+__host__ __device__ __forceinline__ void cmat_uv(const CmatCoef &cm, int U, int V, int &d, int &uo, int &vo) {
+  const int u = U - 128, v = V - 128;
+  d = ((cm.yu * u + cm.yv * v + 1081344) >> 16) - 16;
+  uo = cmat_clip8_16(cm.uu * u + cm.uv * v + 8421376);
+  vo = cmat_clip8_16(cm.vu * u + cm.vv * v + 8421376);
+}
+
+template <int HS, int VS>
+__host__ __device__ __forceinline__ void cmat_work(const SegList &src, uint8_t *dst, const CmatGeom &g,
+                                                   const CmatCoef &coef, int t, int tid) {
+  const CmatCoef cm{cmat_c24(coef.yu), cmat_c24(coef.yv), cmat_c24(coef.uu), cmat_c24(coef.uv), cmat_c24(coef.vu),
+                    cmat_c24(coef.vv)};
+  const int f = deint_div(t, g.gxy_magic, g.gxy), blk = t - f * g.gxy;
+  const int piece = blk * kCmatThreads + tid;
+  if (piece >= g.np) return;
+  int k = 0;
+#pragma unroll
+  for (int j = 1; j < kMaxSegs; j++)
+    if (f >= src.f0[j]) k = j;
+  const uint8_t *s = src.p[k] + (long long)(f - (k ? src.f0[k] : 0)) * g.s_fstride;
+  uint8_t *d = dst + (long long)f * g.d_fstride;
+  const int w = g.w, cw = g.cw;
+  const size_t uo = (size_t)w * g.h, vo = uo + (size_t)cw * g.ch;  // the U and the V plane in a frame
+  const int r = deint_div(piece, g.ppr_magic, g.ppr), c0 = (piece - r * g.ppr) << 4;
+  const int y0 = r << VS, x0 = c0 << HS;
+  const int nr = imin(1 << VS, g.h - y0);  // the cell rows the frame has
+  const size_t ci = (size_t)r * cw + c0;
+  if (c0 + 16 <= cw && x0 + (16 << HS) <= w) {
+    const u32x4 U = *(const u32x4_a1 *)(s + uo + ci), V = *(const u32x4_a1 *)(s + vo + ci);
+    u32x4 Y[1 << VS][1 << HS];
+#pragma unroll
+    for (int ry = 0; ry < (1 << VS); ry++)
+#pragma unroll
+      for (int j = 0; j < (1 << HS); j++)
+        Y[ry][j] = ry < nr ? *(const u32x4_a1 *)(s + (size_t)(y0 + ry) * w + x0 + 16 * j) : u32x4{0, 0, 0, 0};
+    int dy[16];
+    u32x4 Uo, Vo;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      uint32_t a = 0, b = 0;
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        int pu, pv;
+        cmat_uv(cm, (int)((U[q] >> (8 * i)) & 255u), (int)((V[q] >> (8 * i)) & 255u), dy[4 * q + i], pu, pv);
+        a |= (uint32_t)pu << (8 * i);
+        b |= (uint32_t)pv << (8 * i);
+      }
+      Uo[q] = a;
+      Vo[q] = b;
+    }
+#pragma unroll
+    for (int ry = 0; ry < (1 << VS); ry++)
+#pragma unroll
+      for (int j = 0; j < (1 << HS); j++) {
+        u32x4 o;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          uint32_t a = 0;
+#pragma unroll
+          for (int i = 0; i < 4; i++)  // luma byte 16 j + 4 q + i of the piece: chroma sample (16 j + 4 q + i) >> HS
+            a |= (uint32_t)cmat_clip8((int)((Y[ry][j][q] >> (8 * i)) & 255u) + dy[(16 * j + 4 * q + i) >> HS]) << (8 * i);
+          o[q] = a;
+        }
+        if (ry < nr) *(u32x4_a1 *)(d + (size_t)(y0 + ry) * w + x0 + 16 * j) = o;
+      }
+    *(u32x4_a1 *)(d + uo + ci) = Uo;
+    *(u32x4_a1 *)(d + vo + ci) = Vo;
+    return;
+  }
+  // over a row end, or the last column's cell is one luma sample wide (rolled: at most one piece a chroma row)
+  const int ce = imin(c0 + 16, cw);
+#pragma unroll 1
+  for (int c = c0; c < ce; c++) {
+    const size_t cj = (size_t)r * cw + c;
+    int dl, pu, pv;
+    cmat_uv(cm, s[uo + cj], s[vo + cj], dl, pu, pv);
+    const int xe = imin((c + 1) << HS, w);
+    for (int ry = 0; ry < nr; ry++)
+      for (int x = c << HS; x < xe; x++) {
+        const size_t yi = (size_t)(y0 + ry) * w + x;
+        d[yi] = (uint8_t)cmat_clip8((int)s[yi] + dl);
+      }
+    d[uo + cj] = (uint8_t)pu;
+    d[vo + cj] = (uint8_t)pv;
+  }
+}
+
+template <int HS, int VS>
+__global__ __launch_bounds__(kCmatThreads) void k_cmat_frame(const SegList src, uint8_t *dst, CmatGeom g, CmatCoef cm) {
+  cmat_work<HS, VS>(src, dst, g, cm, (int)blockIdx.x, (int)threadIdx.x);
+}
+
 }  // namespace mjg

@@ -25,7 +25,9 @@ behind the scale and in front of the pad, the amounts as floats) sharpens or blu
 output planes on the GPU (mjg_open_sharp); the encoder then reads the sharpened planes.  `lut_in=` /
 `lut_out=` ((3, 256) uint8, rows Y, U, V) map every sample through a table per plane on the GPU
 (mjg_open_lut), in front of the sws stage and directly behind it: `-vf eq=...` in front of the scale or
-directly behind it, with profile.eq_tables.  No CPU fallback.
+directly behind it, with profile.eq_tables.  `cmat=` (c2, ..., c7: six 16.16 ints) is a colour matrix
+on whole frames behind the orientation and in front of `lut_in` (mjg_open_cmat): `-vf
+colormatrix=SRC:DST` with profile.colormatrix_coefs.  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -76,7 +78,7 @@ class MjpegEncoder:
                  debug_coefs: bool = False, sws_bitexact: bool = True, com_itu601: bool = False,
                  huffman: str = "default", chroma: str = "420", rst: bool = False,
                  merge: bool = False, src_chroma: Optional[str] = None, crop=None, pad=None, orient: int = 0,
-                 deint: Optional[int] = None, unsharp=None, lut_in=None, lut_out=None):
+                 deint: Optional[int] = None, unsharp=None, lut_in=None, lut_out=None, cmat=None):
         self._L = _lib.load()
         self.device = int(device)
         self.src_w, self.src_h = int(src_w), int(src_h)
@@ -162,7 +164,26 @@ class MjpegEncoder:
                     raise ValueError(f"{name}: a (3, 256) uint8 array, not {t.shape} {t.dtype}")
             luts.append(t)
         self.lut_in, self.lut_out = luts
-        if lut_in is not None or lut_out is not None:
+        # cmat: (c2, c3, c4, c5, c6, c7), the six 16.16 coefficients of a colour matrix on the frames behind
+        # the orientation, in front of lut_in (mjg_open_cmat).  `-vf colormatrix` is
+        # profile.colormatrix_coefs.  None, the default, opens as without it
+        self.cmat = None
+        if cmat is not None:
+            if len(cmat) != 6:
+                raise ValueError(f"cmat {cmat!r}: (c2, c3, c4, c5, c6, c7)")
+            self.cmat = tuple(int(v) for v in cmat)
+        if self.cmat is not None:
+            if not hasattr(self._L, "mjg_open_cmat"):
+                raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_cmat")
+            rect = self.crop if self.crop is not None else (0, 0, self.or_w, self.or_h)
+            canvas = self.pad if self.pad is not None else (0, 0, self.dst_w, self.dst_h)
+            us = None if self.unsharp is None else C.byref(_lib.MjgUnsharp(*self.unsharp))
+            tabs = [None if t is None else C.byref(_lib.MjgLut.from_buffer_copy(t.tobytes())) for t in luts]
+            cm = _lib.MjgCmatrix(*self.cmat)
+            check(self._L.mjg_open_cmat(self.device, C.byref(cfg), _lib.CHROMA_FORMATS[self.src_chroma],
+                                        self.deint, self.orient, *rect, C.byref(cm), tabs[0], tabs[1], us, *canvas,
+                                        C.byref(h)))
+        elif lut_in is not None or lut_out is not None:
             if not hasattr(self._L, "mjg_open_lut"):
                 raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_lut")
             rect = self.crop if self.crop is not None else (0, 0, self.or_w, self.or_h)
@@ -485,6 +506,28 @@ class MjpegEncoder:
         out = np.zeros(self.frame_bytes, np.uint8)
         check(self._L.mjg_debug_lut_in(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size))
         return out
+
+    def debug_cmat_out(self, frame: int = 0) -> np.ndarray:
+        """k_cmat_frame's output of a frame of the last synced submit: a whole frame behind the
+        orientation in the input format `src_chroma`, frame_bytes bytes (mapped by `lut_in`, which runs in
+        place behind the stage, when there is one).  Only for an encoder opened with a `cmat` that is not
+        the identity."""
+        if not hasattr(self._L, "mjg_debug_cmat_out"):
+            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_debug_cmat_out")
+        out = np.zeros(self.frame_bytes, np.uint8)
+        check(self._L.mjg_debug_cmat_out(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size))
+        return out
+
+    def debug_cmat(self):
+        """The six coefficients the context holds, or None without a matrix (none given, or the
+        identity).  Host state only."""
+        if not hasattr(self._L, "mjg_debug_cmat"):
+            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_debug_cmat")
+        m = _lib.MjgCmatrix()
+        rc = self._L.mjg_debug_cmat(self._h, C.byref(m))
+        if rc < 0:
+            check(rc)
+        return (m.yu, m.yv, m.uu, m.uv, m.vu, m.vv) if rc else None
 
     def debug_lut(self, slot: str = "in"):
         """The (3, 256) tables the context holds for slot "in" or "out", or None without (none given,

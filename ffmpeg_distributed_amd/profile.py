@@ -36,7 +36,16 @@ behind the yadif and the orientation run is `Profile.eq`: anywhe
 scale (slot "in"; without a scale, in front of the unsharp and the pad) or directly behind it (slot
 "out").  Plain numbers inside the filter's ranges only; `eval=`, an expression, a second eq and an eq
 behind the unsharp or the pad are outside the profile.  `eq_tables` makes the three byte tables, a
-restatement of vf_eq.c's 8-bit path that is unpinned against FFmpeg.  An orientation filter after a crop, scale
+restatement of vf_eq.c's 8-bit path that is unpinned against FFmpeg.  One
+    colormatrix=SRC:DST                     (also src=, dst=; bt709, fcc, bt601, smpte240m, bt2020, and bt470,
+                                            bt470bg, smpte170m for bt601)
+behind the yadif and the orientation run, in front of any eq and of the scale (without a scale: in
+front of the unsharp and the pad), before or after the crop, is `Profile.colormatrix` = the canonical
+(src, dst).  A second colormatrix, a missing dst, a missing src (FFmpeg takes it from
+frame metadata), src equal to dst (FFmpeg refuses it itself), an unknown name or key and any other
+position are outside the profile, each with a reason that names it.  `colormatrix_coefs` makes the six
+16.16 coefficients, a restatement of vf_colormatrix.c's 8-bit planar path that is unpinned against
+FFmpeg.  An orientation filter after a crop, scale
 or pad, transpose values 4..7, a passthrough other than none and any other option are outside the
 profile.  The crop values are decimal integers (no expressions); `Profile.crop` is the request as
 given and `resolve_crop` turns it into a rectangle of a given input (vf_crop.c's rounding,
@@ -95,6 +104,9 @@ class Profile:
     # behind the scale, on its full-range output), and the filter's eight numbers (EQ_NAMES), the
     # defaults filled in}; eq_tables turns them into the three tables.  None: no eq
     eq: Optional[dict] = None
+    # -vf ...,colormatrix=SRC:DST: the canonical (src, dst) names (COLORMATRIX_LUMA's keys), in front of
+    # any eq and the scale; colormatrix_coefs turns them into the six coefficients.  None: no colormatrix
+    colormatrix: Optional[Tuple[str, str]] = None
 
 
 class Unsupported(ValueError):
@@ -476,6 +488,102 @@ def _take_eq(vf: str):
     return (",".join(rest) if rest else None), eq
 
 
+# luma weights (G, B, R) per colour space, and the other names of bt601
+COLORMATRIX_LUMA = {"bt709": (0.7152, 0.0722, 0.2126), "fcc": (0.59, 0.11, 0.30), "bt601": (0.587, 0.114, 0.299),
+                    "smpte240m": (0.701, 0.087, 0.212), "bt2020": (0.678, 0.0593, 0.2627)}
+COLORMATRIX_ALIASES = {"bt470": "bt601", "bt470bg": "bt601", "smpte170m": "bt601"}
+
+
+def _colormatrix_name(v: str) -> Optional[str]:
+    v = COLORMATRIX_ALIASES.get(v, v)
+    return v if v in COLORMATRIX_LUMA else None
+
+
+def _yuv_matrix(name: str):
+    g, b, r = COLORMATRIX_LUMA[name]
+    bs, rs = 0.5 / (b - 1.0), 0.5 / (r - 1.0)
+    return [[g, b, r], [bs * g, 0.5, bs * r], [rs * g, rs * b, 0.5]]
+
+
+def _inverse3(m):
+    (a, b, c), (d, e, f), (g, h, i) = m
+    co = [[e * i - f * h, c * h - b * i, b * f - c * e],
+          [f * g - d * i, a * i - c * g, c * d - a * f],
+          [d * h - e * g, b * g - a * h, a * e - b * d]]
+    det = a * co[0][0] + b * co[1][0] + c * co[2][0]
+    return [[v / det for v in row] for row in co]
+
+
+def colormatrix_coefs(src: str, dst: str) -> Tuple[int, int, int, int, int, int]:
+    """(c2, c3, c4, c5, c6, c7): the six 16.16 coefficients `-vf colormatrix=src:dst` applies to 8-bit
+    planar frames, as DESIGN §4.16 restates vf_colormatrix.c: C = M_dst inverse(M_src) in double, each
+    entry rounded half away from zero by the filter's NS(); the first column is always (65536, 0, 0)
+    and is left out.  The names are COLORMATRIX_LUMA's and the other names of bt601."""
+    import sys
+    names = (_colormatrix_name(src), _colormatrix_name(dst))
+    if None in names:
+        raise ValueError(f"colormatrix {src}:{dst}: not two of {', '.join(COLORMATRIX_LUMA)}")
+    md, inv = _yuv_matrix(names[1]), _inverse3(_yuv_matrix(names[0]))
+    c = [[sum(md[i][k] * inv[k][j] for k in range(3)) for j in range(3)] for i in range(3)]
+
+    def ns(n: float) -> int:
+        return int(n * 65536.0 - 0.5 + sys.float_info.epsilon) if n < 0 else int(n * 65536.0 + 0.5)
+    return (ns(c[0][1]), ns(c[0][2]), ns(c[1][1]), ns(c[1][2]), ns(c[2][1]), ns(c[2][2]))
+
+
+def _parse_colormatrix(f: str) -> Tuple[str, str]:
+    """`colormatrix=SRC:DST` (also src=, dst=, and mixed) -> the canonical (src, dst)."""
+    _, _, opts = f.partition("=")
+    vals = {}
+    pos = 0
+    for p in opts.split(":") if opts else []:
+        if "=" in p:
+            k, v = p.split("=", 1)
+            if k not in ("src", "dst"):
+                raise Unsupported(f"colormatrix option {k!r} (only src and dst are GPU-accelerated)")
+        else:
+            if pos >= 2:
+                raise Unsupported(f"colormatrix option {p!r} (positional options are src:dst)")
+            k, v = ("src", "dst")[pos], p
+            pos += 1
+        name = _colormatrix_name(v)
+        if name is None:
+            raise Unsupported(f"colormatrix {k}={v}: not one of {', '.join(list(COLORMATRIX_LUMA) + list(COLORMATRIX_ALIASES))}")
+        vals[k] = name
+    if "dst" not in vals:
+        raise Unsupported(f"colormatrix without a dst ({f!r}: the filter needs one)")
+    if "src" not in vals:
+        raise Unsupported(f"colormatrix without a src ({f!r}: FFmpeg takes it from the frame's metadata, which is not "
+                          f"GPU-accelerated)")
+    if vals["src"] == vals["dst"]:
+        raise Unsupported(f"colormatrix src and dst are both {vals['src']} ({f!r}: FFmpeg refuses it)")
+    return vals["src"], vals["dst"]
+
+
+def _take_colormatrix(vf: str):
+    """A graph that names colormatrix -> (the graph without it, or None when nothing is left; the
+    canonical (src, dst)).  One colormatrix, behind the yadif and the orientation run, in front of any
+    eq and of the scale (without a scale: in front of the unsharp and the pad); before or after the crop,
+    with which it commutes (crop offsets are multiples of the sub-sampling)."""
+    fs = vf.split(",")
+    names = [f.split("=", 1)[0] for f in fs]
+    if names.count("colormatrix") > 1:
+        raise Unsupported(f"filter graph {vf!r}: a second colormatrix (one colormatrix, in front of the eq and the scale, "
+                          f"is GPU-accelerated)")
+    at = names.index("colormatrix")
+    for nm in names[at + 1:]:
+        if nm == "yadif" or nm in ORIENT_FILTERS or nm in OTHER_DEINTERLACERS or nm == "hflip":
+            raise Unsupported(f"filter graph {vf!r}: colormatrix in front of {nm} (colormatrix is GPU-accelerated only "
+                              f"behind the yadif and the orientation run)")
+    for nm in ("eq", "scale", "unsharp", "pad"):
+        if nm in names[:at]:
+            raise Unsupported(f"filter graph {vf!r}: colormatrix behind the {nm} (colormatrix is GPU-accelerated only in "
+                              f"front of the eq, the scale, the unsharp and the pad)")
+    pair = _parse_colormatrix(fs[at])
+    rest = fs[:at] + fs[at + 1:]
+    return (",".join(rest) if rest else None), pair
+
+
 def _parse_vf(vf: str):
     """-vf value -> (crop request or None, scale size or None, sws flags, pad request or None,
     unsharp request or None, orientation, yadif request or None).  A `yadif` at the very front is taken off first; then a
@@ -685,6 +793,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
     deint = None
     unsharp = None
     eq = None
+    cmat = None
     flags: Tuple[str, ...] = ("bicubic",)
     i = 0
 
@@ -726,8 +835,10 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
                 raise Unsupported(f"-fflags {v}")
         elif o in ("-vf", "-filter:v"):
             vf = val()
-            eq = None
-            if ";" not in vf and "eq" in [f.split("=", 1)[0] for f in vf.split(",")]:
+            eq = cmat = None
+            if ";" not in vf and "colormatrix" in [f.split("=", 1)[0] for f in vf.split(",")]:
+                vf, cmat = _take_colormatrix(vf)   # the rest of the graph is parsed as without it
+            if vf is not None and ";" not in vf and "eq" in [f.split("=", 1)[0] for f in vf.split(",")]:
                 vf, eq = _take_eq(vf)              # the rest of the graph is parsed as without it
             if vf is not None:
                 crop, scale, flags, pad, unsharp, orient, deint = _parse_vf(vf)
@@ -781,7 +892,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
         huff = "default"  # mjpegenc.c: slice_context_count > 1 forces HUFFMAN_TABLE_DEFAULT
     return Profile(qscale=effective_qscale(q), q_arg=q, scale=scale, sws_flags=flags, huffman=huff,
                    rst=rst, chroma=chroma, crop=crop, pad=pad, orient=orient, deint=deint, unsharp=unsharp,
-                   eq=eq)
+                   eq=eq, colormatrix=cmat)
 
 
 PIX_FMT_CHROMA = {"yuvj420p": "420", "yuvj422p": "422", "yuvj444p": "444"}

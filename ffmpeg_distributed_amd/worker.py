@@ -43,6 +43,10 @@ One `eq` (profile.Profile.eq) becomes three byte tables (profile.eq_tables) that
 front of the sws stage (slot "in": the decoded samples, before any conversion) or on its output (slot
 "out": directly behind the scale); eq_fallthrough_reason names the inputs that still go to the real
 ffmpeg.
+One `colormatrix=SRC:DST` (profile.Profile.colormatrix) becomes six 16.16 coefficients
+(profile.colormatrix_coefs) that the GPU applies to the decoded frames behind the yadif and the
+orientation, in front of everything else; cmat_fallthrough_reason names the inputs that still go to
+the real ffmpeg.
 """
 from __future__ import annotations
 
@@ -479,7 +483,7 @@ def resample_plan(prof, info):
 
 
 def encoder_key(prof, info, dst_w, dst_h, sar, com_itu601, batch, rect=None, pad=None, orient=0, deint=0,
-                unsharp=None, luts=None):
+                unsharp=None, luts=None, cmat=None):
     """What an encoder context kept between segments (serve / resident mode) depends on: the
     input's shape and format and everything of the profile the context is opened with, the
     encoded chroma format (-pix_fmt), the resolved crop rectangle (x, y, w, h), the resolved
@@ -487,13 +491,15 @@ def encoder_key(prof, info, dst_w, dst_h, sar, com_itu601, batch, rect=None, pad
     resolve_deint: the batch buffers of such a context hold two more frames) included, and the
     six values of an unsharp (profile.Profile.unsharp; None without one), and the bytes of the
     tables in front of and behind the sws stage (luts: (lut_in, lut_out), each a (3, 256) uint8
-    array or None: two eq filters with different options are different contexts)."""
+    array or None: two eq filters with different options are different contexts), and the six
+    coefficients of a colour matrix (cmat; without one the key is what it was)."""
     src_chroma, dst_chroma = resample_plan(prof, info)
-    return (info.width, info.height, dst_w, dst_h, info.full_range, prof.qscale, sar,
-            com_itu601, prof.huffman, src_chroma, dst_chroma, prof.rst, batch,
-            None if rect is None else tuple(rect), None if pad is None else tuple(pad), int(orient), int(deint),
-            tuple(None if t is None else t.tobytes() for t in (luts or (None, None))),
-            None if unsharp is None else tuple(unsharp))
+    key = (info.width, info.height, dst_w, dst_h, info.full_range, prof.qscale, sar,
+           com_itu601, prof.huffman, src_chroma, dst_chroma, prof.rst, batch,
+           None if rect is None else tuple(rect), None if pad is None else tuple(pad), int(orient), int(deint),
+           tuple(None if t is None else t.tobytes() for t in (luts or (None, None))),
+           None if unsharp is None else tuple(unsharp))
+    return key if cmat is None else key + (("cmat",) + tuple(int(v) for v in cmat),)
 
 
 def resolve_deint(spec, info):
@@ -596,6 +602,21 @@ def eq_fallthrough_reason(prof, info) -> Optional[str]:
     bits = int(getattr(info, "bits", 8))
     if bits != 8:
         return f"eq on a {bits}-bit input: only the filter's 8-bit path is GPU-accelerated"
+    return None
+
+
+def cmat_fallthrough_reason(prof, info) -> Optional[str]:
+    """Why a graph with a `colormatrix` runs on the CPU for this input, or None.  The filter takes
+    yuv420p / yuv422p / yuv444p (and uyvy422): FFmpeg converts a full-range (yuvj) input to one of them
+    first, which is not restated; and the coefficients are the 8-bit path's."""
+    if prof.colormatrix is None:
+        return None
+    if info.full_range:
+        return ("colormatrix on a full-range (yuvj) input: the filter takes yuv420p / yuv422p / yuv444p, and FFmpeg "
+                "converts the range first, which is not GPU-accelerated")
+    bits = int(getattr(info, "bits", 8))
+    if bits != 8:
+        return f"colormatrix on a {bits}-bit input: only the filter's 8-bit planar path is GPU-accelerated"
     return None
 
 
@@ -709,6 +730,13 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
         stderr.flush()
         return ffmpeg_fallthrough(src, args, stdout, stderr)
     lut_in, lut_out = eq_luts(prof)
+    # -vf ...,colormatrix: six coefficients on the decoded frames
+    why = cmat_fallthrough_reason(prof, info)
+    if why is not None:
+        stderr.write(f"gpu:{device}: {why}; running ffmpeg on the CPU\n")
+        stderr.flush()
+        return ffmpeg_fallthrough(src, args, stdout, stderr)
+    cmat = None if prof.colormatrix is None else profile.colormatrix_coefs(*prof.colormatrix)
     # the one scale the library refuses (a filter of 256 taps or more, about 64:1), decided here
     # without a device: as the up-sampling -pix_fmt pairs, the segment goes to ffmpeg
     why = scale_cascade_reason(in_size, (dst_w, dst_h), src_chroma, dst_chroma)
@@ -726,7 +754,7 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
     # (a transpose hands on 1 / SAR when the SAR is known: vf_transpose config_props_output)
     sar = profile.scaled_sar(oriented_sar(info.sar, orient), in_size, (dst_w, dst_h))
     key = encoder_key(prof, info, dst_w, dst_h, sar, opts.com_itu601 and not info.full_range, batch, rect, pad,
-                      orient, deint, prof.unsharp, (lut_in, lut_out))
+                      orient, deint, prof.unsharp, (lut_in, lut_out), cmat)
     nbuf = NBUF
     if cache is not None and cache.get("key") == key:
         enc, bufs, obufs = cache["enc"], cache["bufs"], cache["obufs"]
@@ -738,7 +766,7 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
                            com_itu601=opts.com_itu601 and not info.full_range, huffman=prof.huffman,
                            chroma=dst_chroma, src_chroma=src_chroma, rst=prof.rst, crop=rect, pad=pad,
                            orient=orient, deint=deint or None, unsharp=prof.unsharp,
-                           lut_in=lut_in, lut_out=lut_out)
+                           lut_in=lut_in, lut_out=lut_out, cmat=cmat)
         # (a deinterlacer: room for the frame in front of a batch and the one behind it)
         bufs = [PinnedBuffer((batch + (2 if deint else 0)) * enc.frame_bytes) for _ in range(nbuf)]
         # page-locked output buffers: the packets are DMA'd into one (enc.fetch_into) and the

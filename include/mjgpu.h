@@ -7,7 +7,10 @@
  * and launched/supervised at ffmpeg_distributed.py:139-141 (FFMPEGProc.run,
  * ffmpeg_distributed.py:59-91).  For the north-star profile
  *     [-vf [yadif[=0|2],][vflip|transpose=N,...][crop=w:h:x:y,][scale=W:H:flags=bicubic][,unsharp[=lx:ly:la:cx:cy:ca]][,pad=W:H:x:y]] -c:v mjpeg -q:v N -dct int -huffman default -bitexact
- * (one `eq=...` in front of the scale, or directly behind it: a table per plane, mjg_open_lut, a
+ * (one `colormatrix=SRC:DST` behind the yadif and the orientation and in front of any eq and the
+ * scale: six 16.16 coefficients on whole frames, mjg_open_cmat, a restatement of vf_colormatrix.c's
+ * 8-bit planar path that no FFmpeg build has been compared with yet;
+ * one `eq=...` in front of the scale, or directly behind it: a table per plane, mjg_open_lut, a
  * restatement of vf_eq.c's 8-bit path that no FFmpeg build has been compared with yet; `unsharp` behind the scale and in front of the pad: the sharpen, mjg_open_sharp, a restatement of
  * vf_unsharp.c's 8-bit path that no FFmpeg build has been compared with yet; `yadif` as the very first filter, frame-rate modes 0 and 2: the deinterlacer, mjg_open_deint,
  * a restatement of the filter's C path that no FFmpeg build has been compared with yet; a leading run of vflip / transpose: one of eight plane maps, mjg_open_orient; and `-pix_fmt yuvj420p|yuvj422p` from a 4:4:4 or 4:2:2 input: the chroma down-sampling
@@ -259,6 +262,32 @@ int mjg_open_lut(int device, const mjg_config *cfg, int src_chroma_format, int d
                  int crop_x, int crop_y, int crop_w, int crop_h,
                  const mjg_lut *lut_in, const mjg_lut *lut_out, const mjg_unsharp *us,
                  int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
+
+/* A colour matrix on whole frames: the six 16.16 coefficients c2..c7 of
+ *   u = U - 128, v = V - 128          (U, V: the chroma pair of the luma sample's cell)
+ *   Y' = clip8((65536 (Y - 16) + yu u + yv v + 1081344) >> 16)
+ *   U' = clip8((uu u + uv v + 8421376) >> 16),  V' = clip8((vu u + vv v + 8421376) >> 16)
+ * in C int with an arithmetic shift.  `-vf colormatrix=SRC:DST` on 8-bit planar frames is six such
+ * numbers (profile.colormatrix_coefs makes them); the library knows the numbers, not the filter. */
+typedef struct mjg_cmatrix { int32_t yu, yv, uu, uv, vu, vv; } mjg_cmatrix;
+/* mjg_open_lut with a colour matrix.  A NULL cm, or the identity (0, 0, 65536, 0, 0, 65536), is
+ * exactly mjg_open_lut: no buffer and the same launches.
+ * The stage stands behind the deinterlacer and the orientation, and in front of lut_in, the crop
+ * and the sws stage: it acts on whole frames in the source format, before any range conversion.
+ * k_cmat_frame (scale.hip) covers all three planes of every frame of a submit in one
+ * launch.  Behind a deinterlacer or an orientation it runs in place in that stage's buffer (so
+ * mjg_debug_oriented, or mjg_debug_deint without an orientation, then return the converted
+ * frames); otherwise it writes the buffer of the launch slot that a lut_in alone would write, and a
+ * lut_in then runs in place there.  The caller's frames are never written.  The stage works per
+ * frame (MJG_F_MERGE, mjg_submit_segments and mjg_submit_halo are unchanged) and belongs to the
+ * MJG_K_SCALE interval, which a matrix alone opens too.
+ * MJG_E_INVALID, with a message that starts "cmatrix", for a coefficient outside [-262144, 262144]
+ * (four times unity: every sum then stays below 2^27 and int32 holds it), before any device call.
+ * (Added without a version step, as mjg_open_orient.) */
+int mjg_open_cmat(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient,
+                  int crop_x, int crop_y, int crop_w, int crop_h, const mjg_cmatrix *cm,
+                  const mjg_lut *lut_in, const mjg_lut *lut_out, const mjg_unsharp *us,
+                  int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
 void mjg_close(mjg_ctx *ctx);
 
 /* Bytes of one packed planar input frame (src_w x src_h in the source chroma format). */
@@ -377,6 +406,15 @@ int mjg_debug_lut(mjg_ctx *ctx, int slot, mjg_lut *out);
  * MJG_E_STATE for a context without a lut_in.  Under a lut_out, mjg_debug_planes and
  * mjg_debug_presharp return the mapped planes.  (With mjg_open_lut.) */
 int mjg_debug_lut_in(mjg_ctx *ctx, int frame, uint8_t *out, size_t cap);
+/* 1 and the colour matrix in *out (which may be NULL) when the context has one, 0 without (none
+ * given, or the identity), or a negative MJG_E_* code for a null context.  Host state only.  (With
+ * mjg_open_cmat.) */
+int mjg_debug_cmat(mjg_ctx *ctx, mjg_cmatrix *out);
+/* k_cmat_frame's output for frame `frame` of the last synced submit: a whole frame in the source
+ * format (behind the orientation: the oriented one), from wherever the stage left it.  A lut_in
+ * runs in place behind the stage, so with one these are the mapped frames.  MJG_E_STATE for a
+ * context without a matrix.  (With mjg_open_cmat.) */
+int mjg_debug_cmat_out(mjg_ctx *ctx, int frame, uint8_t *out, size_t cap);
 /* Which kernel the sws stage runs for a plane (0 = luma, 1 = chroma): 0 no sws stage for it (the
  * context has none), 1 k_plane_copy (the plane keeps its size), 2 k_scale (one LDS tile per 64-column
  * tile: down to about 4:1), 3 k_scale_stream (any ratio whose filters stay below 256 taps, about
