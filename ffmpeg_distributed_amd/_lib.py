@@ -48,6 +48,7 @@ EXPORTS = (
     "mjg_open_lut", "mjg_debug_lut", "mjg_debug_lut_in",
     "mjg_debug_tail",
     "mjg_open_cmat", "mjg_debug_cmat", "mjg_debug_cmat_out",
+    "mjg_open_chain",
 )
 
 # mjg_open_deint's `deint`
@@ -100,6 +101,17 @@ class MjgCmatrix(C.Structure):
     """mjg_cmatrix: the six 16.16 coefficients c2..c7 of a colour matrix."""
     _fields_ = [("yu", C.c_int32), ("yv", C.c_int32), ("uu", C.c_int32), ("uv", C.c_int32), ("vu", C.c_int32),
                 ("vv", C.c_int32)]
+
+
+class MjgChain(C.Structure):
+    """mjg_chain: what mjg_open_chain opens, the fields in the order the stages run (mjgpu.h)."""
+    _fields_ = [("src_chroma_format", C.c_int32), ("deint", C.c_int32), ("orient", C.c_int32),
+                ("cmat", C.POINTER(MjgCmatrix)), ("lut_in", C.POINTER(MjgLut)),
+                ("has_crop", C.c_int32), ("crop_x", C.c_int32), ("crop_y", C.c_int32),
+                ("crop_w", C.c_int32), ("crop_h", C.c_int32),
+                ("lut_out", C.POINTER(MjgLut)), ("unsharp", C.POINTER(MjgUnsharp)),
+                ("has_pad", C.c_int32), ("pad_x", C.c_int32), ("pad_y", C.c_int32),
+                ("pad_w", C.c_int32), ("pad_h", C.c_int32)]
 
 
 _lib = None
@@ -164,6 +176,9 @@ def load():
             L.mjg_debug_cmat.restype = C.c_int
             L.mjg_debug_cmat_out.argtypes = [vp, C.c_int, u8p, sz]
             L.mjg_debug_cmat_out.restype = C.c_int
+        if hasattr(L, "mjg_open_chain"):  # absent from libraries built before the chain descriptor (A/B builds)
+            L.mjg_open_chain.argtypes = [C.c_int, C.POINTER(MjgConfig), C.POINTER(MjgChain), C.POINTER(vp)]
+            L.mjg_open_chain.restype = C.c_int
         L.mjg_close.argtypes = [vp]
         L.mjg_close.restype = None
         L.mjg_frame_bytes.argtypes = [vp]
@@ -217,7 +232,7 @@ def load():
                  "mjg_open_deint", "mjg_submit_halo", "mjg_debug_deint", "mjg_debug_deint_flags",
                  "mjg_open_sharp", "mjg_debug_presharp", "mjg_debug_unsharp",
                  "mjg_open_lut", "mjg_debug_lut", "mjg_debug_lut_in", "mjg_debug_tail",
-                 "mjg_open_cmat", "mjg_debug_cmat", "mjg_debug_cmat_out")
+                 "mjg_open_cmat", "mjg_debug_cmat", "mjg_debug_cmat_out", "mjg_open_chain")
                 if os.environ.get("MJG_LIBRARY") else ())
         for name in EXPORTS:
             if name not in late:

@@ -709,18 +709,14 @@ int alloc_slot(mjg_ctx *c, Slot &S) {
   return MJG_OK;
 }
 
-// open, step 1: the config, the rectangle and the pad (no device, no environment).
-// deint: MJG_DEINT_* bits (mjgpu.h), the deinterlacer in front of everything, on the decoded frames
-// orient: T | FX << 1 | FY << 2 (mjgpu.h), applied next: the crop, dst_w / dst_h and the pad
-// refer to the oriented frame
-// crop: x, y, w, h in luma samples of the oriented frame, or nullptr for the whole frame
-// pad: x, y, w, h in luma samples of the encoded frame (the picture's place and the canvas size),
-// or nullptr for no pad
-// us: -vf unsharp between the sws stage and the pad, or nullptr (both amounts 0: no filter either)
-// lut_in, lut_out: the tables in front of and behind the sws stage, or nullptr (three identity tables: none either)
-// cm: the colour matrix in front of lut_in, or nullptr (the identity: none either)
-int check_config(const mjg_config &k, int src_cf, int deint, int orient, const int *crop, const mjg_cmatrix *cm,
-                 const mjg_lut *lut_in, const mjg_lut *lut_out, const mjg_unsharp *us, const int *pad, Layout *lay) {
+// open, step 1: the config and the chain (no device, no environment).  mjgpu.h says what each field of
+// ch means; the crop is in luma samples of the oriented frame, the pad (the picture's place and the
+// canvas size) in luma samples of the encoded one.  The structs ch points to are read here and, through
+// lay, until open_ctx returns.
+int check_config(const mjg_config &k, const mjg_chain &ch, Layout *lay) {
+  const int src_cf = ch.src_chroma_format, deint = ch.deint, orient = ch.orient;
+  const mjg_cmatrix *cm = ch.cmat;
+  const mjg_unsharp *us = ch.unsharp;
   if (std::min({k.src_w, k.src_h, k.dst_w, k.dst_h}) < 1 || std::max({k.src_w, k.src_h, k.dst_w, k.dst_h}) > 16384)
     return set_err(MJG_E_INVALID, "bad frame size %dx%d -> %dx%d", k.src_w, k.src_h, k.dst_w, k.dst_h);
   if (k.qscale < 1 || k.qscale > 31) return set_err(MJG_E_INVALID, "qscale %d not in 1..31", k.qscale);
@@ -749,8 +745,8 @@ int check_config(const mjg_config &k, int src_cf, int deint, int orient, const i
     return set_err(MJG_E_INVALID, "orient %d transposes a 4:2:2 source (only 4:2:0 and 4:4:4 keep their format)", orient);
   const int ow = (orient & 1) ? k.src_h : k.src_w, oh = (orient & 1) ? k.src_w : k.src_h;
   // the rectangle (the frame sizes and the source format are valid here)
-  const int cx = crop ? crop[0] : 0, cy = crop ? crop[1] : 0;
-  const int crw = crop ? crop[2] : ow, crh = crop ? crop[3] : oh;  // the sws stage's / k_encode's input size
+  const int cx = ch.has_crop ? ch.crop_x : 0, cy = ch.has_crop ? ch.crop_y : 0;
+  const int crw = ch.has_crop ? ch.crop_w : ow, crh = ch.has_crop ? ch.crop_h : oh;  // the sws stage's / k_encode's input size
   if (crw < 1 || crh < 1)
     return set_err(MJG_E_INVALID, "crop %dx%d at (%d,%d): the size is not positive", crw, crh, cx, cy);
   if (cx < 0 || cy < 0 || cx > ow - crw || cy > oh - crh)
@@ -761,8 +757,8 @@ int check_config(const mjg_config &k, int src_cf, int deint, int orient, const i
                    "sub-sampling (%dx%d)", crw, crh, cx, cy, 1 << s_hsh, 1 << s_vsh);
   // the pad (the encoded format and the picture size are valid here): the trivial rectangle is no pad
   const int e_hsh = k.chroma_format == MJG_CHROMA_444 ? 0 : 1, e_vsh = k.chroma_format == MJG_CHROMA_420 ? 1 : 0;
-  const int px = pad ? pad[0] : 0, py = pad ? pad[1] : 0;
-  const int pw = pad ? pad[2] : k.dst_w, ph = pad ? pad[3] : k.dst_h;
+  const int px = ch.has_pad ? ch.pad_x : 0, py = ch.has_pad ? ch.pad_y : 0;
+  const int pw = ch.has_pad ? ch.pad_w : k.dst_w, ph = ch.has_pad ? ch.pad_h : k.dst_h;
   if (pw < 1 || ph < 1)
     return set_err(MJG_E_INVALID, "pad %dx%d with the picture at (%d,%d): the size is not positive", pw, ph, px, py);
   if (pw > 16384 || ph > 16384)
@@ -809,7 +805,7 @@ int check_config(const mjg_config &k, int src_cf, int deint, int orient, const i
                        i ? "chroma" : "luma", sz[2 * i], sz[2 * i + 1], hs, kSharpMaxHalfSum);
     }
   }
-  const mjg_lut *luts[2] = {lut_in, lut_out};
+  const mjg_lut *luts[2] = {ch.lut_in, ch.lut_out};
   for (const mjg_lut *&l : luts) {
     bool id = true;
     for (int i = 0; l && i < 256; i++) id = id && l->y[i] == i && l->u[i] == i && l->v[i] == i;
@@ -826,7 +822,16 @@ int check_config(const mjg_config &k, int src_cf, int deint, int orient, const i
                        kCmatMaxCoef);
     if (v[0] == 0 && v[1] == 0 && v[2] == 65536 && v[3] == 0 && v[4] == 0 && v[5] == 65536) cm = nullptr;
   }
-  *lay = Layout{deint, sharp, u, {luts[0], luts[1]}, cm, orient, ow, oh, cx, cy, crw, crh, px, py, pw, ph, has_pad, s_hsh, s_vsh, e_hsh, e_vsh};
+  Layout &l = *lay;
+  l.deint = deint;
+  l.sharp = sharp, l.us = u;
+  l.lut[0] = luts[0], l.lut[1] = luts[1];
+  l.cm = cm;
+  l.orient = orient, l.ow = ow, l.oh = oh;
+  l.cx = cx, l.cy = cy, l.crw = crw, l.crh = crh;
+  l.px = px, l.py = py, l.pw = pw, l.ph = ph;
+  l.has_pad = has_pad;
+  l.s_hsh = s_hsh, l.s_vsh = s_vsh, l.hsh = e_hsh, l.vsh = e_vsh;
   return MJG_OK;
 }
 
@@ -1352,15 +1357,13 @@ int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
   return alloc_slot(c, c->slot[0]);
 }
 
-int open_ctx(int device, const mjg_config *cfg, int src_cf, int deint, int orient, const int *crop,
-             const mjg_cmatrix *cm, const mjg_lut *lut_in, const mjg_lut *lut_out, const mjg_unsharp *us, const int *pad, mjg_ctx *c) {
+int open_ctx(int device, const mjg_config &k, const mjg_chain &chain, mjg_ctx *c) {
   c->device = device;
-  c->cfg = *cfg;
-  const mjg_config &k = *cfg;
+  c->cfg = k;
   Layout lay;
   int rc;
-  if ((rc = check_config(k, src_cf, deint, orient, crop, cm, lut_in, lut_out, us, pad, &lay))) return rc;
-  if ((rc = plan_geometry(k, src_cf, lay, env_int("MJG_UNALIGNED_FETCH", 1) != 0, c))) return rc;
+  if ((rc = check_config(k, chain, &lay))) return rc;
+  if ((rc = plan_geometry(k, chain.src_chroma_format, lay, env_int("MJG_UNALIGNED_FETCH", 1) != 0, c))) return rc;
   plan_orient(k, lay, c);
   plan_deint(k, lay, c);
   plan_sharp(k, lay, c);
@@ -1443,13 +1446,11 @@ int mjg_device_numa_node(int device) {
   return node < 0 ? -1 : node;
 }
 
-namespace {
-int open_any(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, const int *crop,
-             const mjg_cmatrix *cm, const mjg_lut *lut_in, const mjg_lut *lut_out, const mjg_unsharp *us, const int *pad, mjg_ctx **out) {
-  if (!cfg || !out) return set_err(MJG_E_INVALID, "null argument");
+int mjg_open_chain(int device, const mjg_config *cfg, const mjg_chain *chain, mjg_ctx **out) {
+  if (!cfg || !chain || !out) return set_err(MJG_E_INVALID, "null argument");
   *out = nullptr;
   mjg_ctx *c = new mjg_ctx();
-  const int rc = open_ctx(device, cfg, src_chroma_format, deint, orient, crop, cm, lut_in, lut_out, us, pad, c);
+  const int rc = open_ctx(device, *cfg, *chain, c);
   if (rc) {
     const std::string keep = g_err;
     free_ctx(c);
@@ -1459,56 +1460,87 @@ int open_any(int device, const mjg_config *cfg, int src_chroma_format, int deint
   *out = c;
   return MJG_OK;
 }
-}  // namespace
 
-int mjg_open_crop(int device, const mjg_config *cfg, int src_chroma_format, int crop_x, int crop_y, int crop_w,
-                  int crop_h, mjg_ctx **out) {
-  const int crop[4] = {crop_x, crop_y, crop_w, crop_h};
-  return open_any(device, cfg, src_chroma_format, 0, 0, crop, nullptr, nullptr, nullptr, nullptr, nullptr, out);
-}
-
-int mjg_open_orient(int device, const mjg_config *cfg, int src_chroma_format, int orient, int crop_x, int crop_y,
-                    int crop_w, int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
-  const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, 0, orient, crop, nullptr, nullptr, nullptr, nullptr, pad, out);
-}
-
-int mjg_open_deint(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, int crop_x,
-                   int crop_y, int crop_w, int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
-  const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, deint, orient, crop, nullptr, nullptr, nullptr, nullptr, pad, out);
-}
-
-int mjg_open_sharp(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, int crop_x,
-                   int crop_y, int crop_w, int crop_h, const mjg_unsharp *us, int pad_x, int pad_y, int pad_w,
-                   int pad_h, mjg_ctx **out) {
-  const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, deint, orient, crop, nullptr, nullptr, nullptr, us, pad, out);
+// The entry points from before mjg_chain: each is the chain it fills here, member by member.
+// mjg_open_src gives neither rectangle, mjg_open_crop a crop and no pad, the others both.
+int mjg_open_cmat(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, int crop_x,
+                  int crop_y, int crop_w, int crop_h, const mjg_cmatrix *cm, const mjg_lut *lut_in,
+                  const mjg_lut *lut_out, const mjg_unsharp *us, int pad_x, int pad_y, int pad_w, int pad_h,
+                  mjg_ctx **out) {
+  mjg_chain ch{};
+  ch.src_chroma_format = src_chroma_format, ch.deint = deint, ch.orient = orient;
+  ch.cmat = cm;
+  ch.lut_in = lut_in;
+  ch.has_crop = 1, ch.crop_x = crop_x, ch.crop_y = crop_y, ch.crop_w = crop_w, ch.crop_h = crop_h;
+  ch.lut_out = lut_out;
+  ch.unsharp = us;
+  ch.has_pad = 1, ch.pad_x = pad_x, ch.pad_y = pad_y, ch.pad_w = pad_w, ch.pad_h = pad_h;
+  return mjg_open_chain(device, cfg, &ch, out);
 }
 
 int mjg_open_lut(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, int crop_x,
                  int crop_y, int crop_w, int crop_h, const mjg_lut *lut_in, const mjg_lut *lut_out,
                  const mjg_unsharp *us, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
-  const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, deint, orient, crop, nullptr, lut_in, lut_out, us, pad, out);
+  mjg_chain ch{};
+  ch.src_chroma_format = src_chroma_format, ch.deint = deint, ch.orient = orient;
+  ch.lut_in = lut_in;
+  ch.has_crop = 1, ch.crop_x = crop_x, ch.crop_y = crop_y, ch.crop_w = crop_w, ch.crop_h = crop_h;
+  ch.lut_out = lut_out;
+  ch.unsharp = us;
+  ch.has_pad = 1, ch.pad_x = pad_x, ch.pad_y = pad_y, ch.pad_w = pad_w, ch.pad_h = pad_h;
+  return mjg_open_chain(device, cfg, &ch, out);
 }
 
-int mjg_open_cmat(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, int crop_x,
-                  int crop_y, int crop_w, int crop_h, const mjg_cmatrix *cm, const mjg_lut *lut_in,
-                  const mjg_lut *lut_out, const mjg_unsharp *us, int pad_x, int pad_y, int pad_w, int pad_h,
-                  mjg_ctx **out) {
-  const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, deint, orient, crop, cm, lut_in, lut_out, us, pad, out);
+int mjg_open_sharp(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, int crop_x,
+                   int crop_y, int crop_w, int crop_h, const mjg_unsharp *us, int pad_x, int pad_y, int pad_w,
+                   int pad_h, mjg_ctx **out) {
+  mjg_chain ch{};
+  ch.src_chroma_format = src_chroma_format, ch.deint = deint, ch.orient = orient;
+  ch.has_crop = 1, ch.crop_x = crop_x, ch.crop_y = crop_y, ch.crop_w = crop_w, ch.crop_h = crop_h;
+  ch.unsharp = us;
+  ch.has_pad = 1, ch.pad_x = pad_x, ch.pad_y = pad_y, ch.pad_w = pad_w, ch.pad_h = pad_h;
+  return mjg_open_chain(device, cfg, &ch, out);
+}
+
+int mjg_open_deint(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient, int crop_x,
+                   int crop_y, int crop_w, int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
+  mjg_chain ch{};
+  ch.src_chroma_format = src_chroma_format, ch.deint = deint, ch.orient = orient;
+  ch.has_crop = 1, ch.crop_x = crop_x, ch.crop_y = crop_y, ch.crop_w = crop_w, ch.crop_h = crop_h;
+  ch.has_pad = 1, ch.pad_x = pad_x, ch.pad_y = pad_y, ch.pad_w = pad_w, ch.pad_h = pad_h;
+  return mjg_open_chain(device, cfg, &ch, out);
+}
+
+int mjg_open_orient(int device, const mjg_config *cfg, int src_chroma_format, int orient, int crop_x, int crop_y,
+                    int crop_w, int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
+  mjg_chain ch{};
+  ch.src_chroma_format = src_chroma_format, ch.orient = orient;
+  ch.has_crop = 1, ch.crop_x = crop_x, ch.crop_y = crop_y, ch.crop_w = crop_w, ch.crop_h = crop_h;
+  ch.has_pad = 1, ch.pad_x = pad_x, ch.pad_y = pad_y, ch.pad_w = pad_w, ch.pad_h = pad_h;
+  return mjg_open_chain(device, cfg, &ch, out);
 }
 
 int mjg_open_pad(int device, const mjg_config *cfg, int src_chroma_format, int crop_x, int crop_y, int crop_w,
                  int crop_h, int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out) {
-  const int crop[4] = {crop_x, crop_y, crop_w, crop_h}, pad[4] = {pad_x, pad_y, pad_w, pad_h};
-  return open_any(device, cfg, src_chroma_format, 0, 0, crop, nullptr, nullptr, nullptr, nullptr, pad, out);
+  mjg_chain ch{};
+  ch.src_chroma_format = src_chroma_format;
+  ch.has_crop = 1, ch.crop_x = crop_x, ch.crop_y = crop_y, ch.crop_w = crop_w, ch.crop_h = crop_h;
+  ch.has_pad = 1, ch.pad_x = pad_x, ch.pad_y = pad_y, ch.pad_w = pad_w, ch.pad_h = pad_h;
+  return mjg_open_chain(device, cfg, &ch, out);
+}
+
+int mjg_open_crop(int device, const mjg_config *cfg, int src_chroma_format, int crop_x, int crop_y, int crop_w,
+                  int crop_h, mjg_ctx **out) {
+  mjg_chain ch{};
+  ch.src_chroma_format = src_chroma_format;
+  ch.has_crop = 1, ch.crop_x = crop_x, ch.crop_y = crop_y, ch.crop_w = crop_w, ch.crop_h = crop_h;
+  return mjg_open_chain(device, cfg, &ch, out);
 }
 
 int mjg_open_src(int device, const mjg_config *cfg, int src_chroma_format, mjg_ctx **out) {
-  return open_any(device, cfg, src_chroma_format, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out);
+  mjg_chain ch{};
+  ch.src_chroma_format = src_chroma_format;
+  return mjg_open_chain(device, cfg, &ch, out);
 }
 
 int mjg_open(int device, const mjg_config *cfg, mjg_ctx **out) {
@@ -1777,6 +1809,24 @@ int sync_for_read(mjg_ctx *c) {
   if (pending_jobs(c) > 0 && !c->synced_since_submit)
     if (const int rc = mjg_sync(c, nullptr, nullptr)) return rc;
   return c->last < 0 ? set_err(MJG_E_STATE, "nothing submitted") : MJG_OK;
+}
+
+// The frame readbacks (mjg_debug_planes and its kin): frame `frame` of the latest synced submit, out of
+// the buffer `buf` names in that submit's slot, whose frames are nbytes apart.  Pending submits are
+// synced first
+int read_frame(mjg_ctx *c, int frame, uint8_t *out, size_t cap, size_t nbytes,
+               uint8_t *(*buf)(const mjg_ctx *, const Slot &)) {
+  if (pending_jobs(c) > 0) {
+    const int rc = mjg_sync(c, nullptr, nullptr);
+    if (rc) return rc;
+  }
+  if (pending_jobs(c) > 0 || c->last < 0) return set_err(MJG_E_STATE, "sync every queued submit first");
+  const Slot &L = c->slot[c->last];
+  if (frame < 0 || frame >= L.jn[c->last_job]) return set_err(MJG_E_INVALID, "frame %d", frame);
+  if (cap < nbytes) return set_err(MJG_E_CAPACITY, "need %zu bytes", nbytes);
+  const size_t f = (size_t)L.jf0[c->last_job] + (size_t)frame;
+  HIP_TRY(hipMemcpy(out, buf(c, L) + f * nbytes, nbytes, hipMemcpyDeviceToHost));
+  return MJG_OK;
 }
 }  // namespace
 
@@ -2074,35 +2124,15 @@ int mjg_debug_encode_path(mjg_ctx *c) {
 int mjg_debug_planes(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
   if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
   if (!c->scale) return set_err(MJG_E_STATE, "context has no sws stage (same size, same chroma format)");
-  if (pending_jobs(c) > 0) {  // the latest synced submit's planes
-    const int rc = mjg_sync(c, nullptr, nullptr);
-    if (rc) return rc;
-  }
-  if (pending_jobs(c) > 0 || c->last < 0) return set_err(MJG_E_STATE, "sync every queued submit first");
-  const Slot &L = c->slot[c->last];
-  if (frame < 0 || frame >= L.jn[c->last_job]) return set_err(MJG_E_INVALID, "frame %d", frame);
-  if (cap < c->enc_frame_bytes) return set_err(MJG_E_CAPACITY, "need %zu bytes", c->enc_frame_bytes);
-  const size_t f = (size_t)L.jf0[c->last_job] + (size_t)frame;
   // the encoder's input: under a sharpen its output
-  const uint8_t *buf = c->sharp ? L.d_sharp : L.d_scaled;
-  HIP_TRY(hipMemcpy(out, buf + f * c->enc_frame_bytes, c->enc_frame_bytes, hipMemcpyDeviceToHost));
-  return MJG_OK;
+  return read_frame(c, frame, out, cap, c->enc_frame_bytes,
+                    [](const mjg_ctx *x, const Slot &S) { return x->sharp ? S.d_sharp : S.d_scaled; });
 }
 
 int mjg_debug_presharp(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
   if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
   if (!c->sharp) return set_err(MJG_E_STATE, "context has no sharpen (no unsharp, or both amounts 0)");
-  if (pending_jobs(c) > 0) {  // the latest synced submit's planes
-    const int rc = mjg_sync(c, nullptr, nullptr);
-    if (rc) return rc;
-  }
-  if (pending_jobs(c) > 0 || c->last < 0) return set_err(MJG_E_STATE, "sync every queued submit first");
-  const Slot &L = c->slot[c->last];
-  if (frame < 0 || frame >= L.jn[c->last_job]) return set_err(MJG_E_INVALID, "frame %d", frame);
-  if (cap < c->enc_frame_bytes) return set_err(MJG_E_CAPACITY, "need %zu bytes", c->enc_frame_bytes);
-  const size_t f = (size_t)L.jf0[c->last_job] + (size_t)frame;
-  HIP_TRY(hipMemcpy(out, L.d_scaled + f * c->enc_frame_bytes, c->enc_frame_bytes, hipMemcpyDeviceToHost));
-  return MJG_OK;
+  return read_frame(c, frame, out, cap, c->enc_frame_bytes, [](const mjg_ctx *, const Slot &S) { return S.d_scaled; });
 }
 
 int mjg_debug_unsharp(mjg_ctx *c, mjg_unsharp *out) {
@@ -2121,18 +2151,8 @@ int mjg_debug_lut(mjg_ctx *c, int slot, mjg_lut *out) {
 int mjg_debug_lut_in(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
   if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
   if (!c->has_lut[0]) return set_err(MJG_E_STATE, "context has no table in front of the sws stage (none, or identity tables)");
-  if (pending_jobs(c) > 0) {  // the latest synced submit's frames
-    const int rc = mjg_sync(c, nullptr, nullptr);
-    if (rc) return rc;
-  }
-  if (pending_jobs(c) > 0 || c->last < 0) return set_err(MJG_E_STATE, "sync every queued submit first");
-  const Slot &L = c->slot[c->last];
-  if (frame < 0 || frame >= L.jn[c->last_job]) return set_err(MJG_E_INVALID, "frame %d", frame);
-  if (cap < c->in_frame_bytes) return set_err(MJG_E_CAPACITY, "need %zu bytes", c->in_frame_bytes);
-  const size_t f = (size_t)L.jf0[c->last_job] + (size_t)frame;
   // (in place in the buffer of the stage in front of it, else d_lut)
-  HIP_TRY(hipMemcpy(out, lut_in_buf(c, L) + f * c->in_frame_bytes, c->in_frame_bytes, hipMemcpyDeviceToHost));
-  return MJG_OK;
+  return read_frame(c, frame, out, cap, c->in_frame_bytes, lut_in_buf);
 }
 
 int mjg_debug_cmat(mjg_ctx *c, mjg_cmatrix *out) {
@@ -2144,34 +2164,14 @@ int mjg_debug_cmat(mjg_ctx *c, mjg_cmatrix *out) {
 int mjg_debug_cmat_out(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
   if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
   if (!c->has_cmat) return set_err(MJG_E_STATE, "context has no colour matrix (none, or the identity)");
-  if (pending_jobs(c) > 0) {  // the latest synced submit's frames
-    const int rc = mjg_sync(c, nullptr, nullptr);
-    if (rc) return rc;
-  }
-  if (pending_jobs(c) > 0 || c->last < 0) return set_err(MJG_E_STATE, "sync every queued submit first");
-  const Slot &L = c->slot[c->last];
-  if (frame < 0 || frame >= L.jn[c->last_job]) return set_err(MJG_E_INVALID, "frame %d", frame);
-  if (cap < c->in_frame_bytes) return set_err(MJG_E_CAPACITY, "need %zu bytes", c->in_frame_bytes);
-  const size_t f = (size_t)L.jf0[c->last_job] + (size_t)frame;
   // (in place in the buffer of the stage in front of it, else d_lut; a lut_in has mapped it there)
-  HIP_TRY(hipMemcpy(out, lut_in_buf(c, L) + f * c->in_frame_bytes, c->in_frame_bytes, hipMemcpyDeviceToHost));
-  return MJG_OK;
+  return read_frame(c, frame, out, cap, c->in_frame_bytes, lut_in_buf);
 }
 
 int mjg_debug_oriented(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
   if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
   if (!c->orient) return set_err(MJG_E_STATE, "context has no orientation (orient 0)");
-  if (pending_jobs(c) > 0) {  // the latest synced submit's frames
-    const int rc = mjg_sync(c, nullptr, nullptr);
-    if (rc) return rc;
-  }
-  if (pending_jobs(c) > 0 || c->last < 0) return set_err(MJG_E_STATE, "sync every queued submit first");
-  const Slot &L = c->slot[c->last];
-  if (frame < 0 || frame >= L.jn[c->last_job]) return set_err(MJG_E_INVALID, "frame %d", frame);
-  if (cap < c->in_frame_bytes) return set_err(MJG_E_CAPACITY, "need %zu bytes", c->in_frame_bytes);
-  const size_t f = (size_t)L.jf0[c->last_job] + (size_t)frame;
-  HIP_TRY(hipMemcpy(out, L.d_orient + f * c->in_frame_bytes, c->in_frame_bytes, hipMemcpyDeviceToHost));
-  return MJG_OK;
+  return read_frame(c, frame, out, cap, c->in_frame_bytes, [](const mjg_ctx *, const Slot &S) { return S.d_orient; });
 }
 
 int mjg_debug_orient(mjg_ctx *c) {
@@ -2182,17 +2182,7 @@ int mjg_debug_orient(mjg_ctx *c) {
 int mjg_debug_deint(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
   if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
   if (!c->deint) return set_err(MJG_E_STATE, "context has no deinterlacer (deint 0)");
-  if (pending_jobs(c) > 0) {  // the latest synced submit's frames
-    const int rc = mjg_sync(c, nullptr, nullptr);
-    if (rc) return rc;
-  }
-  if (pending_jobs(c) > 0 || c->last < 0) return set_err(MJG_E_STATE, "sync every queued submit first");
-  const Slot &L = c->slot[c->last];
-  if (frame < 0 || frame >= L.jn[c->last_job]) return set_err(MJG_E_INVALID, "frame %d", frame);
-  if (cap < c->in_frame_bytes) return set_err(MJG_E_CAPACITY, "need %zu bytes", c->in_frame_bytes);
-  const size_t f = (size_t)L.jf0[c->last_job] + (size_t)frame;
-  HIP_TRY(hipMemcpy(out, L.d_deint + f * c->in_frame_bytes, c->in_frame_bytes, hipMemcpyDeviceToHost));
-  return MJG_OK;
+  return read_frame(c, frame, out, cap, c->in_frame_bytes, [](const mjg_ctx *, const Slot &S) { return S.d_deint; });
 }
 
 int mjg_debug_deint_flags(mjg_ctx *c) {

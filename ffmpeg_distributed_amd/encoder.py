@@ -22,12 +22,14 @@ the orientation: every output frame is made from the frames before and after it,
 each segment of a submit_segments) is a whole sequence, and `submit(..., halo=)` hands over a
 piece of a longer one with its neighbour frames.  `unsharp=` (lx, ly, la, cx, cy, ca: `-vf unsharp`
 behind the scale and in front of the pad, the amounts as floats) sharpens or blurs the sws stage's
-output planes on the GPU (mjg_open_sharp); the encoder then reads the sharpened planes.  `lut_in=` /
-`lut_out=` ((3, 256) uint8, rows Y, U, V) map every sample through a table per plane on the GPU
-(mjg_open_lut), in front of the sws stage and directly behind it: `-vf eq=...` in front of the scale or
+output planes on the GPU; the encoder then reads the sharpened planes.  `lut_in=` /
+`lut_out=` ((3, 256) uint8, rows Y, U, V) map every sample through a table per plane on the GPU,
+in front of the sws stage and directly behind it: `-vf eq=...` in front of the scale or
 directly behind it, with profile.eq_tables.  `cmat=` (c2, ..., c7: six 16.16 ints) is a colour matrix
-on whole frames behind the orientation and in front of `lut_in` (mjg_open_cmat): `-vf
-colormatrix=SRC:DST` with profile.colormatrix_coefs.  No CPU fallback.
+on whole frames behind the orientation and in front of `lut_in`: `-vf
+colormatrix=SRC:DST` with profile.colormatrix_coefs.  An encoder with any of these opens as one
+mjg_chain (include/mjgpu.h, which says what each stage does) through mjg_open_chain; one with none
+through mjg_open / mjg_open_src.  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -84,11 +86,11 @@ class MjpegEncoder:
         self.src_w, self.src_h = int(src_w), int(src_h)
         # crop: (x, y, w, h) in luma samples of the src_w x src_h frames, resolved as
         # profile.resolve_crop does (x, y multiples of the source's sub-sampling); the encoded
-        # size defaults to the rectangle's.  None: whole frames, through mjg_open / mjg_open_src
+        # size defaults to the rectangle's.  None: whole frames
         self.crop = None if crop is None else tuple(int(v) for v in crop)
         if self.crop is not None and len(self.crop) != 4:
             raise ValueError(f"crop {crop!r}: (x, y, w, h)")
-        # orient: T | FX << 1 | FY << 2, the first filter (mjg_open_orient); or_w x or_h is the oriented
+        # orient: T | FX << 1 | FY << 2, the first filter behind a deinterlacer; or_w x or_h is the oriented
         # frame, which the crop, the encoded size and the pad refer to
         self.orient = int(orient)
         self.or_w, self.or_h = (self.src_h, self.src_w) if self.orient & 1 else (self.src_w, self.src_h)
@@ -139,21 +141,21 @@ class MjpegEncoder:
                         int(qscale), int(sar[0]), int(sar[1]), self.max_batch, flags,
                         _lib.CHROMA_FORMATS[self.chroma])
         h = C.c_void_p()
-        # deint: 0, or MJG_DEINT_YADIF | MJG_DEINT_NOSPATIAL | MJG_DEINT_BFF (mjg_open_deint): yadif on
-        # the decoded frames, in front of the orientation.  Every submit is then a whole sequence
-        # (or a piece of one: submit(..., halo=)).  deint=0 opens through mjg_open_deint all the same
-        # (exactly mjg_open_orient); None, the default, through the entry points below
+        # deint: 0, or MJG_DEINT_YADIF | MJG_DEINT_NOSPATIAL | MJG_DEINT_BFF: yadif on the decoded
+        # frames, in front of the orientation.  Every submit is then a whole sequence (or a piece of
+        # one: submit(..., halo=)).  deint=0 and None, the default, are both no deinterlacer (chain
+        # field 0); deint=0 opens through mjg_open_chain all the same
         self.deint = int(deint or 0)
-        # unsharp: (lx, ly, la, cx, cy, ca), `-vf unsharp` between the sws stage and the pad
-        # (mjg_open_sharp); the amounts are floats and become the filter's integers here, (int)(amount
-        # * 65536.0).  None, the default, opens as without it
+        # unsharp: (lx, ly, la, cx, cy, ca), `-vf unsharp` between the sws stage and the pad; the
+        # amounts are floats and become the filter's integers here, (int)(amount * 65536.0).  None,
+        # the default, opens as without it
         self.unsharp = None
         if unsharp is not None:
             if len(unsharp) != 6:
                 raise ValueError(f"unsharp {unsharp!r}: (lx, ly, la, cx, cy, ca)")
             lx, ly, la, cx, cy, ca = unsharp
             self.unsharp = (int(lx), int(ly), int(float(la) * 65536.0), int(cx), int(cy), int(float(ca) * 65536.0))
-        # lut_in / lut_out: a (3, 256) uint8 array each, rows Y, U, V, out = t[in] (mjg_open_lut): in front
+        # lut_in / lut_out: a (3, 256) uint8 array each, rows Y, U, V, out = t[in]: in front
         # of the sws stage on the frames behind the orientation, and on the sws stage's output picture
         # in front of the unsharp.  `-vf eq` is profile.eq_tables.  None, the default, opens as without them
         luts = []
@@ -165,73 +167,43 @@ class MjpegEncoder:
             luts.append(t)
         self.lut_in, self.lut_out = luts
         # cmat: (c2, c3, c4, c5, c6, c7), the six 16.16 coefficients of a colour matrix on the frames behind
-        # the orientation, in front of lut_in (mjg_open_cmat).  `-vf colormatrix` is
+        # the orientation, in front of lut_in.  `-vf colormatrix` is
         # profile.colormatrix_coefs.  None, the default, opens as without it
         self.cmat = None
         if cmat is not None:
             if len(cmat) != 6:
                 raise ValueError(f"cmat {cmat!r}: (c2, c3, c4, c5, c6, c7)")
             self.cmat = tuple(int(v) for v in cmat)
-        if self.cmat is not None:
-            if not hasattr(self._L, "mjg_open_cmat"):
-                raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_cmat")
-            rect = self.crop if self.crop is not None else (0, 0, self.or_w, self.or_h)
-            canvas = self.pad if self.pad is not None else (0, 0, self.dst_w, self.dst_h)
-            us = None if self.unsharp is None else C.byref(_lib.MjgUnsharp(*self.unsharp))
-            tabs = [None if t is None else C.byref(_lib.MjgLut.from_buffer_copy(t.tobytes())) for t in luts]
-            cm = _lib.MjgCmatrix(*self.cmat)
-            check(self._L.mjg_open_cmat(self.device, C.byref(cfg), _lib.CHROMA_FORMATS[self.src_chroma],
-                                        self.deint, self.orient, *rect, C.byref(cm), tabs[0], tabs[1], us, *canvas,
-                                        C.byref(h)))
-        elif lut_in is not None or lut_out is not None:
-            if not hasattr(self._L, "mjg_open_lut"):
-                raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_lut")
-            rect = self.crop if self.crop is not None else (0, 0, self.or_w, self.or_h)
-            canvas = self.pad if self.pad is not None else (0, 0, self.dst_w, self.dst_h)
-            us = None if self.unsharp is None else C.byref(_lib.MjgUnsharp(*self.unsharp))
-            tabs = [None if t is None else C.byref(_lib.MjgLut.from_buffer_copy(t.tobytes())) for t in luts]
-            check(self._L.mjg_open_lut(self.device, C.byref(cfg), _lib.CHROMA_FORMATS[self.src_chroma],
-                                       self.deint, self.orient, *rect, tabs[0], tabs[1], us, *canvas, C.byref(h)))
-        elif unsharp is not None:
-            if not hasattr(self._L, "mjg_open_sharp"):
-                raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_sharp")
-            rect = self.crop if self.crop is not None else (0, 0, self.or_w, self.or_h)
-            canvas = self.pad if self.pad is not None else (0, 0, self.dst_w, self.dst_h)
-            us = _lib.MjgUnsharp(*self.unsharp)
-            check(self._L.mjg_open_sharp(self.device, C.byref(cfg), _lib.CHROMA_FORMATS[self.src_chroma],
-                                         self.deint, self.orient, *rect, C.byref(us), *canvas, C.byref(h)))
-        elif deint is not None:
-            if not hasattr(self._L, "mjg_open_deint"):
-                raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_deint")
-            rect = self.crop if self.crop is not None else (0, 0, self.or_w, self.or_h)
-            canvas = self.pad if self.pad is not None else (0, 0, self.dst_w, self.dst_h)
-            check(self._L.mjg_open_deint(self.device, C.byref(cfg), _lib.CHROMA_FORMATS[self.src_chroma],
-                                         self.deint, self.orient, *rect, *canvas, C.byref(h)))
-        elif self.orient:
-            if not hasattr(self._L, "mjg_open_orient"):
-                raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_orient")
-            rect = self.crop if self.crop is not None else (0, 0, self.or_w, self.or_h)
-            canvas = self.pad if self.pad is not None else (0, 0, self.dst_w, self.dst_h)
-            check(self._L.mjg_open_orient(self.device, C.byref(cfg), _lib.CHROMA_FORMATS[self.src_chroma],
-                                          self.orient, *rect, *canvas, C.byref(h)))
-        elif self.pad is not None:
-            if not hasattr(self._L, "mjg_open_pad"):
-                raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_pad")
-            rect = self.crop if self.crop is not None else (0, 0, self.src_w, self.src_h)
-            check(self._L.mjg_open_pad(self.device, C.byref(cfg), _lib.CHROMA_FORMATS[self.src_chroma],
-                                       *rect, *self.pad, C.byref(h)))
-        elif self.crop is not None:
-            if not hasattr(self._L, "mjg_open_crop"):
-                raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_crop")
-            check(self._L.mjg_open_crop(self.device, C.byref(cfg), _lib.CHROMA_FORMATS[self.src_chroma],
-                                        *self.crop, C.byref(h)))
-        elif self.src_chroma == self.chroma:
-            check(self._L.mjg_open(self.device, C.byref(cfg), C.byref(h)))
-        elif not hasattr(self._L, "mjg_open_src"):
-            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_src")
+        # one open: a chain with nothing in it through mjg_open / mjg_open_src (which every library
+        # has, an older one named by MJG_LIBRARY too), everything else as one mjg_chain
+        src_cf = _lib.CHROMA_FORMATS[self.src_chroma]
+        if (self.crop is None and self.pad is None and not self.orient and deint is None and unsharp is None
+                and lut_in is None and lut_out is None and self.cmat is None):
+            if self.src_chroma == self.chroma:
+                check(self._L.mjg_open(self.device, C.byref(cfg), C.byref(h)))
+            elif not hasattr(self._L, "mjg_open_src"):
+                raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_src")
+            else:
+                check(self._L.mjg_open_src(self.device, C.byref(cfg), src_cf, C.byref(h)))
+        elif not hasattr(self._L, "mjg_open_chain"):
+            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_chain")
         else:
-            check(self._L.mjg_open_src(self.device, C.byref(cfg), _lib.CHROMA_FORMATS[self.src_chroma],
-                                       C.byref(h)))
+            chain = _lib.MjgChain(src_chroma_format=src_cf, deint=self.deint, orient=self.orient)
+            if self.cmat is not None:
+                chain.cmat = C.pointer(_lib.MjgCmatrix(*self.cmat))
+            if self.lut_in is not None:
+                chain.lut_in = C.pointer(_lib.MjgLut.from_buffer_copy(self.lut_in.tobytes()))
+            if self.crop is not None:
+                chain.has_crop = 1
+                chain.crop_x, chain.crop_y, chain.crop_w, chain.crop_h = self.crop
+            if self.lut_out is not None:
+                chain.lut_out = C.pointer(_lib.MjgLut.from_buffer_copy(self.lut_out.tobytes()))
+            if self.unsharp is not None:
+                chain.unsharp = C.pointer(_lib.MjgUnsharp(*self.unsharp))
+            if self.pad is not None:
+                chain.has_pad = 1
+                chain.pad_x, chain.pad_y, chain.pad_w, chain.pad_h = self.pad
+            check(self._L.mjg_open_chain(self.device, C.byref(cfg), C.byref(chain), C.byref(h)))
         self._h = h
         self.frame_bytes = int(self._L.mjg_frame_bytes(h))
         self._queued = deque()        # (nframes, host buffer kept alive) per queued submit
@@ -460,31 +432,28 @@ class MjpegEncoder:
         """The encoder-input planes (after the scale / range / chroma stage) of a frame of the
         last synced submit: packed planar, enc_w x enc_h (dst size; the canvas under a pad), the
         encoded format `chroma`."""
-        n = i420_frame_bytes(self.enc_w, self.enc_h, self.chroma)
-        out = np.zeros(n, np.uint8)
-        check(self._L.mjg_debug_planes(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)), n))
+        return self._debug_frame("mjg_debug_planes", i420_frame_bytes(self.enc_w, self.enc_h, self.chroma), frame)
+
+    def _debug_frame(self, symbol: str, nbytes: int, frame: int) -> np.ndarray:
+        """A frame readback of the library (mjg_debug_planes and its kin): `nbytes` bytes of frame
+        `frame` of the last synced submit."""
+        if not hasattr(self._L, symbol):
+            raise MjgError(_lib.MJG_E_STATE, f"library lacks {symbol}")
+        out = np.zeros(nbytes, np.uint8)
+        check(getattr(self._L, symbol)(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)), nbytes))
         return out
 
     def debug_oriented(self, frame: int = 0) -> np.ndarray:
         """The oriented frame (k_orient_plane's output) of a frame of the last synced submit:
         packed planar, or_w x or_h in the input format `src_chroma`, frame_bytes bytes.  Only for
         an encoder opened with a non-zero `orient`."""
-        if not hasattr(self._L, "mjg_debug_oriented"):
-            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_debug_oriented")
-        out = np.zeros(self.frame_bytes, np.uint8)
-        check(self._L.mjg_debug_oriented(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                         out.size))
-        return out
+        return self._debug_frame("mjg_debug_oriented", self.frame_bytes, frame)
 
     def debug_presharp(self, frame: int = 0) -> np.ndarray:
         """The sws stage's output (k_unsharp_plane's input) of a frame of the last synced submit, laid
         out as debug_planes(), which under a sharpen returns the sharpened planes.  Only for an
         encoder opened with an `unsharp` whose amounts are not both 0."""
-        if not hasattr(self._L, "mjg_debug_presharp"):
-            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_debug_presharp")
-        out = np.zeros(i420_frame_bytes(self.enc_w, self.enc_h, self.chroma), np.uint8)
-        check(self._L.mjg_debug_presharp(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size))
-        return out
+        return self._debug_frame("mjg_debug_presharp", i420_frame_bytes(self.enc_w, self.enc_h, self.chroma), frame)
 
     def debug_unsharp(self):
         """(lx, ly, la, cx, cy, ca) as the context holds them (la, ca the filter's integers), or None
@@ -501,22 +470,14 @@ class MjpegEncoder:
         """k_lut_plane's slot-"in" output of a frame of the last synced submit: a whole frame behind the
         orientation in the input format `src_chroma`, frame_bytes bytes.  Only for an encoder opened
         with a `lut_in` that is not three identity tables."""
-        if not hasattr(self._L, "mjg_debug_lut_in"):
-            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_debug_lut_in")
-        out = np.zeros(self.frame_bytes, np.uint8)
-        check(self._L.mjg_debug_lut_in(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size))
-        return out
+        return self._debug_frame("mjg_debug_lut_in", self.frame_bytes, frame)
 
     def debug_cmat_out(self, frame: int = 0) -> np.ndarray:
         """k_cmat_frame's output of a frame of the last synced submit: a whole frame behind the
         orientation in the input format `src_chroma`, frame_bytes bytes (mapped by `lut_in`, which runs in
         place behind the stage, when there is one).  Only for an encoder opened with a `cmat` that is not
         the identity."""
-        if not hasattr(self._L, "mjg_debug_cmat_out"):
-            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_debug_cmat_out")
-        out = np.zeros(self.frame_bytes, np.uint8)
-        check(self._L.mjg_debug_cmat_out(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size))
-        return out
+        return self._debug_frame("mjg_debug_cmat_out", self.frame_bytes, frame)
 
     def debug_cmat(self):
         """The six coefficients the context holds, or None without a matrix (none given, or the
@@ -544,11 +505,7 @@ class MjpegEncoder:
         """The deinterlaced frame (k_yadif_plane's output) of a frame of the last synced submit:
         packed planar, src_w x src_h in the input format `src_chroma`, frame_bytes bytes.  Only for
         an encoder opened with a non-zero `deint`."""
-        if not hasattr(self._L, "mjg_debug_deint"):
-            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_debug_deint")
-        out = np.zeros(self.frame_bytes, np.uint8)
-        check(self._L.mjg_debug_deint(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size))
-        return out
+        return self._debug_frame("mjg_debug_deint", self.frame_bytes, frame)
 
     def scale_path(self, plane: int) -> int:
         """Which kernel the sws stage runs for a plane (0 luma, 1 chroma): 0 none, 1 k_plane_copy,

@@ -7,16 +7,20 @@
  * and launched/supervised at ffmpeg_distributed.py:139-141 (FFMPEGProc.run,
  * ffmpeg_distributed.py:59-91).  For the north-star profile
  *     [-vf [yadif[=0|2],][vflip|transpose=N,...][crop=w:h:x:y,][scale=W:H:flags=bicubic][,unsharp[=lx:ly:la:cx:cy:ca]][,pad=W:H:x:y]] -c:v mjpeg -q:v N -dct int -huffman default -bitexact
- * (one `colormatrix=SRC:DST` behind the yadif and the orientation and in front of any eq and the
- * scale: six 16.16 coefficients on whole frames, mjg_open_cmat, a restatement of vf_colormatrix.c's
- * 8-bit planar path that no FFmpeg build has been compared with yet;
- * one `eq=...` in front of the scale, or directly behind it: a table per plane, mjg_open_lut, a
- * restatement of vf_eq.c's 8-bit path that no FFmpeg build has been compared with yet; `unsharp` behind the scale and in front of the pad: the sharpen, mjg_open_sharp, a restatement of
- * vf_unsharp.c's 8-bit path that no FFmpeg build has been compared with yet; `yadif` as the very first filter, frame-rate modes 0 and 2: the deinterlacer, mjg_open_deint,
- * a restatement of the filter's C path that no FFmpeg build has been compared with yet; a leading run of vflip / transpose: one of eight plane maps, mjg_open_orient; and `-pix_fmt yuvj420p|yuvj422p` from a 4:4:4 or 4:2:2 input: the chroma down-sampling
- * FFmpeg's auto-inserted scaler does, taken to be its default bicubic; `-vf crop=...` alone or
- * before the scale: a rectangle of the decoded frames, mjg_open_crop; `pad=...` as the last
- * filter: the picture on a black canvas, mjg_open_pad)
+ * (every filter is a field of mjg_chain, which documents the stages in the order they run: `-pix_fmt
+ * yuvj420p|yuvj422p` from a 4:4:4 or 4:2:2 input, src_chroma_format: the chroma down-sampling
+ * FFmpeg's auto-inserted scaler does, taken to be its default bicubic; `yadif` as the very first
+ * filter, frame-rate modes 0 and 2, deint: the deinterlacer, a restatement of the filter's C path
+ * that no FFmpeg build has been compared with yet; a leading run of vflip / transpose, orient: one of
+ * eight plane maps; one `colormatrix=SRC:DST` behind the yadif and the orientation and in front of
+ * any eq and the scale, cmat: six 16.16 coefficients on whole frames, a restatement of
+ * vf_colormatrix.c's 8-bit planar path that no FFmpeg build has been compared with yet; one `eq=...`
+ * in front of the scale, or directly behind it, lut_in / lut_out: a table per plane, a restatement of
+ * vf_eq.c's 8-bit path that no FFmpeg build has been compared with yet; `-vf crop=...` alone or
+ * before the scale, the crop group: a rectangle of the decoded frames; `unsharp` behind the scale and
+ * in front of the pad, unsharp: the sharpen, a restatement of vf_unsharp.c's 8-bit path that no
+ * FFmpeg build has been compared with yet; `pad=...` as the last filter, the pad group: the picture
+ * on a black canvas)
  * this library replaces the arithmetic that worker runs (swscale bicubic + tv->pc
  * range conversion, jfdctint + quantiser + default-table Huffman + 0xFF stuffing)
  * and the Python host code in ffmpeg_distributed_amd/ (worker.py, dispatcher.py)
@@ -121,147 +125,20 @@ int mjg_device_numa_node(int device);
  * swscale's cascade").  Planes down to about 4:1 run on k_scale (one LDS tile per output tile),
  * steeper ones on k_scale_stream (mjg_debug_scale_path). */
 int mjg_open(int device, const mjg_config *cfg, mjg_ctx **out);
-/* mjg_open for input frames in another chroma format than the encoded one (`-pix_fmt`):
- * the frames are src_w x src_h in src_chroma_format (MJG_CHROMA_*), the JPEGs dst_w x dst_h in
- * cfg->chroma_format.  The conversion is swscale's: one bicubic pass per plane from the
- * source plane size to the encoded one (default chroma siting; tv->pc in the same pass; a
- * plane that keeps its size, luma without -vf scale, goes through one-tap identity filters,
- * which the library runs as a streaming copy with the tv->pc byte table).  Any pair of
- * formats is accepted; the worker sends the down-sampling pairs (444->422, 444->420,
- * 422->420) here.  mjg_open(d, cfg, out) = mjg_open_src(d, cfg, cfg->chroma_format, out).
- * (mjg_version() >= 101.) */
-int mjg_open_src(int device, const mjg_config *cfg, int src_chroma_format, mjg_ctx **out);
-/* mjg_open_src for a rectangle of the input frames (`-vf crop=w:h:x:y`, alone or before
- * `scale`): crop_w x crop_h luma samples at (crop_x, crop_y) of the src_w x src_h frame, its
- * chroma planes at (crop_x >> hs, crop_y >> vs) with the chroma size of a crop_w x crop_h frame
- * (hs, vs: the source format's sub-sampling shifts).  The rectangle is the input of the sws
- * stage, which runs when crop_w x crop_h != dst_w x dst_h or the formats differ (its filters are
- * made for the rectangle: the edge taps replicate the crop's edge), and else of k_encode, which
- * then reads the frames in place.  cfg->src_w / src_h stay the decoded frame size:
- * mjg_frame_bytes, host submits and device pointers are whole frames as before.
- * MJG_E_INVALID (before any HIP call, with a message that names the rectangle) for a
- * non-positive size, a rectangle outside the frame, or a crop_x / crop_y that is not a multiple
- * of the source format's sub-sampling.  mjg_open_src(d, cfg, f, out) =
- * mjg_open_crop(d, cfg, f, 0, 0, src_w, src_h, out), with the same launches.
- * MJG_UNALIGNED_FETCH=0 in the environment at open keeps k_encode's aligned-only row fetch for
- * a crop read in place (misaligned blocks then load byte by byte; A/B runs and tests).
- * (mjg_version() >= 102.) */
-int mjg_open_crop(int device, const mjg_config *cfg, int src_chroma_format,
-                  int crop_x, int crop_y, int crop_w, int crop_h, mjg_ctx **out);
-/* mjg_open_crop with a letterbox (`-vf pad=W:H:x:y` as the last filter, after crop and / or
- * scale): the JPEGs are pad_w x pad_h with the picture -- the sws stage's output, cfg->dst_w x
- * dst_h, which stay the picture's size as src_w / src_h stay the decoded frame's under a crop --
- * at (pad_x, pad_y) and black everywhere else: Y = 0, Cb = Cr = 128 in the full-range encoder
- * input, for tv and for full-range sources alike.  mjg_header, the MCU grid and mjg_debug_planes
- * follow the canvas, mjg_frame_bytes the source.  With a pad the sws stage always runs: a plane
- * whose size changes is written into the canvas by k_scale / k_scale_stream (rows at the canvas
- * stride), the border by k_pad_plane, which also copies a plane that keeps its size (through
- * the tv->pc byte table).  The trivial rectangle (0, 0, dst_w, dst_h) is no pad:
- * mjg_open_crop(d, cfg, f, x, y, w, h, out) = mjg_open_pad(d, cfg, f, x, y, w, h, 0, 0, dst_w,
- * dst_h, out), with the same launches.  MJG_E_INVALID (before any HIP call, with a message that
- * names the pad) for a non-positive canvas size, a picture outside the canvas, and, when the
- * rectangle is not the trivial one, a pad_x / pad_y / pad_w / pad_h or a dst_w / dst_h that is
- * not a multiple of the encoded format's sub-sampling.  (mjg_version() >= 104.) */
-int mjg_open_pad(int device, const mjg_config *cfg, int src_chroma_format,
-                 int crop_x, int crop_y, int crop_w, int crop_h,
-                 int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
-/* mjg_open_pad behind an orientation (`-vf hflip`, `vflip`, `transpose=N`, any run of them at the
- * front of the graph): orient = (T ? 1 : 0) | (FX ? 2 : 0) | (FY ? 4 : 0) maps every plane P
- * (w x h) of the decoded frame, the chroma planes as planes of their own, to
- *     out[y][x] = in'[FY ? H-1-y : y][FX ? W-1-x : x],   in' = T ? transpose(P) : P   (W x H),
- * so hflip is 2, vflip 4, the half turn 6, transpose=0 (cclock_flip) 1, transpose=1 (clock) 3,
- * transpose=2 (cclock) 5 and transpose=3 (clock_flip) 7.  The orientation is the first filter:
- * cfg->src_w / src_h stay the decoded frame's size (mjg_frame_bytes and every submit carry whole
- * decoded frames), while the crop rectangle, dst_w / dst_h and the pad refer to the oriented frame,
- * src_h x src_w when orient & 1; without a crop the caller passes that frame's full rectangle.
- * k_orient_plane writes the oriented frames (same format, same bytes per frame, no range
- * conversion) into a buffer of the launch slot, from the submit's segments; the sws stage, or
- * without one k_encode in place, reads that buffer.  Its launches are part of the MJG_K_SCALE
- * interval, which an orientation alone opens too.  orient 0 is exactly mjg_open_pad: no buffer,
- * the same launches.  MJG_E_INVALID (before any HIP call, with a message that names the
- * orientation) for an orient outside 0..7 and for orient & 1 with a 4:2:2 source (vf_transpose
- * converts such a format first); then mjg_open_pad's checks against the oriented size.
- * (Added without a version step: mjg_version() stays 105, which tests/test_abi.py pins; a caller
- * that may meet an older library looks for the symbol, as _lib.py does.) */
-int mjg_open_orient(int device, const mjg_config *cfg, int src_chroma_format, int orient,
-                    int crop_x, int crop_y, int crop_w, int crop_h,
-                    int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
 
-/* mjg_open_deint's `deint` */
+/* mjg_chain.deint */
 #define MJG_DEINT_YADIF 1      /* -vf yadif, mode 0 (send_frame), deint=all */
 #define MJG_DEINT_NOSPATIAL 2  /* ... mode 2 (send_frame_nospatial): no spatial interlacing check */
 #define MJG_DEINT_BFF 4        /* bottom field first (parity=bff): the even rows are interpolated; without
                                   it top field first, the odd rows */
-/* mjg_open_orient behind a deinterlacer (`-vf yadif[=0|2]` as the first filter of the graph):
- * deint = 0 (none) or MJG_DEINT_YADIF | MJG_DEINT_NOSPATIAL | MJG_DEINT_BFF.  k_yadif_plane
- * (scale.hip, which restates the filter: the C path of FFmpeg's vf_yadif.c / yadif_common.c as this
- * project's issue text gives it, not checked against an FFmpeg build here) writes the
- * deinterlaced frames -- same format, same bytes per frame, no range conversion, every plane
- * filtered alike -- into a buffer of the launch slot; the orientation stage, the sws stage, or
- * without either k_encode in place, reads that buffer.  Frame i of a sequence of n is made from
- * frames max(i - 1, 0), i and min(i + 1, n - 1): n outputs for n inputs.  On such a context every
- * mjg_submit is a whole sequence and every segment of a mjg_submit_segments is one (the bytes of
- * one mjg_submit per segment, as ever); a sequence longer than a submit is handed over with
- * mjg_submit_halo.  The context neither holds nor merges submits: MJG_F_MERGE is accepted and has
- * no effect, mjg_ctx_queue_depth is mjg_queue_depth().  The deinterlacer's launches are part of
- * the MJG_K_SCALE interval, which a deinterlacer alone opens too.  cfg->src_w / src_h, orient, the
- * crop and the pad mean what they mean for mjg_open_orient.  deint 0 is exactly mjg_open_orient:
- * no buffer, the same launches.  MJG_E_INVALID (before any HIP call, with a message that names
- * the deinterlacer: "deint ...") for unknown bits, option bits without MJG_DEINT_YADIF, and a
- * source whose luma or chroma plane is smaller than 3 x 3.  (Added without a version step, as
- * mjg_open_orient.) */
-int mjg_open_deint(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient,
-                   int crop_x, int crop_y, int crop_w, int crop_h,
-                   int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
 
 /* -vf unsharp: luma and chroma matrix sizes (odd, 3..23) and amounts as the filter holds them,
  * (int)(amount * 65536.0) with C truncation; the filter's defaults are {5, 5, 65536, 5, 5, 0}. */
 typedef struct mjg_unsharp { int32_t lx, ly, la, cx, cy, ca; } mjg_unsharp;
-/* mjg_open_deint with a sharpen (`unsharp[=lx:ly:la:cx:cy:ca]` behind the scale, in front of the
- * pad).  us == NULL, or la == 0 and ca == 0, is exactly mjg_open_deint: no buffer, the same
- * launches (the sizes of a given us are checked all the same).  Otherwise the sws stage always runs, as it does with a pad (a plane that keeps its
- * size goes through k_plane_copy / k_pad_plane with the tv->pc table), and k_unsharp_plane
- * (scale.hip, which restates the filter: the 8-bit planar path of FFmpeg's vf_unsharp.c as this
- * project's issue text gives it, not checked against an FFmpeg build) makes from every
- * plane of its output the same plane of a second buffer of the launch slot, which k_encode reads:
- *   blur = (sum_j sum_i C(2sy, j) C(2sx, i) P[clamp(y + j - sy)][clamp(x + i - sx)] + half) >> scalebits
- *   out  = clip_uint8(P[y][x] + (((P[y][x] - blur) * amount) >> 16))
- * with sx = size_x / 2, sy = size_y / 2, scalebits = 2 (sx + sy), half = 1 << (scalebits - 1), the
- * indices clamped into the picture (dst_w x dst_h; its chroma planes at their own size with cx, cy,
- * ca) and C int arithmetic.  A plane whose amount is 0 (the default chroma) is copied by the same
- * launch.  Under a pad the launch covers the canvas: the border is copied and never enters a sum.
- * Works per frame: MJG_F_MERGE, mjg_submit_segments and mjg_submit_halo are unchanged.  Its
- * launches are part of the MJG_K_SCALE interval.  MJG_E_INVALID (before any HIP call, with a
- * message that starts "unsharp") for an even size, a size outside 3..23, an amount outside
- * [-2 * 65536, 5 * 65536], and size_x / 2 + size_y / 2 > 12 for a plane whose amount is not 0: the
- * filter's 32-bit sum would wrap.  (Added without a version step, as mjg_open_orient.) */
-int mjg_open_sharp(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient,
-                   int crop_x, int crop_y, int crop_w, int crop_h, const mjg_unsharp *us,
-                   int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
 
 /* A table per plane: out = t[in].  `-vf eq` on 8-bit planar frames is three such tables
  * (profile.eq_tables makes them); the library knows tables, not the filter. */
 typedef struct mjg_lut { uint8_t y[256], u[256], v[256]; } mjg_lut;   /* out = t[in], per plane */
-/* mjg_open_sharp with tables in front of the sws stage (lut_in) and behind it (lut_out).  NULL, or
- * three identity tables, is no table; with neither the call is exactly mjg_open_sharp: no buffer,
- * the same launches.
- * lut_in acts on the frames that enter the sws stage, or k_encode in place: behind the
- * deinterlacer and the orientation, on whole frames in the source format, before any range
- * conversion.  k_lut_plane (scale.hip) writes them into a buffer of the launch slot,
- * which the sws stage or k_encode then reads; the caller's frames are never written.  Behind a
- * deinterlacer or an orientation the stage runs in place in that stage's buffer instead (so
- * mjg_debug_oriented, or mjg_debug_deint without an orientation, then return the mapped frames).
- * lut_out forces the sws stage, as a pad and a sharpen do, and acts in place on the picture
- * rectangle of its output (dst_w x dst_h and its chroma size, at the canvas stride under a pad),
- * behind every sws pass, the pad's border among them, and in front of the sharpen; the border is
- * never mapped.  A plane whose table is the identity is copied by the same launch, or left alone
- * in place.  Both stages work per frame (MJG_F_MERGE, mjg_submit_segments and mjg_submit_halo are
- * unchanged) and belong to the MJG_K_SCALE interval, which a lut_in alone opens too.
- * (Added without a version step, as mjg_open_orient.) */
-int mjg_open_lut(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient,
-                 int crop_x, int crop_y, int crop_w, int crop_h,
-                 const mjg_lut *lut_in, const mjg_lut *lut_out, const mjg_unsharp *us,
-                 int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
 
 /* A colour matrix on whole frames: the six 16.16 coefficients c2..c7 of
  *   u = U - 128, v = V - 128          (U, V: the chroma pair of the luma sample's cell)
@@ -270,20 +147,180 @@ int mjg_open_lut(int device, const mjg_config *cfg, int src_chroma_format, int d
  * in C int with an arithmetic shift.  `-vf colormatrix=SRC:DST` on 8-bit planar frames is six such
  * numbers (profile.colormatrix_coefs makes them); the library knows the numbers, not the filter. */
 typedef struct mjg_cmatrix { int32_t yu, yv, uu, uv, vu, vv; } mjg_cmatrix;
-/* mjg_open_lut with a colour matrix.  A NULL cm, or the identity (0, 0, 65536, 0, 0, 65536), is
- * exactly mjg_open_lut: no buffer and the same launches.
- * The stage stands behind the deinterlacer and the orientation, and in front of lut_in, the crop
- * and the sws stage: it acts on whole frames in the source format, before any range conversion.
- * k_cmat_frame (scale.hip) covers all three planes of every frame of a submit in one
- * launch.  Behind a deinterlacer or an orientation it runs in place in that stage's buffer (so
- * mjg_debug_oriented, or mjg_debug_deint without an orientation, then return the converted
- * frames); otherwise it writes the buffer of the launch slot that a lut_in alone would write, and a
- * lut_in then runs in place there.  The caller's frames are never written.  The stage works per
- * frame (MJG_F_MERGE, mjg_submit_segments and mjg_submit_halo are unchanged) and belongs to the
- * MJG_K_SCALE interval, which a matrix alone opens too.
- * MJG_E_INVALID, with a message that starts "cmatrix", for a coefficient outside [-262144, 262144]
- * (four times unity: every sum then stays below 2^27 and int32 holds it), before any device call.
- * (Added without a version step, as mjg_open_orient.) */
+
+/* What a context does to the frames handed over before it encodes them: the filter chain, one
+ * field (or group) per stage, in the order the stages run.  A chain that is all zeros apart from
+ * src_chroma_format has no stage but the sws stage's format conversion: it is mjg_open_src.  The
+ * structs the pointers name are read during mjg_open_chain only.  Fields are only ever appended to
+ * this struct, and a new field's zero means "as before" (a caller zeroes the struct and sets what
+ * it knows).
+ *
+ * Common to every stage.  cfg->src_w / src_h stay the decoded frame's size whatever the chain holds:
+ * mjg_frame_bytes, host submits and device pointers are whole decoded frames.  Every refusal below
+ * is MJG_E_INVALID before any HIP call (so on a host without a GPU too), with a message that starts
+ * with the prefix given.  The stages in front of the sws stage (deint, orient, cmat, lut_in) work on
+ * whole frames in the source format, same bytes per frame, no range conversion, and never write the
+ * caller's frames; their launches, lut_out's and the sharpen's are part of the MJG_K_SCALE interval,
+ * which any one of them alone opens too.  A stage that is "none" has no buffer and no launch: the
+ * context then launches exactly what it would without the field.  All stages but deint work per
+ * frame: MJG_F_MERGE, mjg_submit_segments and mjg_submit_halo are unchanged by them.
+ *
+ * src_chroma_format  (`-pix_fmt`; "src_chroma_format")  The frames are src_w x src_h in this format
+ *   (MJG_CHROMA_*), the JPEGs in cfg->chroma_format.  The conversion is swscale's and belongs to the
+ *   sws stage: one bicubic pass per plane from the source plane size to the encoded one (default
+ *   chroma siting; tv->pc in the same pass; a plane that keeps its size, luma without -vf scale,
+ *   goes through one-tap identity filters, which the library runs as a streaming copy with the tv->pc
+ *   byte table).  Any pair of formats is accepted; the worker sends the down-sampling pairs
+ *   (444->422, 444->420, 422->420).  Formats that differ force the sws stage.  Refused: a value
+ *   that is no MJG_CHROMA_*.
+ *
+ * deint  (`-vf yadif[=0|2]` as the first filter of the graph; "deint")  0, or MJG_DEINT_YADIF |
+ *   MJG_DEINT_NOSPATIAL | MJG_DEINT_BFF.  Acts on the decoded frames, every plane filtered alike.
+ *   k_yadif_plane (scale.hip, which restates the filter: the C path of FFmpeg's vf_yadif.c /
+ *   yadif_common.c as this project's issue text gives it, not checked against an FFmpeg build here;
+ *   DESIGN §4.13) writes the deinterlaced frames into a buffer of the launch slot; the orientation
+ *   stage, the sws stage, or without either k_encode in place, reads that buffer.  Frame i of a
+ *   sequence of n is made from frames max(i - 1, 0), i and min(i + 1, n - 1): n outputs for n
+ *   inputs.  On such a context every mjg_submit is a whole sequence and every segment of a
+ *   mjg_submit_segments is one (the bytes of one mjg_submit per segment, as ever); a sequence longer
+ *   than a submit is handed over with mjg_submit_halo.  The context neither holds nor merges submits:
+ *   MJG_F_MERGE is accepted and has no effect, mjg_ctx_queue_depth is mjg_queue_depth().  Refused:
+ *   unknown bits, option bits without MJG_DEINT_YADIF, and a source whose luma or chroma plane is
+ *   smaller than 3 x 3.
+ *
+ * orient  (`-vf hflip`, `vflip`, `transpose=N`, any run of them at the front of the graph, behind a
+ *   yadif; "orient")  orient = (T ? 1 : 0) | (FX ? 2 : 0) | (FY ? 4 : 0) maps every plane P (w x h) of
+ *   the frame, the chroma planes as planes of their own, to
+ *       out[y][x] = in'[FY ? H-1-y : y][FX ? W-1-x : x],   in' = T ? transpose(P) : P   (W x H),
+ *   so hflip is 2, vflip 4, the half turn 6, transpose=0 (cclock_flip) 1, transpose=1 (clock) 3,
+ *   transpose=2 (cclock) 5 and transpose=3 (clock_flip) 7; 0 is none.  Everything behind it -- the
+ *   matrix, the tables, the crop rectangle, dst_w / dst_h and the pad -- refers to the oriented frame,
+ *   src_h x src_w when orient & 1.  k_orient_plane writes the oriented frames into a buffer of the
+ *   launch slot, from the submit's segments or the deinterlacer's buffer; the sws stage, or without
+ *   one k_encode in place, reads that buffer.  Refused: an orient outside 0..7, and orient & 1 with a
+ *   4:2:2 source (vf_transpose converts such a format first).
+ *
+ * cmat  (`-vf colormatrix=SRC:DST` behind the yadif and the orientation; "cmatrix")  NULL, or the
+ *   identity (0, 0, 65536, 0, 0, 65536), is none.  Acts on whole frames, in front of lut_in, the crop
+ *   and the sws stage.  k_cmat_frame (scale.hip) covers all three planes of every frame
+ *   of a submit in one launch.  Behind a deinterlacer or an orientation it runs in place in that
+ *   stage's buffer (so mjg_debug_oriented, or mjg_debug_deint without an orientation, then return the
+ *   converted frames); otherwise it writes the buffer of the launch slot that a lut_in alone would
+ *   write, and a lut_in then runs in place there.  Refused: a coefficient outside [-262144, 262144]
+ *   (four times unity: every sum then stays below 2^27 and int32 holds it).
+ *
+ * lut_in  (`-vf eq=...` in front of the scale)  NULL, or three identity tables, is none.  Acts on the
+ *   frames that enter the sws stage, or k_encode in place: behind the deinterlacer, the orientation
+ *   and the matrix, on whole frames, in front of the crop.  k_lut_plane (scale.hip)
+ *   writes them into a buffer of the launch slot, which the sws stage or k_encode then reads.  Behind
+ *   a deinterlacer, an orientation or a matrix the stage runs in place in that stage's buffer instead
+ *   (so mjg_debug_oriented, or mjg_debug_deint without an orientation, then return the mapped
+ *   frames).  A plane whose table is the identity is copied by the same launch, or left alone in
+ *   place.  Nothing is refused: every table is valid.
+ *
+ * has_crop, crop_x, crop_y, crop_w, crop_h  (`-vf crop=w:h:x:y`, alone or before `scale`; "crop")
+ *   has_crop 0 is the whole oriented frame and the four values are not read.  Otherwise crop_w x
+ *   crop_h luma samples at (crop_x, crop_y) of the oriented frame, its chroma planes at (crop_x >>
+ *   hs, crop_y >> vs) with the chroma size of a crop_w x crop_h frame (hs, vs: the source format's
+ *   sub-sampling shifts).  No launch of its own: the rectangle is the input of the sws stage, which
+ *   runs when crop_w x crop_h != dst_w x dst_h or the formats differ (its filters are made for the
+ *   rectangle: the edge taps replicate the crop's edge), and else of k_encode, which then reads the
+ *   frames in place.  The full rectangle (0, 0, the oriented size) is has_crop 0, with the same
+ *   launches.  MJG_UNALIGNED_FETCH=0 in the environment at open keeps k_encode's aligned-only row
+ *   fetch for a crop read in place (misaligned blocks then load byte by byte; A/B runs and tests).
+ *   Refused, with a message that names the rectangle: a non-positive size, a rectangle outside the
+ *   oriented frame, or a crop_x / crop_y that is not a multiple of the source format's sub-sampling.
+ *
+ * the sws stage  (`-vf scale=W:H:flags=bicubic`; no field: cfg->dst_w / dst_h)  See mjg_open.  It
+ *   runs when the size or the format changes, and whenever a lut_out, a sharpen or a pad needs its
+ *   output buffer.
+ *
+ * lut_out  (`-vf eq=...` directly behind the scale)  NULL, or three identity tables, is none.  Forces
+ *   the sws stage, as a pad and a sharpen do, and acts in place on the picture rectangle of its
+ *   output (dst_w x dst_h and its chroma size, at the canvas stride under a pad), behind every sws
+ *   pass, the pad's border among them, and in front of the sharpen; the border is never mapped.  A
+ *   plane whose table is the identity is left alone.  k_lut_plane, as lut_in.  Under a lut_out,
+ *   mjg_debug_planes and mjg_debug_presharp return the mapped planes.  Nothing is refused.
+ *
+ * unsharp  (`unsharp[=lx:ly:la:cx:cy:ca]` behind the scale, in front of the pad; "unsharp")  NULL, or
+ *   la == 0 and ca == 0, is none (the sizes of a given struct are checked all the same).  Otherwise
+ *   the sws stage always runs, as it does with a pad (a plane that keeps its size goes through
+ *   k_plane_copy / k_pad_plane with the tv->pc table), and k_unsharp_plane (scale.hip, which restates
+ *   the filter: the 8-bit planar path of FFmpeg's vf_unsharp.c as this project's issue text gives it,
+ *   not checked against an FFmpeg build) makes from every plane of its output the same
+ *   plane of a second buffer of the launch slot, which k_encode reads:
+ *     blur = (sum_j sum_i C(2sy, j) C(2sx, i) P[clamp(y + j - sy)][clamp(x + i - sx)] + half) >> scalebits
+ *     out  = clip_uint8(P[y][x] + (((P[y][x] - blur) * amount) >> 16))
+ *   with sx = size_x / 2, sy = size_y / 2, scalebits = 2 (sx + sy), half = 1 << (scalebits - 1), the
+ *   indices clamped into the picture (dst_w x dst_h; its chroma planes at their own size with cx, cy,
+ *   ca) and C int arithmetic.  A plane whose amount is 0 (the default chroma) is copied by the same
+ *   launch.  Under a pad the launch covers the canvas: the border is copied and never enters a sum.
+ *   Refused: an even size, a size outside 3..23, an amount outside [-2 * 65536, 5 * 65536], and
+ *   size_x / 2 + size_y / 2 > 12 for a plane whose amount is not 0: the filter's 32-bit sum would wrap.
+ *
+ * has_pad, pad_x, pad_y, pad_w, pad_h  (`-vf pad=W:H:x:y` as the last filter; "pad")  has_pad 0 is
+ *   no pad and the four values are not read.  Otherwise the JPEGs are pad_w x pad_h with the picture
+ *   -- the sws stage's output, cfg->dst_w x dst_h, which stay the picture's size -- at (pad_x, pad_y)
+ *   and black everywhere else: Y = 0, Cb = Cr = 128 in the full-range encoder input, for tv and for
+ *   full-range sources alike.  mjg_header, the MCU grid and mjg_debug_planes follow the canvas,
+ *   mjg_frame_bytes the source.  With a pad the sws stage always runs: a plane whose size changes is
+ *   written into the canvas by k_scale / k_scale_stream (rows at the canvas stride), the border by
+ *   k_pad_plane, which also copies a plane that keeps its size (through the tv->pc byte table).  The
+ *   trivial rectangle (0, 0, dst_w, dst_h) is has_pad 0, with the same launches.  Refused, with a
+ *   message that names the pad: a non-positive canvas size or one beyond 16384, a picture outside the
+ *   canvas, and, when the rectangle is not the trivial one, a pad_x / pad_y / pad_w / pad_h or a
+ *   dst_w / dst_h that is not a multiple of the encoded format's sub-sampling. */
+typedef struct mjg_chain {
+  int32_t src_chroma_format;                 /* MJG_CHROMA_* of the frames handed over */
+  int32_t deint;                             /* MJG_DEINT_* bits; 0: none */
+  int32_t orient;                            /* T | FX << 1 | FY << 2; 0: none */
+  const mjg_cmatrix *cmat;                   /* NULL or the identity: none */
+  const mjg_lut *lut_in;                     /* NULL or three identity tables: none */
+  int32_t has_crop, crop_x, crop_y, crop_w, crop_h;  /* has_crop 0: the whole oriented frame, the four values unread */
+  const mjg_lut *lut_out;
+  const mjg_unsharp *unsharp;                /* NULL, or both amounts 0: none */
+  int32_t has_pad, pad_x, pad_y, pad_w, pad_h;       /* has_pad 0: no pad, the four values unread */
+} mjg_chain;
+/* mjg_open with a filter chain: cfg as for mjg_open, *chain as above.  MJG_E_INVALID ("null
+ * argument") for a NULL cfg, chain or out.  (Added without a version step: mjg_version() stays 105,
+ * which tests/test_abi.py pins; a caller that may meet an older library looks for the symbol, as
+ * _lib.py does.) */
+int mjg_open_chain(int device, const mjg_config *cfg, const mjg_chain *chain, mjg_ctx **out);
+
+/* The entry points from before mjg_chain.  Each is mjg_open_chain with the chain it names: the
+ * fields not listed are zero, and a rectangle that is listed always has its has_crop / has_pad set,
+ * so a caller without a crop or a pad passes the full rectangle (0, 0, the oriented size) or the
+ * trivial one (0, 0, dst_w, dst_h). */
+/* {src_chroma_format}; mjg_open(d, cfg, out) = mjg_open_src(d, cfg, cfg->chroma_format, out).
+ * (mjg_version() >= 101.) */
+int mjg_open_src(int device, const mjg_config *cfg, int src_chroma_format, mjg_ctx **out);
+/* {src_chroma_format, crop}: a crop and no pad.  (mjg_version() >= 102.) */
+int mjg_open_crop(int device, const mjg_config *cfg, int src_chroma_format,
+                  int crop_x, int crop_y, int crop_w, int crop_h, mjg_ctx **out);
+/* {src_chroma_format, crop, pad}.  (mjg_version() >= 104.) */
+int mjg_open_pad(int device, const mjg_config *cfg, int src_chroma_format,
+                 int crop_x, int crop_y, int crop_w, int crop_h,
+                 int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
+/* {src_chroma_format, orient, crop, pad}.  (This one and those below: added without a version
+ * step, as mjg_open_chain.) */
+int mjg_open_orient(int device, const mjg_config *cfg, int src_chroma_format, int orient,
+                    int crop_x, int crop_y, int crop_w, int crop_h,
+                    int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
+/* {src_chroma_format, deint, orient, crop, pad}. */
+int mjg_open_deint(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient,
+                   int crop_x, int crop_y, int crop_w, int crop_h,
+                   int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
+/* {src_chroma_format, deint, orient, crop, unsharp = us, pad}. */
+int mjg_open_sharp(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient,
+                   int crop_x, int crop_y, int crop_w, int crop_h, const mjg_unsharp *us,
+                   int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
+/* {src_chroma_format, deint, orient, lut_in, crop, lut_out, unsharp = us, pad}. */
+int mjg_open_lut(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient,
+                 int crop_x, int crop_y, int crop_w, int crop_h,
+                 const mjg_lut *lut_in, const mjg_lut *lut_out, const mjg_unsharp *us,
+                 int pad_x, int pad_y, int pad_w, int pad_h, mjg_ctx **out);
+/* {src_chroma_format, deint, orient, cmat = cm, lut_in, crop, lut_out, unsharp = us, pad}: every
+ * field. */
 int mjg_open_cmat(int device, const mjg_config *cfg, int src_chroma_format, int deint, int orient,
                   int crop_x, int crop_y, int crop_w, int crop_h, const mjg_cmatrix *cm,
                   const mjg_lut *lut_in, const mjg_lut *lut_out, const mjg_unsharp *us,

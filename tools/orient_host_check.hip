@@ -31,17 +31,19 @@ int main() {
       mjg_config k{};
       k.src_w = s.w, k.src_h = s.h, k.dst_w = ow, k.dst_h = oh;
       k.in_full_range = 0, k.qscale = 5, k.sar_num = k.sar_den = 1, k.max_batch = 3, k.chroma_format = s.cf;
+      mjg_chain chain{};
+      chain.src_chroma_format = s.cf, chain.orient = orient;
       Layout lay{};
-      const int rc = check_config(k, s.cf, orient, nullptr, nullptr, &lay);
+      const int rc = check_config(k, chain, &lay);
       const bool bad = orient < 0 || orient > 7 || (T && s.cf == MJG_CHROMA_422);
       expect((rc == MJG_E_INVALID) == bad && (rc == MJG_OK) == !bad, "check_config", s.w, s.h, s.cf, orient);
       if (rc) continue;
       // a crop that fits the source but not the oriented frame
       if (T && s.w != s.h) {
-        const int crop[4] = {0, 0, s.w, s.h};
+        mjg_chain c2 = chain;
+        c2.has_crop = 1, c2.crop_w = s.w, c2.crop_h = s.h;
         Layout l2{};
-        expect(check_config(k, s.cf, orient, crop, nullptr, &l2) == MJG_E_INVALID, "crop of the source size", s.w, s.h,
-               s.cf, orient);
+        expect(check_config(k, c2, &l2) == MJG_E_INVALID, "crop of the source size", s.w, s.h, s.cf, orient);
       }
       mjg_ctx *c = new mjg_ctx();
       expect(plan_geometry(k, s.cf, lay, true, c) == MJG_OK, "plan_geometry", s.w, s.h, s.cf, orient);
