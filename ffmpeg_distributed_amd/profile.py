@@ -66,6 +66,9 @@ which the GPU path does not: the worker finds that out before it touches the GPU
     chroma samples the GPU path down-samples, worker.resample_plan);
   - options that do not change the video bitstream: -an -sn -dn -y -threads N
     -thread_type frame -f matroska -map 0:v[:0].
+Of several -vf / -filter:v options the last one wins, as in FFmpeg: each replaces every chain field
+of the one before it (an earlier graph outside the profile still refuses the arguments).  The graph
+is split once into filters, and the stages of GRAPH_STAGES take theirs off that list in turn.
 """
 from __future__ import annotations
 
@@ -125,6 +128,7 @@ _FLAGS_OK = {"bicubic", "accurate_rnd", "bitexact", "full_chroma_int", "full_chr
 
 class CropError(ValueError):
     """A crop request that does not fit the input (ffmpeg fails to configure the filter)."""
+    filter = "crop"
 
 
 _CROP_KEYS = {"w": "w", "out_w": "w", "h": "h", "out_h": "h", "x": "x", "y": "y"}
@@ -156,6 +160,7 @@ def _parse_crop(f: str) -> dict:
 
 class PadError(ValueError):
     """A pad request that does not fit its input (ffmpeg fails to configure the filter)."""
+    filter = "pad"
 
 
 PAD_CENTRE = {"x": "(ow-iw)/2", "y": "(oh-ih)/2"}   # the two expressions taken, each for its own option
@@ -225,7 +230,7 @@ def resolve_pad(spec: dict, in_w: int, in_h: int, chroma: str) -> Tuple[int, int
     return x, y, W, H
 
 
-ORIENT_FILTERS = ("vflip", "transpose")     # what _parse_vf takes as a leading run (hflip: see the module docstring)
+ORIENT_FILTERS = ("vflip", "transpose")     # what _take_orient takes as a leading run (hflip: see the module docstring)
 TRANSPOSE_DIRS = {"cclock_flip": 0, "clock": 1, "cclock": 2, "clock_flip": 3}
 
 
@@ -459,35 +464,6 @@ def eq_tables(spec: dict):
     return np.array([eq_plane_table(*p) for p in planes], np.uint8)
 
 
-def _take_eq(vf: str):
-    """A graph that names eq -> (the graph without it, or None when nothing is left; the eq request with
-    its slot).  One eq, behind the yadif and the orientation run: slot "in" anywhere in front of the
-    scale (without a scale: in front of the unsharp and the pad), slot "out" directly behind the scale."""
-    fs = vf.split(",")
-    names = [f.split("=", 1)[0] for f in fs]
-    if names.count("eq") > 1:
-        raise Unsupported(f"filter graph {vf!r}: a second eq (one eq, in front of the scale or directly behind it, is "
-                          f"GPU-accelerated)")
-    at = names.index("eq")
-    if any(nm == "yadif" or nm in ORIENT_FILTERS or nm in OTHER_DEINTERLACERS or nm == "hflip" for nm in names[at + 1:]):
-        _parse_vf(vf)                              # "yadif after eq", "vflip after eq", ...: the reasons these have
-        raise Unsupported(f"filter graph {vf!r}: eq in front of {names[at + 1]}")
-    for nm in ("unsharp", "pad"):
-        if nm in names[:at]:
-            raise Unsupported(f"filter graph {vf!r}: eq behind the {nm} (eq is GPU-accelerated only in front of the "
-                              f"scale or directly behind it, in front of the unsharp and the pad)")
-    slot = "in"
-    if "scale" in names:
-        si = names.index("scale")
-        if at > si + 1:
-            raise Unsupported(f"filter graph {vf!r}: eq behind {names[at - 1]} (behind the scale, eq is GPU-accelerated "
-                              f"only directly behind it)")
-        slot = "in" if at < si else "out"
-    eq = dict(_parse_eq(fs[at]), slot=slot)
-    rest = fs[:at] + fs[at + 1:]
-    return (",".join(rest) if rest else None), eq
-
-
 # luma weights (G, B, R) per colour space, and the other names of bt601
 COLORMATRIX_LUMA = {"bt709": (0.7152, 0.0722, 0.2126), "fcc": (0.59, 0.11, 0.30), "bt601": (0.587, 0.114, 0.299),
                     "smpte240m": (0.701, 0.087, 0.212), "bt2020": (0.678, 0.0593, 0.2627)}
@@ -560,148 +536,173 @@ def _parse_colormatrix(f: str) -> Tuple[str, str]:
     return vals["src"], vals["dst"]
 
 
-def _take_colormatrix(vf: str):
-    """A graph that names colormatrix -> (the graph without it, or None when nothing is left; the
-    canonical (src, dst)).  One colormatrix, behind the yadif and the orientation run, in front of any
-    eq and of the scale (without a scale: in front of the unsharp and the pad); before or after the crop,
-    with which it commutes (crop offsets are multiples of the sub-sampling)."""
-    fs = vf.split(",")
-    names = [f.split("=", 1)[0] for f in fs]
+# The graph layer.  parse_graph splits a -vf value once into (name, text) filters; every stage below
+# takes its filter or filters off that list (`fs`, never empty when a stage gets it) and writes its
+# own field of `out`.  A reason that quotes "the graph" quotes what is on the list at that stage.
+
+def _names(fs) -> List[str]:
+    return [name for name, _ in fs]
+
+
+def _graph(fs) -> str:
+    return ",".join(text for _, text in fs)
+
+
+def _in_front(name: str) -> bool:
+    """A filter whose place is in front of the colormatrix and the eq (or that refuses the graph)."""
+    return name == "yadif" or name in ORIENT_FILTERS or name in OTHER_DEINTERLACERS or name == "hflip"
+
+
+def _take_colormatrix(fs, out):
+    """One colormatrix, behind the yadif and the orientation run, in front of any eq and of the scale
+    (without a scale: in front of the unsharp and the pad); before or after the crop, with which it
+    commutes (crop offsets are multiples of the sub-sampling)."""
+    names = _names(fs)
+    if "colormatrix" not in names:
+        return
     if names.count("colormatrix") > 1:
-        raise Unsupported(f"filter graph {vf!r}: a second colormatrix (one colormatrix, in front of the eq and the scale, "
-                          f"is GPU-accelerated)")
+        raise Unsupported(f"filter graph {_graph(fs)!r}: a second colormatrix (one colormatrix, in front of the eq and "
+                          f"the scale, is GPU-accelerated)")
     at = names.index("colormatrix")
     for nm in names[at + 1:]:
-        if nm == "yadif" or nm in ORIENT_FILTERS or nm in OTHER_DEINTERLACERS or nm == "hflip":
-            raise Unsupported(f"filter graph {vf!r}: colormatrix in front of {nm} (colormatrix is GPU-accelerated only "
-                              f"behind the yadif and the orientation run)")
+        if _in_front(nm):
+            raise Unsupported(f"filter graph {_graph(fs)!r}: colormatrix in front of {nm} (colormatrix is GPU-accelerated "
+                              f"only behind the yadif and the orientation run)")
     for nm in ("eq", "scale", "unsharp", "pad"):
         if nm in names[:at]:
-            raise Unsupported(f"filter graph {vf!r}: colormatrix behind the {nm} (colormatrix is GPU-accelerated only in "
-                              f"front of the eq, the scale, the unsharp and the pad)")
-    pair = _parse_colormatrix(fs[at])
-    rest = fs[:at] + fs[at + 1:]
-    return (",".join(rest) if rest else None), pair
+            raise Unsupported(f"filter graph {_graph(fs)!r}: colormatrix behind the {nm} (colormatrix is GPU-accelerated "
+                              f"only in front of the eq, the scale, the unsharp and the pad)")
+    out["colormatrix"] = _parse_colormatrix(fs.pop(at)[1])
 
 
-def _parse_vf(vf: str):
-    """-vf value -> (crop request or None, scale size or None, sws flags, pad request or None,
-    unsharp request or None, orientation, yadif request or None).  A `yadif` at the very front is taken off first; then a
-    leading run of orientation filters is composed and taken off; the limits on the number and
-    order of filters apply to what follows."""
-    deint = None
-    if ";" not in vf:
-        fs = vf.split(",")
-        names = [f.split("=", 1)[0] for f in fs]
-        other = [nm for nm in names if nm in OTHER_DEINTERLACERS]
-        if other:
-            raise Unsupported(f"filter graph {vf!r}: {other[0]} is not GPU-accelerated (of the deinterlacers only "
-                              f"yadif is)")
-        if "yadif" in names[1:]:
-            at = 1 + names[1:].index("yadif")
-            raise Unsupported(f"filter graph {vf!r}: yadif after {names[at - 1]} (yadif is GPU-accelerated only as "
-                              f"the first filter)")
-        if names[0] == "yadif":
-            deint = _parse_yadif(fs[0])
-            if len(fs) == 1:
-                return None, None, ("bicubic",), None, None, 0, deint
-            vf = ",".join(fs[1:])
-    return _parse_vf_rest(vf) + (deint,)
+def _take_eq(fs, out):
+    """One eq, behind the yadif and the orientation run: slot "in" anywhere in front of the scale
+    (without a scale: in front of the unsharp and the pad), slot "out" directly behind the scale."""
+    names = _names(fs)
+    if "eq" not in names:
+        return
+    if names.count("eq") > 1:
+        raise Unsupported(f"filter graph {_graph(fs)!r}: a second eq (one eq, in front of the scale or directly behind "
+                          f"it, is GPU-accelerated)")
+    at = names.index("eq")
+    if any(_in_front(nm) for nm in names[at + 1:]):
+        # "yadif after eq", "vflip after eq", ...: the eq stays on the list, and the stage that owns the
+        # filter behind it refuses the graph (at the latest _take_crop_scale, which knows no eq)
+        return
+    for nm in ("unsharp", "pad"):
+        if nm in names[:at]:
+            raise Unsupported(f"filter graph {_graph(fs)!r}: eq behind the {nm} (eq is GPU-accelerated only in front of "
+                              f"the scale or directly behind it, in front of the unsharp and the pad)")
+    slot = "in"
+    if "scale" in names:
+        si = names.index("scale")
+        if at > si + 1:
+            raise Unsupported(f"filter graph {_graph(fs)!r}: eq behind {names[at - 1]} (behind the scale, eq is "
+                              f"GPU-accelerated only directly behind it)")
+        slot = "in" if at < si else "out"
+    out["eq"] = dict(_parse_eq(fs.pop(at)[1]), slot=slot)
 
 
-def _parse_vf_rest(vf: str):
-    """What follows a yadif: (crop request or None, scale size or None, sws flags, pad request or
-    None, unsharp request or None, orientation)."""
-    if ";" not in vf:
-        fs = vf.split(",")
-        names = [f.split("=", 1)[0] for f in fs]
-        n = 0
-        while n < len(fs) and names[n] in ORIENT_FILTERS:
-            n += 1
-        late = [nm for nm in names[n:] if nm in ORIENT_FILTERS]
-        if late:
-            raise Unsupported(f"filter graph {vf!r}: {len(fs)} filters, {late[0]} after {names[n]} (vflip and "
-                              f"transpose are GPU-accelerated only in front of [crop,][scale,][pad])")
-        if n and "hflip" in names:
-            raise Unsupported(f"filter graph {vf!r}: hflip is not GPU-accelerated (of the orientation filters only "
-                              f"vflip and transpose are)")
-        if n:
-            orient = compose_orient(fs[:n])
-            if n == len(fs):
-                return None, None, ("bicubic",), None, None, orient
-            return _parse_chain(",".join(fs[n:])) + (orient,)
-    return _parse_chain(vf) + (0,)
+def _take_deint(fs, out):
+    """A yadif as the very first filter; any other deinterlacer refuses the graph."""
+    names = _names(fs)
+    other = [nm for nm in names if nm in OTHER_DEINTERLACERS]
+    if other:
+        raise Unsupported(f"filter graph {_graph(fs)!r}: {other[0]} is not GPU-accelerated (of the deinterlacers only "
+                          f"yadif is)")
+    if "yadif" in names[1:]:
+        at = 1 + names[1:].index("yadif")
+        raise Unsupported(f"filter graph {_graph(fs)!r}: yadif after {names[at - 1]} (yadif is GPU-accelerated only as "
+                          f"the first filter)")
+    if names[0] == "yadif":
+        out["deint"] = _parse_yadif(fs.pop(0)[1])
 
 
-def _parse_chain(vf: str):
-    """[crop][,scale][,unsharp][,pad] -> (crop request or None, scale size or None, sws flags, pad
-    request or None, unsharp request or None)."""
-    fs = vf.split(",")
-    names = [f.split("=", 1)[0] for f in fs]
-    if ";" not in vf and "unsharp" in names:
-        return _parse_chain_unsharp(vf, fs, names)
-    return _parse_chain_plain(vf, fs, names) + (None,)
+def _take_orient(fs, out):
+    """A leading run of vflip / transpose filters, composed; the limits on the number and order of
+    filters apply to what follows."""
+    names = _names(fs)
+    n = 0
+    while n < len(fs) and names[n] in ORIENT_FILTERS:
+        n += 1
+    late = [nm for nm in names[n:] if nm in ORIENT_FILTERS]
+    if late:
+        raise Unsupported(f"filter graph {_graph(fs)!r}: {len(fs)} filters, {late[0]} after {names[n]} (vflip and "
+                          f"transpose are GPU-accelerated only in front of [crop,][scale,][pad])")
+    if n and "hflip" in names:
+        raise Unsupported(f"filter graph {_graph(fs)!r}: hflip is not GPU-accelerated (of the orientation filters only "
+                          f"vflip and transpose are)")
+    if n:
+        out["orient"] = compose_orient(text for _, text in fs[:n])
+        del fs[:n]
 
 
-def _parse_chain_unsharp(vf: str, fs, names):
-    """A chain that names unsharp: the pad is taken off, then the unsharp, which must be the last
-    of what is left; the rest is [crop][,scale] as without it."""
+def _take_pad_unsharp(fs, out):
+    """The end of the graph, [unsharp][,pad]: the pad is taken off, then the unsharp, which must be
+    the last of what is left.  One stage for the two, because a graph that names unsharp is checked
+    for a second one before its pad is looked at, and quotes the graph with the pad still on it.  A
+    pad that is not taken (without options, or behind more than two filters of a graph without
+    unsharp) stays on the list for _take_crop_scale to refuse."""
+    names, vf = _names(fs), _graph(fs)
+    sharp = "unsharp" in names
     if names.count("unsharp") > 1:
         raise Unsupported(f"filter graph {vf!r}: a second unsharp (one unsharp, directly in front of the pad or the "
                           f"end, is GPU-accelerated)")
     if "pad" in names[:-1]:
-        raise Unsupported(f"filter graph {vf!r}: pad is not the last filter (only [crop,][scale,][unsharp,]pad in "
-                          f"this order is GPU-accelerated)")
-    pad = None
+        raise Unsupported(f"filter graph {vf!r}: pad is not the last filter (only [crop,][scale,]"
+                          f"{'[unsharp,]' if sharp else ''}pad in this order is GPU-accelerated)")
     if names[-1] == "pad":
-        if "=" not in fs[-1]:
+        if "=" in fs[-1][1]:
+            if sharp or len(fs) <= 3:
+                out["pad"] = _parse_pad(fs.pop()[1])
+        elif sharp:
             raise Unsupported(f"filter graph {vf!r}: pad without options")
-        pad = _parse_pad(fs[-1])
-        fs, names = fs[:-1], names[:-1]
-    if names[-1] != "unsharp":
-        at = names.index("unsharp")
-        raise Unsupported(f"filter graph {vf!r}: unsharp before {names[at + 1]} (unsharp is GPU-accelerated only "
-                          f"behind [crop,][scale] and directly in front of the pad or the end)")
-    us = _parse_unsharp(fs[-1])
-    if len(fs) == 1:
-        return None, None, ("bicubic",), pad, us
-    return _parse_crop_scale(",".join(fs[:-1])) + (pad, us)
+    if sharp:
+        names = _names(fs)
+        if names[-1] != "unsharp":
+            at = names.index("unsharp")
+            raise Unsupported(f"filter graph {vf!r}: unsharp before {names[at + 1]} (unsharp is GPU-accelerated only "
+                              f"behind [crop,][scale] and directly in front of the pad or the end)")
+        out["unsharp"] = _parse_unsharp(fs.pop()[1])
 
 
-def _parse_chain_plain(vf: str, fs, names):
-    """[crop][,scale][,pad] -> (crop request or None, scale size or None, sws flags, pad request or None)."""
-    if ";" not in vf and "pad" in names[:-1]:
-        raise Unsupported(f"filter graph {vf!r}: pad is not the last filter (only [crop,][scale,]pad in this "
-                          f"order is GPU-accelerated)")
-    if ";" not in vf and names[-1] == "pad" and "=" in fs[-1] and len(fs) <= 3:
-        pad = _parse_pad(fs[-1])
-        if len(fs) == 1:
-            return None, None, ("bicubic",), pad
-        return _parse_crop_scale(",".join(fs[:-1])) + (pad,)
-    return _parse_crop_scale(vf) + (None,)
-
-
-def _parse_crop_scale(vf: str):
-    """[crop][,scale] -> (crop request or None, scale size or None, sws flags)."""
-    if ";" in vf:
-        raise Unsupported(f"filter graph {vf!r} (only crop, scale or crop,scale is GPU-accelerated)")
-    fs = vf.split(",")
-    names = [f.split("=", 1)[0] for f in fs]
+def _take_crop_scale(fs, out):
+    """[crop][,scale]: all that may be left, so this stage takes the whole list or refuses it."""
+    names, vf = _names(fs), _graph(fs)
     if len(fs) > 2:
         raise Unsupported(f"filter graph {vf!r}: {len(fs)} filters (only crop, scale or crop,scale is "
                           f"GPU-accelerated)")
     if names == ["scale", "crop"]:
         raise Unsupported(f"filter graph {vf!r}: scale before crop (only crop,scale in this order is "
                           f"GPU-accelerated)")
-    if names == ["crop"] and "=" in fs[0]:
-        return _parse_crop(fs[0]), None, ("bicubic",)
-    if names == ["crop", "scale"] and "=" in fs[0]:
-        scale, flags = _parse_scale(fs[1])
-        return _parse_crop(fs[0]), scale, flags
-    if len(fs) == 1:
-        scale, flags = _parse_scale(vf)
-        return None, scale, flags
-    raise Unsupported(f"filter graph {vf!r} (only crop, scale or crop,scale is GPU-accelerated)")
+    if names in (["crop"], ["crop", "scale"]) and "=" in fs[0][1]:
+        if len(fs) == 2:
+            out["scale"], out["sws_flags"] = _parse_scale(fs[1][1])
+        out["crop"] = _parse_crop(fs[0][1])
+    elif len(fs) == 1:
+        out["scale"], out["sws_flags"] = _parse_scale(vf)
+    else:
+        raise Unsupported(f"filter graph {vf!r} (only crop, scale or crop,scale is GPU-accelerated)")
+    del fs[:]
+
+
+# in this order, which decides the reason a graph outside the profile is refused with
+GRAPH_STAGES = (_take_colormatrix, _take_eq, _take_deint, _take_orient, _take_pad_unsharp, _take_crop_scale)
+
+
+def parse_graph(vf: str) -> dict:
+    """A -vf value -> the chain fields of Profile that the graph sets, by name (crop, scale,
+    sws_flags, pad, orient, deint, unsharp, eq, colormatrix; a field the graph does not set is left
+    out, so Profile's own defaults are the only ones), or Unsupported."""
+    if ";" in vf:
+        raise Unsupported(f"filter graph {vf!r} (only crop, scale or crop,scale is GPU-accelerated)")
+    fs = [(f.split("=", 1)[0], f) for f in vf.split(",")]
+    out: dict = {}
+    for take in GRAPH_STAGES:
+        if not fs:
+            break
+        take(fs, out)
+    return out
 
 
 def resolve_crop(spec: dict, in_w: int, in_h: int, src_chroma: str) -> Tuple[int, int, int, int]:
@@ -786,15 +787,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
     threads: Optional[int] = None     # None: auto (0)
     thread_type = "slice+frame"       # AVCodecContext default: FF_THREAD_FRAME | FF_THREAD_SLICE
     chroma = None
-    scale = None
-    crop = None
-    pad = None
-    orient = 0
-    deint = None
-    unsharp = None
-    eq = None
-    cmat = None
-    flags: Tuple[str, ...] = ("bicubic",)
+    chain: dict = {}                  # the chain fields the last -vf sets (parse_graph)
     i = 0
 
     def val():
@@ -834,14 +827,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
             if any(name != "bitexact" for _, name in _flag_ops(v)):
                 raise Unsupported(f"-fflags {v}")
         elif o in ("-vf", "-filter:v"):
-            vf = val()
-            eq = cmat = None
-            if ";" not in vf and "colormatrix" in [f.split("=", 1)[0] for f in vf.split(",")]:
-                vf, cmat = _take_colormatrix(vf)   # the rest of the graph is parsed as without it
-            if vf is not None and ";" not in vf and "eq" in [f.split("=", 1)[0] for f in vf.split(",")]:
-                vf, eq = _take_eq(vf)              # the rest of the graph is parsed as without it
-            if vf is not None:
-                crop, scale, flags, pad, unsharp, orient, deint = _parse_vf(vf)
+            chain = parse_graph(val())   # FFmpeg applies only the last -vf of a stream: all of an earlier one goes
         elif o in ("-an", "-sn", "-dn", "-y"):
             pass
         elif o in ("-threads", "-threads:v"):
@@ -890,9 +876,7 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
     rst = uses_slices(slices, threads, thread_type)
     if rst:
         huff = "default"  # mjpegenc.c: slice_context_count > 1 forces HUFFMAN_TABLE_DEFAULT
-    return Profile(qscale=effective_qscale(q), q_arg=q, scale=scale, sws_flags=flags, huffman=huff,
-                   rst=rst, chroma=chroma, crop=crop, pad=pad, orient=orient, deint=deint, unsharp=unsharp,
-                   eq=eq, colormatrix=cmat)
+    return Profile(qscale=effective_qscale(q), q_arg=q, huffman=huff, rst=rst, chroma=chroma, **chain)
 
 
 PIX_FMT_CHROMA = {"yuvj420p": "420", "yuvj422p": "422", "yuvj444p": "444"}

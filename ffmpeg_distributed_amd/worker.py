@@ -47,6 +47,8 @@ One `colormatrix=SRC:DST` (profile.Profile.colormatrix) becomes six 16.16 coeffi
 (profile.colormatrix_coefs) that the GPU applies to the decoded frames behind the yadif and the
 orientation, in front of everything else; cmat_fallthrough_reason names the inputs that still go to
 the real ffmpeg.
+All of this is resolved against the segment's input by plan_segment, a pure function, before run()
+binds to the GPU's NUMA node: a SegmentPlan, a Fallthrough (the real ffmpeg) or a CropError / PadError.
 """
 from __future__ import annotations
 
@@ -597,7 +599,7 @@ def eq_fallthrough_reason(prof, info) -> Optional[str]:
     8-bit path: samples of more than 8 bits go through another one."""
     if prof.eq is None:
         return None
-    # slot "out" is directly behind a scale (profile._take_eq)
+    # slot "out" is directly behind a scale (profile._take_eq gives no other)
     assert prof.eq["slot"] == "in" or prof.scale is not None, prof
     bits = int(getattr(info, "bits", 8))
     if bits != 8:
@@ -648,6 +650,97 @@ def scale_cascade_reason(in_size, out_size, src_chroma, dst_chroma) -> Optional[
     return None
 
 
+class Fallthrough(Exception):
+    """This segment runs on the CPU ffmpeg; str() is the reason.  (The other way out of plan_segment is
+    profile.CropError / PadError: FFmpeg itself fails to configure the filter, nothing is passed through.)"""
+
+
+@dataclass(frozen=True, eq=False)
+class SegmentPlan:
+    """A profile resolved against one segment's input (plan_segment): what the encoder context is
+    opened with and the muxer told, beyond what Profile and StreamInfo hold themselves."""
+    src_chroma: str                  # the input frames' format and the one to encode (resample_plan)
+    dst_chroma: str
+    deint: int                       # the MJG_DEINT_* bits (resolve_deint); 0: no deinterlacer
+    orient: int                      # T | FX << 1 | FY << 2; the fields below are of the oriented frame
+    rect: Optional[tuple]            # the crop's (x, y, w, h), or None
+    in_size: tuple                   # the sws stage's input: the rectangle's size, or the oriented frame's
+    dst_w: int                       # the picture: the scale's output, or in_size
+    dst_h: int
+    pad: Optional[tuple]             # the picture's place and the canvas, (x, y, W, H), or None
+    enc_w: int                       # what is encoded and muxed: the canvas, or the picture
+    enc_h: int
+    unsharp: Optional[tuple]
+    lut_in: object                   # the eq's (3, 256) uint8 tables in its slot, None elsewhere
+    lut_out: object
+    cmat: Optional[tuple]            # the colormatrix's six coefficients, or None
+    sar: tuple                       # of the picture (a crop and a pad leave it alone)
+
+    def encoder_kwargs(self) -> dict:
+        """The MjpegEncoder keyword arguments this plan decides (dst_w and dst_h go by position)."""
+        return dict(sar=self.sar, chroma=self.dst_chroma, src_chroma=self.src_chroma, crop=self.rect, pad=self.pad,
+                    orient=self.orient, deint=self.deint or None, unsharp=self.unsharp, lut_in=self.lut_in,
+                    lut_out=self.lut_out, cmat=self.cmat)
+
+    def key(self, prof, info, com_itu601, batch):
+        """encoder_key of a context opened with this plan."""
+        return encoder_key(prof, info, self.dst_w, self.dst_h, self.sar, com_itu601, batch, self.rect, self.pad,
+                           self.orient, self.deint, self.unsharp, (self.lut_in, self.lut_out), self.cmat)
+
+
+def plan_segment(prof, info) -> SegmentPlan:
+    """Resolve a profile against a segment's input (container.StreamInfo): no device, no streams.
+    Raises Fallthrough(reason) for a segment the CPU ffmpeg runs, and lets profile.CropError /
+    PadError through for a request FFmpeg fails to configure.  The order of the checks decides which
+    reason a user reads."""
+    formats = resample_plan(prof, info)
+    if isinstance(formats, str):
+        raise Fallthrough(formats)
+    src_chroma, dst_chroma = formats
+    # -vf yadif in front of everything: the parity from the request or the stream's field order
+    deint = resolve_deint(prof.deint, info)
+    if isinstance(deint, str):
+        raise Fallthrough(deint)
+    # -vf vflip / transpose in front: everything below starts from the oriented frame.
+    # vf_transpose takes only formats whose two chroma shifts are equal
+    orient = prof.orient
+    if orient & 1 and src_chroma == "422":
+        raise Fallthrough("transpose of a 4:2:2 input: FFmpeg converts the format first")
+    or_w, or_h = oriented_size(info.width, info.height, orient)
+    # -vf crop: the rectangle of this input (the filter sees the decoded format); the scale
+    # filter, the SAR and the encoded size then start from its size
+    rect = None if prof.crop is None else profile.resolve_crop(prof.crop, or_w, or_h, src_chroma)
+    in_size = (or_w, or_h) if rect is None else (rect[2], rect[3])
+    dst_w, dst_h = prof.scale or in_size
+    # -vf ...,pad: the canvas around the picture (dst_w x dst_h).  With a scale in front the pad
+    # sees the encoded format (the scale converts), else the input's, which is then the encoded one
+    pad = None
+    if prof.pad is not None:
+        why = pad_fallthrough_reason(prof, (dst_w, dst_h), src_chroma, dst_chroma)
+        if why is not None:
+            raise Fallthrough(why)
+        pad = profile.resolve_pad(prof.pad, dst_w, dst_h, dst_chroma)
+    enc_w, enc_h = (dst_w, dst_h) if pad is None else pad[2:]
+    # -vf ...,unsharp: behind the sws stage; without a scale only when nothing is converted.
+    # -vf ...,eq: tables in front of or behind the sws stage.  -vf ...,colormatrix: six coefficients
+    # on the decoded frames.  Last the one scale the library refuses (a filter of 256 taps or more,
+    # about 64:1), decided without a device
+    why = (unsharp_fallthrough_reason(prof, info.full_range, src_chroma, dst_chroma)
+           or eq_fallthrough_reason(prof, info) or cmat_fallthrough_reason(prof, info)
+           or scale_cascade_reason(in_size, (dst_w, dst_h), src_chroma, dst_chroma))
+    if why is not None:
+        raise Fallthrough(why)
+    lut_in, lut_out = eq_luts(prof)
+    cmat = None if prof.colormatrix is None else profile.colormatrix_coefs(*prof.colormatrix)
+    # (a crop leaves the SAR as it is: keep_aspect=0; scaled_sar of equal sizes only reduces it;
+    # a pad leaves it alone too: the scale's SAR, from the picture's size, not the canvas's)
+    # (a transpose hands on 1 / SAR when the SAR is known: vf_transpose config_props_output)
+    sar = profile.scaled_sar(oriented_sar(info.sar, orient), in_size, (dst_w, dst_h))
+    return SegmentPlan(src_chroma=src_chroma, dst_chroma=dst_chroma, deint=deint, orient=orient, rect=rect,
+                       in_size=in_size, dst_w=dst_w, dst_h=dst_h, pad=pad, enc_w=enc_w, enc_h=enc_h,
+                       unsharp=prof.unsharp, lut_in=lut_in, lut_out=lut_out, cmat=cmat, sar=sar)
+
+
 def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cache=None,
         batch_bytes: Optional[int] = None, opts: Optional[Options] = None) -> int:
     """One segment, stdin -> stdout.  `cache` (serve / resident mode): a dict that keeps the
@@ -666,109 +759,34 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
 
     src = Source(stdin, opts.read_threads, stderr)
     info = src.info
-    plan = resample_plan(prof, info)
-    if isinstance(plan, str):
-        stderr.write(f"gpu:{device}: {plan}; running ffmpeg on the CPU\n")
+    try:
+        plan = plan_segment(prof, info)
+    except Fallthrough as e:
+        stderr.write(f"gpu:{device}: {e}; running ffmpeg on the CPU\n")
         stderr.flush()
         return ffmpeg_fallthrough(src, args, stdout, stderr)
-    src_chroma, dst_chroma = plan
-    # -vf yadif in front of everything: the parity from the request or the stream's field order
-    deint = resolve_deint(prof.deint, info)
-    if isinstance(deint, str):
-        stderr.write(f"gpu:{device}: {deint}; running ffmpeg on the CPU\n")
+    except (profile.CropError, profile.PadError) as e:  # ffmpeg fails to configure the filter: no pass-through
+        stderr.write(f"gpu:{device}: {e.filter}: {e}\n")
         stderr.flush()
-        return ffmpeg_fallthrough(src, args, stdout, stderr)
-    # -vf vflip / transpose in front: everything below starts from the oriented frame.
-    # vf_transpose takes only formats whose two chroma shifts are equal
-    orient = prof.orient
-    if orient & 1 and src_chroma == "422":
-        stderr.write(f"gpu:{device}: transpose of a 4:2:2 input: FFmpeg converts the format first; "
-                     f"running ffmpeg on the CPU\n")
-        stderr.flush()
-        return ffmpeg_fallthrough(src, args, stdout, stderr)
-    or_w, or_h = oriented_size(info.width, info.height, orient)
-    # -vf crop: the rectangle of this input (the filter sees the decoded format); the scale
-    # filter, the SAR and the encoded size then start from its size
-    rect = None
-    if prof.crop is not None:
-        try:
-            rect = profile.resolve_crop(prof.crop, or_w, or_h, src_chroma)
-        except profile.CropError as e:  # ffmpeg fails to configure the filter: no pass-through
-            stderr.write(f"gpu:{device}: crop: {e}\n")
-            stderr.flush()
-            src.close(kill=True)
-            return 1
-    in_size = (or_w, or_h) if rect is None else (rect[2], rect[3])
-    dst_w, dst_h = prof.scale or in_size
-    # -vf ...,pad: the canvas around the picture (dst_w x dst_h).  With a scale in front the pad
-    # sees the encoded format (the scale converts), else the input's, which is then the encoded one
-    pad = None
-    if prof.pad is not None:
-        why = pad_fallthrough_reason(prof, (dst_w, dst_h), src_chroma, dst_chroma)
-        if why is not None:
-            stderr.write(f"gpu:{device}: {why}; running ffmpeg on the CPU\n")
-            stderr.flush()
-            return ffmpeg_fallthrough(src, args, stdout, stderr)
-        try:
-            pad = profile.resolve_pad(prof.pad, dst_w, dst_h, dst_chroma)
-        except profile.PadError as e:  # ffmpeg fails to configure the filter: no pass-through
-            stderr.write(f"gpu:{device}: pad: {e}\n")
-            stderr.flush()
-            src.close(kill=True)
-            return 1
-    enc_w, enc_h = (dst_w, dst_h) if pad is None else pad[2:]
-    # -vf ...,unsharp: behind the sws stage; without a scale only when nothing is converted
-    why = unsharp_fallthrough_reason(prof, info.full_range, src_chroma, dst_chroma)
-    if why is not None:
-        stderr.write(f"gpu:{device}: {why}; running ffmpeg on the CPU\n")
-        stderr.flush()
-        return ffmpeg_fallthrough(src, args, stdout, stderr)
-    # -vf ...,eq: tables in front of or behind the sws stage
-    why = eq_fallthrough_reason(prof, info)
-    if why is not None:
-        stderr.write(f"gpu:{device}: {why}; running ffmpeg on the CPU\n")
-        stderr.flush()
-        return ffmpeg_fallthrough(src, args, stdout, stderr)
-    lut_in, lut_out = eq_luts(prof)
-    # -vf ...,colormatrix: six coefficients on the decoded frames
-    why = cmat_fallthrough_reason(prof, info)
-    if why is not None:
-        stderr.write(f"gpu:{device}: {why}; running ffmpeg on the CPU\n")
-        stderr.flush()
-        return ffmpeg_fallthrough(src, args, stdout, stderr)
-    cmat = None if prof.colormatrix is None else profile.colormatrix_coefs(*prof.colormatrix)
-    # the one scale the library refuses (a filter of 256 taps or more, about 64:1), decided here
-    # without a device: as the up-sampling -pix_fmt pairs, the segment goes to ffmpeg
-    why = scale_cascade_reason(in_size, (dst_w, dst_h), src_chroma, dst_chroma)
-    if why is not None:
-        stderr.write(f"gpu:{device}: {why}; running ffmpeg on the CPU\n")
-        stderr.flush()
-        return ffmpeg_fallthrough(src, args, stdout, stderr)
+        src.close(kill=True)
+        return 1
     bind_numa(device)  # before the reader threads and the batch buffers
     from .encoder import MjpegEncoder, PinnedBuffer   # GPU work starts here
 
     batch = batch_frames(opts, info.frame_bytes)
-
-    # (a crop leaves the SAR as it is: keep_aspect=0; scaled_sar of equal sizes only reduces it;
-    # a pad leaves it alone too: the scale's SAR, from the picture's size, not the canvas's)
-    # (a transpose hands on 1 / SAR when the SAR is known: vf_transpose config_props_output)
-    sar = profile.scaled_sar(oriented_sar(info.sar, orient), in_size, (dst_w, dst_h))
-    key = encoder_key(prof, info, dst_w, dst_h, sar, opts.com_itu601 and not info.full_range, batch, rect, pad,
-                      orient, deint, prof.unsharp, (lut_in, lut_out), cmat)
+    com_itu601 = opts.com_itu601 and not info.full_range
+    key = plan.key(prof, info, com_itu601, batch)
     nbuf = NBUF
     if cache is not None and cache.get("key") == key:
         enc, bufs, obufs = cache["enc"], cache["bufs"], cache["obufs"]
     else:
         if cache is not None:
             release(cache)
-        enc = MjpegEncoder(device, info.width, info.height, dst_w, dst_h, full_range=info.full_range,
-                           qscale=prof.qscale, sar=sar, max_batch=batch,
-                           com_itu601=opts.com_itu601 and not info.full_range, huffman=prof.huffman,
-                           chroma=dst_chroma, src_chroma=src_chroma, rst=prof.rst, crop=rect, pad=pad,
-                           orient=orient, deint=deint or None, unsharp=prof.unsharp,
-                           lut_in=lut_in, lut_out=lut_out, cmat=cmat)
+        enc = MjpegEncoder(device, info.width, info.height, plan.dst_w, plan.dst_h, full_range=info.full_range,
+                           qscale=prof.qscale, max_batch=batch, com_itu601=com_itu601, huffman=prof.huffman,
+                           rst=prof.rst, **plan.encoder_kwargs())
         # (a deinterlacer: room for the frame in front of a batch and the one behind it)
-        bufs = [PinnedBuffer((batch + (2 if deint else 0)) * enc.frame_bytes) for _ in range(nbuf)]
+        bufs = [PinnedBuffer((batch + (2 if plan.deint else 0)) * enc.frame_bytes) for _ in range(nbuf)]
         # page-locked output buffers: the packets are DMA'd into one (enc.fetch_into) and the
         # muxer writes them from it; regrown when a submit's JPEGs do not fit
         obufs = [None] * NOUT
@@ -776,7 +794,7 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
             cache.update(key=key, enc=enc, bufs=bufs, obufs=obufs)
     prog = Progress(stderr, info.fps, prof.qscale)
     prog.duration(src.duration)
-    mkv = container.MkvWriter(stdout, enc_w, enc_h, info.fps, sar)
+    mkv = container.MkvWriter(stdout, plan.enc_w, plan.enc_h, info.fps, plan.sar)
 
     # NBUF page-locked batches: the reader fills one while two are queued on the GPU (the
     # encoder takes a second submit before the first is synced, so its kernels run back to
@@ -845,7 +863,7 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
         except BaseException as e:   # surfaced by the main loop
             full.put(e)
 
-    th = threading.Thread(target=deint_reader if deint else reader, daemon=True)
+    th = threading.Thread(target=deint_reader if plan.deint else reader, daemon=True)
     th.start()
     frames = 0
     queued: "list" = []  # buffer index and frame count per submit, oldest first
