@@ -49,6 +49,7 @@ EXPORTS = (
     "mjg_debug_tail",
     "mjg_open_cmat", "mjg_debug_cmat", "mjg_debug_cmat_out",
     "mjg_open_chain",
+    "mjg_open_sheet", "mjg_frames_out", "mjg_debug_sheet", "mjg_debug_cell",
 )
 
 # mjg_open_deint's `deint`
@@ -112,6 +113,12 @@ class MjgChain(C.Structure):
                 ("lut_out", C.POINTER(MjgLut)), ("unsharp", C.POINTER(MjgUnsharp)),
                 ("has_pad", C.c_int32), ("pad_x", C.c_int32), ("pad_y", C.c_int32),
                 ("pad_w", C.c_int32), ("pad_h", C.c_int32)]
+
+
+class MjgSheet(C.Structure):
+    """mjg_sheet: -vf tile's contact sheet behind the chain (mjg_open_sheet); nb_frames 0 is cols * rows."""
+    _fields_ = [("cols", C.c_int32), ("rows", C.c_int32), ("nb_frames", C.c_int32), ("margin", C.c_int32),
+                ("padding", C.c_int32)]
 
 
 _lib = None
@@ -179,6 +186,16 @@ def load():
         if hasattr(L, "mjg_open_chain"):  # absent from libraries built before the chain descriptor (A/B builds)
             L.mjg_open_chain.argtypes = [C.c_int, C.POINTER(MjgConfig), C.POINTER(MjgChain), C.POINTER(vp)]
             L.mjg_open_chain.restype = C.c_int
+        if hasattr(L, "mjg_open_sheet"):  # absent from libraries built before the contact sheet (A/B builds)
+            L.mjg_open_sheet.argtypes = [C.c_int, C.POINTER(MjgConfig), C.POINTER(MjgChain), C.POINTER(MjgSheet),
+                                         C.POINTER(vp)]
+            L.mjg_open_sheet.restype = C.c_int
+            L.mjg_frames_out.argtypes = [vp, C.c_int]
+            L.mjg_frames_out.restype = C.c_int
+            L.mjg_debug_sheet.argtypes = [vp, C.POINTER(MjgSheet)]
+            L.mjg_debug_sheet.restype = C.c_int
+            L.mjg_debug_cell.argtypes = [vp, C.c_int, u8p, sz]
+            L.mjg_debug_cell.restype = C.c_int
         L.mjg_close.argtypes = [vp]
         L.mjg_close.restype = None
         L.mjg_frame_bytes.argtypes = [vp]
@@ -232,7 +249,8 @@ def load():
                  "mjg_open_deint", "mjg_submit_halo", "mjg_debug_deint", "mjg_debug_deint_flags",
                  "mjg_open_sharp", "mjg_debug_presharp", "mjg_debug_unsharp",
                  "mjg_open_lut", "mjg_debug_lut", "mjg_debug_lut_in", "mjg_debug_tail",
-                 "mjg_open_cmat", "mjg_debug_cmat", "mjg_debug_cmat_out", "mjg_open_chain")
+                 "mjg_open_cmat", "mjg_debug_cmat", "mjg_debug_cmat_out", "mjg_open_chain",
+                 "mjg_open_sheet", "mjg_frames_out", "mjg_debug_sheet", "mjg_debug_cell")
                 if os.environ.get("MJG_LIBRARY") else ())
         for name in EXPORTS:
             if name not in late:

@@ -277,8 +277,10 @@ struct Slot {
   uint8_t *d_deint = nullptr;      // -vf yadif: k_yadif_plane's output frames
   uint8_t *d_sharp = nullptr;      // -vf unsharp: k_unsharp_plane's output, the encoder's input
   uint8_t *d_lut = nullptr;        // a table in front of the sws stage on a caller's frames: k_lut_plane's output frames
+  uint8_t *d_tile = nullptr;       // -vf tile: k_tile_plane's output, the sheets, the encoder's input
   uint32_t *d_stage_bits = nullptr;  // k_encode: per wave, lane-major staging of blocks past 128 bits
-  int n = 0;  // frames of the launch
+  int n = 0;  // frames of the launch (under a sheet: the sheets, the frames k_encode codes)
+  int nin = 0;  // ... and its input frames (the same without a sheet)
   uint32_t *d_scratch = nullptr;
   uint32_t *d_stream = nullptr;  // k_count_ff's realigned words, per segment (k_write reads them)
   uint32_t *d_chunk_bits = nullptr, *d_chunk_off = nullptr, *d_group_ff = nullptr, *d_ff_off = nullptr;
@@ -342,7 +344,18 @@ struct mjg_ctx {
   mjg_cmatrix cmat{};
   CmatGeom cgeom{};             // its launch
   void (*cmat_launch)(const SegList &, uint8_t *, const CmatGeom &, const CmatCoef &, int, hipStream_t) = nullptr;
+  // -vf tile (mjg_open_sheet): behind the sws stage (which then always runs) and the sharpen; k_encode
+  // reads the sheets in d_tile.  geom, enc_frame_bytes, the header and the output-side slot buffers are
+  // then the sheet's, pic_* the cell's.  Every submit (every segment of one) is a sequence of its own:
+  // no merging
+  bool sheet = false;
+  mjg_sheet sh{};               // nb_frames resolved (1..cols rows)
+  TileGeom tpass[2];            // its launches: 0 luma, 1 chroma
   size_t in_frame_bytes = 0, enc_frame_bytes = 0;
+  // the sws stage's output frame (the picture, the canvas under a pad; k_encode's input without a
+  // sheet): its bytes, its U plane's offset and the bytes of a chroma plane
+  size_t pic_frame_bytes = 0;
+  long long pic_u_off = 0, pic_cplane = 0;
   // the crop rectangle (mjg_open_crop; the whole frame otherwise): the input of the sws stage,
   // or of k_encode without one
   long long src_off[3] = {0, 0, 0};  // byte offsets of the rectangle's Y, U, V planes in a source frame
@@ -366,6 +379,7 @@ struct mjg_ctx {
   Pass pass[2][2];   // ... and their launches
   EncodeFn enc_count = nullptr, enc_emit = nullptr;  // k_encode<.., kCount / kEmitDefault, ..> of this context
   size_t slot_B = 0, slot_NC = 0, slot_NS = 0;  // slot sizes: frames, chunks and segments per frame
+  size_t slot_BO = 0;  // ... and encoded frames (slot_B; under a sheet the sheets a launch may yield)
 
   Slot slot[kSlots];
   int head = 0;   // slot of the next launch
@@ -404,7 +418,7 @@ void free_ctx(mjg_ctx *c) {
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (Slot &S : c->slot) {
-    void *sp[] = {S.d_stage, S.d_scaled, S.d_orient, S.d_deint, S.d_sharp, S.d_lut, S.d_stage_bits, S.d_scratch, S.d_stream, S.d_work, S.d_chunk_bits, S.d_chunk_off, S.d_group_ff, S.d_ff_off, S.d_frame_bits,
+    void *sp[] = {S.d_stage, S.d_scaled, S.d_orient, S.d_deint, S.d_sharp, S.d_lut, S.d_tile, S.d_stage_bits, S.d_scratch, S.d_stream, S.d_work, S.d_chunk_bits, S.d_chunk_off, S.d_group_ff, S.d_ff_off, S.d_frame_bits,
                   S.d_status, S.d_frame_size, S.d_frame_offsets, S.d_seg_size, S.d_seg_off, S.d_done, S.d_out,
                   S.d_hist, S.d_ftabs, S.d_dht_nval, S.d_hdr_lens, S.d_dht, S.d_dbg, S.d_syms, S.d_symn};
     for (void *p : sp)
@@ -465,6 +479,9 @@ struct Layout {
   int px, py, pw, ph;          // the picture's place in the canvas and the canvas size (no pad: the picture)
   bool has_pad;                // false for the trivial rectangle
   int s_hsh, s_vsh, hsh, vsh;  // chroma shifts of the source format and of the encoded one
+  bool has_sheet;              // a contact sheet behind the sws stage (check_sheet; false for the trivial one)
+  mjg_sheet sheet;             // ... nb_frames resolved
+  int tw, th;                  // ... and its size, the encoded frame's
 };
 
 // A plane's filter tables as the kernels read them (plan_plane_scale), before their upload
@@ -660,7 +677,7 @@ int upload_plane_scale(PlaneScale &p, const ScaleTabs &t) {
 hipStream_t slot_stream(const mjg_ctx *c, int i) { return i ? c->more[i - 1] : c->stream; }
 
 int alloc_slot(mjg_ctx *c, Slot &S) {
-  const size_t B = c->slot_B, NC = c->slot_NC, NS = c->slot_NS;
+  const size_t BI = c->slot_B, B = c->slot_BO, NC = c->slot_NC, NS = c->slot_NS;  // input frames, encoded frames
   const EncGeom &g = c->geom;
   int rc;
   // Each slot on its own stream: consecutive submits (queued kSlots deep) overlap, so the next
@@ -671,11 +688,12 @@ int alloc_slot(mjg_ctx *c, Slot &S) {
   // launches).  Each launch's own event interval then includes its neighbour's overlap.
   S.st = slot_stream(c, (int)(&S - c->slot));
   if ((rc = dmalloc(&S.d_stage_bits, c->stage_cols * 64 * kStageWords))) return rc;
-  if (c->scale && (rc = dmalloc(&S.d_scaled, B * c->enc_frame_bytes))) return rc;
-  if (c->orient && (rc = dmalloc(&S.d_orient, B * c->in_frame_bytes))) return rc;
-  if (c->deint && (rc = dmalloc(&S.d_deint, B * c->in_frame_bytes))) return rc;
-  if (c->sharp && (rc = dmalloc(&S.d_sharp, B * c->enc_frame_bytes))) return rc;
-  if ((c->has_lut[0] || c->has_cmat) && !c->orient && !c->deint && (rc = dmalloc(&S.d_lut, B * c->in_frame_bytes))) return rc;
+  if (c->scale && (rc = dmalloc(&S.d_scaled, BI * c->pic_frame_bytes))) return rc;
+  if (c->orient && (rc = dmalloc(&S.d_orient, BI * c->in_frame_bytes))) return rc;
+  if (c->deint && (rc = dmalloc(&S.d_deint, BI * c->in_frame_bytes))) return rc;
+  if (c->sharp && (rc = dmalloc(&S.d_sharp, BI * c->pic_frame_bytes))) return rc;
+  if ((c->has_lut[0] || c->has_cmat) && !c->orient && !c->deint && (rc = dmalloc(&S.d_lut, BI * c->in_frame_bytes))) return rc;
+  if (c->sheet && (rc = dmalloc(&S.d_tile, B * c->enc_frame_bytes))) return rc;
   if ((rc = dmalloc(&S.d_scratch, B * NC * (size_t)kSlotWords)) ||
       (rc = dmalloc(&S.d_stream, B * NC * (size_t)kSlotWords)) ||
       (rc = dmalloc(&S.d_chunk_bits, B * NC)) || (rc = dmalloc(&S.d_chunk_off, B * NC)) ||
@@ -832,6 +850,37 @@ int check_config(const mjg_config &k, const mjg_chain &ch, Layout *lay) {
   l.px = px, l.py = py, l.pw = pw, l.ph = ph;
   l.has_pad = has_pad;
   l.s_hsh = s_hsh, l.s_vsh = s_vsh, l.hsh = e_hsh, l.vsh = e_vsh;
+  l.has_sheet = false, l.sheet = mjg_sheet{}, l.tw = l.th = 0;
+  return MJG_OK;
+}
+
+// open, step 1b: the sheet (mjg_open_sheet; null: none) on the layout check_config resolved.  The
+// trivial sheet is no sheet.
+int check_sheet(const mjg_config &k, const mjg_sheet *sp, Layout *lay) {
+  if (!sp) return MJG_OK;
+  const mjg_sheet &s = *sp;
+  if (s.cols < 1 || s.rows < 1) return set_err(MJG_E_INVALID, "sheet %dx%d: cols or rows below 1", s.cols, s.rows);
+  const long long cells = (long long)s.cols * s.rows;
+  if (s.nb_frames < 0 || s.nb_frames > cells)
+    return set_err(MJG_E_INVALID, "sheet %dx%d: nb_frames %d not in 0..%lld (cols x rows)", s.cols, s.rows, s.nb_frames, cells);
+  if (s.margin < 0 || s.padding < 0)
+    return set_err(MJG_E_INVALID, "sheet %dx%d: margin %d or padding %d is negative", s.cols, s.rows, s.margin, s.padding);
+  const long long W = (long long)s.cols * k.dst_w + (long long)(s.cols - 1) * s.padding + 2ll * s.margin;
+  const long long H = (long long)s.rows * k.dst_h + (long long)(s.rows - 1) * s.padding + 2ll * s.margin;
+  if (W > 16384 || H > 16384)
+    return set_err(MJG_E_INVALID, "sheet %dx%d of %dx%d cells, margin %d, padding %d: %lldx%lld, a side is beyond 16384",
+                   s.cols, s.rows, k.dst_w, k.dst_h, s.margin, s.padding, W, H);
+  if (cells == 1 && s.margin == 0) return MJG_OK;  // one cell that is the picture: no sheet
+  if (lay->has_pad) return set_err(MJG_E_INVALID, "sheet %dx%d behind a pad: the chain's has_pad is set", s.cols, s.rows);
+  const int mh = (1 << lay->hsh) - 1, mv = (1 << lay->vsh) - 1;
+  if ((k.dst_w & mh) || (k.dst_h & mv) || (s.margin & (mh | mv)) || (s.padding & (mh | mv)))
+    return set_err(MJG_E_INVALID, "sheet %dx%d of %dx%d cells, margin %d, padding %d: not multiples of the encoded "
+                   "format's chroma sub-sampling (%dx%d)", s.cols, s.rows, k.dst_w, k.dst_h, s.margin, s.padding,
+                   1 << lay->hsh, 1 << lay->vsh);
+  lay->has_sheet = true;
+  lay->sheet = s;
+  if (!s.nb_frames) lay->sheet.nb_frames = (int)cells;
+  lay->tw = (int)W, lay->th = (int)H;
   return MJG_OK;
 }
 
@@ -861,7 +910,10 @@ int plan_geometry(const mjg_config &k, int src_cf, const Layout &lay, bool unali
   }
   c->has_cmat = lay.cm != nullptr;
   if (lay.cm) c->cmat = *lay.cm;
-  c->scale = (crw != k.dst_w || crh != k.dst_h || src_cf != cf || c->has_pad || c->sharp || c->has_lut[1]);
+  // (and a sheet: k_tile_plane reads the cells from d_scaled / d_sharp)
+  c->sheet = lay.has_sheet;
+  c->sh = lay.sheet;
+  c->scale = (crw != k.dst_w || crh != k.dst_h || src_cf != cf || c->has_pad || c->sharp || c->has_lut[1] || c->sheet);
   const int scw = (fw + s_hsh) >> s_hsh, sch = (fh + s_vsh) >> s_vsh;
   // the rectangle's chroma planes: at (cx >> hs, cy >> vs), the chroma size of a crw x crh frame
   // (inside the source's: cx, cy are multiples of the sub-sampling)
@@ -872,18 +924,26 @@ int plan_geometry(const mjg_config &k, int src_cf, const Layout &lay, bool unali
   c->src_off[2] = c->src_off[1] + c->src_cplane;
   // the encoded frame: the canvas under a pad, else the picture (the sws stage's output, or the
   // source rectangle itself); pcw x pch: the picture's chroma planes
-  const int w = lay.pw, h = lay.ph, cw = (w + hsh) >> hsh, ch = (h + vsh) >> vsh;
   const int pcw = (k.dst_w + hsh) >> hsh, pch = (k.dst_h + vsh) >> vsh;
-  for (int p = 0; p < 2; p++) {
-    PadGeom &q = c->pad[p];
-    q.cw = p ? cw : w;
-    q.ch = p ? ch : h;
-    q.cw_magic = magic32((uint32_t)q.cw);
-    q.px = p ? px >> hsh : px;
-    q.py = p ? py >> vsh : py;
-    q.fill = p ? 128 : 0;
+  {
+    const int w = lay.pw, h = lay.ph, cw = (w + hsh) >> hsh, ch = (h + vsh) >> vsh;
+    for (int p = 0; p < 2; p++) {
+      PadGeom &q = c->pad[p];
+      q.cw = p ? cw : w;
+      q.ch = p ? ch : h;
+      q.cw_magic = magic32((uint32_t)q.cw);
+      q.px = p ? px >> hsh : px;
+      q.py = p ? py >> vsh : py;
+      q.fill = p ? 128 : 0;
+    }
+    c->pic_frame_bytes = (size_t)w * h + 2 * (size_t)cw * ch;
+    c->pic_u_off = (long long)w * h;
+    c->pic_cplane = (long long)cw * ch;
   }
   c->in_frame_bytes = (size_t)fw * fh + 2 * (size_t)scw * sch;
+  // ... and under a sheet the sheet, which k_tile_plane makes of the sws stage's output
+  const int w = lay.has_sheet ? lay.tw : lay.pw, h = lay.has_sheet ? lay.th : lay.ph;
+  const int cw = (w + hsh) >> hsh, ch = (h + vsh) >> vsh;
   c->enc_frame_bytes = (size_t)w * h + 2 * (size_t)cw * ch;
 
   EncGeom &g = c->geom;
@@ -910,7 +970,10 @@ int plan_geometry(const mjg_config &k, int src_cf, const Layout &lay, bool unali
   g.nchunks_magic = magic40((unsigned long long)g.nchunks);
   g.nseg_magic = magic40((unsigned long long)g.nseg);
   // task t / nchunks by magic (exact while t * nchunks < 2^40, t < max_batch * nseg * nchunks)
-  if ((unsigned long long)k.max_batch * g.nseg * g.nchunks * g.nchunks >= ((unsigned long long)1 << 40))
+  // (under a sheet the sheets a launch may yield: each of up to kMaxSegs segments ends with a partial one)
+  const int N = lay.has_sheet ? lay.sheet.nb_frames : 1;
+  const unsigned long long max_enc = lay.has_sheet ? (unsigned long long)((k.max_batch + N - 1) / N + kMaxSegs - 1) : k.max_batch;
+  if (max_enc * g.nseg * g.nchunks * g.nchunks >= ((unsigned long long)1 << 40))
     return set_err(MJG_E_INVALID, "max_batch %d too large for this frame size", k.max_batch);
   // k_encode reads the sws stage's packed output, or the source frames in place: rows at the
   // source planes' strides, the block offsets from the rectangle's first luma byte (submit_impl
@@ -942,7 +1005,7 @@ int plan_geometry(const mjg_config &k, int src_cf, const Layout &lay, bool unali
     sg.sw_magic = magic32((uint32_t)sg.sw);
     sg.d_stride = c->pad[p].cw;  // the encoded plane's rows: dw, or the wider canvas under a pad
     sg.s_fstride = (long long)c->in_frame_bytes;
-    sg.d_fstride = (long long)c->enc_frame_bytes;
+    sg.d_fstride = (long long)c->pic_frame_bytes;
     sg.range = k.in_full_range ? 0 : (p ? 2 : 1);
   }
   return MJG_OK;
@@ -1070,7 +1133,7 @@ void build_plan(mjg_ctx *c) {
     const PlaneScale &ps = c->ps[p];
     Pass *next = c->pass[p];
     ScaleGeom g = ps.g;
-    const long long plane_off = p ? c->geom.u_off : 0;  // the encoded (canvas) plane in a frame
+    const long long plane_off = p ? c->pic_u_off : 0;  // the picture's (canvas) plane in a frame of the stage's output
     g.s_off = c->src_off[p];               // the (cropped) plane's first byte in a source frame
     g.d_off = plane_off + (long long)c->pad[p].py * c->pad[p].cw + c->pad[p].px;  // the picture's first byte in it
     // one dimension: tiles x planes x frames (scale.hip decodes it by multiply-high)
@@ -1187,15 +1250,39 @@ void launch_sharp(const SharpGeom &g, const uint8_t *src, uint8_t *dst, int nz, 
 // same kernel.  submit_impl adds nf and the U + V pairing.
 void plan_sharp(const mjg_config &k, const Layout &lay, mjg_ctx *c) {
   if (!lay.sharp) return;
-  const EncGeom &e = c->geom;
   for (int p = 0; p < 2; p++) {
     const PadGeom &q = c->pad[p];
     const int w = p ? (k.dst_w + lay.hsh) >> lay.hsh : k.dst_w, h = p ? (k.dst_h + lay.vsh) >> lay.vsh : k.dst_h;
     const int mx = p ? lay.us.cx : lay.us.lx, my = p ? lay.us.cy : lay.us.ly;
     SharpPass &s = c->shpass[p];
-    s.g = sharp_geom(q.cw, q.ch, q.px, q.py, w, h, p ? e.u_off : 0, (long long)c->enc_frame_bytes, mx, my,
+    s.g = sharp_geom(q.cw, q.ch, q.px, q.py, w, h, p ? c->pic_u_off : 0, (long long)c->pic_frame_bytes, mx, my,
                      p ? lay.us.ca : lay.us.la);
     s.launch = mx == 5 && my == 5 ? launch_sharp<5, 5> : launch_sharp<0, 0>;
+  }
+}
+
+// The sheet's launches for luma and chroma (mjg_ctx::tpass; no device, no environment): the cell's
+// planes in the sws stage's (the sharpen's) buffer -> the sheet's planes in d_tile.  submit_impl adds
+// ns, the U + V pairing and the segments' sheets and frames.
+void plan_tile(const mjg_config &k, const Layout &lay, mjg_ctx *c) {
+  if (!lay.has_sheet) return;
+  const mjg_sheet &s = lay.sheet;
+  const EncGeom &e = c->geom;
+  for (int p = 0; p < 2; p++) {
+    const int hs = p ? lay.hsh : 0, vs = p ? lay.vsh : 0;
+    TileGeom &g = c->tpass[p];
+    g = TileGeom{};
+    g.w = k.dst_w >> hs, g.h = k.dst_h >> vs;  // (multiples of the sub-sampling: check_sheet)
+    g.W = p ? e.cw : e.w, g.H = p ? e.ch : e.h;
+    g.pw = g.w + (s.padding >> hs), g.ph = g.h + (s.padding >> vs);
+    g.mx = s.margin >> hs, g.my = s.margin >> vs;
+    g.cols = s.cols, g.ncells = s.cols * s.rows, g.N = s.nb_frames;
+    g.fill = p ? 128 : 0;
+    g.s_off = p ? c->pic_u_off : 0, g.d_off = p ? e.u_off : 0;
+    g.s_fstride = (long long)c->pic_frame_bytes, g.d_fstride = (long long)c->enc_frame_bytes;
+    g.W_magic = magic32((uint32_t)g.W), g.pw_magic = magic32((uint32_t)g.pw), g.ph_magic = magic32((uint32_t)g.ph);
+    g.gxy = tile_gxy(g.W, g.H);
+    g.gxy_magic = magic32((uint32_t)g.gxy);
   }
 }
 
@@ -1227,8 +1314,8 @@ void plan_lut(const mjg_config &k, const Layout &lay, mjg_ctx *c) {
         const PadGeom &pg = c->pad[p];
         const int w = p ? (k.dst_w + lay.hsh) >> lay.hsh : k.dst_w, h = p ? (k.dst_h + lay.vsh) >> lay.vsh : k.dst_h;
         lut_geom_rect(g, w, h, pg.cw, pg.cw);
-        g.s_off = g.d_off = (p ? c->geom.u_off : 0) + (long long)pg.py * pg.cw + pg.px;
-        g.s_fstride = g.d_fstride = (long long)c->enc_frame_bytes;
+        g.s_off = g.d_off = (p ? c->pic_u_off : 0) + (long long)pg.py * pg.cw + pg.px;
+        g.s_fstride = g.d_fstride = (long long)c->pic_frame_bytes;
       }
       g.tab = p;
       g.ident = ident;
@@ -1295,7 +1382,7 @@ int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
   // merging (kMerge): opt-in with MJG_F_MERGE (a held submit's frames are read after mjg_submit
   // returns); MJG_MERGE=1 turns it off for a process (A/B), =2..4 sets the jobs per launch
   c->merge = (k.flags & MJG_F_MERGE) ? std::max(1, std::min(kMaxSegs, env_int("MJG_MERGE", kMerge))) : 1;
-  if (c->deint) c->merge = 1;  // a deint context neither holds nor merges submits (mjgpu.h)
+  if (c->deint || c->sheet) c->merge = 1;  // a deint or a sheet context neither holds nor merges submits (mjgpu.h)
   c->hold_idle = env_int("MJG_MERGE_HOLD", 1) != 0;
   if (c->merge > 1) {  // slot buffers for merge * max_batch frames: within a share of free memory
     size_t fr = 0, tot = 0;
@@ -1309,6 +1396,8 @@ int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
   if ((unsigned long long)k.max_batch * c->merge * g.nseg * g.nchunks * g.nchunks >= ((unsigned long long)1 << 40))
     c->merge = 1;  // merged launches would overflow k_encode's task magic (checked for max_batch above)
   c->slot_B = (size_t)k.max_batch * (size_t)c->merge;  // frames one launch may carry
+  // ... and the frames it may encode: under a sheet ceil(count / N) sheets for each of up to kMaxSegs segments
+  c->slot_BO = c->sheet ? (size_t)((k.max_batch + c->sh.nb_frames - 1) / c->sh.nb_frames + kMaxSegs - 1) : c->slot_B;
   // k_cmat_frame's grid is workgroups per frame x frames in x alone
   if (c->has_cmat && (unsigned long long)c->cgeom.gxy * c->slot_B > (unsigned long long)INT_MAX)
     return set_err(MJG_E_INVALID, "cmatrix: %d workgroups a frame x %zu frames a launch is past 2^31 - 1", c->cgeom.gxy,
@@ -1357,18 +1446,19 @@ int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
   return alloc_slot(c, c->slot[0]);
 }
 
-int open_ctx(int device, const mjg_config &k, const mjg_chain &chain, mjg_ctx *c) {
+int open_ctx(int device, const mjg_config &k, const mjg_chain &chain, const mjg_sheet *sheet, mjg_ctx *c) {
   c->device = device;
   c->cfg = k;
   Layout lay;
   int rc;
-  if ((rc = check_config(k, chain, &lay))) return rc;
+  if ((rc = check_config(k, chain, &lay)) || (rc = check_sheet(k, sheet, &lay))) return rc;
   if ((rc = plan_geometry(k, chain.src_chroma_format, lay, env_int("MJG_UNALIGNED_FETCH", 1) != 0, c))) return rc;
   plan_orient(k, lay, c);
   plan_deint(k, lay, c);
   plan_sharp(k, lay, c);
   plan_lut(k, lay, c);
   plan_cmat(lay, c);
+  plan_tile(k, lay, c);
   quant_matrix(k.qscale, c->mprime, c->qmat);
   c->hdr = build_header(c->geom.w, c->geom.h, c->mprime, k.sar_num, k.sar_den, (k.flags & MJG_F_COM_ITU601) != 0,
                         k.chroma_format, c->rst, &c->dht_pos, &c->dht_end);
@@ -1447,10 +1537,14 @@ int mjg_device_numa_node(int device) {
 }
 
 int mjg_open_chain(int device, const mjg_config *cfg, const mjg_chain *chain, mjg_ctx **out) {
+  return mjg_open_sheet(device, cfg, chain, nullptr, out);
+}
+
+int mjg_open_sheet(int device, const mjg_config *cfg, const mjg_chain *chain, const mjg_sheet *sheet, mjg_ctx **out) {
   if (!cfg || !chain || !out) return set_err(MJG_E_INVALID, "null argument");
   *out = nullptr;
   mjg_ctx *c = new mjg_ctx();
-  const int rc = open_ctx(device, *cfg, *chain, c);
+  const int rc = open_ctx(device, *cfg, *chain, sheet, c);
   if (rc) {
     const std::string keep = g_err;
     free_ctx(c);
@@ -1609,6 +1703,20 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
   }
   src += (size_t)hp * c->in_frame_bytes;  // the first encoded frame
   SegList in_sl = segs ? *segs : one_seg(src);  // the submit's input frames: the caller's segments, or one at src
+  // the frames k_encode codes: the n input frames, or under a sheet ceil(count / N) sheets for each
+  // segment, a sequence of its own (TileGeom's per-segment fields)
+  int m = n, seg_sheet0[kMaxSegs] = {}, seg_first[kMaxSegs] = {}, seg_count[kMaxSegs] = {};
+  if (c->sheet) {
+    m = 0;
+    for (int k = 0; k < kMaxSegs; k++) {
+      const bool used = in_sl.f0[k] != INT_MAX;
+      const int end = k + 1 < kMaxSegs && in_sl.f0[k + 1] != INT_MAX ? in_sl.f0[k + 1] : n;
+      seg_sheet0[k] = used ? m : INT_MAX;
+      seg_first[k] = used ? in_sl.f0[k] : 0;
+      seg_count[k] = used ? end - in_sl.f0[k] : 0;
+      if (used) m += (seg_count[k] + c->sh.nb_frames - 1) / c->sh.nb_frames;
+    }
+  }
   if (c->scale || c->orient || c->deint || c->has_lut[0] || c->has_cmat) tmark(c, S, MJG_K_SCALE, 0);
   if (c->deint) {  // in front of everything: luma, then U and V in one launch; the rest reads one buffer
     const bool uv1 = 2 * n <= 65535;
@@ -1658,7 +1766,7 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
     // luma, then U and V in one launch (same filters; blockIdx.z >= n is V) while 2n fits the
     // grid's z range, else one launch each
     const bool uv1 = 2 * n <= 65535;
-    const long long d_cplane = (long long)g.cw * g.ch;
+    const long long d_cplane = c->pic_cplane;
     for (int p = 0; p < (uv1 ? 2 : 3); p++) {
       for (const Pass &ps : c->pass[p ? 1 : 0]) {
         if (!ps.launch) continue;
@@ -1688,6 +1796,19 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
       }
       enc_buf = S.d_sharp;
     }
+    if (c->sheet) {  // behind the sharpen: the cells of each segment onto its sheets; luma, then U and V as above
+      const bool tuv1 = 2 * m <= 65535;
+      const long long t_cplane = (long long)g.cw * g.ch;
+      for (int p = 0; p < (tuv1 ? 2 : 3); p++) {
+        TileGeom tg = c->tpass[p ? 1 : 0];
+        tg.ns = m;
+        for (int k = 0; k < kMaxSegs; k++) tg.sheet0[k] = seg_sheet0[k], tg.first[k] = seg_first[k], tg.count[k] = seg_count[k];
+        if (p && tuv1) tg.s_poff = d_cplane, tg.d_poff = t_cplane;
+        if (p == 2) tg.s_off += d_cplane, tg.d_off += t_cplane;
+        k_tile_plane<<<tg.gxy * (p && tuv1 ? 2 * m : m), kCopyThreads, 0, S.st>>>(enc_buf, S.d_tile, tg);
+      }
+      enc_buf = S.d_tile;
+    }
     tmark(c, S, MJG_K_SCALE, 1);
     HIP_TRY(hipGetLastError());
     enc_in = one_seg(enc_buf);  // k_encode reads the scaled (the sharpened) frames, one buffer
@@ -1695,15 +1816,15 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
     if (c->orient || c->deint || c->has_lut[0] || c->has_cmat) tmark(c, S, MJG_K_SCALE, 1);  // an orientation / a deinterlacer / a table / a matrix alone: the interval holds its passes
     for (int k = 0; k < kMaxSegs; k++) enc_in.p[k] += c->src_off[0];
   }
-  const int ntasks = g.nchunks * g.nseg * n;
-  const int nsegs = g.nseg * n;  // entropy-coded segments of this submit
+  const int ntasks = g.nchunks * g.nseg * m;
+  const int nsegs = g.nseg * m;  // entropy-coded segments of this submit
   const int wgs = std::min((ntasks + kWavesPerWg - 1) / kWavesPerWg, c->enc_grid);
   if (c->optimal) {  // pass 1: symbol counts per frame, then the frame's tables
     tmark(c, S, MJG_K_HUFF, 0);
-    HIP_TRY(hipMemsetAsync(S.d_hist, 0, (size_t)n * kFrameTabWords * 4, S.st));
+    HIP_TRY(hipMemsetAsync(S.d_hist, 0, (size_t)m * kFrameTabWords * 4, S.st));
     c->enc_count(c, S, enc_in, std::min(wgs, c->enc_grid_cnt), ntasks);
     HIP_TRY(hipMemsetAsync(S.d_work, 0, (size_t)kXcds * kCtrStride * 4, S.st));  // unit counters for pass 2
-    k_huff_build<<<n * 4, 64, 0, S.st>>>(S.d_hist, S.d_ftabs, S.d_dht, S.d_dht_nval);
+    k_huff_build<<<m * 4, 64, 0, S.st>>>(S.d_hist, S.d_ftabs, S.d_dht, S.d_dht_nval);
     tmark(c, S, MJG_K_HUFF, 1);
     HIP_TRY(hipGetLastError());
   }
@@ -1724,7 +1845,7 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
     k_scan_bits_seg<<<tail_seg_wgs(nsegs), 256, 0, c->tail>>>(S.d_chunk_bits, S.d_chunk_off, S.d_frame_bits, g.nchunks, nsegs,
                                                           S.d_work, S.d_status, S.d_done, ndone);
   else
-    k_scan_bits<<<n, 1024, 0, c->tail>>>(S.d_chunk_bits, S.d_chunk_off, S.d_frame_bits, g.nchunks,
+    k_scan_bits<<<m, 1024, 0, c->tail>>>(S.d_chunk_bits, S.d_chunk_off, S.d_frame_bits, g.nchunks,
                                            S.d_work, S.d_status, S.d_done, ndone);
   tmark(c, S, MJG_K_SCAN_BITS, 1);
   HIP_TRY(hipGetLastError());
@@ -1737,19 +1858,20 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
   HIP_TRY(hipGetLastError());
   // segment and frame sizes, the frames' packed offsets
   tmark(c, S, MJG_K_SCAN_FF, 0);
-  k_scan_ff<<<n, 256, 0, c->tail>>>(S.d_group_ff, S.d_ff_off, S.d_frame_bits, g.nchunks, gps, g.nseg, (int)c->hdr.size(),
+  k_scan_ff<<<m, 256, 0, c->tail>>>(S.d_group_ff, S.d_ff_off, S.d_frame_bits, g.nchunks, gps, g.nseg, (int)c->hdr.size(),
                                       c->optimal ? S.d_dht_nval : nullptr, S.d_hdr_lens, S.d_seg_size,
                                       S.d_seg_off, S.d_frame_size, S.d_frame_offsets, S.d_done);
   tmark(c, S, MJG_K_SCAN_FF, 1);
   HIP_TRY(hipGetLastError());
-  int rc = launch_write(c, S, n, false);
+  int rc = launch_write(c, S, m, false);
   if (rc) return rc;
-  S.n = n;
+  S.n = m;
+  S.nin = n;
   S.pending = true;
   S.njobs = 1;  // the caller records a merged launch's jobs
   S.nsynced = 0;
   S.jf0[0] = 0;
-  S.jn[0] = n;
+  S.jn[0] = m;
   c->head = (c->head + 1) % kSlots;
   c->nout++;
   c->launches++;
@@ -1813,16 +1935,17 @@ int sync_for_read(mjg_ctx *c) {
 
 // The frame readbacks (mjg_debug_planes and its kin): frame `frame` of the latest synced submit, out of
 // the buffer `buf` names in that submit's slot, whose frames are nbytes apart.  Pending submits are
-// synced first
+// synced first.  input: the buffer holds the submit's input frames, which under a sheet are not the
+// frames it encoded (a sheet context's launch is one job)
 int read_frame(mjg_ctx *c, int frame, uint8_t *out, size_t cap, size_t nbytes,
-               uint8_t *(*buf)(const mjg_ctx *, const Slot &)) {
+               uint8_t *(*buf)(const mjg_ctx *, const Slot &), bool input = true) {
   if (pending_jobs(c) > 0) {
     const int rc = mjg_sync(c, nullptr, nullptr);
     if (rc) return rc;
   }
   if (pending_jobs(c) > 0 || c->last < 0) return set_err(MJG_E_STATE, "sync every queued submit first");
   const Slot &L = c->slot[c->last];
-  if (frame < 0 || frame >= L.jn[c->last_job]) return set_err(MJG_E_INVALID, "frame %d", frame);
+  if (frame < 0 || frame >= (input && c->sheet ? L.nin : L.jn[c->last_job])) return set_err(MJG_E_INVALID, "frame %d", frame);
   if (cap < nbytes) return set_err(MJG_E_CAPACITY, "need %zu bytes", nbytes);
   const size_t f = (size_t)L.jf0[c->last_job] + (size_t)frame;
   HIP_TRY(hipMemcpy(out, buf(c, L) + f * nbytes, nbytes, hipMemcpyDeviceToHost));
@@ -2124,15 +2247,33 @@ int mjg_debug_encode_path(mjg_ctx *c) {
 int mjg_debug_planes(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
   if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
   if (!c->scale) return set_err(MJG_E_STATE, "context has no sws stage (same size, same chroma format)");
-  // the encoder's input: under a sharpen its output
+  // the encoder's input: under a sharpen its output, under a sheet the sheets
   return read_frame(c, frame, out, cap, c->enc_frame_bytes,
+                    [](const mjg_ctx *x, const Slot &S) { return x->sheet ? S.d_tile : x->sharp ? S.d_sharp : S.d_scaled; }, false);
+}
+
+int mjg_debug_cell(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
+  if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
+  if (!c->sheet) return set_err(MJG_E_STATE, "context has no sheet (mjg_open_chain, or a trivial sheet)");
+  return read_frame(c, frame, out, cap, c->pic_frame_bytes,
                     [](const mjg_ctx *x, const Slot &S) { return x->sharp ? S.d_sharp : S.d_scaled; });
+}
+
+int mjg_debug_sheet(mjg_ctx *c, mjg_sheet *out) {
+  if (!c) return set_err(MJG_E_INVALID, "null context");
+  if (c->sheet && out) *out = c->sh;
+  return c->sheet ? 1 : 0;
+}
+
+int mjg_frames_out(const mjg_ctx *c, int nframes) {
+  if (!c || nframes < 1) return 0;
+  return c->sheet ? (nframes + c->sh.nb_frames - 1) / c->sh.nb_frames : nframes;
 }
 
 int mjg_debug_presharp(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
   if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
   if (!c->sharp) return set_err(MJG_E_STATE, "context has no sharpen (no unsharp, or both amounts 0)");
-  return read_frame(c, frame, out, cap, c->enc_frame_bytes, [](const mjg_ctx *, const Slot &S) { return S.d_scaled; });
+  return read_frame(c, frame, out, cap, c->pic_frame_bytes, [](const mjg_ctx *, const Slot &S) { return S.d_scaled; });
 }
 
 int mjg_debug_unsharp(mjg_ctx *c, mjg_unsharp *out) {

@@ -1820,4 +1820,143 @@ __global__ __launch_bounds__(kCmatThreads) void k_cmat_frame(const SegList src, 
   cmat_work<HS, VS>(src, dst, g, cm, (int)blockIdx.x, (int)threadIdx.x);
 }
 
+// k_tile_plane: `-vf tile`, several frames on one picture (mjg_open_sheet).  The input is
+// the sws stage's output (under a sharpen, its output): nf cell frames, packed planar, full range, one
+// buffer, s_fstride apart.  The output is the sheets, packed planar in the same format, d_fstride apart.
+// A sheet plane is W x H; cell t of it is the w x h rectangle at (mx + pw (t % cols), my + ph (t / cols)),
+// pw = w + padding, ph = h + padding, every value in samples of this plane (the margin, the padding and
+// the cell are multiples of the sub-sampling, so the chroma values are the luma ones shifted).  Every
+// byte outside a cell that holds a frame is `fill` (the pad's black: 0 luma, 128 chroma).
+// Which frame a cell holds: each segment of the submit is a sequence of its own, and the geometry
+// gives per segment its first sheet, its first frame and its frame count.  Sheet s of the submit is
+// sheet j = s - sheet0[k] of the last segment k with sheet0[k] <= s; its cell t holds the frame
+// first[k] + j N + t when t < N and j N + t < count[k], and is blank otherwise.
+// Layout: as k_plane_copy, the sheet plane of a (plane, sheet) is one byte string of W H bytes (at most
+// 2^28) cut into 16-byte pieces aligned on the destination, kCopyVecs pieces a thread; piece k covers
+// bytes [head + 16 k, + 16), byte i is column i % W of row i / W, and its cell comes from two more
+// multiply-high divisions, by pw and by ph.  A piece inside one row of a cell that holds a frame is one
+// unaligned 16-byte load.  A piece that is blank as a whole is the constant: a piece inside one sheet
+// row that lies in a row of the margin or the padding, in the left margin, in one blank cell (with the
+// gap behind it), in the gap behind a cell or behind the row's last cell.  Any other piece (over a cell edge,
+// over a row end, every piece of a cell narrower than 16) is put together byte by byte in a rolled loop.
+// Each piece is then one aligned 16-byte store, behind all of the thread's loads.  The bytes before the
+// first and behind the last whole piece go byte by byte in the (plane, sheet)'s first workgroup.
+// U and V share a launch (blockIdx >= gxy * ns is V).
+// Addresses.  A load is made only for a cell that holds a frame: f = first[k] + j N + t with t < N
+// and 0 <= j N + t < count[k], so f is one of the segment's frames [first[k], first[k] + count[k]), which
+// the host takes from the submit's nf frames; inside it the byte is (yy, xx) with 0 <= yy < h and
+// 0 <= xx < w (a vector load: xx + 16 <= w) of the plane at s_off (+ s_poff), so every load lies inside a
+// plane of one of the nf cell frames.  No address is formed for a blank cell.  A store is an aligned
+// piece inside [head, head + 16 nv) or a byte i < W H of the sheet plane at d_off (+ d_poff) of sheet
+// s < ns (the grid has gxy workgroups for each of them and no more), so every store lies inside it.
+// The body is a __host__ __device__ function, as yadif_work is, for tools/tile_host.hip.
+struct TileGeom {
+  int w, h;                 // the cell plane
+  int W, H;                 // the sheet plane
+  int pw, ph;               // the cell pitches: w + padding, h + padding
+  int mx, my;               // the margin
+  int cols, ncells, N;      // cells a row, cells a sheet, frames a sheet
+  int fill;                 // the blank byte
+  long long s_off, d_off;   // the plane's first byte inside a cell frame / a sheet frame
+  long long s_fstride, d_fstride;
+  long long s_poff, d_poff; // the next plane's offset from this one (V from U)
+  int ns;                   // sheets per plane
+  uint32_t W_magic, pw_magic, ph_magic;  // ceil(2^32 / W), / pw, / ph
+  int gxy;                  // workgroups per (plane, sheet)
+  uint32_t gxy_magic;
+  int sheet0[kMaxSegs], first[kMaxSegs], count[kMaxSegs];  // per segment: its first sheet (INT_MAX: unused), first frame, frames
+};
+
+// workgroups per (plane, sheet) for a sheet plane of W x H
+inline int tile_gxy(int W, int H) {
+  const size_t pieces = ((size_t)W * H) >> 4, per = (size_t)kCopyThreads * kCopyVecs;
+  return (int)(pieces ? (pieces + per - 1) / per : 1);
+}
+
+__host__ __device__ __forceinline__ void tile_work(const uint8_t *src, uint8_t *dst, const TileGeom &g, int t, int tid) {
+  const int z = deint_div(t, g.gxy_magic, g.gxy), blk = t - z * g.gxy;
+  const int pl = z >= g.ns, sh = z - (pl ? g.ns : 0);
+  int k = 0;
+#pragma unroll
+  for (int i = 1; i < kMaxSegs; i++)
+    if (sh >= g.sheet0[i]) k = i;
+  const int jn = (sh - g.sheet0[k]) * g.N;        // the sheet's first frame in its segment
+  const int left = g.count[k] - jn;               // cells t < left (and < N) hold a frame
+  const uint8_t *s = src + (long long)(g.first[k] + jn) * g.s_fstride + g.s_off + (pl ? g.s_poff : 0);  // cell 0's plane
+  uint8_t *d = dst + (long long)sh * g.d_fstride + g.d_off + (pl ? g.d_poff : 0);
+  const int w = g.w, h = g.h, W = g.W, pw = g.pw, ph = g.ph, cols = g.cols;
+  const int nb = W * g.H;
+  const int head = imin((int)(-(uintptr_t)d & 15), nb);
+  const int nv = (nb - head) >> 4;
+  const uint32_t fill = (uint32_t)g.fill;
+  auto holds = [&](int c) { return c < g.N && c < left; };
+  auto byte_at = [&](int i) -> uint32_t {  // byte i of the sheet plane
+    const int row = deint_div(i, g.W_magic, W), col = i - row * W;
+    const int ry = row - g.my, cx = col - g.mx;
+    if (ry < 0 || cx < 0) return fill;
+    const int r = deint_div(ry, g.ph_magic, ph), yy = ry - r * ph;
+    const int cc = deint_div(cx, g.pw_magic, pw), xx = cx - cc * pw;
+    const int c = r * cols + cc;
+    if (yy >= h || xx >= w || cc >= cols || c >= g.ncells || !holds(c)) return fill;
+    return s[(long long)c * g.s_fstride + (size_t)yy * w + xx];
+  };
+  const int k0 = blk * (kCopyThreads * kCopyVecs) + tid;
+  const u32x4 blank = u32x4{fill * 0x01010101u, fill * 0x01010101u, fill * 0x01010101u, fill * 0x01010101u};
+  u32x4 v[kCopyVecs];
+#pragma unroll
+  for (int i = 0; i < kCopyVecs; i++) {
+    const int kp = k0 + i * kCopyThreads;
+    v[i] = blank;
+    if (kp >= nv) continue;
+    const int j = head + 16 * kp;
+    const int row = deint_div(j, g.W_magic, W), col = j - row * W;
+    const int ry = row - g.my, cx = col - g.mx;
+    int kind = 2;  // 0 blank, 1 one load, 2 byte by byte
+    const uint8_t *at = s;
+    if (col + 16 <= W) {
+      const int r = ry < 0 ? 0 : deint_div(ry, g.ph_magic, ph), yy = ry - r * ph;
+      if (ry < 0 || yy >= h || r * cols >= g.ncells || col + 16 <= g.mx) {
+        kind = 0;
+      } else if (cx >= 0) {
+        const int cc = deint_div(cx, g.pw_magic, pw), xx = cx - cc * pw;
+        const int c = r * cols + cc;
+        if (cc >= cols || (xx >= w && (xx + 16 <= pw || cc == cols - 1)) || (xx + 16 <= pw && !holds(c))) {
+          kind = 0;
+        } else if (xx + 16 <= w) {  // (the cell holds a frame)
+          kind = 1;
+          at = s + (long long)c * g.s_fstride + (size_t)yy * w + xx;
+        }
+      }
+    }
+    if (kind == 1) {
+      v[i] = *(const u32x4_a1 *)at;
+    } else if (kind == 2) {  // rolled: pieces over a cell edge or a row end
+#pragma unroll 1
+      for (int q = 0; q < 4; q++) {
+        uint32_t a = 0;
+#pragma unroll 1
+        for (int b = 0; b < 4; b++) a |= byte_at(j + 4 * q + b) << (8 * b);
+        v[i][q] = a;
+      }
+    }
+  }
+  uint32_t ha = 0, hb = 0;  // the head and tail bytes: the (plane, sheet)'s first workgroup
+  const int ia = tid, ib = head + 16 * nv + tid;
+  const bool edge = blk == 0 && tid < 16;
+  if (edge && ia < head) ha = byte_at(ia);
+  if (edge && ib < nb) hb = byte_at(ib);
+#pragma unroll
+  for (int i = 0; i < kCopyVecs; i++) {
+    const int kp = k0 + i * kCopyThreads;
+    if (kp < nv) *(u32x4 *)(d + head + 16 * kp) = v[i];
+  }
+  if (edge && ia < head) d[ia] = (uint8_t)ha;
+  if (edge && ib < nb) d[ib] = (uint8_t)hb;
+}
+
+__global__ __launch_bounds__(kCopyThreads) void k_tile_plane(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
+                                                             TileGeom g) {
+  tile_work(src, dst, g, (int)blockIdx.x, (int)threadIdx.x);
+}
+
 }  // namespace mjg

@@ -27,7 +27,11 @@ output planes on the GPU; the encoder then reads the sharpened planes.  `lut_in=
 in front of the sws stage and directly behind it: `-vf eq=...` in front of the scale or
 directly behind it, with profile.eq_tables.  `cmat=` (c2, ..., c7: six 16.16 ints) is a colour matrix
 on whole frames behind the orientation and in front of `lut_in`: `-vf
-colormatrix=SRC:DST` with profile.colormatrix_coefs.  An encoder with any of these opens as one
+colormatrix=SRC:DST` with profile.colormatrix_coefs.  `sheet=` (cols, rows, nb_frames, margin, padding:
+`-vf tile` as the last filter) puts every nb_frames frames (0: cols * rows) on one contact sheet on the
+GPU: dst_w x dst_h stay the cell, the JPEGs are the sheets (enc_w x enc_h), a submit of n frames yields
+frames_out(n) of them, and every submit (every segment of a submit_segments) is a sequence of its own;
+such an encoder opens through mjg_open_sheet.  An encoder with any of these opens as one
 mjg_chain (include/mjgpu.h, which says what each stage does) through mjg_open_chain; one with none
 through mjg_open / mjg_open_src.  No CPU fallback.
 """
@@ -80,7 +84,7 @@ class MjpegEncoder:
                  debug_coefs: bool = False, sws_bitexact: bool = True, com_itu601: bool = False,
                  huffman: str = "default", chroma: str = "420", rst: bool = False,
                  merge: bool = False, src_chroma: Optional[str] = None, crop=None, pad=None, orient: int = 0,
-                 deint: Optional[int] = None, unsharp=None, lut_in=None, lut_out=None, cmat=None):
+                 deint: Optional[int] = None, unsharp=None, lut_in=None, lut_out=None, cmat=None, sheet=None):
         self._L = _lib.load()
         self.device = int(device)
         self.src_w, self.src_h = int(src_w), int(src_h)
@@ -104,6 +108,20 @@ class MjpegEncoder:
         if self.pad is not None and len(self.pad) != 4:
             raise ValueError(f"pad {pad!r}: (x, y, W, H)")
         self.enc_w, self.enc_h = (self.dst_w, self.dst_h) if self.pad is None else self.pad[2:]
+        # sheet: (cols, rows, nb_frames, margin, padding), `-vf tile` behind everything else: dst_w x dst_h
+        # is the cell, enc_w x enc_h the sheet, sheet_n the frames a sheet holds (1: no sheet, or the
+        # trivial one, which the library opens as none).  None, the default, opens as without it
+        self.sheet = None if sheet is None else tuple(int(v) for v in sheet)
+        if self.sheet is not None and len(self.sheet) != 5:
+            raise ValueError(f"sheet {sheet!r}: (cols, rows, nb_frames, margin, padding)")
+        self.pic_w, self.pic_h = self.enc_w, self.enc_h  # the sws stage's output frame
+        self.sheet_n = 1
+        if self.sheet is not None:
+            cols, rows, nb, margin, padding = self.sheet
+            if cols * rows != 1 or margin != 0:
+                self.sheet_n = nb or cols * rows
+                self.enc_w = cols * self.dst_w + (cols - 1) * padding + 2 * margin
+                self.enc_h = rows * self.dst_h + (rows - 1) * padding + 2 * margin
         self.max_batch = int(max_batch)
         flags = 0
         if timing == "detail":
@@ -178,7 +196,7 @@ class MjpegEncoder:
         # has, an older one named by MJG_LIBRARY too), everything else as one mjg_chain
         src_cf = _lib.CHROMA_FORMATS[self.src_chroma]
         if (self.crop is None and self.pad is None and not self.orient and deint is None and unsharp is None
-                and lut_in is None and lut_out is None and self.cmat is None):
+                and lut_in is None and lut_out is None and self.cmat is None and self.sheet is None):
             if self.src_chroma == self.chroma:
                 check(self._L.mjg_open(self.device, C.byref(cfg), C.byref(h)))
             elif not hasattr(self._L, "mjg_open_src"):
@@ -187,6 +205,8 @@ class MjpegEncoder:
                 check(self._L.mjg_open_src(self.device, C.byref(cfg), src_cf, C.byref(h)))
         elif not hasattr(self._L, "mjg_open_chain"):
             raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_chain")
+        elif self.sheet is not None and not hasattr(self._L, "mjg_open_sheet"):
+            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_sheet")
         else:
             chain = _lib.MjgChain(src_chroma_format=src_cf, deint=self.deint, orient=self.orient)
             if self.cmat is not None:
@@ -203,13 +223,18 @@ class MjpegEncoder:
             if self.pad is not None:
                 chain.has_pad = 1
                 chain.pad_x, chain.pad_y, chain.pad_w, chain.pad_h = self.pad
-            check(self._L.mjg_open_chain(self.device, C.byref(cfg), C.byref(chain), C.byref(h)))
+            if self.sheet is not None:
+                check(self._L.mjg_open_sheet(self.device, C.byref(cfg), C.byref(chain),
+                                             C.byref(_lib.MjgSheet(*self.sheet)), C.byref(h)))
+            else:
+                check(self._L.mjg_open_chain(self.device, C.byref(cfg), C.byref(chain), C.byref(h)))
         self._h = h
         self.frame_bytes = int(self._L.mjg_frame_bytes(h))
         self._queued = deque()        # (nframes, host buffer kept alive) per queued submit
         self._synced_since_submit = False
         self._last_sizes = np.zeros(0, np.uint64)
-        self._sizes = np.zeros(self.max_batch + 1, np.uint64)
+        # (under a sheet each of up to mjg_max_segments() segments may end with a partial sheet)
+        self._sizes = np.zeros(self.max_batch + (1 if self.sheet_n == 1 else 4), np.uint64)
 
     # ------------------------------------------------------------------ basics
     def close(self):
@@ -239,6 +264,13 @@ class MjpegEncoder:
         buf = (C.c_uint8 * n.value)()
         check(self._L.mjg_header(self._h, buf, n.value, C.byref(n)))
         return bytes(buf)
+
+    def frames_out(self, n: int) -> int:
+        """JPEGs a submit (or one segment of a submit_segments) of `n` frames yields: n without a
+        sheet, ceil(n / sheet_n) with one (mjg_frames_out)."""
+        if hasattr(self._L, "mjg_frames_out"):
+            return int(self._L.mjg_frames_out(self._h, int(n)))
+        return int(n)
 
     # ------------------------------------------------------------------ encode
     @property
@@ -286,7 +318,7 @@ class MjpegEncoder:
             if nframes is None:
                 raise ValueError("nframes is required with device_ptr")
             call(C.c_void_p(int(device_ptr)), int(nframes), 1)
-            self._queued.append((int(nframes), None))
+            self._queued.append((self.frames_out(nframes), None))
             self._synced_since_submit = False
             return
         arr = np.ascontiguousarray(np.frombuffer(frames, dtype=np.uint8)
@@ -299,7 +331,7 @@ class MjpegEncoder:
         if halo and (n + nhalo) * self.frame_bytes > arr.size:
             raise ValueError(f"buffer of {arr.size} bytes holds fewer than {n} frames and {nhalo} halo frame(s)")
         call(C.c_void_p(arr.ctypes.data), n, 0)
-        self._queued.append((n, arr))  # the async H2D copy reads arr until its sync
+        self._queued.append((self.frames_out(n), arr))  # the async H2D copy reads arr until its sync
         self._synced_since_submit = False
 
     def submit_segments(self, segments):
@@ -315,7 +347,7 @@ class MjpegEncoder:
         ptrs = (C.c_void_p * max(k, 1))(*[C.c_void_p(int(p)) for p, _ in segments])
         ns = (C.c_int * max(k, 1))(*[int(n) for _, n in segments])
         check(self._L.mjg_submit_segments(self._h, ptrs, ns, k))
-        self._queued.append((sum(int(n) for _, n in segments), None))
+        self._queued.append((sum(self.frames_out(n) for _, n in segments), None))
         self._synced_since_submit = False
 
     @property
@@ -394,12 +426,16 @@ class MjpegEncoder:
     def encode(self, frames) -> List[bytes]:
         """Encode host frames (any count; split into max_batch submits).  With `deint` the frames
         are one sequence: up to max_batch of them one submit, more of them halo submits that carry
-        each piece's neighbour frames, which gives the same bytes."""
+        each piece's neighbour frames, which gives the same bytes.  With a `sheet` the frames are one
+        sequence too: every submit but the last is a whole number of sheets."""
         arr = np.ascontiguousarray(np.asarray(frames, dtype=np.uint8)).reshape(-1)
         n = arr.size // self.frame_bytes
         out: List[bytes] = []
-        for i in range(0, n, self.max_batch):
-            k = min(self.max_batch, n - i)
+        step = self.max_batch // self.sheet_n * self.sheet_n
+        if n > self.max_batch and not step:
+            raise ValueError(f"a sheet of {self.sheet_n} frames does not fit max_batch {self.max_batch}")
+        for i in range(0, n, step or self.max_batch):
+            k = min(step or self.max_batch, n - i)
             if self.deint and n > self.max_batch:
                 lo, hi = (1 if i else 0), (1 if i + k < n else 0)
                 self.submit(arr[(i - lo) * self.frame_bytes:(i + k + hi) * self.frame_bytes], k, halo=lo | hi << 1)
@@ -431,8 +467,26 @@ class MjpegEncoder:
     def debug_planes(self, frame: int = 0) -> np.ndarray:
         """The encoder-input planes (after the scale / range / chroma stage) of a frame of the
         last synced submit: packed planar, enc_w x enc_h (dst size; the canvas under a pad), the
-        encoded format `chroma`."""
+        encoded format `chroma`.  Under a `sheet`: sheet `frame` of that submit."""
         return self._debug_frame("mjg_debug_planes", i420_frame_bytes(self.enc_w, self.enc_h, self.chroma), frame)
+
+    def debug_cell(self, frame: int = 0) -> np.ndarray:
+        """k_tile_plane's input frame `frame` of the last synced submit, one of its input frames: the
+        cell, packed planar, dst_w x dst_h in the encoded format (under a sharpen the sharpened planes).
+        Only for an encoder opened with a `sheet` that is not the trivial one; debug_planes() then
+        returns a sheet."""
+        return self._debug_frame("mjg_debug_cell", i420_frame_bytes(self.pic_w, self.pic_h, self.chroma), frame)
+
+    def debug_sheet(self):
+        """(cols, rows, nb_frames, margin, padding) as the context holds them (nb_frames resolved), or
+        None for a context without a sheet.  Host state only."""
+        if not hasattr(self._L, "mjg_debug_sheet"):
+            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_debug_sheet")
+        sh = _lib.MjgSheet()
+        rc = self._L.mjg_debug_sheet(self._h, C.byref(sh))
+        if rc < 0:
+            check(rc)
+        return (sh.cols, sh.rows, sh.nb_frames, sh.margin, sh.padding) if rc else None
 
     def _debug_frame(self, symbol: str, nbytes: int, frame: int) -> np.ndarray:
         """A frame readback of the library (mjg_debug_planes and its kin): `nbytes` bytes of frame
@@ -453,7 +507,7 @@ class MjpegEncoder:
         """The sws stage's output (k_unsharp_plane's input) of a frame of the last synced submit, laid
         out as debug_planes(), which under a sharpen returns the sharpened planes.  Only for an
         encoder opened with an `unsharp` whose amounts are not both 0."""
-        return self._debug_frame("mjg_debug_presharp", i420_frame_bytes(self.enc_w, self.enc_h, self.chroma), frame)
+        return self._debug_frame("mjg_debug_presharp", i420_frame_bytes(self.pic_w, self.pic_h, self.chroma), frame)
 
     def debug_unsharp(self):
         """(lx, ly, la, cx, cy, ca) as the context holds them (la, ca the filter's integers), or None

@@ -45,7 +45,17 @@ front of the unsharp and the pad), before or after the crop, is `Profile.colorma
 frame metadata), src equal to dst (FFmpeg refuses it itself), an unknown name or key and any other
 position are outside the profile, each with a reason that names it.  `colormatrix_coefs` makes the six
 16.16 coefficients, a restatement of vf_colormatrix.c's 8-bit planar path that is unpinned against
-FFmpeg.  An orientation filter after a crop, scale
+FFmpeg.  Around all of that,
+    framestep=N | framestep=step=N          (the very first filter; not with yadif)
+    tile[=COLSxROWS[:nb_frames[:margin[:padding[:black[:0[:0]]]]]]]   (also layout=, nb_frames=, margin=, padding=,
+                                            color=, overlap=, init_padding=; the very last filter; not with pad)
+make the profile a `SheetProfile`: `framestep` = N, which the worker's reader applies,
+and `tile` = the request as given, which the worker resolves against the cell.  Decimal integers only; a
+colour other than black, an overlap or init_padding other than 0, an expression, a second one of either,
+any other position and what FFmpeg itself rejects (nb_frames above cols x rows, a step below 1) are
+outside the profile, each with a reason that names it.  `framestep=1` is no filter, and a graph that
+names neither filter parses to the plain `Profile` it always did.  Both are restatements (vf_tile.c,
+vf_framestep.c) that are unpinned against FFmpeg.  An orientation filter after a crop, scale
 or pad, transpose values 4..7, a passthrough other than none and any other option are outside the
 profile.  The crop values are decimal integers (no expressions); `Profile.crop` is the request as
 given and `resolve_crop` turns it into a rectangle of a given input (vf_crop.c's rounding,
@@ -110,6 +120,17 @@ class Profile:
     # -vf ...,colormatrix=SRC:DST: the canonical (src, dst) names (COLORMATRIX_LUMA's keys), in front of
     # any eq and the scale; colormatrix_coefs turns them into the six coefficients.  None: no colormatrix
     colormatrix: Optional[Tuple[str, str]] = None
+
+
+@dataclass
+class SheetProfile(Profile):
+    """The Profile of a graph that names `tile` or a `framestep` above 1 (parse returns one exactly then;
+    every other graph gives a plain Profile, field for field what it was)."""
+    # -vf ...,tile=...: the request as given, {"cols", "rows", "nb_frames" (0: cols * rows), "margin", "padding"};
+    # None: no tile
+    tile: Optional[dict] = None
+    # -vf framestep=N,...: the reader keeps every N-th frame of the segment; 1: every frame
+    framestep: int = 1
 
 
 class Unsupported(ValueError):
@@ -553,6 +574,101 @@ def _in_front(name: str) -> bool:
     return name == "yadif" or name in ORIENT_FILTERS or name in OTHER_DEINTERLACERS or name == "hflip"
 
 
+TILE_OPTIONS = ("layout", "nb_frames", "margin", "padding", "color", "overlap", "init_padding")
+_DEC_RE = re.compile(r"\d+\Z")
+
+
+def _parse_tile(f: str) -> dict:
+    """`tile[=layout:nb_frames:margin:padding:color:overlap:init_padding]`, positional in that order or by
+    name -> {"cols", "rows", "nb_frames", "margin", "padding"} (vf_tile.c's defaults: 6x5, 0 = cols * rows,
+    0, 0).  Unsupported for what the GPU path does not do (a colour other than black, overlap, init_padding,
+    expressions) and for what FFmpeg itself rejects."""
+    vals = {"layout": "6x5", "nb_frames": "0", "margin": "0", "padding": "0", "color": "black", "overlap": "0",
+            "init_padding": "0"}
+    pos = 0
+    for part in (f.split("=", 1)[1].split(":") if "=" in f else []):
+        if "=" in part:
+            k, v = part.split("=", 1)
+            if k not in vals:
+                raise Unsupported(f"tile option {k!r}")
+            pos = len(TILE_OPTIONS)      # (a positional value behind a named one: FFmpeg refuses it)
+        else:
+            if pos >= len(TILE_OPTIONS):
+                raise Unsupported(f"tile {f!r}: a positional value behind a named one, or too many")
+            k, v = TILE_OPTIONS[pos], part
+            pos += 1
+        vals[k] = v
+    m = re.match(r"(\d+)x(\d+)\Z", vals["layout"])
+    if not m:
+        raise Unsupported(f"tile layout {vals['layout']!r}: not COLSxROWS in decimal integers (expressions are not "
+                          f"GPU-accelerated)")
+    cols, rows = int(m.group(1)), int(m.group(2))
+    num = {}
+    for k in ("nb_frames", "margin", "padding", "overlap", "init_padding"):
+        if not _DEC_RE.match(vals[k]):
+            raise Unsupported(f"tile {k} {vals[k]!r}: not a decimal integer of 0 or more (expressions are not "
+                              f"GPU-accelerated; FFmpeg rejects a negative value)")
+        num[k] = int(vals[k])
+    if vals["color"].lower() != "black":
+        raise Unsupported(f"tile color {vals['color']!r} (only black is GPU-accelerated)")
+    if num["overlap"]:
+        raise Unsupported(f"tile overlap {num['overlap']} (only overlap 0 is GPU-accelerated)")
+    if num["init_padding"]:
+        raise Unsupported(f"tile init_padding {num['init_padding']} (only init_padding 0 is GPU-accelerated)")
+    if cols < 1 or rows < 1:
+        raise Unsupported(f"tile layout {cols}x{rows}: FFmpeg rejects a layout below 1x1")
+    if num["nb_frames"] > cols * rows:
+        raise Unsupported(f"tile nb_frames {num['nb_frames']}: FFmpeg rejects more frames than the {cols}x{rows} "
+                          f"layout has cells")
+    return {"cols": cols, "rows": rows, "nb_frames": num["nb_frames"], "margin": num["margin"], "padding": num["padding"]}
+
+
+def _parse_framestep(f: str) -> int:
+    """`framestep=N` / `framestep=step=N` -> N (vf_framestep.c: step, 1 or more; the default is 1)."""
+    v = f.split("=", 1)[1] if "=" in f else "1"
+    if v.startswith("step="):
+        v = v[len("step="):]
+    if not _DEC_RE.match(v):
+        raise Unsupported(f"framestep {v!r}: not a decimal integer (expressions are not GPU-accelerated)")
+    if int(v) < 1:
+        raise Unsupported(f"framestep {v}: FFmpeg rejects a step below 1")
+    return int(v)
+
+
+def _take_sheet(fs, out):
+    """A framestep as the very first filter and a tile as the very last one, taken off before the other
+    stages see the list.  A graph that names neither is left exactly as it is."""
+    names = _names(fs)
+    if "tile" not in names and "framestep" not in names:
+        return
+    vf = _graph(fs)
+    if "framestep" in names:
+        if names.count("framestep") > 1:
+            raise Unsupported(f"filter graph {vf!r}: a second framestep (one framestep, as the first filter, is "
+                              f"GPU-accelerated)")
+        if names[0] != "framestep":
+            at = names.index("framestep")
+            raise Unsupported(f"filter graph {vf!r}: framestep after {names[at - 1]} (framestep is GPU-accelerated only "
+                              f"as the first filter)")
+        if "yadif" in names:
+            raise Unsupported(f"filter graph {vf!r}: framestep together with yadif (the deinterlacer would need the "
+                              f"dropped frames' neighbours)")
+    if "tile" in names:
+        if names.count("tile") > 1:
+            raise Unsupported(f"filter graph {vf!r}: a second tile (one tile, as the last filter, is GPU-accelerated)")
+        if names[-1] != "tile":
+            raise Unsupported(f"filter graph {vf!r}: tile is not the last filter (tile is GPU-accelerated only as the "
+                              f"last filter)")
+        if "pad" in names:
+            raise Unsupported(f"filter graph {vf!r}: tile in a graph with pad (tile behind a pad is not GPU-accelerated)")
+    if names[0] == "framestep":
+        step = _parse_framestep(fs.pop(0)[1])
+        if step > 1:
+            out["framestep"] = step
+    if fs and fs[-1][0] == "tile":
+        out["tile"] = _parse_tile(fs.pop()[1])
+
+
 def _take_colormatrix(fs, out):
     """One colormatrix, behind the yadif and the orientation run, in front of any eq and of the scale
     (without a scale: in front of the unsharp and the pad); before or after the crop, with which it
@@ -687,13 +803,13 @@ def _take_crop_scale(fs, out):
 
 
 # in this order, which decides the reason a graph outside the profile is refused with
-GRAPH_STAGES = (_take_colormatrix, _take_eq, _take_deint, _take_orient, _take_pad_unsharp, _take_crop_scale)
+GRAPH_STAGES = (_take_sheet, _take_colormatrix, _take_eq, _take_deint, _take_orient, _take_pad_unsharp, _take_crop_scale)
 
 
 def parse_graph(vf: str) -> dict:
     """A -vf value -> the chain fields of Profile that the graph sets, by name (crop, scale,
-    sws_flags, pad, orient, deint, unsharp, eq, colormatrix; a field the graph does not set is left
-    out, so Profile's own defaults are the only ones), or Unsupported."""
+    sws_flags, pad, orient, deint, unsharp, eq, colormatrix, and SheetProfile's tile and framestep; a field
+    the graph does not set is left out, so Profile's own defaults are the only ones), or Unsupported."""
     if ";" in vf:
         raise Unsupported(f"filter graph {vf!r} (only crop, scale or crop,scale is GPU-accelerated)")
     fs = [(f.split("=", 1)[0], f) for f in vf.split(",")]
@@ -876,7 +992,9 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
     rst = uses_slices(slices, threads, thread_type)
     if rst:
         huff = "default"  # mjpegenc.c: slice_context_count > 1 forces HUFFMAN_TABLE_DEFAULT
-    return Profile(qscale=effective_qscale(q), q_arg=q, huffman=huff, rst=rst, chroma=chroma, **chain)
+    # (a SheetProfile exactly when the winning graph names a tile or a framestep above 1)
+    cls = SheetProfile if "tile" in chain or "framestep" in chain else Profile
+    return cls(qscale=effective_qscale(q), q_arg=q, huffman=huff, rst=rst, chroma=chroma, **chain)
 
 
 PIX_FMT_CHROMA = {"yuvj420p": "420", "yuvj422p": "422", "yuvj444p": "444"}

@@ -47,6 +47,13 @@ One `colormatrix=SRC:DST` (profile.Profile.colormatrix) becomes six 16.16 coeffi
 (profile.colormatrix_coefs) that the GPU applies to the decoded frames behind the yadif and the
 orientation, in front of everything else; cmat_fallthrough_reason names the inputs that still go to
 the real ffmpeg.
+A `tile` as the last filter (profile.SheetProfile.tile) is run by the GPU behind everything else: every
+nb_frames frames become one sheet, a batch is a whole number of sheets (sheet_batch), and the muxer and
+the progress lines run at the input rate / nb_frames; tile_fallthrough_reason names the inputs that still
+go to the real ffmpeg.  A `framestep=N` as the first filter never reaches the GPU: the reader keeps
+frame i of the segment when i % N == 0 and passes over the rest (Source.skip, which reads nothing of
+them from a regular file), and the output runs at the input rate / N.  Such a graph resolves to a
+SheetPlan; every other graph to the SegmentPlan it always did.
 All of this is resolved against the segment's input by plan_segment, a pure function, before run()
 binds to the GPU's NUMA node: a SegmentPlan, a Fallthrough (the real ffmpeg) or a CropError / PadError.
 """
@@ -358,6 +365,24 @@ class Source:
     def _y4m(self, rd):
         self.info = rd.info
         self.read_into = rd.read_into
+
+    def skip(self, n: int) -> int:
+        """Pass over the next n frames (-vf framestep: the frames the reader does not keep); returns how
+        many there were.  A regular-file Matroska advances without reading the frames' bytes (the
+        positional reads are never issued); a pipe or a y4m stream reads them into a scratch frame."""
+        if n <= 0:
+            return 0
+        if getattr(self, "_scratch", None) is None:
+            self._scratch = bytearray(self.info.frame_bytes)
+        if getattr(self, "_fd", None) is not None:
+            try:  # the block headers are parsed, the offsets advance, and no positional read is issued
+                return self._mkv.frames_into_pread(self._track, [memoryview(self._scratch)] * n, lambda off, dest: None)
+            except ValueError as e:
+                raise ValueError(f"V_UNCOMPRESSED {e}") from None
+        for i in range(n):
+            if self.read_into(self._scratch, 1) < 1:
+                return i
+        return n
 
     def _read_mkv(self, buf, n):
         fb = self.info.frame_bytes
@@ -688,6 +713,65 @@ class SegmentPlan:
                            self.orient, self.deint, self.unsharp, (self.lut_in, self.lut_out), self.cmat)
 
 
+TILE_MAX_SIDE = 16384    # the pad's canvas limit (mjg_open_sheet refuses more)
+TILE_MAX_FRAMES = 32     # a sheet never spans two submits, and 32 frames is the most a batch holds (batch_frames)
+
+
+def tile_fallthrough_reason(prof, cell, src_chroma, dst_chroma) -> Optional[str]:
+    """Why a graph that ends in `tile` runs on the CPU for this input, or None: `cell` is the tile's input
+    picture.  The pad's two cases, for the same reasons (pad_fallthrough_reason): a -pix_fmt conversion without
+    a scale would run behind the tile and filter across cell borders, and a cell that is no multiple of the
+    sub-sampling gets a painted last column or row.  Then the sheet's own: a margin or padding that is no
+    multiple of the sub-sampling (the chroma cells would not sit where vf_tile puts them), a sheet side
+    beyond the canvas limit, and more frames a sheet than a batch holds."""
+    t = prof.tile
+    if prof.scale is None and src_chroma != dst_chroma:
+        return (f"tile before the {src_chroma} -> {dst_chroma} -pix_fmt conversion (no scale in the graph: the "
+                f"converter runs after the tile)")
+    hs, vs = _CHROMA_SHIFTS[str(dst_chroma)]
+    w, h = cell
+    if w & ((1 << hs) - 1) or h & ((1 << vs) - 1):
+        return (f"tile of {w}x{h} cells in {dst_chroma}: the size is no multiple of the chroma sub-sampling "
+                f"({1 << hs}x{1 << vs})")
+    m = (1 << max(hs, vs)) - 1
+    if t["margin"] & m or t["padding"] & m:
+        return (f"tile margin {t['margin']} / padding {t['padding']} in {dst_chroma}: no multiple of the chroma "
+                f"sub-sampling ({1 << hs}x{1 << vs})")
+    W, H = sheet_size(w, h, t)
+    if W > TILE_MAX_SIDE or H > TILE_MAX_SIDE:
+        return f"tile {t['cols']}x{t['rows']} of {w}x{h} cells: a {W}x{H} sheet, a side beyond {TILE_MAX_SIDE}"
+    n = t["nb_frames"] or t["cols"] * t["rows"]
+    if n > TILE_MAX_FRAMES:
+        return f"tile of {n} frames a sheet: more than the {TILE_MAX_FRAMES} frames a submit holds"
+    return None
+
+
+def sheet_size(w: int, h: int, t: dict):
+    """The sheet of w x h cells: (cols w + (cols - 1) padding + 2 margin, rows h + (rows - 1) padding + 2 margin)."""
+    return (t["cols"] * w + (t["cols"] - 1) * t["padding"] + 2 * t["margin"],
+            t["rows"] * h + (t["rows"] - 1) * t["padding"] + 2 * t["margin"])
+
+
+def sheet_batch(b: int, n: int) -> int:
+    """Frames per batch under a sheet of n frames: whole sheets, max(n, (b // n) * n) for b = batch_frames(...)."""
+    return max(n, (b // n) * n)
+
+
+@dataclass(frozen=True, eq=False)
+class SheetPlan(SegmentPlan):
+    """The plan of a profile.SheetProfile (a graph with a tile or a framestep above 1): enc_w x enc_h is
+    the sheet."""
+    sheet: Optional[tuple] = None    # (cols, rows, nb_frames, margin, padding), nb_frames resolved; None: framestep alone
+    framestep: int = 1               # the reader keeps every framestep-th frame
+    out_fps: Fraction = Fraction(25)  # what the muxer and the progress lines run at: fps / (framestep * nb_frames)
+
+    def encoder_kwargs(self) -> dict:
+        return dict(super().encoder_kwargs(), sheet=self.sheet)
+
+    def key(self, prof, info, com_itu601, batch):
+        return super().key(prof, info, com_itu601, batch) + (("sheet", self.sheet),)
+
+
 def plan_segment(prof, info) -> SegmentPlan:
     """Resolve a profile against a segment's input (container.StreamInfo): no device, no streams.
     Raises Fallthrough(reason) for a segment the CPU ffmpeg runs, and lets profile.CropError /
@@ -736,6 +820,20 @@ def plan_segment(prof, info) -> SegmentPlan:
     # a pad leaves it alone too: the scale's SAR, from the picture's size, not the canvas's)
     # (a transpose hands on 1 / SAR when the SAR is known: vf_transpose config_props_output)
     sar = profile.scaled_sar(oriented_sar(info.sar, orient), in_size, (dst_w, dst_h))
+    if isinstance(prof, profile.SheetProfile):  # -vf framestep=N,...,tile: frames dropped in front, sheets behind (SAR: the cell's)
+        sheet, n = None, 1
+        if prof.tile is not None:
+            why = tile_fallthrough_reason(prof, (dst_w, dst_h), src_chroma, dst_chroma)
+            if why is not None:
+                raise Fallthrough(why)
+            t = prof.tile
+            n = t["nb_frames"] or t["cols"] * t["rows"]
+            sheet = (t["cols"], t["rows"], n, t["margin"], t["padding"])
+            enc_w, enc_h = sheet_size(dst_w, dst_h, t)
+        return SheetPlan(src_chroma=src_chroma, dst_chroma=dst_chroma, deint=deint, orient=orient, rect=rect,
+                         in_size=in_size, dst_w=dst_w, dst_h=dst_h, pad=pad, enc_w=enc_w, enc_h=enc_h,
+                         unsharp=prof.unsharp, lut_in=lut_in, lut_out=lut_out, cmat=cmat, sar=sar,
+                         sheet=sheet, framestep=prof.framestep, out_fps=Fraction(info.fps) / (prof.framestep * n))
     return SegmentPlan(src_chroma=src_chroma, dst_chroma=dst_chroma, deint=deint, orient=orient, rect=rect,
                        in_size=in_size, dst_w=dst_w, dst_h=dst_h, pad=pad, enc_w=enc_w, enc_h=enc_h,
                        unsharp=prof.unsharp, lut_in=lut_in, lut_out=lut_out, cmat=cmat, sar=sar)
@@ -774,6 +872,12 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
     from .encoder import MjpegEncoder, PinnedBuffer   # GPU work starts here
 
     batch = batch_frames(opts, info.frame_bytes)
+    # -vf framestep / tile (SheetPlan): the reader keeps every step-th frame, a batch is whole sheets, and
+    # the output runs at fps / (step * frames a sheet)
+    step = getattr(plan, "framestep", 1)
+    out_fps = getattr(plan, "out_fps", info.fps)
+    if getattr(plan, "sheet", None) is not None:
+        batch = sheet_batch(batch, plan.sheet[2])
     com_itu601 = opts.com_itu601 and not info.full_range
     key = plan.key(prof, info, com_itu601, batch)
     nbuf = NBUF
@@ -792,9 +896,9 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
         obufs = [None] * NOUT
         if cache is not None:
             cache.update(key=key, enc=enc, bufs=bufs, obufs=obufs)
-    prog = Progress(stderr, info.fps, prof.qscale)
+    prog = Progress(stderr, out_fps, prof.qscale)
     prog.duration(src.duration)
-    mkv = container.MkvWriter(stdout, plan.enc_w, plan.enc_h, info.fps, plan.sar)
+    mkv = container.MkvWriter(stdout, plan.enc_w, plan.enc_h, out_fps, plan.sar)
 
     # NBUF page-locked batches: the reader fills one while two are queued on the GPU (the
     # encoder takes a second submit before the first is synced, so its kernels run back to
@@ -817,7 +921,13 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
                 if i < 0 or abort.is_set():
                     return
                 t0 = time.monotonic()
-                n = src.read_into(bufs[i].array, batch)
+                if step > 1:  # framestep: frame i of the segment is kept when i % step == 0, the rest passed over
+                    n, arr = 0, bufs[i].array
+                    while n < batch and src.read_into(arr[n * fb:(n + 1) * fb], 1) == 1:
+                        n += 1
+                        src.skip(step - 1)
+                else:
+                    n = src.read_into(bufs[i].array, batch)
                 tr["read"] += time.monotonic() - t0
                 full.put((i, n))
                 if n < batch:
@@ -896,7 +1006,7 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
                     mkv.write_frame(p)
                 mkv.flush_pending()  # the packets leave buffer `ob` before it is reused
                 tr["mux"] += time.monotonic() - t0
-                frames += m
+                frames += len(packets)  # (under a sheet fewer than the m frames submitted)
                 prog.update(frames, sum(len(p) for p in packets))
             except BaseException as e:  # surfaced by the main thread
                 mux_err.append(e)

@@ -287,6 +287,42 @@ typedef struct mjg_chain {
  * _lib.py does.) */
 int mjg_open_chain(int device, const mjg_config *cfg, const mjg_chain *chain, mjg_ctx **out);
 
+/* A contact sheet behind the chain (`-vf tile=COLSxROWS:nb_frames:margin:padding` as the last filter;
+ * "sheet"): several frames on one picture.  The cell is the sws stage's output (under a sharpen, its
+ * output), cfg->dst_w x dst_h, which stay the cell's size as they stay the picture's under a pad.  The
+ * JPEGs are sheets of W = cols dst_w + (cols - 1) padding + 2 margin by H = rows dst_h + (rows - 1)
+ * padding + 2 margin.  With N = nb_frames (0: cols rows), frame i of a sequence goes to sheet i / N,
+ * cell t = i % N, whose place is (margin + (dst_w + padding) (t % cols), margin + (dst_h + padding)
+ * (t / cols)), the chroma planes at that place shifted by the encoded format's sub-sampling.  Whatever
+ * is not a cell that holds a frame -- the margin, the padding, the cells N .. cols rows - 1 of every
+ * sheet, the cells of a sequence's last sheet behind its last frame -- is the pad's black: Y = 0,
+ * Cb = Cr = 128 in the full-range encoder input, for tv and for full-range sources alike.
+ *   Every submit is a whole sequence, and so is every segment of mjg_submit_segments: a sheet never
+ * spans two.  max_batch and every nframes count input frames; a submit of n frames yields
+ * mjg_frames_out(ctx, n) = ceil(n / N) JPEGs (a segment list: the sum over its segments, each
+ * segment's sheets behind those of the one before).  mjg_sync's frame_sizes has that many entries, and
+ * mjg_fetch, mjg_output_device's offsets, mjg_debug_coefs and mjg_debug_planes index sheets;
+ * mjg_debug_cell and the debug readbacks of the stages in front (mjg_debug_presharp, mjg_debug_deint,
+ * ...) index input frames.  mjg_header, the MCU grid and mjg_debug_planes follow the sheet,
+ * mjg_frame_bytes the source.  RST and -huffman optimal work per sheet.
+ *   Like a deinterlacer context a sheet context neither holds nor merges submits: MJG_F_MERGE is
+ * accepted and has no effect.  A sheet composes with a deinterlacer and mjg_submit_halo, whose nframes
+ * are the encoded input frames as without one.  With a sheet the sws stage always runs, as under a pad
+ * or a sharpen; k_tile_plane reads its buffer (the sharpen's) and writes the sheets, which k_encode
+ * then reads.  Its launches are part of the MJG_K_SCALE interval.
+ *   NULL, or a sheet of one cell without margin (cols = rows = 1, nb_frames 0 or 1, margin 0), is
+ * exactly mjg_open_chain: the context launches what it launches without a sheet.
+ *   Refused with MJG_E_INVALID and a message that starts with "sheet", before any HIP call: cols or
+ * rows below 1, nb_frames below 0 or above cols rows, a negative margin or padding, a sheet side
+ * above 16384, a pad in the chain (one that is not the trivial rectangle), and a dst_w, dst_h, margin
+ * or padding that is not a multiple of the encoded format's sub-sampling.  The chain's own refusals
+ * come first.  (Added without a version step, as mjg_open_chain.) */
+typedef struct mjg_sheet { int32_t cols, rows, nb_frames, margin, padding; } mjg_sheet;
+int mjg_open_sheet(int device, const mjg_config *cfg, const mjg_chain *chain, const mjg_sheet *sheet, mjg_ctx **out);
+/* JPEGs a submit (or one segment of mjg_submit_segments) of nframes frames yields: nframes without
+ * a sheet, ceil(nframes / N) with one.  0 for a NULL ctx or nframes below 1. */
+int mjg_frames_out(const mjg_ctx *ctx, int nframes);
+
 /* The entry points from before mjg_chain.  Each is mjg_open_chain with the chain it names: the
  * fields not listed are zero, and a rectangle that is listed always has its has_crop / has_pad set,
  * so a caller without a crop or a pad passes the full rectangle (0, 0, the oriented size) or the
@@ -430,6 +466,15 @@ int mjg_debug_planes(mjg_ctx *ctx, int frame, uint8_t *out, size_t cap);
 /* The sws stage's output under a sharpen (k_unsharp_plane's input; layout as mjg_debug_planes).
  * MJG_E_STATE for a context without a sharpen.  (With mjg_open_sharp.) */
 int mjg_debug_presharp(mjg_ctx *ctx, int frame, uint8_t *out, size_t cap);
+/* 1 and the context's sheet in *out (which may be NULL; nb_frames resolved: 0 has become cols rows)
+ * when it has one, 0 without (mjg_open_chain, a NULL or a trivial sheet), or a negative MJG_E_* code
+ * for a null context.  Host state only.  (With mjg_open_sheet.) */
+int mjg_debug_sheet(mjg_ctx *ctx, mjg_sheet *out);
+/* k_tile_plane's input frame `frame` of the last synced submit, an input frame of it: the cell, packed
+ * planar at dst size in the encoded chroma format, full range (under a sharpen the sharpened planes).
+ * Under a sheet mjg_debug_planes returns sheet `frame` instead.  MJG_E_STATE for a context without a
+ * sheet.  (With mjg_open_sheet.) */
+int mjg_debug_cell(mjg_ctx *ctx, int frame, uint8_t *out, size_t cap);
 /* 1 and the context's sizes and amounts in *out (which may be NULL) when it has a sharpen, 0
  * without one, or a negative MJG_E_* code for a null context.  Host state only.  (With
  * mjg_open_sharp.) */

@@ -1,0 +1,92 @@
+#!/usr/bin/env python3
+"""k_tile_plane's body on the CPU: builds tools/tile_host.hip (the kernel's __host__ __device__ body run over
+every (workgroup, thread) of its launches) with AddressSanitizer and UBSan on the host side, and compares
+its sheets with tests/tile_ref.py for every geometry of tests/test_gpu_tile.py (tile_ref.GPU_GEOMETRY) and
+a few more: cells of one sample, cells of exactly 16 and of 17 bytes a row, one column, one row, a margin
+wider than a piece, a padding of a piece and more, N = 1.  Each geometry runs with the buffers at three
+alignments (the pieces are cut on the sheet plane's alignment) and once with U and V in a launch each.
+Every buffer is allocated at exactly its size, so a load or store outside the frames stops the program.
+No GPU.
+
+usage: python3 tools/tile_host_check.py [--keep] [--csrc DIR]   (--csrc: scale.hip and kernels.hip from DIR, a
+changed copy of ffmpeg_distributed_amd/csrc: the recorded mutations of profiles/tile/mutations.txt)"""
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import tile_ref  # noqa: E402
+from ffmpeg_distributed_amd.encoder import i420_frame_bytes, split_i420  # noqa: E402
+
+SHIFTS = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}
+MORE = [
+    (1, 1, "444", (3, 2, 0, 0, 0), (7,)),
+    (2, 2, "420", (9, 1, 0, 2, 2), (9, 1)),
+    (16, 4, "444", (3, 2, 4, 0, 0), (9,)),
+    (17, 3, "444", (2, 3, 0, 1, 1), (5, 6)),
+    (32, 6, "422", (1, 4, 0, 0, 2), (3,)),
+    (20, 4, "444", (4, 1, 0, 19, 0), (4,)),
+    (24, 8, "420", (2, 2, 0, 32, 16), (3, 4, 1, 2)),
+    (48, 8, "420", (2, 2, 1, 0, 18), (3,)),
+    (300, 20, "444", (2, 3, 5, 7, 33), (11,)),
+]
+
+
+def main():
+    tmp = tempfile.mkdtemp(prefix="tile_host_")
+    exe = os.path.join(tmp, "tile_host")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    csrc = ([sys.argv[i + 1] for i, a in enumerate(sys.argv[:-1]) if a == "--csrc"]
+            or [os.path.join(ROOT, "ffmpeg_distributed_amd", "csrc")])[0]
+    subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
+                    "-Xarch_host", "-fno-omit-frame-pointer", "-Wno-pass-failed", "-I", os.path.join(ROOT, "include"),
+                    "-I", csrc, "-o", exe,
+                    os.path.join(ROOT, "tools", "tile_host.hip")], check=True)
+
+    def run(frames, w, h, c, sheet, segs, apart, shift):
+        hs, vs = SHIFTS[c]
+        cols, rows, N, margin, padding = tile_ref.resolve(sheet)
+        fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
+        frames.tofile(fin)
+        cmd = [exe, fin, fout] + [str(v) for v in (w, h, hs, vs, cols, rows, N, margin, padding)] + [
+            ",".join(str(v) for v in segs), str(apart), str(shift)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode:
+            sys.exit(f"tile_host failed ({r.returncode}) at {w}x{h} {c} sheet {sheet} segments {segs} apart {apart} "
+                     f"shift {shift}:\n" + r.stderr[-4000:])
+        return np.fromfile(fout, np.uint8)
+
+    rng = np.random.default_rng(17)
+    bad = 0
+    for (w, h, c, sheet, segs) in tile_ref.GPU_GEOMETRY + MORE:
+        n = sum(segs)
+        frames = rng.integers(1, 256, (n, i420_frame_bytes(w, h, c)), dtype=np.uint8)  # (no 0: a blank luma byte shows)
+        frames[:, w * h:][frames[:, w * h:] == 128] = 127                               # (nor a blank chroma byte)
+        want, at = [], 0
+        for k in segs:
+            cells = [split_i420(f, w, h, c) for f in frames[at:at + k]]
+            want += [tile_ref.pack(s) for s in tile_ref.sheets_numpy(cells, w, h, c, sheet)]
+            at += k
+        want = np.concatenate(want)
+        ok = []
+        for apart, shift in ((0, 0), (0, 1), (0, 9), (1, 0)):
+            got = run(frames, w, h, c, sheet, segs, apart, shift)
+            ok.append(got.size == want.size and bool((got == want).all()))
+        W, H = tile_ref.sheet_size(w, h, sheet)
+        print(f"{w}x{h} {c} sheet {sheet} -> {W}x{H}, segments {segs}: shift 0 {ok[0]}, 1 {ok[1]}, 9 {ok[2]}, U and V apart {ok[3]}")
+        bad += ok.count(False)
+    if "--keep" not in sys.argv:
+        for f in os.listdir(tmp):
+            os.unlink(os.path.join(tmp, f))
+        os.rmdir(tmp)
+    print("all equal" if not bad else f"{bad} mismatches")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
