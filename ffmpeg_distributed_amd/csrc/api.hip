@@ -150,9 +150,7 @@ int dmalloc(T **p, size_t count) {
   return MJG_OK;
 }
 
-// ceil(2^32 / d) for the kernels' divisions by multiply-high (div_magic), 0 when d is 1; and
-// ceil(2^40 / d) for k_encode's task index (EncGeom)
-uint32_t magic32(uint32_t d) { return d > 1 ? (uint32_t)((((uint64_t)1 << 32) + d - 1) / d) : 0u; }
+// ceil(2^40 / d) for k_encode's task index (EncGeom); scale.hip's magic32 is ceil(2^32 / d)
 unsigned long long magic40(unsigned long long d) { return (((unsigned long long)1 << 40) + d - 1) / d; }
 
 // mpegvideo_enc.c encode_picture FMT_MJPEG matrix + ff_convert_matrix (qscale -> 8); qmat may be null
@@ -1446,19 +1444,29 @@ int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
   return alloc_slot(c, c->slot[0]);
 }
 
+// open, steps 1 and 2 as one: the checks, the geometry and every stage's launches (no device, no
+// environment: unaligned_fetch is plan_geometry's).  A host program can call it on a `new mjg_ctx()`
+// and walk the launches the *_launch functions below make of the plan (tools/stage_host.hip).
+int plan_ctx(const mjg_config &k, const mjg_chain &chain, const mjg_sheet *sheet, bool unaligned_fetch, mjg_ctx *c,
+             Layout *lay) {
+  int rc;
+  if ((rc = check_config(k, chain, lay)) || (rc = check_sheet(k, sheet, lay))) return rc;
+  if ((rc = plan_geometry(k, chain.src_chroma_format, *lay, unaligned_fetch, c))) return rc;
+  plan_orient(k, *lay, c);
+  plan_deint(k, *lay, c);
+  plan_sharp(k, *lay, c);
+  plan_lut(k, *lay, c);
+  plan_cmat(*lay, c);
+  plan_tile(k, *lay, c);
+  return MJG_OK;
+}
+
 int open_ctx(int device, const mjg_config &k, const mjg_chain &chain, const mjg_sheet *sheet, mjg_ctx *c) {
   c->device = device;
   c->cfg = k;
   Layout lay;
   int rc;
-  if ((rc = check_config(k, chain, &lay)) || (rc = check_sheet(k, sheet, &lay))) return rc;
-  if ((rc = plan_geometry(k, chain.src_chroma_format, lay, env_int("MJG_UNALIGNED_FETCH", 1) != 0, c))) return rc;
-  plan_orient(k, lay, c);
-  plan_deint(k, lay, c);
-  plan_sharp(k, lay, c);
-  plan_lut(k, lay, c);
-  plan_cmat(lay, c);
-  plan_tile(k, lay, c);
+  if ((rc = plan_ctx(k, chain, sheet, env_int("MJG_UNALIGNED_FETCH", 1) != 0, c, &lay))) return rc;
   quant_matrix(k.qscale, c->mprime, c->qmat);
   c->hdr = build_header(c->geom.w, c->geom.h, c->mprime, k.sar_num, k.sar_den, (k.flags & MJG_F_COM_ITU601) != 0,
                         k.chroma_format, c->rst, &c->dht_pos, &c->dht_end);
@@ -1659,20 +1667,112 @@ namespace {
 // where slot "in"'s table stage and the colour matrix leave their frames: the buffer of the stage in front of them (in place), else d_lut
 uint8_t *lut_in_buf(const mjg_ctx *c, const Slot &S) { return c->orient ? S.d_orient : c->deint ? S.d_deint : S.d_lut; }
 
-// One table stage of a submit: luma, then U and V in one launch (V's blocks behind U's) when uv1 (2n fits
-// the grid, as for the other plane stages), else one launch each.  in_place: dst holds the frames
-// already, so a launch whose planes all have the identity table is left out; otherwise it copies
-// them.  cplane: bytes from the U to the V plane.
-void launch_lut(const mjg_ctx *c, const Slot &S, int slot, const SegList &in, uint8_t *dst, int n, bool uv1,
-                bool in_place, long long cplane) {
-  for (int p = 0; p < (uv1 ? 2 : 3); p++) {
-    LutGeom g = c->lpass[slot][p ? 1 : 0];
-    g.nf = n;
-    if (p && uv1) g.s_poff = g.d_poff = cplane;
-    if (p == 2) g.s_off += cplane, g.d_off += cplane, g.tab = 2;
-    const int tabs = p && uv1 ? 6 : 1 << g.tab;  // the launch's tables, as bits of g.ident
-    if (in_place && (g.ident & tabs) == tabs) continue;
-    k_lut_plane<<<g.gxy * (p && uv1 ? 2 * n : n), kCopyThreads, 0, S.st>>>(in, dst, c->d_luts + slot * sizeof(mjg_lut), g);
+// The per-submit geometry: what a submit adds to the plan of open (plan_ctx).  No HIP call, so the
+// host checks walk these very launches (tools/stage_host.hip).  A plane stage launches luma (p = 0),
+// then U and V: in one launch (p = 1; V's blocks behind U's, reached through poff) while uv1, else
+// in one each (p = 1 and 2; V alone moves off).  uv1 is uv_paired(frames): 2n fits the grid's z
+// range.  Launch p has gxy * uv_nz(p, uv1, frames) workgroups.
+constexpr bool uv_paired(int n) { return 2 * n <= 65535; }
+static_assert(uv_paired(32767) && !uv_paired(32768), "submit_impl's three `uv1` locals state 65535 (tests/chain_geom.py)");
+int uv_launches(bool uv1) { return uv1 ? 2 : 3; }
+int uv_nz(int p, bool uv1, int n) { return p && uv1 ? 2 * n : n; }
+// off, poff: one side's fields of the chroma plan's geom; cplane: bytes from the U to the V plane there
+void uv_place(int p, bool uv1, long long cplane, long long &off, long long &poff) {
+  if (p && uv1) poff = cplane;
+  if (p == 2) off += cplane;
+}
+
+// frames of segment k of a submit of n: up to the next segment's first, or n (an unused one: 0)
+int seg_count(const SegList &in, int k, int n) {
+  if (in.f0[k] == INT_MAX) return 0;
+  return (k + 1 < kMaxSegs && in.f0[k + 1] != INT_MAX ? in.f0[k + 1] : n) - in.f0[k];
+}
+
+// each segment is a sequence of its own: its frames [0, count), widened by the halo frames
+DeintGeom deint_launch(const mjg_ctx *c, int p, bool uv1, int n, const SegList &in, int halo) {
+  DeintGeom g = c->dpass[p ? 1 : 0].g;
+  g.nf = n;
+  for (int k = 0; k < kMaxSegs; k++) {
+    g.lo[k] = -(halo & 1);
+    g.hi[k] = in.f0[k] == INT_MAX ? 0 : seg_count(in, k, n) - 1 + ((halo >> 1) & 1);
+  }
+  uv_place(p, uv1, c->src_cplane, g.off, g.poff);
+  return g;
+}
+
+OrientGeom orient_launch(const mjg_ctx *c, int p, bool uv1, int n) {
+  OrientGeom g = c->opass[p ? 1 : 0].g;
+  g.nf = n;
+  uv_place(p, uv1, c->src_cplane, g.s_off, g.s_poff);
+  uv_place(p, uv1, c->src_cplane, g.d_off, g.d_poff);
+  return g;
+}
+
+// One launch of a table stage (slot 0 "in": source planes; 1 "out": the picture's).  in_place: dst
+// holds the frames already, so a launch whose planes all have the identity table is left out
+// (false); otherwise it copies them.
+bool lut_launch(const mjg_ctx *c, int slot, int p, bool uv1, int n, bool in_place, LutGeom *out) {
+  LutGeom &g = *out = c->lpass[slot][p ? 1 : 0];
+  g.nf = n;
+  const long long cplane = slot ? c->pic_cplane : c->src_cplane;
+  uv_place(p, uv1, cplane, g.s_off, g.s_poff);
+  uv_place(p, uv1, cplane, g.d_off, g.d_poff);
+  if (p == 2) g.tab = 2;
+  const int tabs = p && uv1 ? 6 : 1 << g.tab;  // the launch's tables, as bits of g.ident
+  return !(in_place && (g.ident & tabs) == tabs);
+}
+
+ScaleGeom scale_launch(const mjg_ctx *c, const Pass &ps, int p, bool uv1, int n) {
+  ScaleGeom g = ps.g;
+  g.nf = n;
+  uv_place(p, uv1, c->src_cplane, g.s_off, g.s_poff);
+  uv_place(p, uv1, c->pic_cplane, g.d_off, g.d_poff);
+  return g;
+}
+
+SharpGeom sharp_launch(const mjg_ctx *c, int p, bool uv1, int n) {
+  SharpGeom g = c->shpass[p ? 1 : 0].g;
+  g.nf = n;
+  uv_place(p, uv1, c->pic_cplane, g.off, g.poff);
+  return g;
+}
+
+// The frames k_encode codes: the n input frames, or under a sheet ceil(count / N) sheets for each
+// segment, a sequence of its own (TileGeom's per-segment fields)
+struct SheetSplit {
+  int m, sheet0[kMaxSegs], first[kMaxSegs], count[kMaxSegs];
+};
+SheetSplit sheet_split(const mjg_ctx *c, const SegList &in, int n) {
+  SheetSplit s{};
+  s.m = n;
+  if (!c->sheet) return s;
+  s.m = 0;
+  for (int k = 0; k < kMaxSegs; k++) {
+    const bool used = in.f0[k] != INT_MAX;
+    s.sheet0[k] = used ? s.m : INT_MAX;
+    s.first[k] = used ? in.f0[k] : 0;
+    s.count[k] = seg_count(in, k, n);
+    s.m += (s.count[k] + c->sh.nb_frames - 1) / c->sh.nb_frames;
+  }
+  return s;
+}
+
+// the cells of each segment onto its sheets (uv1 is of the s.m sheets)
+TileGeom tile_launch(const mjg_ctx *c, int p, bool uv1, const SheetSplit &s) {
+  TileGeom g = c->tpass[p ? 1 : 0];
+  g.ns = s.m;
+  for (int k = 0; k < kMaxSegs; k++) g.sheet0[k] = s.sheet0[k], g.first[k] = s.first[k], g.count[k] = s.count[k];
+  uv_place(p, uv1, c->pic_cplane, g.s_off, g.s_poff);
+  uv_place(p, uv1, (long long)c->geom.cw * c->geom.ch, g.d_off, g.d_poff);
+  return g;
+}
+
+// One table stage of a submit
+void launch_lut(const mjg_ctx *c, const Slot &S, int slot, const SegList &in, uint8_t *dst, int n, bool uv1, bool in_place) {
+  for (int p = 0; p < uv_launches(uv1); p++) {
+    LutGeom g;
+    if (!lut_launch(c, slot, p, uv1, n, in_place, &g)) continue;
+    k_lut_plane<<<g.gxy * uv_nz(p, uv1, n), kCopyThreads, 0, S.st>>>(in, dst, c->d_luts + slot * sizeof(mjg_lut), g);
   }
 }
 
@@ -1703,48 +1803,20 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
   }
   src += (size_t)hp * c->in_frame_bytes;  // the first encoded frame
   SegList in_sl = segs ? *segs : one_seg(src);  // the submit's input frames: the caller's segments, or one at src
-  // the frames k_encode codes: the n input frames, or under a sheet ceil(count / N) sheets for each
-  // segment, a sequence of its own (TileGeom's per-segment fields)
-  int m = n, seg_sheet0[kMaxSegs] = {}, seg_first[kMaxSegs] = {}, seg_count[kMaxSegs] = {};
-  if (c->sheet) {
-    m = 0;
-    for (int k = 0; k < kMaxSegs; k++) {
-      const bool used = in_sl.f0[k] != INT_MAX;
-      const int end = k + 1 < kMaxSegs && in_sl.f0[k + 1] != INT_MAX ? in_sl.f0[k + 1] : n;
-      seg_sheet0[k] = used ? m : INT_MAX;
-      seg_first[k] = used ? in_sl.f0[k] : 0;
-      seg_count[k] = used ? end - in_sl.f0[k] : 0;
-      if (used) m += (seg_count[k] + c->sh.nb_frames - 1) / c->sh.nb_frames;
-    }
-  }
+  const SheetSplit sheets = sheet_split(c, in_sl, n);
+  const int m = sheets.m;  // the frames k_encode codes
   if (c->scale || c->orient || c->deint || c->has_lut[0] || c->has_cmat) tmark(c, S, MJG_K_SCALE, 0);
-  if (c->deint) {  // in front of everything: luma, then U and V in one launch; the rest reads one buffer
+  if (c->deint) {  // in front of everything; the rest reads one buffer
     const bool uv1 = 2 * n <= 65535;
-    for (int p = 0; p < (uv1 ? 2 : 3); p++) {
-      DeintGeom dg = c->dpass[p ? 1 : 0].g;
-      dg.nf = n;
-      // each segment is a sequence of its own: its frames [0, count), widened by the halo frames
-      for (int k = 0; k < kMaxSegs; k++) {
-        const int end = k + 1 < kMaxSegs && in_sl.f0[k + 1] != INT_MAX ? in_sl.f0[k + 1] : n;
-        dg.lo[k] = -hp;
-        dg.hi[k] = in_sl.f0[k] == INT_MAX ? 0 : end - in_sl.f0[k] - 1 + hn;
-      }
-      if (p && uv1) dg.poff = c->src_cplane;
-      if (p == 2) dg.off += c->src_cplane;
-      c->dpass[p ? 1 : 0].launch(dg, in_sl, S.d_deint, p && uv1 ? 2 * n : n, S.st);
-    }
+    for (int p = 0; p < uv_launches(uv1); p++)
+      c->dpass[p ? 1 : 0].launch(deint_launch(c, p, uv1, n, in_sl, halo), in_sl, S.d_deint, uv_nz(p, uv1, n), S.st);
     HIP_TRY(hipGetLastError());
     in_sl = one_seg(S.d_deint);
   }
-  if (c->orient) {  // the first filter: luma, then U and V in one launch as below; the rest reads one buffer
+  if (c->orient) {  // the first filter; the rest reads one buffer
     const bool uv1 = 2 * n <= 65535;
-    for (int p = 0; p < (uv1 ? 2 : 3); p++) {
-      OrientGeom og = c->opass[p ? 1 : 0].g;
-      og.nf = n;
-      if (p && uv1) og.s_poff = og.d_poff = c->src_cplane;
-      if (p == 2) og.s_off += c->src_cplane, og.d_off += c->src_cplane;
-      c->opass[p ? 1 : 0].launch(og, in_sl, S.d_orient, p && uv1 ? 2 * n : n, S.st);
-    }
+    for (int p = 0; p < uv_launches(uv1); p++)
+      c->opass[p ? 1 : 0].launch(orient_launch(c, p, uv1, n), in_sl, S.d_orient, uv_nz(p, uv1, n), S.st);
     HIP_TRY(hipGetLastError());
     in_sl = one_seg(S.d_orient);
   }
@@ -1757,55 +1829,29 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
   }
   if (c->has_lut[0]) {  // behind the colour matrix: in place in the buffer in front, else the caller's frames -> d_lut
     uint8_t *buf = lut_in_buf(c, S);
-    launch_lut(c, S, 0, in_sl, buf, n, 2 * n <= 65535, buf != S.d_lut || c->has_cmat, c->src_cplane);
+    launch_lut(c, S, 0, in_sl, buf, n, uv_paired(n), buf != S.d_lut || c->has_cmat);
     HIP_TRY(hipGetLastError());
     in_sl = one_seg(buf);
   }
   SegList enc_in = in_sl;
   if (c->scale) {
-    // luma, then U and V in one launch (same filters; blockIdx.z >= n is V) while 2n fits the
-    // grid's z range, else one launch each
     const bool uv1 = 2 * n <= 65535;
-    const long long d_cplane = c->pic_cplane;
-    for (int p = 0; p < (uv1 ? 2 : 3); p++) {
-      for (const Pass &ps : c->pass[p ? 1 : 0]) {
-        if (!ps.launch) continue;
-        ScaleGeom sg = ps.g;
-        sg.nf = n;
-        if (p && uv1) {
-          sg.s_poff = c->src_cplane;
-          sg.d_poff = d_cplane;
-        }
-        if (p == 2) {  // V on its own
-          sg.s_off += c->src_cplane;
-          sg.d_off += d_cplane;
-        }
-        ps.launch(ps, sg, in_sl, S.d_scaled, p && uv1 ? 2 * n : n, S.st);
-      }
-    }
+    for (int p = 0; p < uv_launches(uv1); p++)  // (U and V: the same filters)
+      for (const Pass &ps : c->pass[p ? 1 : 0])
+        if (ps.launch) ps.launch(ps, scale_launch(c, ps, p, uv1, n), in_sl, S.d_scaled, uv_nz(p, uv1, n), S.st);
     // a table on the picture, in place: behind every sws pass, in front of the sharpen
-    if (c->has_lut[1]) launch_lut(c, S, 1, one_seg(S.d_scaled), S.d_scaled, n, uv1, true, d_cplane);
+    if (c->has_lut[1]) launch_lut(c, S, 1, one_seg(S.d_scaled), S.d_scaled, n, uv1, true);
     const uint8_t *enc_buf = S.d_scaled;
-    if (c->sharp) {  // behind the sws stage's passes (the pad's border among them): luma, then U and V as above
-      for (int p = 0; p < (uv1 ? 2 : 3); p++) {
-        SharpGeom hg = c->shpass[p ? 1 : 0].g;
-        hg.nf = n;
-        if (p && uv1) hg.poff = d_cplane;
-        if (p == 2) hg.off += d_cplane;
-        c->shpass[p ? 1 : 0].launch(hg, S.d_scaled, S.d_sharp, p && uv1 ? 2 * n : n, S.st);
-      }
+    if (c->sharp) {  // behind the sws stage's passes (the pad's border among them)
+      for (int p = 0; p < uv_launches(uv1); p++)
+        c->shpass[p ? 1 : 0].launch(sharp_launch(c, p, uv1, n), S.d_scaled, S.d_sharp, uv_nz(p, uv1, n), S.st);
       enc_buf = S.d_sharp;
     }
-    if (c->sheet) {  // behind the sharpen: the cells of each segment onto its sheets; luma, then U and V as above
-      const bool tuv1 = 2 * m <= 65535;
-      const long long t_cplane = (long long)g.cw * g.ch;
-      for (int p = 0; p < (tuv1 ? 2 : 3); p++) {
-        TileGeom tg = c->tpass[p ? 1 : 0];
-        tg.ns = m;
-        for (int k = 0; k < kMaxSegs; k++) tg.sheet0[k] = seg_sheet0[k], tg.first[k] = seg_first[k], tg.count[k] = seg_count[k];
-        if (p && tuv1) tg.s_poff = d_cplane, tg.d_poff = t_cplane;
-        if (p == 2) tg.s_off += d_cplane, tg.d_off += t_cplane;
-        k_tile_plane<<<tg.gxy * (p && tuv1 ? 2 * m : m), kCopyThreads, 0, S.st>>>(enc_buf, S.d_tile, tg);
+    if (c->sheet) {  // behind the sharpen: the cells of each segment onto its sheets
+      const bool tuv1 = uv_paired(m);
+      for (int p = 0; p < uv_launches(tuv1); p++) {
+        const TileGeom tg = tile_launch(c, p, tuv1, sheets);
+        k_tile_plane<<<tg.gxy * uv_nz(p, tuv1, m), kCopyThreads, 0, S.st>>>(enc_buf, S.d_tile, tg);
       }
       enc_buf = S.d_tile;
     }

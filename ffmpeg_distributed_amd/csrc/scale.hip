@@ -83,6 +83,8 @@ __device__ __forceinline__ int div_magic(int t, uint32_t magic, int d) {
   const int q = (int)__umulhi((uint32_t)t, magic);
   return q * d > t ? q - 1 : q;
 }
+// ... and that m for the geoms' *_magic fields (host)
+inline uint32_t magic32(uint32_t d) { return d > 1 ? (uint32_t)((((uint64_t)1 << 32) + d - 1) / d) : 0u; }
 
 __device__ __forceinline__ int sws_range(int v, int range) {
   if (range == 1) {  // |v| < 2^15: the 24-bit multiply is exact
@@ -1284,7 +1286,7 @@ __global__ __launch_bounds__(kDeintThreads) void k_yadif_plane(const SegList src
 // is every other size.  LDS: at most 3,672 bytes of samples and 54 x 64 dwords of row sums, 17.5 KB
 // (<5, 5>: 11.7 KB), so eight workgroups fit a CU.  U and V share a launch (blockIdx >= gxy * nf is
 // V).  The address arithmetic and the three steps are __host__ __device__ functions:
-// tools/unsharp_host.hip walks every (workgroup, thread, iteration) of a launch on the CPU.
+// tools/stage_host.hip walks every (workgroup, thread, iteration) of a launch on the CPU.
 constexpr int kSharpTileW = 64;
 constexpr int kSharpTileH = 32;
 constexpr int kSharpThreads = 256;
@@ -1326,16 +1328,15 @@ __host__ __device__ constexpr int sharp_lds_sums(int my) {
 // The geometry of one plane's launch (host; submit adds nf and the U + V pairing)
 inline SharpGeom sharp_geom(int cw, int ch, int px, int py, int w, int h, long long off, long long fstride, int mx,
                             int my, int amount) {
-  auto magic = [](uint32_t d) { return d > 1 ? (uint32_t)((((uint64_t)1 << 32) + d - 1) / d) : 0u; };
   SharpGeom g{};
   g.cw = cw, g.ch = ch, g.px = px, g.py = py, g.w = w, g.h = h;
   g.off = off, g.fstride = fstride;
   g.sx = mx / 2, g.sy = my / 2, g.amount = amount;
   g.tx = (cw + kSharpTileW - 1) / kSharpTileW;
   g.gxy = g.tx * ((ch + kSharpTileH - 1) / kSharpTileH);
-  g.tx_magic = magic((uint32_t)g.tx);
-  g.gxy_magic = magic((uint32_t)g.gxy);
-  g.nq_magic = magic((uint32_t)(sharp_pitch(g.sx) / 4));
+  g.tx_magic = magic32((uint32_t)g.tx);
+  g.gxy_magic = magic32((uint32_t)g.gxy);
+  g.nq_magic = magic32((uint32_t)(sharp_pitch(g.sx) / 4));
   for (int d = 0; d < 2; d++) {  // a row of Pascal's triangle by pair sums, as the filter's own cascade
     uint32_t *b = d ? g.by : g.bx;
     const int n = 2 * (d ? g.sy : g.sx);
@@ -1563,7 +1564,7 @@ __global__ __launch_bounds__(kSharpThreads) void k_unsharp_plane(const uint8_t *
 // identity (g.ident) is copied without the lookups, or left alone when dst is src.  The LDS reads
 // are k_plane_copy<RANGE>'s: byte reads at data-dependent addresses of a 256-byte table, 64 banks of
 // one dword, so a wave's conflicts are those of 64 random draws from 64 banks.
-// The body is a __host__ __device__ function, as yadif_work is, for tools/lut_host.hip.
+// The body is a __host__ __device__ function, as yadif_work is, for tools/stage_host.hip.
 struct LutGeom {
   int w, h;                    // the rectangle
   int s_stride, d_stride;      // its row strides
@@ -1683,7 +1684,7 @@ __global__ __launch_bounds__(kCopyThreads) void k_lut_plane(const SegList src, u
 // whose gxy x frames would pass 2^31 - 1.
 // Sums: |coefficient| <= 2^18 (mjg_open_cmat) and |u|, |v| <= 128, so |yu u + yv v| <= 2^26 and every
 // sum is below 2^26 + 2^24 in magnitude: int32 holds it, and k fits an int16.
-// The body is a __host__ __device__ function, as lut_work is, for tools/cmat_host.hip.
+// The body is a __host__ __device__ function, as lut_work is, for tools/stage_host.hip.
 struct CmatCoef { int yu, yv, uu, uv, vu, vv; };
 struct CmatGeom {
   int w, h;                    // the luma plane
@@ -1849,7 +1850,7 @@ __global__ __launch_bounds__(kCmatThreads) void k_cmat_frame(const SegList src, 
 // plane of one of the nf cell frames.  No address is formed for a blank cell.  A store is an aligned
 // piece inside [head, head + 16 nv) or a byte i < W H of the sheet plane at d_off (+ d_poff) of sheet
 // s < ns (the grid has gxy workgroups for each of them and no more), so every store lies inside it.
-// The body is a __host__ __device__ function, as yadif_work is, for tools/tile_host.hip.
+// The body is a __host__ __device__ function, as yadif_work is, for tools/stage_host.hip.
 struct TileGeom {
   int w, h;                 // the cell plane
   int W, H;                 // the sheet plane

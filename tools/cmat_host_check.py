@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""k_cmat_frame's body on the CPU: builds tools/cmat_host.hip (the kernel's __host__ __device__ body run
-over every (workgroup, thread) of its launch) with AddressSanitizer and UBSan on the host side, and
+"""k_cmat_frame's body on the CPU: tools/stage_host.hip's cmat (the kernel's __host__ __device__ body run
+over every (workgroup, thread) of the launch api.hip plans: host_check.py) with AddressSanitizer and UBSan on the host side, and
 compares its output with tests/colormatrix_ref.py for every shape of tests/test_gpu_colormatrix.py and a
 few smaller ones: three frames into a second buffer, in place, and five frames as segments of 1 + 3 + 1
 and 1 + 1 + 2 + 1 in allocations of their own, each one byte in; with bt709 -> bt601, bt601 -> bt709 and
@@ -8,16 +8,12 @@ the made-up matrix whose six coefficients all differ.  One plane of every case i
 235..255}, so both clips occur.  Every buffer is allocated at exactly its size, so a load or store
 outside a frame stops the program.  No GPU.
 
-usage: python3 tools/cmat_host_check.py [--keep]"""
-import os
-import subprocess
+usage: python3 tools/cmat_host_check.py [--keep] [--csrc DIR]"""
 import sys
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from host_check import run_check, split_arg
 import colormatrix_ref as ref  # noqa: E402
 
 # tests/test_gpu_colormatrix.py's frames (203x301: 301x203 behind a transpose; 40x24: the worker's), and smaller ones
@@ -30,25 +26,13 @@ MATRICES = [("bt709->bt601", ref.coefs("bt709", "bt601")), ("bt601->bt709", ref.
             ("made up", ref.MADE_UP)]
 
 
-def main():
-    tmp = tempfile.mkdtemp(prefix="cmat_host_")
-    exe = os.path.join(tmp, "cmat_host")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
-                    "-Xarch_host", "-fno-omit-frame-pointer", "-Wno-pass-failed", "-I", os.path.join(ROOT, "include"),
-                    "-I", os.path.join(ROOT, "ffmpeg_distributed_amd", "csrc"), "-o", exe,
-                    os.path.join(ROOT, "tools", "cmat_host.hip")], check=True)
-
+def check(host, args):
     def run(frames, c, w, h, fmt, split=0, inplace=0):
-        hs, vs = ref.SHIFTS[fmt]
-        fin, fout = (os.path.join(tmp, nm) for nm in ("in.bin", "out.bin"))
+        fin, fout = host.path("in.bin"), host.path("out.bin")
         frames.tofile(fin)
         n = frames.shape[0]
-        cmd = [exe, fin, fout, str(w), str(h), str(hs), str(vs), str(n),
-               ",".join(str(v) for v in split) if split else "0", str(inplace)] + [str(v) for v in c]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode:
-            sys.exit(f"cmat_host failed ({r.returncode}) at {w}x{h} {fmt} split {split} inplace {inplace}:\n" + r.stderr[-4000:])
+        host.run("cmat", [fin, fout, w, h, *ref.SHIFTS[fmt], n, split_arg(split), inplace, *c],
+                 f"{w}x{h} {fmt} split {split} inplace {inplace}")
         return np.fromfile(fout, np.uint8).reshape(n, -1)
 
     bad = 0
@@ -63,13 +47,8 @@ def main():
             line.append(f"{name}: copy {ok[0]} in place {ok[1]} 1+3+1 {ok[2]} 1+1+2+1 {ok[3]} (clipped {lo} low, {hi} high)")
             bad += ok.count(False)
         print(f"{w}x{h} {fmt}: " + ", ".join(line), flush=True)
-    if "--keep" not in sys.argv:
-        for f in os.listdir(tmp):
-            os.unlink(os.path.join(tmp, f))
-        os.rmdir(tmp)
-    print("all equal" if not bad else f"{bad} mismatches")
-    return 1 if bad else 0
+    return bad
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(run_check(check))

@@ -1,4 +1,4 @@
-// Host-side check of the open path's device-free steps (check_config, plan_geometry, plan_orient)
+// Host-side check of the open path's device-free steps (check_config, and plan_ctx for what it accepts)
 // for the eight orientations of the test shapes, meant for a sanitizer build on a machine without
 // a GPU: no HIP call is made.  Every geometry is checked against the sizes computed here: the
 // frame byte count, the plane offsets and strides of the oriented frame, and that each orientation
@@ -46,8 +46,7 @@ int main() {
         expect(check_config(k, c2, &l2) == MJG_E_INVALID, "crop of the source size", s.w, s.h, s.cf, orient);
       }
       mjg_ctx *c = new mjg_ctx();
-      expect(plan_geometry(k, s.cf, lay, true, c) == MJG_OK, "plan_geometry", s.w, s.h, s.cf, orient);
-      plan_orient(k, lay, c);
+      expect(plan_ctx(k, chain, nullptr, true, c, &lay) == MJG_OK, "plan_ctx", s.w, s.h, s.cf, orient);
       const int hs = s.cf == MJG_CHROMA_444 ? 0 : 1, vs = s.cf == MJG_CHROMA_420 ? 1 : 0;
       const int cw = (s.w + hs) >> hs, ch = (s.h + vs) >> vs;
       const int ocw = (ow + hs) >> hs, och = (oh + vs) >> vs;

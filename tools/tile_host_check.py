@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""k_tile_plane's body on the CPU: builds tools/tile_host.hip (the kernel's __host__ __device__ body run over
-every (workgroup, thread) of its launches) with AddressSanitizer and UBSan on the host side, and compares
+"""k_tile_plane's body on the CPU: tools/stage_host.hip's tile (the kernel's __host__ __device__ body run over
+every (workgroup, thread) of the launches api.hip plans: host_check.py) with AddressSanitizer and UBSan on the host side, and compares
 its sheets with tests/tile_ref.py for every geometry of tests/test_gpu_tile.py (tile_ref.GPU_GEOMETRY) and
 a few more: cells of one sample, cells of exactly 16 and of 17 bytes a row, one column, one row, a margin
 wider than a piece, a padding of a piece and more, N = 1.  Each geometry runs with the buffers at three
@@ -8,22 +8,16 @@ alignments (the pieces are cut on the sheet plane's alignment) and once with U a
 Every buffer is allocated at exactly its size, so a load or store outside the frames stops the program.
 No GPU.
 
-usage: python3 tools/tile_host_check.py [--keep] [--csrc DIR]   (--csrc: scale.hip and kernels.hip from DIR, a
-changed copy of ffmpeg_distributed_amd/csrc: the recorded mutations of profiles/tile/mutations.txt)"""
-import os
-import subprocess
+usage: python3 tools/tile_host_check.py [--keep] [--csrc DIR]   (--csrc: the sources from DIR, a changed
+copy of ffmpeg_distributed_amd/csrc: the recorded mutations of profiles/tile/mutations.txt)"""
 import sys
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from host_check import SHIFTS, run_check, split_arg
 import tile_ref  # noqa: E402
 from ffmpeg_distributed_amd.encoder import i420_frame_bytes, split_i420  # noqa: E402
 
-SHIFTS = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}
 MORE = [
     (1, 1, "444", (3, 2, 0, 0, 0), (7,)),
     (2, 2, "420", (9, 1, 0, 2, 2), (9, 1)),
@@ -37,28 +31,12 @@ MORE = [
 ]
 
 
-def main():
-    tmp = tempfile.mkdtemp(prefix="tile_host_")
-    exe = os.path.join(tmp, "tile_host")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    csrc = ([sys.argv[i + 1] for i, a in enumerate(sys.argv[:-1]) if a == "--csrc"]
-            or [os.path.join(ROOT, "ffmpeg_distributed_amd", "csrc")])[0]
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
-                    "-Xarch_host", "-fno-omit-frame-pointer", "-Wno-pass-failed", "-I", os.path.join(ROOT, "include"),
-                    "-I", csrc, "-o", exe,
-                    os.path.join(ROOT, "tools", "tile_host.hip")], check=True)
-
+def check(host, args):
     def run(frames, w, h, c, sheet, segs, apart, shift):
-        hs, vs = SHIFTS[c]
-        cols, rows, N, margin, padding = tile_ref.resolve(sheet)
-        fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
+        fin, fout = host.path("in.bin"), host.path("out.bin")
         frames.tofile(fin)
-        cmd = [exe, fin, fout] + [str(v) for v in (w, h, hs, vs, cols, rows, N, margin, padding)] + [
-            ",".join(str(v) for v in segs), str(apart), str(shift)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode:
-            sys.exit(f"tile_host failed ({r.returncode}) at {w}x{h} {c} sheet {sheet} segments {segs} apart {apart} "
-                     f"shift {shift}:\n" + r.stderr[-4000:])
+        host.run("tile", [fin, fout, w, h, *SHIFTS[c], *tile_ref.resolve(sheet), split_arg(segs), apart, shift],
+                 f"{w}x{h} {c} sheet {sheet} segments {segs} apart {apart} shift {shift}")
         return np.fromfile(fout, np.uint8)
 
     rng = np.random.default_rng(17)
@@ -80,13 +58,8 @@ def main():
         W, H = tile_ref.sheet_size(w, h, sheet)
         print(f"{w}x{h} {c} sheet {sheet} -> {W}x{H}, segments {segs}: shift 0 {ok[0]}, 1 {ok[1]}, 9 {ok[2]}, U and V apart {ok[3]}")
         bad += ok.count(False)
-    if "--keep" not in sys.argv:
-        for f in os.listdir(tmp):
-            os.unlink(os.path.join(tmp, f))
-        os.rmdir(tmp)
-    print("all equal" if not bad else f"{bad} mismatches")
-    return 1 if bad else 0
+    return bad
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(run_check(check))

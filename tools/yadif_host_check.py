@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""k_yadif_plane's body on the CPU: builds tools/yadif_host.hip (the kernel's __host__ __device__ body
-run over every (workgroup, thread) of its launches) with AddressSanitizer and UBSan on the host
+"""k_yadif_plane's body on the CPU: tools/stage_host.hip's yadif (the kernel's __host__ __device__ body
+run over every (workgroup, thread) of the launches api.hip plans: host_check.py) with AddressSanitizer and UBSan on the host
 side, and compares its output with tests/yadif_ref.py for every shape of the GPU tests and a few
 smaller ones, both parities, both modes: one submit of 5 frames, the same frames as halo submits of
 2 + 2 + 1, and as segments of their own in one launch: 3 + 2, 1 + 3 + 1 (a one-frame segment
@@ -15,51 +15,32 @@ frames, where U and V get a launch each (poff 0, off advanced by the chroma plan
 segments of 38,000 with a boundary at frame 32,767; the frames cycle through 61 base frames as in
 that file, so the reference is made once per distinct (prev, cur, next).  No GPU.
 
-usage: python3 tools/yadif_host_check.py [--keep] [--sweep | --long]"""
-import os
-import subprocess
+usage: python3 tools/yadif_host_check.py [--keep] [--csrc DIR] [--sweep | --long]"""
 import sys
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from host_check import SHIFTS, run_check, split_arg
 from yadif_ref import deint_frame, deint_frames  # noqa: E402
 from ffmpeg_distributed_amd.encoder import i420_frame_bytes  # noqa: E402
 
-SHIFTS = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}
 SHAPES = [(130, 66, "420"), (131, 67, "420"), (130, 66, "422"), (33, 17, "444"), (6, 6, "420"), (20, 8, "444"),
           (4100, 5, "444"), (3, 3, "444"), (16, 3, "444"), (19, 4, "444"), (40, 7, "420"),
           (256, 160, "420"), (256, 160, "444"), (130, 66, "444"), (301, 203, "420")]      # tests/test_gpu_filter_chain.py
 SPLITS = [(3, 2), (1, 3, 1), (1, 1, 2, 1)]
 
 
-def main():
-    tmp = tempfile.mkdtemp(prefix="yadif_host_")
-    exe = os.path.join(tmp, "yadif_host")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
-                    "-Xarch_host", "-fno-omit-frame-pointer", "-Wno-pass-failed", "-I", os.path.join(ROOT, "include"),
-                    "-I", os.path.join(ROOT, "ffmpeg_distributed_amd", "csrc"), "-o", exe,
-                    os.path.join(ROOT, "tools", "yadif_host.hip")], check=True)
-
+def check(host, args):
     def run(frames, w, h, c, mode, tff, n, halo, split, apart=0):
-        hs, vs = SHIFTS[c]
-        fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
+        fin, fout = host.path("in.bin"), host.path("out.bin")
         frames.tofile(fin)
-        r = subprocess.run([exe, fin, fout, str(w), str(h), str(hs), str(vs), str(1 if mode == 2 else 0), str(tff ^ 1),
-                            str(n), str(halo), ",".join(str(v) for v in split) if split else "0", str(apart)],
-                           capture_output=True, text=True)
-        if r.returncode:
-            sys.exit(f"yadif_host failed ({r.returncode}) at {w}x{h} {c} mode {mode} tff {tff} halo {halo} split {split}:\n"
-                     + r.stderr[-4000:])
+        host.run("yadif", [fin, fout, w, h, *SHIFTS[c], 1 if mode == 2 else 0, tff ^ 1, n, halo, split_arg(split), apart],
+                 f"{w}x{h} {c} mode {mode} tff {tff} halo {halo} split {split}")
         return np.fromfile(fout, np.uint8).reshape(n, -1)
 
     rng = np.random.default_rng(5)
     bad = 0
-    if "--long" in sys.argv:
+    if "--long" in args:
         import chain_geom as cg
 
         def want_of(base, idx, seqs, w, h, c, mode, tff):      # seqs: (first, count) of each sequence in the buffer
@@ -93,7 +74,7 @@ def main():
             print(f"{w}x{h} {c} U, V apart: one submit of {n} (mode 0 tff) {ok[0]}, halo 3 of {n} out of {n + 2} (mode 2 tff) {ok[1]}, "
                   f"segments {'+'.join(map(str, lens))} {ok[2]}, 5 frames bff forced apart {ok[3]}")
             bad += ok.count(False)
-    if "--sweep" in sys.argv:
+    if "--sweep" in args:
         import chain_geom as cg
         seen = set()
         for k in cg.filter_sweep_configs(cg.FILTER_SWEEP_SEED, 120):
@@ -110,7 +91,7 @@ def main():
             ok = [(one == deint_frames(frames, w, h, c, mode, tff)).all(), (segs == want_segs).all()]
             print(f"{w}x{h} {c} {k.deint}: one submit {ok[0]}, segments 2+1 {ok[1]}")
             bad += ok.count(False)
-    for (w, h, c) in ([] if "--sweep" in sys.argv or "--long" in sys.argv else SHAPES):
+    for (w, h, c) in ([] if "--sweep" in args or "--long" in args else SHAPES):
         fb = i420_frame_bytes(w, h, c)
         frames = rng.integers(0, 256, (5, fb), dtype=np.uint8)
         frames[3] = (np.arange(fb) * 3 % 256).astype(np.uint8)
@@ -129,13 +110,8 @@ def main():
                 print(f"{w}x{h} {c} {'tff' if tff else 'bff'} mode {mode}: one submit {ok[0]}, halo 2+2+1 {ok[1]}, "
                       + ", ".join(f"segments {'+'.join(map(str, sp))} {o}" for sp, o in zip(SPLITS, ok[2:])))
                 bad += ok.count(False)
-    if "--keep" not in sys.argv:
-        for f in os.listdir(tmp):
-            os.unlink(os.path.join(tmp, f))
-        os.rmdir(tmp)
-    print("all equal" if not bad else f"{bad} mismatches")
-    return 1 if bad else 0
+    return bad
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(run_check(check))
