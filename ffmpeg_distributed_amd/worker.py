@@ -34,7 +34,7 @@ plane below 3 x 3, go to the real ffmpeg, which is told the source's field order
 Every output frame reads the frame before and the frame after it, so with a deinterlacer the
 page-locked batches hold two more frames, the reader keeps one frame of look-ahead and copies the
 previous batch's last frame and its look-ahead frame to the head of the next (deint_step is the
-schedule; run()'s deint_reader follows it), and each batch is a halo submit (encoder.submit(halo=)).
+schedule; Pipeline.read_deint follows it), and each batch is a halo submit (encoder.submit(halo=)).
 An `unsharp` behind the crop and the scale (profile.Profile.unsharp) is run by the GPU on the sws
 stage's output.  Without a scale in the graph FFmpeg sharpens the decoded frames and converts them
 afterwards, so a tv-range or to-be-converted input then goes to the real ffmpeg
@@ -56,6 +56,10 @@ them from a regular file), and the output runs at the input rate / N.  Such a gr
 SheetPlan; every other graph to the SegmentPlan it always did.
 All of this is resolved against the segment's input by plan_segment, a pure function, before run()
 binds to the GPU's NUMA node: a SegmentPlan, a Fallthrough (the real ffmpeg) or a CropError / PadError.
+run() is then a sequence: Context.acquire opens the encoder and its page-locked buffers (or takes the serve
+cache's), a Pipeline (reader thread, submit / drain loop, muxer thread; no GPU import of its own, so it runs
+with stand-ins) takes the segment through them, Pipeline.stop ends the threads and closes the source, and
+Context.settle keeps, frees or leaks what the context holds.
 """
 from __future__ import annotations
 
@@ -701,6 +705,18 @@ class SegmentPlan:
     cmat: Optional[tuple]            # the colormatrix's six coefficients, or None
     sar: tuple                       # of the picture (a crop and a pad leave it alone)
 
+    # what only a SheetPlan decides: plain class attributes here, fields there (fields() and key() stay as they are)
+    framestep = 1
+    sheet = None
+
+    def rate(self, info):
+        """What the muxer and the progress lines run at: the input's frame rate."""
+        return info.fps
+
+    def batch(self, b: int) -> int:
+        """Frames per batch for b = batch_frames(...)."""
+        return b
+
     def encoder_kwargs(self) -> dict:
         """The MjpegEncoder keyword arguments this plan decides (dst_w and dst_h go by position)."""
         return dict(sar=self.sar, chroma=self.dst_chroma, src_chroma=self.src_chroma, crop=self.rect, pad=self.pad,
@@ -764,6 +780,12 @@ class SheetPlan(SegmentPlan):
     sheet: Optional[tuple] = None    # (cols, rows, nb_frames, margin, padding), nb_frames resolved; None: framestep alone
     framestep: int = 1               # the reader keeps every framestep-th frame
     out_fps: Fraction = Fraction(25)  # what the muxer and the progress lines run at: fps / (framestep * nb_frames)
+
+    def rate(self, info):
+        return self.out_fps
+
+    def batch(self, b: int) -> int:
+        return b if self.sheet is None else sheet_batch(b, self.sheet[2])  # whole sheets
 
     def encoder_kwargs(self) -> dict:
         return dict(super().encoder_kwargs(), sheet=self.sheet)
@@ -839,10 +861,282 @@ def plan_segment(prof, info) -> SegmentPlan:
                        unsharp=prof.unsharp, lut_in=lut_in, lut_out=lut_out, cmat=cmat, sar=sar)
 
 
+JOIN_TIMEOUT = 5.0  # Pipeline.stop: what the reader and the muxer thread each get to end; one still alive after it is stuck
+
+
+class Pipeline:
+    """One segment through an open encoder: a reader thread fills the batch buffers from `src`, run()
+    submits them and drains the synced submits into output buffers, a muxer thread writes those to `mkv`.
+    All it works with is handed in, so it runs without a GPU: `enc` is used through frame_bytes, host_depth,
+    submit(arr, n, halo=), sync(), last_total and fetch_into(buf); `bufs` through .array; `obufs` (a list
+    filled and regrown here; None: not made yet) through .nbytes, .free() and what fetch_into needs;
+    `new_obuf(nbytes)` makes one.  `batch` frames a submit, every `step`-th frame kept, `deint`: halo submits.
+
+    The reader fills one batch while two are queued on the GPU (the encoder takes a second submit before
+    the first is synced, so its kernels run back to back); a batch returns to the reader as soon as its
+    submit is synced (the H2D has read it), before the packets are fetched, so the reader never waits on
+    the fetch.  The reader posts (buffer, encoded frames, halo bits) to `full`, None at the end of the
+    input, or the exception that stopped it.  After run(), failed or not, comes stop()."""
+
+    def __init__(self, enc, bufs, obufs, new_obuf, src, mkv, prog, batch: int, step: int = 1, deint: bool = False):
+        self.enc, self.bufs, self.obufs, self.new_obuf = enc, bufs, obufs, new_obuf
+        self.src, self.mkv, self.prog = src, mkv, prog
+        self.batch, self.step, self.deint, self.fb = batch, step, deint, enc.frame_bytes
+        self.done = self.nread = 0  # read_deint: frames encoded and frames read so far
+        self.prev = None            # read_deint: the previous buffer and the slot of its last encoded frame
+        self.free: "queue.Queue[int]" = queue.Queue()
+        self.full: "queue.Queue" = queue.Queue()
+        # the muxer thread writes each synced submit's packets while the main thread keeps the
+        # GPU fed (a 4K segment's 120 JPEGs are ~20 MB of writes)
+        self.outq: "queue.Queue" = queue.Queue(maxsize=4)
+        self.ofree: "queue.Queue[int]" = queue.Queue()  # output buffers the muxer has written
+        for i in range(len(bufs)):
+            self.free.put(i)
+        for i in range(len(obufs)):
+            self.ofree.put(i)
+        self.abort = threading.Event()
+        self.mux_err: list = []
+        self.queued: list = []  # buffer index and frame count per submit, oldest first
+        self.frames = 0
+        self.tr = {"read": 0.0, "submit": 0.0, "sync": 0.0, "fetch": 0.0, "mux": 0.0, "wait": 0.0}
+        self.failed, self.reader_stuck, self.muxer_stuck = True, False, False
+        self.th = threading.Thread(target=self.reader, daemon=True)
+        self.mt = threading.Thread(target=self.muxer, daemon=True)
+
+    def read_plain(self, i):
+        n = self.src.read_into(self.bufs[i].array, self.batch)
+        return n, 0, n < self.batch
+
+    def read_step(self, i):
+        """-vf framestep: frame k of the segment is kept when k % step == 0, the rest passed over."""
+        n, arr, fb = 0, self.bufs[i].array, self.fb
+        while n < self.batch and self.src.read_into(arr[n * fb:(n + 1) * fb], 1) == 1:
+            n += 1
+            self.src.skip(self.step - 1)
+        return n, 0, n < self.batch
+
+    def read_deint(self, i):
+        """A deinterlaced segment: a batch needs the frame in front of it and the one behind it, so the
+        reader keeps one frame of look-ahead and every buffer but the first starts with the previous
+        buffer's last encoded frame and its look-ahead frame (two host frame copies per batch; the
+        previous buffer is only read, the reader thread is the only writer).  The encoded frames come
+        after the halo frame in front (deint_step is the schedule)."""
+        arr, fb, base = self.bufs[i].array, self.fb, 0
+        if self.prev is not None:
+            pi, slot = self.prev
+            if pi == i:
+                raise RuntimeError("deinterlacer: the previous batch buffer came back before the next was filled")
+            arr[:2 * fb] = self.bufs[pi].array[slot * fb:(slot + 2) * fb]
+            base = 2
+        want = self.done + self.batch + 1 - self.nread
+        got = self.src.read_into(arr[base * fb:(base + want) * fb], want)
+        self.nread += got
+        eof = got < want
+        _, n, hp, hn = deint_step(self.done, self.nread, self.batch, eof)
+        self.prev = (i, int(hp) + n - 1)
+        self.done += n
+        return n, int(hp) | int(hn) << 1, eof
+
+    def reader(self):
+        """The reader thread: one of the three strategies above fills buffer i and returns (encoded
+        frames, halo bits, end of input)."""
+        read = self.read_deint if self.deint else self.read_step if self.step > 1 else self.read_plain
+        try:
+            while True:
+                i = self.free.get()
+                if i < 0 or self.abort.is_set():
+                    return
+                t0 = time.monotonic()
+                n, halo, eof = read(i)
+                self.tr["read"] += time.monotonic() - t0
+                self.full.put((i, n, halo))
+                if eof:
+                    self.full.put(None)
+                    return
+        except BaseException as e:   # surfaced by run()
+            self.full.put(e)
+
+    def muxer(self):
+        while True:
+            try:
+                item = self.outq.get(timeout=0.1)
+            except queue.Empty:
+                if self.abort.is_set():  # error path: the main thread may not be able to post None
+                    return
+                continue
+            if item is None:
+                return
+            packets, ob = item
+            if self.mux_err:
+                self.ofree.put(ob)
+                continue  # drain after a failure
+            try:
+                t0 = time.monotonic()
+                for p in packets:
+                    self.mkv.write_frame(p)
+                self.mkv.flush_pending()  # the packets leave buffer `ob` before it is reused
+                self.tr["mux"] += time.monotonic() - t0
+                self.frames += len(packets)  # (under a sheet fewer than the frames submitted)
+                self.prog.update(self.frames, sum(len(p) for p in packets))
+            except BaseException as e:  # surfaced by the main thread
+                self.mux_err.append(e)
+            self.ofree.put(ob)
+
+    def drain_one(self):
+        enc, obufs = self.enc, self.obufs
+        j = self.queued.pop(0)
+        t0 = time.monotonic()
+        enc.sync()
+        self.free.put(j)  # consumed by its H2D: back to the reader before the fetch
+        t1 = time.monotonic()
+        while True:  # a written output buffer (the muxer returns them); a muxer that failed returns no more
+            try:
+                ob = self.ofree.get(timeout=0.1)
+                break
+            except queue.Empty:
+                if self.mux_err:
+                    raise self.mux_err[0]
+        need = enc.last_total
+        # page-locked output buffers: the packets are DMA'd into one (enc.fetch_into) and the
+        # muxer writes them from it; regrown when a submit's JPEGs do not fit
+        if obufs[ob] is None or obufs[ob].nbytes < need:
+            if obufs[ob] is not None:
+                obufs[ob].free()
+            obufs[ob] = self.new_obuf(max(need + need // 2, 1 << 20))
+        packets = enc.fetch_into(obufs[ob])  # one DMA into page-locked memory, no copy
+        self.tr["sync"] += t1 - t0
+        self.tr["fetch"] += time.monotonic() - t1
+        if self.mux_err:
+            raise self.mux_err[0]
+        self.outq.put((packets, ob))
+
+    def run(self) -> None:
+        enc, tr, fb = self.enc, self.tr, self.fb
+        self.th.start()
+        self.mt.start()
+        while True:
+            t0 = time.monotonic()
+            item = self.full.get()
+            tr["wait"] += time.monotonic() - t0
+            if item is None:
+                break
+            if isinstance(item, BaseException):
+                raise item
+            i, n, halo = item
+            if not n:  # the input ended on a batch boundary: nothing in this buffer
+                self.free.put(i)
+                continue
+            if len(self.queued) == enc.host_depth:  # host submits: one launch each
+                self.drain_one()
+            t0 = time.monotonic()
+            nh = (halo & 1) + (halo >> 1)
+            enc.submit(self.bufs[i].array[:(n + nh) * fb], n, halo=halo)
+            tr["submit"] += time.monotonic() - t0
+            self.queued.append(i)
+        while self.queued:
+            self.drain_one()
+        self.outq.put(None)
+        self.mt.join()
+        if self.mux_err:
+            raise self.mux_err[0]
+        self.mkv.close()
+        self.prog.update(self.frames, 0, final=True)
+        self.failed = False
+
+    def stop(self) -> int:
+        """After run(), however it ended: nothing may be freed while a reader could still write into a
+        batch buffer, so stop the reader thread (it finishes at most the read in flight, whose
+        positional reads it waits for), killing a decoder child whose pipe it may be blocked on, and
+        then close the source.  Returns the decoder's exit code."""
+        self.abort.set()
+        self.free.put(-1)
+        if self.mt.is_alive():  # error path: let the muxer finish what it holds, then stop
+            try:  # never block here: a full queue means the muxer is inside a write, and it
+                self.outq.put_nowait(None)  # sees `abort` once that write returns
+            except queue.Full:
+                pass
+            self.mt.join(timeout=JOIN_TIMEOUT)
+        self.th.join(timeout=JOIN_TIMEOUT)
+        if self.th.is_alive():
+            self.src.close(kill=True)
+            self.th.join(timeout=JOIN_TIMEOUT)
+        self.reader_stuck = self.th.is_alive()  # blocked on a stdin pipe that never delivers
+        self.muxer_stuck = self.mt.is_alive()   # inside a write to a stdout pipe that does not drain
+        return self.src.close(kill=self.failed)
+
+
+class Context:
+    """An encoder context with its page-locked buffers: NBUF batch buffers and NOUT output buffers, the
+    latter made and regrown by the pipeline that fetches into them.  acquire() opens one or takes the
+    serve / resident cache's, settle() decides after the segment whether it is kept, freed or leaked."""
+
+    def __init__(self, device: int, prof, info, plan: SegmentPlan, batch: int, com_itu601: bool):
+        from .encoder import MjpegEncoder, PinnedBuffer   # GPU work starts here
+        self.enc = MjpegEncoder(device, info.width, info.height, plan.dst_w, plan.dst_h, full_range=info.full_range,
+                                qscale=prof.qscale, max_batch=batch, com_itu601=com_itu601, huffman=prof.huffman,
+                                rst=prof.rst, **plan.encoder_kwargs())
+        # (a deinterlacer: room for the frame in front of a batch and the one behind it)
+        self.bufs = [PinnedBuffer((batch + (2 if plan.deint else 0)) * self.enc.frame_bytes) for _ in range(NBUF)]
+        self.obufs = [None] * NOUT
+        self.new_obuf = PinnedBuffer
+
+    @classmethod
+    def acquire(cls, cache, device: int, prof, info, plan: SegmentPlan, batch: int, com_itu601: bool) -> "Context":
+        """The cache's context when it was opened for the same plan.key(...), else a new one, in
+        place of whatever the cache (a dict, or None: one segment) held."""
+        key = plan.key(prof, info, com_itu601, batch)
+        if cache is not None and cache.get("key") == key:
+            return cache["ctx"]
+        if cache is not None:
+            release(cache)
+        ctx = cls(device, prof, info, plan, batch, com_itu601)
+        if cache is not None:
+            cache.update(key=key, ctx=ctx)
+        return ctx
+
+    def settle(self, cache, pipe: Pipeline) -> None:
+        """After pipe.stop(): the cache keeps the context of a segment that went through.  A failed
+        segment, or one with a stuck thread, may have a submit queued: its cache entry goes and the next
+        segment starts afresh.  The encoder is closed here, after the reader has stopped and the source is
+        closed.  A stuck reader may yet write into a batch buffer, and a stuck muxer holds packets that are
+        views into the output buffers: such buffers are leaked, never freed."""
+        if cache is not None and not (pipe.failed or pipe.reader_stuck or pipe.muxer_stuck):
+            return
+        if cache is not None:
+            cache.pop("key", None)
+            cache.pop("ctx", None)
+        self.free(bufs=not pipe.reader_stuck, obufs=not pipe.muxer_stuck)
+
+    def free(self, bufs: bool = True, obufs: bool = True) -> None:
+        self.enc.close()
+        for b in (self.bufs if bufs else []) + (self.obufs if obufs else []):
+            if b is not None:
+                b.free()
+
+
+def release(cache) -> None:
+    """Close the encoder context and free the buffers a serve cache holds."""
+    ctx = cache.pop("ctx", None)
+    cache.pop("key", None)
+    if ctx is not None:
+        ctx.free()
+
+
+def trace_line(opts: Options, pipe: Pipeline, t_run: float, t_seg: float) -> str:
+    """MJG_WORKER_TRACE's line for a segment that went through (bench.py parses it)."""
+    hand = ""  # the resident's hand-off: client start -> accept -> worker.run
+    if opts.t_accept:
+        hand += f"handoff={t_run - opts.t_accept:.4f} "
+        if opts.client_t0:
+            hand += f"client={opts.t_accept - opts.client_t0:.4f} "
+    return (f"mjg-trace: frames={pipe.frames} total={time.monotonic() - t_seg:.4f} setup={t_seg - t_run:.4f} {hand}"
+            + " ".join(f"{k}={v:.4f}" for k, v in pipe.tr.items()) + f" {placement()}\n")
+
+
 def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cache=None,
         batch_bytes: Optional[int] = None, opts: Optional[Options] = None) -> int:
     """One segment, stdin -> stdout.  `cache` (serve / resident mode): a dict that keeps the
-    encoder context and the page-locked batch buffers between segments of the same stream
+    encoder context and its page-locked buffers between segments of the same stream
     shape.  `opts`: the segment's settings (default: this process's, process_options)."""
     t_run = time.monotonic()
     opts = opts or process_options(batch_bytes)
@@ -869,270 +1163,26 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
         src.close(kill=True)
         return 1
     bind_numa(device)  # before the reader threads and the batch buffers
-    from .encoder import MjpegEncoder, PinnedBuffer   # GPU work starts here
-
-    batch = batch_frames(opts, info.frame_bytes)
-    # -vf framestep / tile (SheetPlan): the reader keeps every step-th frame, a batch is whole sheets, and
-    # the output runs at fps / (step * frames a sheet)
-    step = getattr(plan, "framestep", 1)
-    out_fps = getattr(plan, "out_fps", info.fps)
-    if getattr(plan, "sheet", None) is not None:
-        batch = sheet_batch(batch, plan.sheet[2])
-    com_itu601 = opts.com_itu601 and not info.full_range
-    key = plan.key(prof, info, com_itu601, batch)
-    nbuf = NBUF
-    if cache is not None and cache.get("key") == key:
-        enc, bufs, obufs = cache["enc"], cache["bufs"], cache["obufs"]
-    else:
-        if cache is not None:
-            release(cache)
-        enc = MjpegEncoder(device, info.width, info.height, plan.dst_w, plan.dst_h, full_range=info.full_range,
-                           qscale=prof.qscale, max_batch=batch, com_itu601=com_itu601, huffman=prof.huffman,
-                           rst=prof.rst, **plan.encoder_kwargs())
-        # (a deinterlacer: room for the frame in front of a batch and the one behind it)
-        bufs = [PinnedBuffer((batch + (2 if plan.deint else 0)) * enc.frame_bytes) for _ in range(nbuf)]
-        # page-locked output buffers: the packets are DMA'd into one (enc.fetch_into) and the
-        # muxer writes them from it; regrown when a submit's JPEGs do not fit
-        obufs = [None] * NOUT
-        if cache is not None:
-            cache.update(key=key, enc=enc, bufs=bufs, obufs=obufs)
+    batch = plan.batch(batch_frames(opts, info.frame_bytes))
+    ctx = Context.acquire(cache, device, prof, info, plan, batch, opts.com_itu601 and not info.full_range)
+    out_fps = plan.rate(info)
     prog = Progress(stderr, out_fps, prof.qscale)
     prog.duration(src.duration)
     mkv = container.MkvWriter(stdout, plan.enc_w, plan.enc_h, out_fps, plan.sar)
-
-    # NBUF page-locked batches: the reader fills one while two are queued on the GPU (the
-    # encoder takes a second submit before the first is synced, so its kernels run back to
-    # back); a batch returns to the reader as soon as its submit is synced (the H2D has read
-    # it), before the packets are fetched, so the reader never waits on the fetch.
-    fb = enc.frame_bytes
-    free: "queue.Queue[int]" = queue.Queue()
-    full: "queue.Queue" = queue.Queue()
-    abort = threading.Event()
-    for i in range(nbuf):
-        free.put(i)
-
-    tr = {"read": 0.0, "submit": 0.0, "sync": 0.0, "fetch": 0.0, "mux": 0.0, "wait": 0.0}
+    pipe = Pipeline(ctx.enc, ctx.bufs, ctx.obufs, ctx.new_obuf, src, mkv, prog, batch, plan.framestep, bool(plan.deint))
     t_seg = time.monotonic()
-
-    def reader():
-        try:
-            while True:
-                i = free.get()
-                if i < 0 or abort.is_set():
-                    return
-                t0 = time.monotonic()
-                if step > 1:  # framestep: frame i of the segment is kept when i % step == 0, the rest passed over
-                    n, arr = 0, bufs[i].array
-                    while n < batch and src.read_into(arr[n * fb:(n + 1) * fb], 1) == 1:
-                        n += 1
-                        src.skip(step - 1)
-                else:
-                    n = src.read_into(bufs[i].array, batch)
-                tr["read"] += time.monotonic() - t0
-                full.put((i, n))
-                if n < batch:
-                    full.put(None)
-                    return
-        except BaseException as e:   # surfaced by the main loop
-            full.put(e)
-
-    def deint_reader():
-        """The reader of a deinterlaced segment: a batch needs the frame in front of it and the
-        one behind it, so the reader keeps one frame of look-ahead and every buffer but the first
-        starts with the previous buffer's last encoded frame and its look-ahead frame (two host
-        frame copies per batch; the previous buffer is only read, this thread is the only writer).
-        Posts (buffer, encoded frames, halo) with the encoded frames after the halo frame in front."""
-        try:
-            done = read = 0
-            prev = None  # the previous buffer and the slot of its last encoded frame
-            while True:
-                i = free.get()
-                if i < 0 or abort.is_set():
-                    return
-                t0 = time.monotonic()
-                arr = bufs[i].array
-                base = 0
-                if prev is not None:
-                    pi, slot = prev
-                    if pi == i:
-                        raise RuntimeError("deinterlacer: the previous batch buffer came back before the next was filled")
-                    arr[:2 * fb] = bufs[pi].array[slot * fb:(slot + 2) * fb]
-                    base = 2
-                want = done + batch + 1 - read
-                got = src.read_into(arr[base * fb:(base + want) * fb], want)
-                read += got
-                eof = got < want
-                _, n, hp, hn = deint_step(done, read, batch, eof)
-                tr["read"] += time.monotonic() - t0
-                full.put((i, n, int(hp) | int(hn) << 1))
-                prev = (i, int(hp) + n - 1)
-                done += n
-                if eof:
-                    full.put(None)
-                    return
-        except BaseException as e:   # surfaced by the main loop
-            full.put(e)
-
-    th = threading.Thread(target=deint_reader if plan.deint else reader, daemon=True)
-    th.start()
-    frames = 0
-    queued: "list" = []  # buffer index and frame count per submit, oldest first
-    # the muxer thread writes each synced submit's packets while the main thread keeps the
-    # GPU fed (a 4K segment's 120 JPEGs are ~20 MB of writes)
-    outq: "queue.Queue" = queue.Queue(maxsize=4)
-    ofree: "queue.Queue[int]" = queue.Queue()  # output buffers the muxer has written
-    for i in range(NOUT):
-        ofree.put(i)
-    mux_err: list = []
-
-    def muxer():
-        nonlocal frames
-        while True:
-            try:
-                item = outq.get(timeout=0.1)
-            except queue.Empty:
-                if abort.is_set():  # error path: the main thread may not be able to post None
-                    return
-                continue
-            if item is None:
-                return
-            packets, m, ob = item
-            if mux_err:
-                ofree.put(ob)
-                continue  # drain after a failure
-            try:
-                t0 = time.monotonic()
-                for p in packets:
-                    mkv.write_frame(p)
-                mkv.flush_pending()  # the packets leave buffer `ob` before it is reused
-                tr["mux"] += time.monotonic() - t0
-                frames += len(packets)  # (under a sheet fewer than the m frames submitted)
-                prog.update(frames, sum(len(p) for p in packets))
-            except BaseException as e:  # surfaced by the main thread
-                mux_err.append(e)
-            ofree.put(ob)
-
-    mt = threading.Thread(target=muxer, daemon=True)
-    mt.start()
-
-    def drain_one():
-        j, m = queued.pop(0)
-        t0 = time.monotonic()
-        enc.sync()
-        free.put(j)  # consumed by its H2D: back to the reader before the fetch
-        t1 = time.monotonic()
-        while True:  # a written output buffer (the muxer returns them); abort: error path
-            try:
-                ob = ofree.get(timeout=0.1)
-                break
-            except queue.Empty:
-                if mux_err:
-                    raise mux_err[0]
-        need = enc.last_total
-        if obufs[ob] is None or obufs[ob].nbytes < need:
-            if obufs[ob] is not None:
-                obufs[ob].free()
-            obufs[ob] = PinnedBuffer(max(need + need // 2, 1 << 20))
-        packets = enc.fetch_into(obufs[ob])  # one DMA into page-locked memory, no copy
-        tr["sync"] += t1 - t0
-        tr["fetch"] += time.monotonic() - t1
-        if mux_err:
-            raise mux_err[0]
-        outq.put((packets, m, ob))
-
-    failed = True
     try:
-        while True:
-            t0 = time.monotonic()
-            item = full.get()
-            tr["wait"] += time.monotonic() - t0
-            if item is None:
-                break
-            if isinstance(item, BaseException):
-                raise item
-            i, n, *halo = item  # (a deinterlacer's reader adds the halo bits)
-            if n:
-                if len(queued) == enc.host_depth:  # host submits: one launch each
-                    drain_one()
-                t0 = time.monotonic()
-                if halo:
-                    nh = (halo[0] & 1) + (halo[0] >> 1)
-                    enc.submit(bufs[i].array[: (n + nh) * fb], n, halo=halo[0])
-                else:
-                    enc.submit(bufs[i].array[: n * fb], n)
-                tr["submit"] += time.monotonic() - t0
-                queued.append((i, n))
-            else:
-                free.put(i)
-        while queued:
-            drain_one()
-        outq.put(None)
-        mt.join()
-        if mux_err:
-            raise mux_err[0]
-        mkv.close()
-        prog.update(frames, 0, final=True)
-        failed = False
+        pipe.run()
         if opts.trace:
-            hand = ""  # the resident's hand-off: client start -> accept -> worker.run
-            if opts.t_accept:
-                hand += f"handoff={t_run - opts.t_accept:.4f} "
-                if opts.client_t0:
-                    hand += f"client={opts.t_accept - opts.client_t0:.4f} "
-            stderr.write(f"mjg-trace: frames={frames} total={time.monotonic() - t_seg:.4f} "
-                         f"setup={t_seg - t_run:.4f} {hand}"
-                         + " ".join(f"{k}={v:.4f}" for k, v in tr.items()) + f" {placement()}\n")
+            stderr.write(trace_line(opts, pipe, t_run, t_seg))
             stderr.flush()
     finally:
-        # Nothing is freed while a reader could still write into a batch buffer: stop the
-        # reader thread (it finishes at most the read in flight, whose positional reads it
-        # waits for), killing a decoder child whose pipe it may be blocked on; then close
-        # the source, and only then the encoder and the page-locked buffers.
-        abort.set()
-        free.put(-1)
-        if mt.is_alive():  # error path: let the muxer finish what it holds, then stop
-            try:  # never block here: a full queue means the muxer is inside a write, and it
-                outq.put_nowait(None)  # sees `abort` once that write returns
-            except queue.Full:
-                pass
-            mt.join(timeout=5.0)
-        th.join(timeout=5.0)
-        if th.is_alive():
-            src.close(kill=True)
-            th.join(timeout=5.0)
-        stuck = th.is_alive()  # blocked on a stdin pipe that never delivers: leak, never free
-        # the muxer's packets are views into the page-locked output buffers: one still inside
-        # a write (a stdout pipe that does not drain) keeps them, so they are leaked, not freed
-        mux_stuck = mt.is_alive()
-        rc = src.close(kill=failed)
-        if (failed or stuck or mux_stuck) and cache is not None:  # a submit may still be queued: start afresh
-            for k in ("key", "enc", "bufs", "obufs"):
-                cache.pop(k, None)
-            cache = None
-        if cache is None:
-            enc.close()
-            if not stuck:
-                for b in bufs:
-                    b.free()
-            if not mux_stuck:
-                for b in obufs:
-                    if b is not None:
-                        b.free()
+        rc = pipe.stop()
+        ctx.settle(cache, pipe)
     if rc:
         stderr.write(f"decoder exited with {rc}\n")
         return 1
     return 0
-
-
-def release(cache) -> None:
-    """Close the encoder context and free the batch buffers a serve cache holds."""
-    enc, bufs = cache.pop("enc", None), cache.pop("bufs", None) or []
-    obufs = [b for b in (cache.pop("obufs", None) or []) if b is not None]
-    cache.pop("key", None)
-    if enc is not None:
-        enc.close()
-    for b in bufs + obufs:
-        b.free()
 
 
 SERVE_DONE = "mjg-serve: segment done rc="
