@@ -50,6 +50,7 @@ EXPORTS = (
     "mjg_open_cmat", "mjg_debug_cmat", "mjg_debug_cmat_out",
     "mjg_open_chain",
     "mjg_open_sheet", "mjg_frames_out", "mjg_debug_sheet", "mjg_debug_cell",
+    "mjg_hist_open", "mjg_hist_frames", "mjg_hist_close",
 )
 
 # mjg_open_deint's `deint`
@@ -196,6 +197,13 @@ def load():
             L.mjg_debug_sheet.restype = C.c_int
             L.mjg_debug_cell.argtypes = [vp, C.c_int, u8p, sz]
             L.mjg_debug_cell.restype = C.c_int
+        if hasattr(L, "mjg_hist_open"):  # absent from libraries built before the histogram object (A/B builds)
+            L.mjg_hist_open.argtypes = [C.c_int] * 5 + [C.POINTER(vp)]
+            L.mjg_hist_open.restype = C.c_int
+            L.mjg_hist_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(C.c_uint32)]
+            L.mjg_hist_frames.restype = C.c_int
+            L.mjg_hist_close.argtypes = [vp]
+            L.mjg_hist_close.restype = None
         L.mjg_close.argtypes = [vp]
         L.mjg_close.restype = None
         L.mjg_frame_bytes.argtypes = [vp]
@@ -250,7 +258,8 @@ def load():
                  "mjg_open_sharp", "mjg_debug_presharp", "mjg_debug_unsharp",
                  "mjg_open_lut", "mjg_debug_lut", "mjg_debug_lut_in", "mjg_debug_tail",
                  "mjg_open_cmat", "mjg_debug_cmat", "mjg_debug_cmat_out", "mjg_open_chain",
-                 "mjg_open_sheet", "mjg_frames_out", "mjg_debug_sheet", "mjg_debug_cell")
+                 "mjg_open_sheet", "mjg_frames_out", "mjg_debug_sheet", "mjg_debug_cell",
+                 "mjg_hist_open", "mjg_hist_frames", "mjg_hist_close")
                 if os.environ.get("MJG_LIBRARY") else ())
         for name in EXPORTS:
             if name not in late:

@@ -2217,6 +2217,107 @@ int mjg_host_free(void *ptr) {
   return MJG_OK;
 }
 
+// The histogram object (mjgpu.h): k_frame_hist on a stream and buffers of its own, no mjg_ctx
+struct mjg_hist {
+  int device = 0, max_frames = 0;
+  size_t frame_bytes = 0;
+  HistGeom g{};
+  hipStream_t stream = nullptr;
+  uint8_t *d_frames = nullptr;  // max_frames frames, for host input
+  uint32_t *d_hist = nullptr;   // [max_frames][768]
+  uint32_t *h_hist = nullptr;   // the same, page-locked
+};
+
+namespace {
+// The object's launch for w x h frames of one format and calls of up to max_frames (no HIP call: the
+// host check walks it, tools/stage_host.hip); a call of n frames launches g.gpf * n workgroups
+int hist_plan(int w, int h, int cf, int max_frames, HistGeom *g, size_t *frame_bytes) {
+  if (w < 1 || h < 1 || w > 16384 || h > 16384) return set_err(MJG_E_INVALID, "hist: %dx%d not in 1..16384", w, h);
+  if (cf != MJG_CHROMA_420 && cf != MJG_CHROMA_422 && cf != MJG_CHROMA_444)
+    return set_err(MJG_E_INVALID, "hist: chroma_format %d is no MJG_CHROMA_* value", cf);
+  if (max_frames < 1) return set_err(MJG_E_INVALID, "hist: max_frames %d below 1", max_frames);
+  const int hs = cf != MJG_CHROMA_444, vs = cf == MJG_CHROMA_420;
+  *g = HistGeom{};
+  g->nb[0] = w * h;
+  g->nb[1] = ((w + hs) >> hs) * ((h + vs) >> vs);
+  g->fstride = (long long)g->nb[0] + 2 * (long long)g->nb[1];
+  g->gy = hist_wgs(g->nb[0]), g->gc = hist_wgs(g->nb[1]);
+  g->gpf = g->gy + 2 * g->gc;
+  g->gpf_magic = magic32((uint32_t)g->gpf);
+  // k_frame_hist's grid is workgroups per frame x frames in x alone (and deint_div forms q d <= t + d)
+  if ((long long)g->gpf * ((long long)max_frames + 1) > (long long)INT_MAX)
+    return set_err(MJG_E_INVALID, "hist: %d workgroups a frame x %d frames a call is past 2^31 - 1", g->gpf, max_frames);
+  *frame_bytes = (size_t)g->fstride;
+  return MJG_OK;
+}
+
+void free_hist(mjg_hist *h) {
+  if (!h) return;
+  if (h->stream) {  // (without one nothing was allocated, and the device may be none)
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    if (h->d_frames) (void)hipFree(h->d_frames);
+    if (h->d_hist) (void)hipFree(h->d_hist);
+    if (h->h_hist) (void)hipHostFree(h->h_hist);
+    (void)hipStreamDestroy(h->stream);
+  }
+  delete h;
+}
+
+int open_hist(mjg_hist *h) {
+  int ndev = 0, rc;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (h->device < 0 || h->device >= ndev) return set_err(MJG_E_INVALID, "hist: device %d of %d", h->device, ndev);
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  if ((rc = dmalloc(&h->d_frames, (size_t)h->max_frames * h->frame_bytes)) || (rc = dmalloc(&h->d_hist, (size_t)h->max_frames * 768)))
+    return rc;
+  if (hipHostMalloc((void **)&h->h_hist, (size_t)h->max_frames * 768 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) {
+    h->h_hist = nullptr;
+    (void)hipGetLastError();
+    return set_err(MJG_E_NOMEM, "hist: hipHostMalloc(%zu) failed", (size_t)h->max_frames * 768 * sizeof(uint32_t));
+  }
+  return MJG_OK;
+}
+}  // namespace
+
+int mjg_hist_open(int device, int w, int h, int chroma_format, int max_frames, mjg_hist **out) {
+  if (!out) return set_err(MJG_E_INVALID, "hist: null argument");
+  *out = nullptr;
+  mjg_hist *o = new mjg_hist();
+  o->device = device, o->max_frames = max_frames;
+  int rc = hist_plan(w, h, chroma_format, max_frames, &o->g, &o->frame_bytes);
+  if (rc) {
+    delete o;  // (no HIP call was made)
+    return rc;
+  }
+  if ((rc = open_hist(o))) {
+    free_hist(o);
+    return rc;
+  }
+  *out = o;
+  return MJG_OK;
+}
+
+int mjg_hist_frames(mjg_hist *h, const uint8_t *frames, int n, int src_is_device, uint32_t *hist) {
+  if (!h || !frames || !hist) return set_err(MJG_E_INVALID, "hist: null argument");
+  if (n < 1 || n > h->max_frames) return set_err(MJG_E_INVALID, "hist: nframes %d not in 1..%d", n, h->max_frames);
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t words = (size_t)n * 768;
+  if (!src_is_device)
+    HIP_TRY(hipMemcpyAsync(h->d_frames, frames, (size_t)n * h->frame_bytes, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemsetAsync(h->d_hist, 0, words * sizeof(uint32_t), h->stream));  // the kernel adds: every call from zero
+  (void)hipGetLastError();  // (an earlier call's error is not this launch's)
+  k_frame_hist<<<h->g.gpf * n, kHistThreads, 0, h->stream>>>(one_seg(src_is_device ? frames : h->d_frames), h->d_hist, h->g);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h->h_hist, h->d_hist, words * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  memcpy(hist, h->h_hist, words * sizeof(uint32_t));
+  return MJG_OK;
+}
+
+void mjg_hist_close(mjg_hist *h) { free_hist(h); }
+
 int mjg_kernel_times(mjg_ctx *c, double *ms, int *launches, int reset) {
   if (!c) return set_err(MJG_E_INVALID, "null ctx");
   if (!c->timing) return set_err(MJG_E_STATE, "context opened without MJG_F_TIMING");

@@ -1960,4 +1960,115 @@ __global__ __launch_bounds__(kCopyThreads) void k_tile_plane(const uint8_t *__re
   tile_work(src, dst, g, (int)blockIdx.x, (int)threadIdx.x);
 }
 
+// k_frame_hist: the per-frame, per-plane histograms that `-vf thumbnail` selects by (DESIGN §4.18;
+// mjg_hist_open).  The input is a SegList of decoded frames, packed planar in the source format, fstride
+// apart; the output is hist[nframes][768] uint32 counters, zeroed by the caller: hist[f][256 p + v] is
+// the number of samples of value v in plane p (0 Y, 1 U, 2 V) of frame f, each plane at its own size.
+// The chain's first reduction: nothing is written but counters.
+// Layout: a plane of a frame is one byte string of nb bytes, cut into 16-byte pieces aligned on the
+// SOURCE (there is no destination to align on), kHistVecs pieces a thread, so a workgroup covers 16 KiB
+// of one plane of one frame.  One launch covers all three planes of every frame: the grid's x is
+// workgroups per frame (gy for Y, then gc for U, then gc for V) x frames, split by multiply-high as in
+// the other stage kernels, so no plane and no frame is a grid index and there is no 32,767-frame limit;
+// open refuses a gpf x frames past 2^31 - 1.  The bytes before the first and behind the last whole piece
+// (up to 15 each; all of a plane below one piece) are counted one by one by the (plane, frame)'s first
+// workgroup.
+// Counting: a workgroup counts into LDS, kHistCopies copies of the 256 bins interleaved as
+// lh[v kHistCopies + copy] with copy = lane % kHistCopies: a flat plane, where all 64 lanes of a wave add
+// to one bin, lands on kHistCopies addresses in as many banks (4 lanes each) and not on one.  All of a
+// thread's loads are issued before its first add.  Behind a barrier thread v sums bin v's copies and
+// adds a non-zero sum to hist with one global integer atomic: at most 256 a workgroup.  Integer adds
+// commute, so the counts are exact whatever the order; a counter holds 2^32 - 1 and a plane at most
+// 2^28 samples.
+// Addresses.  A piece is bytes [head + 16 k, + 16) of the plane with k < nv = (nb - head) >> 4, so it
+// ends at or before byte nb; a single byte is a < head <= nb or b < nb.  The plane is [off, off + nb)
+// of frame f < nf of its segment, so every load lies inside a plane of a frame of the call.  The stores
+// are hist[f][256 p + v] with f < nf, p < 3, v < 256.
+// The body is two __host__ __device__ functions (count, flush; a barrier between them), as yadif_work
+// is one, for tools/stage_host.hip: on the host the adds are plain.
+struct HistGeom {
+  int nb[2];           // bytes of the Y plane, of a chroma plane (<= 2^28)
+  long long fstride;   // frame bytes
+  int gy, gc;          // workgroups of the Y plane, of a chroma plane
+  int gpf;             // workgroups per frame: gy + 2 gc
+  uint32_t gpf_magic;
+};
+
+constexpr int kHistThreads = 256;  // = the bins: thread v flushes bin v
+constexpr int kHistVecs = 4;       // pieces per thread, all loaded before the first is counted
+constexpr int kHistCopies = 16;    // LDS copies of a bin, on consecutive banks
+
+// workgroups of a plane of nb >= 1 bytes: its at most nb / 16 pieces (a plane below one piece: one, for its bytes)
+inline int hist_wgs(int nb) { return (nb + kHistThreads * kHistVecs * 16 - 1) / (kHistThreads * kHistVecs * 16); }
+
+__device__ __forceinline__ void hist_add(uint32_t *p, uint32_t v) { atomicAdd(p, v); }
+__host__ inline void hist_add(uint32_t *p, uint32_t v) { *p += v; }
+
+// the (plane, frame) of workgroup t and its index inside that plane
+__host__ __device__ __forceinline__ void hist_block(const HistGeom &g, int t, int *f, int *pl, int *pblk) {
+  *f = deint_div(t, g.gpf_magic, g.gpf);
+  const int blk = t - *f * g.gpf;
+  *pl = blk < g.gy ? 0 : blk < g.gy + g.gc ? 1 : 2;
+  *pblk = blk - (*pl ? g.gy : 0) - (*pl == 2 ? g.gc : 0);
+}
+
+__host__ __device__ __forceinline__ void hist_count(const SegList &src, uint32_t *lh, const HistGeom &g, int t, int tid) {
+  int f, pl, pblk;
+  hist_block(g, t, &f, &pl, &pblk);
+  int k = 0;
+#pragma unroll
+  for (int j = 1; j < kMaxSegs; j++)
+    if (f >= src.f0[j]) k = j;
+  const long long off = pl ? (long long)g.nb[0] + (pl == 2 ? g.nb[1] : 0) : 0;
+  const uint8_t *s = src.p[k] + (long long)(f - (k ? src.f0[k] : 0)) * g.fstride + off;
+  const int nb = g.nb[pl ? 1 : 0];
+  const int head = imin((int)(-(uintptr_t)s & 15), nb);
+  const int nv = (nb - head) >> 4;  // whole pieces: bytes [head, head + 16 nv) of the plane
+  uint32_t *mine = lh + (tid & (kHistCopies - 1));
+  auto count = [&](uint32_t v) { hist_add(mine + v * kHistCopies, 1u); };
+  const int k0 = pblk * (kHistThreads * kHistVecs) + tid;
+  u32x4 v[kHistVecs];
+#pragma unroll
+  for (int i = 0; i < kHistVecs; i++) {
+    const int kp = k0 + i * kHistThreads;
+    if (kp < nv) v[i] = *(const u32x4 *)(s + head + 16 * (size_t)kp);
+  }
+#pragma unroll
+  for (int i = 0; i < kHistVecs; i++) {
+    const int kp = k0 + i * kHistThreads;
+    if (kp < nv) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const uint32_t x = v[i][q];
+        count(x & 255u), count((x >> 8) & 255u), count((x >> 16) & 255u), count(x >> 24);
+      }
+    }
+  }
+  if (pblk == 0 && tid < 16) {
+    const int a = tid, b = head + 16 * nv + tid;
+    if (a < head) count(s[a]);
+    if (b < nb) count(s[b]);
+  }
+}
+
+__host__ __device__ __forceinline__ void hist_flush(const uint32_t *lh, uint32_t *hist, const HistGeom &g, int t, int tid) {
+  int f, pl, pblk;
+  hist_block(g, t, &f, &pl, &pblk);
+  uint32_t sum = 0;
+#pragma unroll
+  for (int c = 0; c < kHistCopies; c++) sum += lh[tid * kHistCopies + c];
+  if (sum) hist_add(hist + (size_t)f * 768 + 256 * pl + tid, sum);
+}
+
+__global__ __launch_bounds__(kHistThreads) void k_frame_hist(const SegList src, uint32_t *__restrict__ hist, HistGeom g) {
+  __shared__ __attribute__((aligned(16))) uint32_t lh[256 * kHistCopies];
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int c = 0; c < kHistCopies / 4; c++) ((u32x4 *)lh)[c * kHistThreads + tid] = u32x4{0, 0, 0, 0};
+  __syncthreads();
+  hist_count(src, lh, g, (int)blockIdx.x, tid);
+  __syncthreads();
+  hist_flush(lh, hist, g, (int)blockIdx.x, tid);
+}
+
 }  // namespace mjg

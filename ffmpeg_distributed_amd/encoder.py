@@ -611,5 +611,66 @@ class PinnedBuffer:
             pass
 
 
-__all__ = ["MjpegEncoder", "MjgError", "PinnedBuffer", "i420_frame_bytes", "split_i420",
+class FrameHist:
+    """Per-frame, per-plane histograms of decoded frames on one GPU (mjg_hist, k_frame_hist): what `-vf
+    thumbnail` selects by (profile.thumbnail_pick).  An object of its own with its own stream and buffers,
+    no encoder context: the worker's reader thread counts while the submit thread owns the encoder.  Frames
+    are w x h, 8 bits, packed planar in `chroma`, frame_bytes apart.  No CPU fallback."""
+
+    def __init__(self, device: int, w: int, h: int, chroma: str = "420", max_frames: int = 16):
+        self._L = _lib.load()
+        if not hasattr(self._L, "mjg_hist_open"):
+            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_hist_open")
+        if str(chroma) not in _lib.CHROMA_FORMATS:
+            raise ValueError(f"chroma {chroma!r}")
+        self.device, self.w, self.h, self.chroma = int(device), int(w), int(h), str(chroma)
+        self.max_frames = int(max_frames)
+        h_ = C.c_void_p()
+        check(self._L.mjg_hist_open(self.device, self.w, self.h, _lib.CHROMA_FORMATS[self.chroma], self.max_frames,
+                                    C.byref(h_)))
+        self._h = h_
+        self.frame_bytes = i420_frame_bytes(self.w, self.h, self.chroma)
+
+    def count(self, frames=None, nframes: Optional[int] = None, device_ptr: Optional[int] = None) -> np.ndarray:
+        """The (n, 768) uint32 histograms of n frames: row f, entry 256 p + v is the number of samples of
+        value v in plane p (0 Y, 1 U, 2 V) of frame f.  `frames` is a host buffer (numpy / bytes; n defaults
+        to its frames), or `device_ptr` the frames on this GPU with `nframes`.  Synchronous; every call counts
+        from zero."""
+        if device_ptr is not None:
+            if nframes is None:
+                raise ValueError("nframes is required with device_ptr")
+            ptr, n, dev, keep = C.c_void_p(int(device_ptr)), int(nframes), 1, None
+        else:
+            keep = np.ascontiguousarray(np.frombuffer(frames, dtype=np.uint8)
+                                        if isinstance(frames, (bytes, bytearray, memoryview))
+                                        else np.asarray(frames, dtype=np.uint8))
+            if keep.size % self.frame_bytes:
+                raise ValueError(f"buffer of {keep.size} bytes is not a whole number of {self.frame_bytes}-byte frames")
+            n = keep.size // self.frame_bytes if nframes is None else int(nframes)
+            if n * self.frame_bytes > keep.size:
+                raise ValueError(f"buffer of {keep.size} bytes holds fewer than {n} frames")
+            ptr, dev = C.c_void_p(keep.ctypes.data), 0
+        out = np.zeros((max(n, 0), 768), np.uint32)
+        check(self._L.mjg_hist_frames(self._h, ptr, n, dev, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.mjg_hist_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+__all__ = ["MjpegEncoder", "MjgError", "PinnedBuffer", "FrameHist", "i420_frame_bytes", "split_i420",
            "pack_i420"]

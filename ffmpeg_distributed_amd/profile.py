@@ -55,7 +55,16 @@ colour other than black, an overlap or init_padding other than 0, an expression,
 any other position and what FFmpeg itself rejects (nb_frames above cols x rows, a step below 1) are
 outside the profile, each with a reason that names it.  `framestep=1` is no filter, and a graph that
 names neither filter parses to the plain `Profile` it always did.  Both are restatements (vf_tile.c,
-vf_framestep.c) that are unpinned against FFmpeg.  An orientation filter after a crop, scale
+vf_framestep.c) that are unpinned against FFmpeg.  In front of such a graph,
+    thumbnail | thumbnail=N | thumbnail=n=N (the very first filter, or the second directly behind a leading
+                                            framestep; only in a graph that ends in tile; not with yadif)
+makes it a `ThumbProfile`: `thumbnail` = N (2 or more; the default is 100), the group of
+consecutive frames of which the worker's reader keeps one, the frame whose histogram is closest to the
+group's mean histogram (`thumbnail_pick`, on histograms the GPU counts).  A second thumbnail, any other
+position, a graph that also names yadif, a graph whose last filter is no tile (the filter keeps its link's
+frame rate and emits sparse timestamps, which MkvWriter does not write), N below 2, a non-integer and an
+unknown key are outside the profile, each with a reason that names it.  A restatement of vf_thumbnail.c's
+8-bit planar path (FFmpeg 5.1 and later) that is unpinned against FFmpeg.  An orientation filter after a crop, scale
 or pad, transpose values 4..7, a passthrough other than none and any other option are outside the
 profile.  The crop values are decimal integers (no expressions); `Profile.crop` is the request as
 given and `resolve_crop` turns it into a rectangle of a given input (vf_crop.c's rounding,
@@ -131,6 +140,17 @@ class SheetProfile(Profile):
     tile: Optional[dict] = None
     # -vf framestep=N,...: the reader keeps every N-th frame of the segment; 1: every frame
     framestep: int = 1
+
+
+THUMBNAIL_DEFAULT = 100  # vf_thumbnail.c's n
+
+
+@dataclass
+class ThumbProfile(SheetProfile):
+    """The SheetProfile of a graph that names `thumbnail` (parse returns one exactly then)."""
+    # -vf [framestep=S,]thumbnail=N,...,tile: of every N consecutive frames (behind the framestep) the reader keeps
+    # the one that thumbnail_pick selects
+    thumbnail: int = THUMBNAIL_DEFAULT
 
 
 class Unsupported(ValueError):
@@ -635,13 +655,75 @@ def _parse_framestep(f: str) -> int:
     return int(v)
 
 
+def _parse_thumbnail(f: str) -> int:
+    """`thumbnail` / `thumbnail=N` / `thumbnail=n=N` -> N (vf_thumbnail.c: n, 2 or more; the default is 100)."""
+    n = str(THUMBNAIL_DEFAULT)
+    for at, part in enumerate(f.split("=", 1)[1].split(":") if "=" in f else []):
+        if "=" in part:
+            k, v = part.split("=", 1)
+            if k != "n":
+                raise Unsupported(f"thumbnail option {k!r} (only n is GPU-accelerated)")
+        elif at:
+            raise Unsupported(f"thumbnail {f!r}: more than one positional value")
+        else:
+            v = part
+        n = v
+    if not _DEC_RE.match(n):
+        raise Unsupported(f"thumbnail {n!r}: not a decimal integer (expressions are not GPU-accelerated)")
+    if int(n) < 2:
+        raise Unsupported(f"thumbnail {n}: FFmpeg rejects a group below 2 frames")
+    return int(n)
+
+
+def thumbnail_pick(hists) -> int:
+    """vf_thumbnail.c's selection among the n frames of a group: `hists` is n rows of 768
+    counters, and the pick is the first frame whose sum of squared differences from the mean row is smallest.
+    Python floats are C doubles, and the order is the filter's: the mean column by column, each a sum over
+    the frames in order divided by n; then per frame a sequential sum over j = 0..767 of d * d with d = avg[j] -
+    hist[i][j]; a strict `<`, so ties go to the earliest frame (n = 2: both errors are equal, frame 0)."""
+    rows = [[float(v) for v in h] for h in hists]
+    n = len(rows)
+    if not n:
+        raise ValueError("thumbnail_pick: no frame")
+    avg = []
+    for j in range(len(rows[0])):
+        a = 0.0
+        for i in range(n):
+            a += rows[i][j]
+        avg.append(a / n)
+    best, best_e = 0, 0.0
+    for i in range(n):
+        e = 0.0
+        row = rows[i]
+        for j in range(len(avg)):
+            d = avg[j] - row[j]
+            e += d * d
+        if i == 0 or e < best_e:
+            best, best_e = i, e
+    return best
+
+
 def _take_sheet(fs, out):
-    """A framestep as the very first filter and a tile as the very last one, taken off before the other
-    stages see the list.  A graph that names neither is left exactly as it is."""
+    """A framestep as the very first filter, a thumbnail as the first or directly behind that framestep, and
+    a tile as the very last one, taken off before the other stages see the list.  A graph that names none of
+    them is left exactly as it is."""
     names = _names(fs)
-    if "tile" not in names and "framestep" not in names:
+    if "tile" not in names and "framestep" not in names and "thumbnail" not in names:
         return
     vf = _graph(fs)
+    if "thumbnail" in names:
+        at = names.index("thumbnail")
+        if names.count("thumbnail") > 1:
+            raise Unsupported(f"filter graph {vf!r}: a second thumbnail (one thumbnail, in front, is GPU-accelerated)")
+        if at and not (at == 1 and names[0] == "framestep"):
+            raise Unsupported(f"filter graph {vf!r}: thumbnail after {names[at - 1]} (thumbnail is GPU-accelerated only as "
+                              f"the first filter, or directly behind a leading framestep)")
+        if "yadif" in names:
+            raise Unsupported(f"filter graph {vf!r}: thumbnail together with yadif (the deinterlacer would need the "
+                              f"dropped frames' neighbours)")
+        if names[-1] != "tile":
+            raise Unsupported(f"filter graph {vf!r}: thumbnail without a tile as the last filter (thumbnail keeps its "
+                              f"link's frame rate and emits sparse timestamps, which MkvWriter does not write)")
     if "framestep" in names:
         if names.count("framestep") > 1:
             raise Unsupported(f"filter graph {vf!r}: a second framestep (one framestep, as the first filter, is "
@@ -665,6 +747,8 @@ def _take_sheet(fs, out):
         step = _parse_framestep(fs.pop(0)[1])
         if step > 1:
             out["framestep"] = step
+    if fs and fs[0][0] == "thumbnail":
+        out["thumbnail"] = _parse_thumbnail(fs.pop(0)[1])
     if fs and fs[-1][0] == "tile":
         out["tile"] = _parse_tile(fs.pop()[1])
 
@@ -808,7 +892,8 @@ GRAPH_STAGES = (_take_sheet, _take_colormatrix, _take_eq, _take_deint, _take_ori
 
 def parse_graph(vf: str) -> dict:
     """A -vf value -> the chain fields of Profile that the graph sets, by name (crop, scale,
-    sws_flags, pad, orient, deint, unsharp, eq, colormatrix, and SheetProfile's tile and framestep; a field
+    sws_flags, pad, orient, deint, unsharp, eq, colormatrix, SheetProfile's tile and framestep and ThumbProfile's
+    thumbnail; a field
     the graph does not set is left out, so Profile's own defaults are the only ones), or Unsupported."""
     if ";" in vf:
         raise Unsupported(f"filter graph {vf!r} (only crop, scale or crop,scale is GPU-accelerated)")
@@ -993,7 +1078,8 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
     if rst:
         huff = "default"  # mjpegenc.c: slice_context_count > 1 forces HUFFMAN_TABLE_DEFAULT
     # (a SheetProfile exactly when the winning graph names a tile or a framestep above 1)
-    cls = SheetProfile if "tile" in chain or "framestep" in chain else Profile
+    # (and a ThumbProfile exactly when it names a thumbnail)
+    cls = ThumbProfile if "thumbnail" in chain else SheetProfile if "tile" in chain or "framestep" in chain else Profile
     return cls(qscale=effective_qscale(q), q_arg=q, huffman=huff, rst=rst, chroma=chroma, **chain)
 
 

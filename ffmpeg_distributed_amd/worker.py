@@ -54,6 +54,13 @@ go to the real ffmpeg.  A `framestep=N` as the first filter never reaches the GP
 frame i of the segment when i % N == 0 and passes over the rest (Source.skip, which reads nothing of
 them from a regular file), and the output runs at the input rate / N.  Such a graph resolves to a
 SheetPlan; every other graph to the SegmentPlan it always did.
+A `thumbnail=N` in front of such a graph (profile.ThumbProfile; a ThumbPlan) never reaches the encoder either:
+the reader collects every N frames (behind the framestep) in a page-locked group store, has the GPU count
+their histograms as they arrive (encoder.FrameHist, an object with a stream of its own, so the reader thread
+uses it while the submit thread owns the encoder), selects one with profile.thumbnail_pick when the group
+closes or the input ends, and copies that frame into the batch (Pipeline.read_thumb).  The submit side sees a
+plain frame sequence, and the output runs at the rate it has without the thumbnail, as the filter leaves its
+link's frame rate alone; thumbnail_fallthrough_reason names the inputs that still go to the real ffmpeg.
 All of this is resolved against the segment's input by plan_segment, a pure function, before run()
 binds to the GPU's NUMA node: a SegmentPlan, a Fallthrough (the real ffmpeg) or a CropError / PadError.
 run() is then a sequence: Context.acquire opens the encoder and its page-locked buffers (or takes the serve
@@ -794,6 +801,34 @@ class SheetPlan(SegmentPlan):
         return super().key(prof, info, com_itu601, batch) + (("sheet", self.sheet),)
 
 
+THUMB_MAX_STORE = 2 << 30  # bytes of page-locked host memory a group may take (a guard, not a measured limit)
+
+
+def thumbnail_fallthrough_reason(prof, info) -> Optional[str]:
+    """Why a graph with a `thumbnail` runs on the CPU for this input, or None: the group store holds N decoded
+    frames in page-locked host memory (100 4K 4:2:0 frames are 1.24 GB), and the histograms are of 8-bit
+    samples."""
+    hs, vs = _CHROMA_SHIFTS[str(info.chroma)]
+    eight = info.width * info.height + 2 * ((info.width + hs) >> hs) * ((info.height + vs) >> vs)
+    if info.frame_bytes != eight:
+        return (f"thumbnail of an input of {info.frame_bytes} bytes a frame ({eight} at 8 bits): more than 8 bits a "
+                f"sample are not GPU-accelerated")
+    if prof.thumbnail * info.frame_bytes > THUMB_MAX_STORE:
+        return (f"thumbnail={prof.thumbnail} of {info.width}x{info.height} {info.chroma} frames: a group of "
+                f"{prof.thumbnail * info.frame_bytes} bytes, beyond the {THUMB_MAX_STORE} bytes of the page-locked group store")
+    return None
+
+
+@dataclass(frozen=True, eq=False)
+class ThumbPlan(SheetPlan):
+    """The plan of a profile.ThumbProfile: a SheetPlan whose reader keeps one frame of every `thumbnail`.  The
+    rate, the batch and the encoder are the SheetPlan's: the filter does not change its link's frame rate."""
+    thumbnail: int = 100
+
+    def key(self, prof, info, com_itu601, batch):
+        return super().key(prof, info, com_itu601, batch) + (("thumbnail", self.thumbnail),)
+
+
 def plan_segment(prof, info) -> SegmentPlan:
     """Resolve a profile against a segment's input (container.StreamInfo): no device, no streams.
     Raises Fallthrough(reason) for a segment the CPU ffmpeg runs, and lets profile.CropError /
@@ -852,10 +887,16 @@ def plan_segment(prof, info) -> SegmentPlan:
             n = t["nb_frames"] or t["cols"] * t["rows"]
             sheet = (t["cols"], t["rows"], n, t["margin"], t["padding"])
             enc_w, enc_h = sheet_size(dst_w, dst_h, t)
-        return SheetPlan(src_chroma=src_chroma, dst_chroma=dst_chroma, deint=deint, orient=orient, rect=rect,
-                         in_size=in_size, dst_w=dst_w, dst_h=dst_h, pad=pad, enc_w=enc_w, enc_h=enc_h,
-                         unsharp=prof.unsharp, lut_in=lut_in, lut_out=lut_out, cmat=cmat, sar=sar,
-                         sheet=sheet, framestep=prof.framestep, out_fps=Fraction(info.fps) / (prof.framestep * n))
+        cls, more = SheetPlan, {}
+        if isinstance(prof, profile.ThumbProfile):  # -vf [framestep=S,]thumbnail=N,...,tile: one frame of every N, picked by the reader
+            why = thumbnail_fallthrough_reason(prof, info)
+            if why is not None:
+                raise Fallthrough(why)
+            cls, more = ThumbPlan, dict(thumbnail=prof.thumbnail)
+        return cls(src_chroma=src_chroma, dst_chroma=dst_chroma, deint=deint, orient=orient, rect=rect,
+                   in_size=in_size, dst_w=dst_w, dst_h=dst_h, pad=pad, enc_w=enc_w, enc_h=enc_h,
+                   unsharp=prof.unsharp, lut_in=lut_in, lut_out=lut_out, cmat=cmat, sar=sar,
+                   sheet=sheet, framestep=prof.framestep, out_fps=Fraction(info.fps) / (prof.framestep * n), **more)
     return SegmentPlan(src_chroma=src_chroma, dst_chroma=dst_chroma, deint=deint, orient=orient, rect=rect,
                        in_size=in_size, dst_w=dst_w, dst_h=dst_h, pad=pad, enc_w=enc_w, enc_h=enc_h,
                        unsharp=prof.unsharp, lut_in=lut_in, lut_out=lut_out, cmat=cmat, sar=sar)
@@ -871,6 +912,8 @@ class Pipeline:
     submit(arr, n, halo=), sync(), last_total and fetch_into(buf); `bufs` through .array; `obufs` (a list
     filled and regrown here; None: not made yet) through .nbytes, .free() and what fetch_into needs;
     `new_obuf(nbytes)` makes one.  `batch` frames a submit, every `step`-th frame kept, `deint`: halo submits.
+    `thumb` (a ThumbPlan): (hist, store, N), `hist` used through count(frames, nframes) -> (n, 768) counters,
+    `store` a page-locked buffer of N frames through .array; the reader keeps one frame of every N.
 
     The reader fills one batch while two are queued on the GPU (the encoder takes a second submit before
     the first is synced, so its kernels run back to back); a batch returns to the reader as soon as its
@@ -878,8 +921,11 @@ class Pipeline:
     the fetch.  The reader posts (buffer, encoded frames, halo bits) to `full`, None at the end of the
     input, or the exception that stopped it.  After run(), failed or not, comes stop()."""
 
-    def __init__(self, enc, bufs, obufs, new_obuf, src, mkv, prog, batch: int, step: int = 1, deint: bool = False):
+    def __init__(self, enc, bufs, obufs, new_obuf, src, mkv, prog, batch: int, step: int = 1, deint: bool = False,
+                 thumb=None):
         self.enc, self.bufs, self.obufs, self.new_obuf = enc, bufs, obufs, new_obuf
+        self.thumb = thumb
+        self.gn, self.ghists = 0, []  # read_thumb: the open group's frames in the store and their histograms
         self.src, self.mkv, self.prog = src, mkv, prog
         self.batch, self.step, self.deint, self.fb = batch, step, deint, enc.frame_bytes
         self.done = self.nread = 0  # read_deint: frames encoded and frames read so far
@@ -915,6 +961,37 @@ class Pipeline:
             self.src.skip(self.step - 1)
         return n, 0, n < self.batch
 
+    def read_thumb(self, i):
+        """-vf [framestep=S,]thumbnail=N: the frames kept by the framestep go into the group store, in runs of at
+        most a batch, each counted by the GPU as it arrives (hist.count, synchronous, on its own stream); when the
+        store holds N frames, or the input ends with at least one in it, profile.thumbnail_pick selects one and it
+        is copied into the batch buffer.  Groups restart with the segment."""
+        hist, store, N = self.thumb
+        arr, fb, n, eof = self.bufs[i].array, self.fb, 0, False
+        while n < self.batch and not eof:
+            while self.gn < N:
+                run = min(self.batch, N - self.gn)
+                dst = store.array[self.gn * fb:(self.gn + run) * fb]
+                if self.step > 1:
+                    got = 0
+                    while got < run and self.src.read_into(dst[got * fb:(got + 1) * fb], 1) == 1:
+                        got += 1
+                        self.src.skip(self.step - 1)
+                else:
+                    got = self.src.read_into(dst, run)
+                if got:
+                    self.ghists.extend(hist.count(dst[:got * fb], got))
+                    self.gn += got
+                if got < run:
+                    eof = True
+                    break
+            if self.gn:  # the group is closed: N frames, or what was left of the input
+                k = profile.thumbnail_pick(self.ghists)
+                arr[n * fb:(n + 1) * fb] = store.array[k * fb:(k + 1) * fb]
+                n += 1
+                self.gn, self.ghists = 0, []
+        return n, 0, eof
+
     def read_deint(self, i):
         """A deinterlaced segment: a batch needs the frame in front of it and the one behind it, so the
         reader keeps one frame of look-ahead and every buffer but the first starts with the previous
@@ -938,9 +1015,10 @@ class Pipeline:
         return n, int(hp) | int(hn) << 1, eof
 
     def reader(self):
-        """The reader thread: one of the three strategies above fills buffer i and returns (encoded
+        """The reader thread: one of the four strategies above fills buffer i and returns (encoded
         frames, halo bits, end of input)."""
-        read = self.read_deint if self.deint else self.read_step if self.step > 1 else self.read_plain
+        read = (self.read_thumb if self.thumb else self.read_deint if self.deint else self.read_step if self.step > 1
+                else self.read_plain)
         try:
             while True:
                 i = self.free.get()
@@ -1067,8 +1145,11 @@ class Pipeline:
 
 class Context:
     """An encoder context with its page-locked buffers: NBUF batch buffers and NOUT output buffers, the
-    latter made and regrown by the pipeline that fetches into them.  acquire() opens one or takes the
-    serve / resident cache's, settle() decides after the segment whether it is kept, freed or leaked."""
+    latter made and regrown by the pipeline that fetches into them.  Under a ThumbPlan also the histogram
+    object and the page-locked group store of N frames, which the reader thread alone uses.  acquire() opens
+    one or takes the serve / resident cache's, settle() decides after the segment whether it is kept, freed or
+    leaked."""
+    hist = store = None
 
     def __init__(self, device: int, prof, info, plan: SegmentPlan, batch: int, com_itu601: bool):
         from .encoder import MjpegEncoder, PinnedBuffer   # GPU work starts here
@@ -1079,6 +1160,15 @@ class Context:
         self.bufs = [PinnedBuffer((batch + (2 if plan.deint else 0)) * self.enc.frame_bytes) for _ in range(NBUF)]
         self.obufs = [None] * NOUT
         self.new_obuf = PinnedBuffer
+        n = getattr(plan, "thumbnail", 0)
+        if n:
+            from .encoder import FrameHist
+            self.hist = FrameHist(device, info.width, info.height, plan.src_chroma, batch)
+            self.store = PinnedBuffer(n * self.enc.frame_bytes)
+
+    def thumb(self, plan):
+        """Pipeline's `thumb` for this context: (hist, store, N) under a ThumbPlan, else None."""
+        return None if self.hist is None else (self.hist, self.store, plan.thumbnail)
 
     @classmethod
     def acquire(cls, cache, device: int, prof, info, plan: SegmentPlan, batch: int, com_itu601: bool) -> "Context":
@@ -1109,7 +1199,9 @@ class Context:
 
     def free(self, bufs: bool = True, obufs: bool = True) -> None:
         self.enc.close()
-        for b in (self.bufs if bufs else []) + (self.obufs if obufs else []):
+        if self.hist is not None and bufs:  # (a stuck reader may be inside a count)
+            self.hist.close()
+        for b in (self.bufs + [self.store] if bufs else []) + (self.obufs if obufs else []):
             if b is not None:
                 b.free()
 
@@ -1169,7 +1261,8 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
     prog = Progress(stderr, out_fps, prof.qscale)
     prog.duration(src.duration)
     mkv = container.MkvWriter(stdout, plan.enc_w, plan.enc_h, out_fps, plan.sar)
-    pipe = Pipeline(ctx.enc, ctx.bufs, ctx.obufs, ctx.new_obuf, src, mkv, prog, batch, plan.framestep, bool(plan.deint))
+    pipe = Pipeline(ctx.enc, ctx.bufs, ctx.obufs, ctx.new_obuf, src, mkv, prog, batch, plan.framestep, bool(plan.deint),
+                    ctx.thumb(plan))
     t_seg = time.monotonic()
     try:
         pipe.run()

@@ -20,7 +20,10 @@
  * before the scale, the crop group: a rectangle of the decoded frames; `unsharp` behind the scale and
  * in front of the pad, unsharp: the sharpen, a restatement of vf_unsharp.c's 8-bit path that no
  * FFmpeg build has been compared with yet; `pad=...` as the last filter, the pad group: the picture
- * on a black canvas)
+ * on a black canvas; `tile=...` as the last filter is mjg_sheet, and the `thumbnail=N` in front of a
+ * storyboard's chain is no stage at all: mjg_hist counts the decoded frames' histograms and the
+ * caller selects, a restatement of vf_thumbnail.c's planar path that no FFmpeg build has been
+ * compared with yet)
  * this library replaces the arithmetic that worker runs (swscale bicubic + tv->pc
  * range conversion, jfdctint + quantiser + default-table Huffman + 0xFF stuffing)
  * and the Python host code in ffmpeg_distributed_amd/ (worker.py, dispatcher.py)
@@ -439,6 +442,29 @@ int mjg_ctx_queue_depth(const mjg_ctx *ctx);
 /* Pinned host memory for mjg_submit / mjg_fetch. */
 int mjg_host_alloc(size_t bytes, void **ptr);
 int mjg_host_free(void *ptr);
+
+/* Per-frame histograms of decoded frames (k_frame_hist), what `-vf thumbnail` selects its frames by.
+ * An object of its own, not a stage of a context: the worker's reader thread counts while its submit
+ * thread owns the mjg_ctx, and one ctx belongs to one thread.  It knows histograms, not the filter, as
+ * mjg_lut knows tables: the selection (FFmpeg's vf_thumbnail.c, restated in DESIGN §4.18 and profile.py's
+ * thumbnail_pick; no FFmpeg build has been compared with it yet) is the caller's.
+ *   Frames are w x h, 8 bits, packed planar in chroma_format (MJG_CHROMA_*), the decoder's bytes with
+ * no range conversion, frame_bytes apart at any byte alignment.  hist[f][256 p + v] is the number of
+ * samples of value v in plane p (0 Y, 1 U, 2 V) of frame f, each plane at its own size.
+ *   The object owns a stream, a device buffer of max_frames frames for host input, and the device and
+ * page-locked histogram buffers.  mjg_hist_frames is synchronous: H2D copy (asynchronous from
+ * mjg_host_alloc memory; src_is_device: none, the frames are read where they lie), zero, one launch,
+ * D2H copy, wait; every call starts from zero.  It touches no mjg_ctx and may run beside one's calls
+ * from another thread; one mjg_hist per caller thread.
+ *   MJG_E_INVALID with a message that starts with "hist", before any HIP call: a null pointer, w or h
+ * outside 1..16384, a chroma_format that is no MJG_CHROMA_* value, max_frames below 1 (or so many that
+ * workgroups per frame x frames passes 2^31 - 1), nframes outside 1..max_frames.  (Added without a
+ * version step, as mjg_open_chain.) */
+typedef struct mjg_hist mjg_hist;
+int mjg_hist_open(int device, int w, int h, int chroma_format, int max_frames, mjg_hist **out);
+int mjg_hist_frames(mjg_hist *h, const uint8_t *frames, int nframes, int src_is_device,
+                    uint32_t *hist /* host, [nframes][768] */);
+void mjg_hist_close(mjg_hist *h);
 
 /* Average device time (ms) per launch of each kernel (MJG_K_*) since the last reset,
  * and the number of submits it was averaged over.  Needs MJG_F_TIMING. */

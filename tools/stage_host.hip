@@ -6,7 +6,7 @@
 // wrong per-submit adjustment is walked as the GPU would run it.  Every buffer is allocated at exactly the size the
 // plan's frame bytes give, so that AddressSanitizer sees any access outside a readable frame; a refused
 // configuration is exit status 5 with the library's message.  Makes no HIP call.  Built and driven by
-// tools/host_check.py for the five *_host_check.py scripts:
+// tools/host_check.py for the six *_host_check.py scripts:
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -I include \
 //     -I ffmpeg_distributed_amd/csrc -o stage_host tools/stage_host.hip ffmpeg_distributed_amd/csrc/sws_filter.cpp
 // Frames are packed planar with chroma shifts hshift, vshift.  split: 0, or the lengths of up to kMaxSegs segments as
@@ -30,6 +30,10 @@
 //     besides that every staged load (a byte, or a dword of four consecutive bytes) lies inside the picture, that
 //     every other load is the copy of a sample outside it (or of a plane whose amount is 0) from its own place, and
 //     that every byte of every plane of every frame is stored exactly once; LDS arrays at exactly the kernel's sizes.
+//   stage_host hist IN OUT w h hshift vshift nframes split lead
+//     k_frame_hist over the launch that hist_plan (mjg_hist_open's plan, no mjg_ctx) gives; OUT: nframes x 768
+//     uint32 counters; lead: the frames (each segment's) start this many bytes into their allocation (0..15: the
+//     alignment of the source, which the pieces are cut on); the LDS histogram at exactly the kernel's size.
 #include "api.hip"
 
 #include <cstdio>
@@ -237,6 +241,32 @@ int tile(int argc, char **a) {
   return 0;
 }
 
+int hist(int argc, char **a) {
+  if (argc < 9) return 2;
+  const int w = atoi(a[2]), h = atoi(a[3]), hs = atoi(a[4]), vs = atoi(a[5]), n = atoi(a[6]), lead = atoi(a[8]);
+  const std::vector<int> lens = lengths(a[7]);
+  HistGeom g;
+  size_t fb;
+  if (hist_plan(w, h, !hs ? MJG_CHROMA_444 : vs ? MJG_CHROMA_420 : MJG_CHROMA_422, n, &g, &fb)) {
+    fprintf(stderr, "refused: %s\n", mjg_last_error());
+    exit(5);
+  }
+  Input in = load(a[0], fb, n, 0, lead, lens, lead);
+  uint32_t *out = (uint32_t *)calloc((size_t)n * 768, sizeof(uint32_t));
+  uint32_t *lh = (uint32_t *)malloc(sizeof(uint32_t) * 256 * kHistCopies);  // the kernel's LDS, at exactly its size
+  for (int t = 0; t < g.gpf * n; t++) {  // the two steps, thread by thread, with the workgroup barrier between them
+    memset(lh, 0, sizeof(uint32_t) * 256 * kHistCopies);
+    for (int tid = 0; tid < kHistThreads; tid++) hist_count(in.sl, lh, g, t, tid);
+    for (int tid = 0; tid < kHistThreads; tid++) hist_flush(lh, out, g, t, tid);
+  }
+  save(a[1], (const uint8_t *)out, (size_t)n * 768 * sizeof(uint32_t));
+  printf("%d workgroups a frame (Y %d, U and V %d each), %d frames\n", g.gpf, g.gy, g.gc, n);
+  for (uint8_t *b : in.bufs) free(b);
+  free(out);
+  free(lh);
+  return 0;
+}
+
 long g_loads = 0, g_copies = 0;
 
 template <int MX, int MY>
@@ -328,9 +358,9 @@ int main(int argc, char **argv) {
   const struct {
     const char *name;
     int (*run)(int, char **);
-  } stages[] = {{"yadif", yadif}, {"lut", lut}, {"cmat", cmat}, {"tile", tile}, {"unsharp", unsharp}};
+  } stages[] = {{"yadif", yadif}, {"lut", lut}, {"cmat", cmat}, {"tile", tile}, {"unsharp", unsharp}, {"hist", hist}};
   for (const auto &s : stages)
     if (argc > 1 && !strcmp(argv[1], s.name)) return s.run(argc - 2, argv + 2);
-  fprintf(stderr, "usage: stage_host yadif|lut|cmat|tile|unsharp ...\n");
+  fprintf(stderr, "usage: stage_host yadif|lut|cmat|tile|unsharp|hist ...\n");
   return 2;
 }
