@@ -51,6 +51,7 @@ EXPORTS = (
     "mjg_open_chain",
     "mjg_open_sheet", "mjg_frames_out", "mjg_debug_sheet", "mjg_debug_cell",
     "mjg_hist_open", "mjg_hist_frames", "mjg_hist_close",
+    "mjg_open_denoise", "mjg_submit_cont", "mjg_debug_denoise", "mjg_debug_denoise_state",
 )
 
 # mjg_open_deint's `deint`
@@ -120,6 +121,11 @@ class MjgSheet(C.Structure):
     """mjg_sheet: -vf tile's contact sheet behind the chain (mjg_open_sheet); nb_frames 0 is cols * rows."""
     _fields_ = [("cols", C.c_int32), ("rows", C.c_int32), ("nb_frames", C.c_int32), ("margin", C.c_int32),
                 ("padding", C.c_int32)]
+
+
+class MjgDenoise(C.Structure):
+    """mjg_denoise: -vf hqdn3d's four tables (luma / chroma spatial, luma / chroma temporal) behind the deinterlacer."""
+    _fields_ = [("ls", C.c_int16 * 8192), ("cs", C.c_int16 * 8192), ("lt", C.c_int16 * 8192), ("ct", C.c_int16 * 8192)]
 
 
 _lib = None
@@ -204,6 +210,16 @@ def load():
             L.mjg_hist_frames.restype = C.c_int
             L.mjg_hist_close.argtypes = [vp]
             L.mjg_hist_close.restype = None
+        if hasattr(L, "mjg_open_denoise"):  # absent from libraries built before the denoiser (A/B builds)
+            L.mjg_open_denoise.argtypes = [C.c_int, C.POINTER(MjgConfig), C.POINTER(MjgChain), C.POINTER(MjgSheet),
+                                           C.POINTER(MjgDenoise), C.POINTER(vp)]
+            L.mjg_open_denoise.restype = C.c_int
+            L.mjg_submit_cont.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]
+            L.mjg_submit_cont.restype = C.c_int
+            L.mjg_debug_denoise.argtypes = [vp, C.c_int, u8p, sz]
+            L.mjg_debug_denoise.restype = C.c_int
+            L.mjg_debug_denoise_state.argtypes = [vp, C.POINTER(C.c_uint16), sz]
+            L.mjg_debug_denoise_state.restype = C.c_int
         L.mjg_close.argtypes = [vp]
         L.mjg_close.restype = None
         L.mjg_frame_bytes.argtypes = [vp]
@@ -259,7 +275,8 @@ def load():
                  "mjg_open_lut", "mjg_debug_lut", "mjg_debug_lut_in", "mjg_debug_tail",
                  "mjg_open_cmat", "mjg_debug_cmat", "mjg_debug_cmat_out", "mjg_open_chain",
                  "mjg_open_sheet", "mjg_frames_out", "mjg_debug_sheet", "mjg_debug_cell",
-                 "mjg_hist_open", "mjg_hist_frames", "mjg_hist_close")
+                 "mjg_hist_open", "mjg_hist_frames", "mjg_hist_close",
+                 "mjg_open_denoise", "mjg_submit_cont", "mjg_debug_denoise", "mjg_debug_denoise_state")
                 if os.environ.get("MJG_LIBRARY") else ())
         for name in EXPORTS:
             if name not in late:

@@ -169,6 +169,18 @@ SegList one_seg(const uint8_t *p) {
   return sl;
 }
 
+// a launch's frames in one buffer, frame f at p + f * frame_bytes, with the segment starts of `in`: for a stage
+// that reads another stage's buffer and still treats every segment as a sequence of its own
+SegList seg_starts(const SegList &in, const uint8_t *p, size_t frame_bytes) {
+  SegList sl;
+  for (int k = 0; k < kMaxSegs; k++) {
+    const bool used = in.f0[k] != INT_MAX;
+    sl.f0[k] = in.f0[k];
+    sl.p[k] = used ? p + (size_t)in.f0[k] * frame_bytes : p;
+  }
+  return sl;
+}
+
 // an environment switch, read at open
 int env_int(const char *name, int unset) {
   const char *e = getenv(name);
@@ -276,6 +288,9 @@ struct Slot {
   uint8_t *d_sharp = nullptr;      // -vf unsharp: k_unsharp_plane's output, the encoder's input
   uint8_t *d_lut = nullptr;        // a table in front of the sws stage on a caller's frames: k_lut_plane's output frames
   uint8_t *d_tile = nullptr;       // -vf tile: k_tile_plane's output, the sheets, the encoder's input
+  uint16_t *d_dn16 = nullptr;      // -vf hqdn3d: P, then V, of every frame (DnGeom's uint16 layout)
+  uint8_t *d_dn = nullptr;         // ... and k_dn_time's output, the denoised frames
+  hipEvent_t dn_done = nullptr;    // ... recorded behind k_dn_time: the next submit's time scan waits for it
   uint32_t *d_stage_bits = nullptr;  // k_encode: per wave, lane-major staging of blocks past 128 bits
   int n = 0;  // frames of the launch (under a sheet: the sheets, the frames k_encode codes)
   int nin = 0;  // ... and its input frames (the same without a sheet)
@@ -349,6 +364,20 @@ struct mjg_ctx {
   bool sheet = false;
   mjg_sheet sh{};               // nb_frames resolved (1..cols rows)
   TileGeom tpass[2];            // its launches: 0 luma, 1 chroma
+  // -vf hqdn3d (mjg_open_denoise): behind the deinterlacer and in front of the orientation, on whole frames
+  // in the source format; the orientation, cmat / lut_in in place, the sws stage or k_encode read d_dn.
+  // The time scan's state lives here, one frame of uint16, and goes from submit to submit (mjg_submit_cont);
+  // dn_last is the event behind the last submit's k_dn_time, which the next one's stream waits for.  Every
+  // submit is a sequence of its own or a piece of one: no merging
+  bool dn = false;
+  std::vector<mjg_denoise> dn_tabs; // host copy of the tables (one, or none)
+  DnGeom dnpass[2];             // its geometry: 0 luma, 1 chroma (the three kernels' grids: dn_grids)
+  int dn_grid[2][3] = {};       // workgroups per (plane, frame) of k_dn_rows, k_dn_cols; per plane of k_dn_time
+  size_t dn_felems = 0;         // uint16 elements of a frame of d_dn16
+  int16_t *d_dn_tabs = nullptr;
+  uint16_t *d_dn_state = nullptr;
+  hipEvent_t dn_last = nullptr;
+  bool dn_started = false;      // a submit has written the state
   size_t in_frame_bytes = 0, enc_frame_bytes = 0;
   // the sws stage's output frame (the picture, the canvas under a pad; k_encode's input without a
   // sheet): its bytes, its U plane's offset and the bytes of a chroma plane
@@ -410,13 +439,13 @@ void free_ctx(mjg_ctx *c) {
   for (hipStream_t st : c->more)
     if (st) (void)hipStreamSynchronize(st);
   if (c->tail) (void)hipStreamSynchronize(c->tail);
-  void *ptrs[] = {c->d_tabs, c->d_hdr, c->d_luts, c->ps[0].hcp,
+  void *ptrs[] = {c->d_tabs, c->d_hdr, c->d_luts, c->d_dn_tabs, c->d_dn_state, c->ps[0].hcp,
                   c->ps[0].vcp, c->ps[0].hp, c->ps[0].vps, c->ps[1].hcp, c->ps[1].vcp, c->ps[1].hp,
                   c->ps[0].hsum, c->ps[1].hsum, c->ps[1].vps, c->ps[0].mfb, c->ps[1].mfb};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (Slot &S : c->slot) {
-    void *sp[] = {S.d_stage, S.d_scaled, S.d_orient, S.d_deint, S.d_sharp, S.d_lut, S.d_tile, S.d_stage_bits, S.d_scratch, S.d_stream, S.d_work, S.d_chunk_bits, S.d_chunk_off, S.d_group_ff, S.d_ff_off, S.d_frame_bits,
+    void *sp[] = {S.d_stage, S.d_scaled, S.d_orient, S.d_deint, S.d_sharp, S.d_lut, S.d_tile, S.d_dn16, S.d_dn, S.d_stage_bits, S.d_scratch, S.d_stream, S.d_work, S.d_chunk_bits, S.d_chunk_off, S.d_group_ff, S.d_ff_off, S.d_frame_bits,
                   S.d_status, S.d_frame_size, S.d_frame_offsets, S.d_seg_size, S.d_seg_off, S.d_done, S.d_out,
                   S.d_hist, S.d_ftabs, S.d_dht_nval, S.d_hdr_lens, S.d_dht, S.d_dbg, S.d_syms, S.d_symn};
     for (void *p : sp)
@@ -425,6 +454,7 @@ void free_ctx(mjg_ctx *c) {
     if (S.h_status) (void)hipHostFree(S.h_status);
     if (S.done) (void)hipEventDestroy(S.done);
     if (S.enc_done) (void)hipEventDestroy(S.enc_done);
+    if (S.dn_done) (void)hipEventDestroy(S.dn_done);
     for (auto &e : S.ev) {
       if (e[0]) (void)hipEventDestroy(e[0]);
       if (e[1]) (void)hipEventDestroy(e[1]);
@@ -480,6 +510,7 @@ struct Layout {
   bool has_sheet;              // a contact sheet behind the sws stage (check_sheet; false for the trivial one)
   mjg_sheet sheet;             // ... nb_frames resolved
   int tw, th;                  // ... and its size, the encoded frame's
+  const mjg_denoise *dn;       // the denoiser's tables (mjg_open_denoise; null: none)
 };
 
 // A plane's filter tables as the kernels read them (plan_plane_scale), before their upload
@@ -690,7 +721,9 @@ int alloc_slot(mjg_ctx *c, Slot &S) {
   if (c->orient && (rc = dmalloc(&S.d_orient, BI * c->in_frame_bytes))) return rc;
   if (c->deint && (rc = dmalloc(&S.d_deint, BI * c->in_frame_bytes))) return rc;
   if (c->sharp && (rc = dmalloc(&S.d_sharp, BI * c->pic_frame_bytes))) return rc;
-  if ((c->has_lut[0] || c->has_cmat) && !c->orient && !c->deint && (rc = dmalloc(&S.d_lut, BI * c->in_frame_bytes))) return rc;
+  if ((c->has_lut[0] || c->has_cmat) && !c->orient && !c->deint && !c->dn && (rc = dmalloc(&S.d_lut, BI * c->in_frame_bytes))) return rc;
+  if (c->dn && ((rc = dmalloc(&S.d_dn16, BI * c->dn_felems)) || (rc = dmalloc(&S.d_dn, BI * c->in_frame_bytes)))) return rc;
+  if (c->dn) HIP_TRY(hipEventCreateWithFlags(&S.dn_done, hipEventDisableTiming));
   if (c->sheet && (rc = dmalloc(&S.d_tile, B * c->enc_frame_bytes))) return rc;
   if ((rc = dmalloc(&S.d_scratch, B * NC * (size_t)kSlotWords)) ||
       (rc = dmalloc(&S.d_stream, B * NC * (size_t)kSlotWords)) ||
@@ -849,6 +882,7 @@ int check_config(const mjg_config &k, const mjg_chain &ch, Layout *lay) {
   l.has_pad = has_pad;
   l.s_hsh = s_hsh, l.s_vsh = s_vsh, l.hsh = e_hsh, l.vsh = e_vsh;
   l.has_sheet = false, l.sheet = mjg_sheet{}, l.tw = l.th = 0;
+  l.dn = nullptr;
   return MJG_OK;
 }
 
@@ -879,6 +913,17 @@ int check_sheet(const mjg_config &k, const mjg_sheet *sp, Layout *lay) {
   lay->sheet = s;
   if (!s.nb_frames) lay->sheet.nb_frames = (int)cells;
   lay->tw = (int)W, lay->th = (int)H;
+  return MJG_OK;
+}
+
+// open, step 1c: the denoiser (mjg_open_denoise; null: none) on the layout the two steps above resolved.
+// The tables are taken as they are: the kernels clamp every index, so no table can make an address.
+int check_denoise(const mjg_denoise *dn, Layout *lay) {
+  if (!dn) return MJG_OK;
+  if (lay->has_sheet)
+    return set_err(MJG_E_INVALID, "denoise in front of a sheet (%dx%d): a denoiser context has no contact sheet",
+                   lay->sheet.cols, lay->sheet.rows);
+  lay->dn = dn;
   return MJG_OK;
 }
 
@@ -1237,6 +1282,35 @@ void plan_deint(const mjg_config &k, const Layout &lay, mjg_ctx *c) {
   }
 }
 
+// The denoiser's geometry for luma and chroma (mjg_ctx::dnpass, dn_grid, dn_felems; no device, no
+// environment): the decoded frame's planes in the source format -> the same planes of the denoised frame,
+// both packed planar and in_frame_bytes apart, through the uint16 layout of d_dn16 (rows a multiple of 64
+// elements apart).  dn_launch adds nf, cont, the kernel's grid and the U + V pairing.
+void plan_dn(const mjg_config &k, const Layout &lay, mjg_ctx *c) {
+  c->dn = lay.dn != nullptr;
+  if (!lay.dn) return;
+  c->dn_tabs.assign(1, *lay.dn);
+  const int cw = (k.src_w + lay.s_hsh) >> lay.s_hsh, ch = (k.src_h + lay.s_vsh) >> lay.s_vsh;
+  const int py = (k.src_w + 63) & ~63, pc = (cw + 63) & ~63;
+  c->dn_felems = (size_t)py * k.src_h + 2 * (size_t)pc * ch;
+  for (int p = 0; p < 2; p++) {
+    DnGeom &g = c->dnpass[p];
+    g = DnGeom{};
+    g.w = p ? cw : k.src_w, g.h = p ? ch : k.src_h;
+    g.pitch = p ? pc : py;
+    g.off = p ? (long long)k.src_w * k.src_h : 0;
+    g.fstride = (long long)c->in_frame_bytes;
+    g.off16 = p ? (long long)py * k.src_h : 0;
+    g.fstride16 = (long long)c->dn_felems;
+    g.tab = p;
+    g.w_magic = magic32((uint32_t)g.w);
+    c->dn_grid[p][0] = (g.h + 64 * kDnRowWaves - 1) / (64 * kDnRowWaves);
+    c->dn_grid[p][1] = (g.w + 8 * kDnColThreads - 1) / (8 * kDnColThreads);
+    const size_t pieces = ((size_t)g.w * g.h) >> 4;
+    c->dn_grid[p][2] = (int)std::max<size_t>(1, (pieces + kDnTimeThreads - 1) / kDnTimeThreads);
+  }
+}
+
 template <int MX, int MY>
 void launch_sharp(const SharpGeom &g, const uint8_t *src, uint8_t *dst, int nz, hipStream_t st) {
   k_unsharp_plane<MX, MY><<<g.gxy * nz, kSharpThreads, 0, st>>>(src, dst, g);
@@ -1380,7 +1454,7 @@ int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
   // merging (kMerge): opt-in with MJG_F_MERGE (a held submit's frames are read after mjg_submit
   // returns); MJG_MERGE=1 turns it off for a process (A/B), =2..4 sets the jobs per launch
   c->merge = (k.flags & MJG_F_MERGE) ? std::max(1, std::min(kMaxSegs, env_int("MJG_MERGE", kMerge))) : 1;
-  if (c->deint || c->sheet) c->merge = 1;  // a deint or a sheet context neither holds nor merges submits (mjgpu.h)
+  if (c->deint || c->sheet || c->dn) c->merge = 1;  // a deint, a denoise or a sheet context neither holds nor merges submits (mjgpu.h)
   c->hold_idle = env_int("MJG_MERGE_HOLD", 1) != 0;
   if (c->merge > 1) {  // slot buffers for merge * max_batch frames: within a share of free memory
     size_t fr = 0, tot = 0;
@@ -1410,6 +1484,11 @@ int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
   if (c->has_lut[0] || c->has_lut[1]) {
     if ((rc = dmalloc(&c->d_luts, 2 * sizeof(mjg_lut)))) return rc;
     HIP_TRY(hipMemcpy(c->d_luts, c->lut, 2 * sizeof(mjg_lut), hipMemcpyHostToDevice));
+  }
+  if (c->dn) {  // the four tables and the time scan's state (written before it is read: a first submit starts it)
+    if ((rc = dmalloc(&c->d_dn_tabs, 4 * (size_t)kDnTabLen)) || (rc = dmalloc(&c->d_dn_state, c->in_frame_bytes))) return rc;
+    HIP_TRY(hipMemcpy(c->d_dn_tabs, c->dn_tabs.data(), sizeof(mjg_denoise), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(c->d_dn_state, 0, c->in_frame_bytes * sizeof(uint16_t)));
   }
 
   if (c->scale) {
@@ -1448,12 +1527,13 @@ int open_device(mjg_ctx *c, const Layout &lay, const uint32_t *tabs) {
 // environment: unaligned_fetch is plan_geometry's).  A host program can call it on a `new mjg_ctx()`
 // and walk the launches the *_launch functions below make of the plan (tools/stage_host.hip).
 int plan_ctx(const mjg_config &k, const mjg_chain &chain, const mjg_sheet *sheet, bool unaligned_fetch, mjg_ctx *c,
-             Layout *lay) {
+             Layout *lay, const mjg_denoise *dn = nullptr) {
   int rc;
-  if ((rc = check_config(k, chain, lay)) || (rc = check_sheet(k, sheet, lay))) return rc;
+  if ((rc = check_config(k, chain, lay)) || (rc = check_sheet(k, sheet, lay)) || (rc = check_denoise(dn, lay))) return rc;
   if ((rc = plan_geometry(k, chain.src_chroma_format, *lay, unaligned_fetch, c))) return rc;
   plan_orient(k, *lay, c);
   plan_deint(k, *lay, c);
+  plan_dn(k, *lay, c);
   plan_sharp(k, *lay, c);
   plan_lut(k, *lay, c);
   plan_cmat(*lay, c);
@@ -1461,12 +1541,12 @@ int plan_ctx(const mjg_config &k, const mjg_chain &chain, const mjg_sheet *sheet
   return MJG_OK;
 }
 
-int open_ctx(int device, const mjg_config &k, const mjg_chain &chain, const mjg_sheet *sheet, mjg_ctx *c) {
+int open_ctx(int device, const mjg_config &k, const mjg_chain &chain, const mjg_sheet *sheet, const mjg_denoise *dn, mjg_ctx *c) {
   c->device = device;
   c->cfg = k;
   Layout lay;
   int rc;
-  if ((rc = plan_ctx(k, chain, sheet, env_int("MJG_UNALIGNED_FETCH", 1) != 0, c, &lay))) return rc;
+  if ((rc = plan_ctx(k, chain, sheet, env_int("MJG_UNALIGNED_FETCH", 1) != 0, c, &lay, dn))) return rc;
   quant_matrix(k.qscale, c->mprime, c->qmat);
   c->hdr = build_header(c->geom.w, c->geom.h, c->mprime, k.sar_num, k.sar_den, (k.flags & MJG_F_COM_ITU601) != 0,
                         k.chroma_format, c->rst, &c->dht_pos, &c->dht_end);
@@ -1549,10 +1629,15 @@ int mjg_open_chain(int device, const mjg_config *cfg, const mjg_chain *chain, mj
 }
 
 int mjg_open_sheet(int device, const mjg_config *cfg, const mjg_chain *chain, const mjg_sheet *sheet, mjg_ctx **out) {
+  return mjg_open_denoise(device, cfg, chain, sheet, nullptr, out);
+}
+
+int mjg_open_denoise(int device, const mjg_config *cfg, const mjg_chain *chain, const mjg_sheet *sheet,
+                     const mjg_denoise *dn, mjg_ctx **out) {
   if (!cfg || !chain || !out) return set_err(MJG_E_INVALID, "null argument");
   *out = nullptr;
   mjg_ctx *c = new mjg_ctx();
-  const int rc = open_ctx(device, *cfg, *chain, sheet, c);
+  const int rc = open_ctx(device, *cfg, *chain, sheet, dn, c);
   if (rc) {
     const std::string keep = g_err;
     free_ctx(c);
@@ -1665,7 +1750,7 @@ int mjg_header(const mjg_ctx *ctx, uint8_t *out, size_t cap, size_t *len) {
 
 namespace {
 // where slot "in"'s table stage and the colour matrix leave their frames: the buffer of the stage in front of them (in place), else d_lut
-uint8_t *lut_in_buf(const mjg_ctx *c, const Slot &S) { return c->orient ? S.d_orient : c->deint ? S.d_deint : S.d_lut; }
+uint8_t *lut_in_buf(const mjg_ctx *c, const Slot &S) { return c->orient ? S.d_orient : c->dn ? S.d_dn : c->deint ? S.d_deint : S.d_lut; }
 
 // The per-submit geometry: what a submit adds to the plan of open (plan_ctx).  No HIP call, so the
 // host checks walk these very launches (tools/stage_host.hip).  A plane stage launches luma (p = 0),
@@ -1699,6 +1784,22 @@ DeintGeom deint_launch(const mjg_ctx *c, int p, bool uv1, int n, const SegList &
   uv_place(p, uv1, c->src_cplane, g.off, g.poff);
   return g;
 }
+
+// One launch of the denoiser's kernel `kern` (0 k_dn_rows, 1 k_dn_cols, 2 k_dn_time): its workgroups are
+// g.gxy * dn_nz(kern, p, uv1, n).  The time scan runs over the frames inside a thread, so its grid has
+// planes only: U and V paired is two of them.
+DnGeom dn_launch(const mjg_ctx *c, int kern, int p, bool uv1, int n, int cont) {
+  DnGeom g = c->dnpass[p ? 1 : 0];
+  g.nf = n;
+  g.cont = cont ? 1 : 0;
+  g.gxy = c->dn_grid[p ? 1 : 0][kern];
+  g.gxy_magic = magic32((uint32_t)g.gxy);
+  uv_place(p, uv1, c->src_cplane, g.off, g.poff);
+  const DnGeom &q = c->dnpass[1];
+  uv_place(p, uv1, (long long)q.pitch * q.h, g.off16, g.poff16);
+  return g;
+}
+int dn_nz(int kern, int p, bool uv1, int n) { return kern == 2 ? (p && uv1 ? 2 : 1) : uv_nz(p, uv1, n); }
 
 OrientGeom orient_launch(const mjg_ctx *c, int p, bool uv1, int n) {
   OrientGeom g = c->opass[p ? 1 : 0].g;
@@ -1779,8 +1880,9 @@ void launch_lut(const mjg_ctx *c, const Slot &S, int slot, const SegList &in, ui
 // mjg_submit's body; segs (mjg_submit_segments: device frames) replaces the one segment at
 // `frames` as the input of the sws stage, or of k_encode without one.  halo (a deint context's
 // single-segment submit, mjg_submit_halo): bit 1, `frames` starts with one frame that is only
-// read; bit 2, one such frame follows the n encoded ones
-int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, const SegList *segs, int halo = 0) {
+// read; bit 2, one such frame follows the n encoded ones.  cont (a denoise context's single-segment
+// submit, mjg_submit_cont): the time scan starts from the carried state
+int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, const SegList *segs, int halo = 0, int cont = 0) {
   if (n < 1 || (size_t)n > c->slot_B || (!src_is_device && n > c->cfg.max_batch))
     return set_err(MJG_E_INVALID, "nframes %d not in 1..%d", n, c->cfg.max_batch);
   if (c->nout == kSlots) return set_err(MJG_E_STATE, "%d submits queued: sync one first", kSlots);
@@ -1805,13 +1907,37 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
   SegList in_sl = segs ? *segs : one_seg(src);  // the submit's input frames: the caller's segments, or one at src
   const SheetSplit sheets = sheet_split(c, in_sl, n);
   const int m = sheets.m;  // the frames k_encode codes
-  if (c->scale || c->orient || c->deint || c->has_lut[0] || c->has_cmat) tmark(c, S, MJG_K_SCALE, 0);
+  if (c->scale || c->orient || c->deint || c->dn || c->has_lut[0] || c->has_cmat) tmark(c, S, MJG_K_SCALE, 0);
   if (c->deint) {  // in front of everything; the rest reads one buffer
     const bool uv1 = 2 * n <= 65535;
     for (int p = 0; p < uv_launches(uv1); p++)
       c->dpass[p ? 1 : 0].launch(deint_launch(c, p, uv1, n, in_sl, halo), in_sl, S.d_deint, uv_nz(p, uv1, n), S.st);
     HIP_TRY(hipGetLastError());
-    in_sl = one_seg(S.d_deint);
+    // one buffer from here on; the denoiser still restarts at every segment's first frame
+    in_sl = c->dn ? seg_starts(in_sl, S.d_deint, c->in_frame_bytes) : one_seg(S.d_deint);
+  }
+  if (c->dn) {  // behind the deinterlacer: rows, columns, then time, which carries the context's state
+    const bool uv1 = uv_paired(n);
+    for (int p = 0; p < uv_launches(uv1); p++) {
+      const DnGeom g = dn_launch(c, 0, p, uv1, n, cont);
+      k_dn_rows<<<g.gxy * dn_nz(0, p, uv1, n), kDnRowThreads, 0, S.st>>>(in_sl, S.d_dn16, c->d_dn_tabs, g);
+    }
+    for (int p = 0; p < uv_launches(uv1); p++) {
+      const DnGeom g = dn_launch(c, 1, p, uv1, n, cont);
+      k_dn_cols<<<g.gxy * dn_nz(1, p, uv1, n), kDnColThreads, 0, S.st>>>(S.d_dn16, c->d_dn_tabs, g);
+    }
+    // the state: the other slot's stream wrote it last (two streams, no host wait in between)
+    if (c->dn_last) HIP_TRY(hipStreamWaitEvent(S.st, c->dn_last, 0));
+    for (int p = 0; p < uv_launches(uv1); p++) {
+      const DnGeom g = dn_launch(c, 2, p, uv1, n, cont);
+      k_dn_time<<<g.gxy * dn_nz(2, p, uv1, n), kDnTimeThreads, 0, S.st>>>(in_sl, S.d_dn16, c->d_dn_state, S.d_dn,
+                                                                        c->d_dn_tabs, g);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(S.dn_done, S.st));
+    c->dn_last = S.dn_done;
+    c->dn_started = true;
+    in_sl = one_seg(S.d_dn);
   }
   if (c->orient) {  // the first filter; the rest reads one buffer
     const bool uv1 = 2 * n <= 65535;
@@ -1859,7 +1985,7 @@ int submit_impl(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, con
     HIP_TRY(hipGetLastError());
     enc_in = one_seg(enc_buf);  // k_encode reads the scaled (the sharpened) frames, one buffer
   } else {  // in place: EncGeom's offsets count from the rectangle's first luma byte (0: whole frames)
-    if (c->orient || c->deint || c->has_lut[0] || c->has_cmat) tmark(c, S, MJG_K_SCALE, 1);  // an orientation / a deinterlacer / a table / a matrix alone: the interval holds its passes
+    if (c->orient || c->deint || c->dn || c->has_lut[0] || c->has_cmat) tmark(c, S, MJG_K_SCALE, 1);  // an orientation / a deinterlacer / a table / a matrix alone: the interval holds its passes
     for (int k = 0; k < kMaxSegs; k++) enc_in.p[k] += c->src_off[0];
   }
   const int ntasks = g.nchunks * g.nseg * m;
@@ -2031,16 +2157,31 @@ int mjg_submit(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device) {
   return submit_impl(c, frames, n, src_is_device, nullptr);
 }
 
-int mjg_submit_halo(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, int halo) {
-  if (!halo) return mjg_submit(c, frames, n, src_is_device);
-  if (!c || !frames) return set_err(MJG_E_INVALID, "null argument");
-  if (!c->deint) return set_err(MJG_E_INVALID, "halo %d on a context without a deinterlacer (deint 0)", halo);
+namespace {
+// A piece of a longer sequence (a halo, a continued state, or both) on a context that holds nothing (a
+// deinterlacer or a denoiser: merge is 1): the checks mjg_submit_halo and mjg_submit_cont share, and the launch
+int submit_piece(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, int halo, int cont) {
+  if (halo && !c->deint) return set_err(MJG_E_INVALID, "halo %d on a context without a deinterlacer (deint 0)", halo);
   if (halo & ~3) return set_err(MJG_E_INVALID, "halo %d: not 0..3 (1: a frame in front, 2: a frame behind)", halo);
   if (n < 1 || n > c->cfg.max_batch)
     return set_err(MJG_E_INVALID, "nframes %d not in 1..%d", n, c->cfg.max_batch);
-  // (a deint context holds nothing: merge is 1)
   if (c->nout >= kSlots) return set_err(MJG_E_STATE, "%d launches queued: sync one first", kSlots);
-  return submit_impl(c, frames, n, src_is_device, nullptr, halo);
+  return submit_impl(c, frames, n, src_is_device, nullptr, halo, cont);
+}
+}  // namespace
+
+int mjg_submit_halo(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, int halo) {
+  if (!halo) return mjg_submit(c, frames, n, src_is_device);
+  if (!c || !frames) return set_err(MJG_E_INVALID, "null argument");
+  return submit_piece(c, frames, n, src_is_device, halo, 0);
+}
+
+int mjg_submit_cont(mjg_ctx *c, const uint8_t *frames, int n, int src_is_device, int halo, int cont) {
+  if (!cont) return mjg_submit_halo(c, frames, n, src_is_device, halo);
+  if (!c || !frames) return set_err(MJG_E_INVALID, "null argument");
+  if (!c->dn) return set_err(MJG_E_INVALID, "cont %d on a context without a denoiser", cont);
+  if (!c->dn_started) return set_err(MJG_E_INVALID, "cont %d before any submit: there is no sequence to continue", cont);
+  return submit_piece(c, frames, n, src_is_device, halo, 1);
 }
 
 int mjg_max_segments(void) { return kMaxSegs; }
@@ -2105,7 +2246,7 @@ int mjg_sync(mjg_ctx *c, uint64_t *frame_sizes, uint64_t *total) {
       }
       if (c->timing) {
         for (int k = 0; k < MJG_NUM_KERNELS; k++) {
-          if (k == MJG_K_SCALE && !c->scale && !c->orient && !c->deint && !c->has_lut[0] && !c->has_cmat) continue;
+          if (k == MJG_K_SCALE && !c->scale && !c->orient && !c->deint && !c->dn && !c->has_lut[0] && !c->has_cmat) continue;
           if (k == MJG_K_HUFF && !c->optimal) continue;
           const bool tail = is_tail_kernel(k);
           if (tail != c->timing_detail && (tail || k == MJG_K_TAIL)) continue;
@@ -2471,6 +2612,25 @@ int mjg_debug_deint(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
   if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
   if (!c->deint) return set_err(MJG_E_STATE, "context has no deinterlacer (deint 0)");
   return read_frame(c, frame, out, cap, c->in_frame_bytes, [](const mjg_ctx *, const Slot &S) { return S.d_deint; });
+}
+
+int mjg_debug_denoise(mjg_ctx *c, int frame, uint8_t *out, size_t cap) {
+  if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
+  if (!c->dn) return set_err(MJG_E_STATE, "context has no denoiser");
+  return read_frame(c, frame, out, cap, c->in_frame_bytes, [](const mjg_ctx *, const Slot &S) { return S.d_dn; });
+}
+
+int mjg_debug_denoise_state(mjg_ctx *c, uint16_t *out, size_t cap) {
+  if (!c || !out) return set_err(MJG_E_INVALID, "null argument");
+  if (!c->dn) return set_err(MJG_E_STATE, "context has no denoiser");
+  if (cap < c->in_frame_bytes) return set_err(MJG_E_CAPACITY, "need %zu uint16", c->in_frame_bytes);
+  while (pending_jobs(c) > 0)
+    if (const int rc = mjg_sync(c, nullptr, nullptr)) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  for (int i = 0; i < kSlots; i++)  // (a synced submit's time scan is long done; the streams are idle)
+    if (c->slot[i].alloc) HIP_TRY(hipStreamSynchronize(c->slot[i].st));
+  HIP_TRY(hipMemcpy(out, c->d_dn_state, c->in_frame_bytes * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  return MJG_OK;
 }
 
 int mjg_debug_deint_flags(mjg_ctx *c) {

@@ -2071,4 +2071,318 @@ __global__ __launch_bounds__(kHistThreads) void k_frame_hist(const SegList src, 
   hist_flush(lh, hist, g, (int)blockIdx.x, tid);
 }
 
+// k_dn_rows, k_dn_cols, k_dn_time: `-vf hqdn3d` (mjg_open_denoise), the chain's first
+// recursive filter: on every plane of every frame a scan along each row (P), a scan down each column (V)
+// and a scan through time (A), each step c(tab, a, b) = b + tab[4096 + ((a - b) >> 4)] with
+// L(v) = (v << 8) + 127, in C int with an arithmetic shift:
+//   P[y][0] = y ? L(s[y][0]) : c(S, L(s[0][0]), L(s[0][0]));   P[y][x] = c(S, P[y][x-1], L(s[y][x]))
+//   V[0][x] = P[0][x];                                          V[y][x] = c(S, V[y-1][x], P[y][x])
+//   A_t[y][x] = c(M, A_{t-1}[y][x], V_t[y][x]), A_{-1} = L(s_0);  out_t = A_t >> 8
+// S / M: the plane's spatial / temporal table of 8192 int16 (mjg_denoise: luma ls, lt; chroma cs, ct).
+// A step is a table lookup, so no scan can be split: the parallelism is across rows, across columns and
+// across samples, never along a scan.  Each kernel keeps its one 16 KiB table in LDS, and the index is
+// clamped into 0..8191 before an address is made of it.  Every value fits uint16 for tables the filter
+// makes (within about 8 of the span of a step's arguments); other tables wrap, and stay
+// inside every buffer.
+// Buffers.  The source is the submit's SegList (or the deinterlacer's buffer): packed planar bytes, never
+// written.  p16 is the slot's uint16 buffer, a layout of its own: the rows of a plane are g.pitch elements
+// apart, a multiple of 64 (whole tiles, and every 8-element piece 16-byte aligned), the planes and the
+// frames multiples of 64 elements apart (g.off16, g.poff16, g.fstride16).  The columns [w, pitch) of a row
+// are written with zeros where a stored piece reaches past w, and never read by the time scan.  state
+// is the context's one frame of uint16, packed planar with the byte frame's offsets; dst the slot's
+// denoised frames, packed planar bytes like the source.
+// k_dn_rows: a lane per row, a wave per 64 rows, kDnRowWaves waves a workgroup.  Tile by tile along the
+// row: the wave stages 64 rows x 64 source bytes in LDS as 16-byte pieces (four a row; a piece over the
+// row's end byte by byte), each lane walks its own row of the tile a dword at a time and leaves P as
+// uint16 pairs in a second LDS tile, and the wave stores that tile as 16-byte pieces, eight a row.  The
+// tiles' rows are 17 and 33 dwords apart: ds_read_b32 / ds_write_b32 bank on (address / 4) % 32 within
+// each half of the wave, and in the walk an odd stride puts a half's 32 rows on 32 banks.  (The staging writes,
+// four dwords a piece and four pieces a row, are 2-way conflicted at that stride: rows r and r + 4 of a half
+// meet on one bank.  Not tuned: the walk is where the time goes.)  The carry from tile to tile is a
+// register.  Rows >= h and tiles' columns >= w load and store nothing.
+// k_dn_cols: a lane per 8 adjacent columns (one 16-byte piece of every row), in place over P: eight
+// independent chains a lane, four rows' loads in flight before their steps.  Row 0 stays as it is.
+// k_dn_time: a thread per 16-byte piece of a plane's byte string, cut as k_plane_copy cuts it on the
+// first frame's destination; the thread keeps its 16 states in registers over the submit's frames in
+// order, loads them from `state` when the submit continues a sequence (g.cont), starts them from the
+// source bytes at every segment's first frame otherwise, and stores them once at the end.  A piece over
+// a row's end, and the bytes before the first and behind the last whole piece, go sample by sample.
+// The bodies are __host__ __device__ functions, split at the barriers, as yadif_work and hist_count /
+// hist_flush are, for tools/stage_host.hip.
+struct DnGeom {
+  int w, h;                 // the plane
+  int pitch;                // uint16 row pitch of p16 (a multiple of 64)
+  long long off, fstride, poff;        // bytes: the plane in a frame, frame stride, V from U (source, dst, state)
+  long long off16, fstride16, poff16;  // the same in p16, in elements
+  int nf;                   // frames of the submit
+  int tab;                  // 0 luma, 1 chroma: S = tabs + tab * 8192, M = tabs + (2 + tab) * 8192
+  int cont;                 // k_dn_time: the first frame continues the carried state
+  int gxy;                  // workgroups per (plane, frame) (k_dn_time: per plane)
+  uint32_t gxy_magic;
+  uint32_t w_magic;         // ceil(2^32 / w)
+};
+
+constexpr int kDnTabLen = 8192;
+constexpr int kDnRowWaves = 2;               // k_dn_rows: 128 rows a workgroup
+constexpr int kDnRowThreads = 64 * kDnRowWaves;
+constexpr int kDnSrcStride = 68;             // bytes between the rows of the staged source tile (17 dwords)
+constexpr int kDnPStride = 66;               // uint16 between the rows of the P tile (33 dwords)
+constexpr int kDnColThreads = 64;            // k_dn_cols: 512 columns a workgroup
+constexpr int kDnTimeThreads = 256;          // k_dn_time: one piece a thread
+
+__host__ __device__ __forceinline__ int dn_L(int v) { return (v << 8) + 127; }
+__host__ __device__ __forceinline__ int dn_c(const int16_t *tab, int a, int b) {
+  int i = 4096 + ((a - b) >> 4);
+  i = i < 0 ? 0 : i > kDnTabLen - 1 ? kDnTabLen - 1 : i;
+  return b + tab[i];
+}
+
+// the (plane, frame) of workgroup t of k_dn_rows / k_dn_cols and its index there; the source plane
+struct DnBlock {
+  int pl, f, blk;
+};
+__host__ __device__ __forceinline__ DnBlock dn_block(const DnGeom &g, int t) {
+  const int z = deint_div(t, g.gxy_magic, g.gxy);
+  DnBlock b;
+  b.blk = t - z * g.gxy;
+  b.pl = z >= g.nf;
+  b.f = z - (b.pl ? g.nf : 0);
+  return b;
+}
+__host__ __device__ __forceinline__ const uint8_t *dn_src_plane(const SegList &src, const DnGeom &g, int f, int pl) {
+  int k = 0;
+#pragma unroll
+  for (int j = 1; j < kMaxSegs; j++)
+    if (f >= src.f0[j]) k = j;
+  return src.p[k] + (long long)(f - (k ? src.f0[k] : 0)) * g.fstride + g.off + (pl ? g.poff : 0);
+}
+
+// tile ti (columns [64 ti, 64 ti + 64)) of the wave's 64 rows -> ls (kDnRowWaves tiles of 64 x kDnSrcStride bytes)
+__host__ __device__ __forceinline__ void dn_rows_stage(const SegList &src, uint8_t *ls, const DnGeom &g, int t, int tid, int ti) {
+  const DnBlock B = dn_block(g, t);
+  const uint8_t *s = dn_src_plane(src, g, B.f, B.pl);
+  const int wave = tid >> 6, lane = tid & 63, y0 = (B.blk * kDnRowWaves + wave) * 64, x0 = 64 * ti;
+  uint8_t *tile = ls + wave * 64 * kDnSrcStride;
+#pragma unroll
+  for (int it = 0; it < 4; it++) {
+    const int p = it * 64 + lane, row = p >> 2, y = y0 + row, x = x0 + 16 * (p & 3);
+    if (y >= g.h || x >= g.w) continue;
+    const uint8_t *sp = s + (size_t)y * g.w + x;
+    uint8_t *lp = tile + row * kDnSrcStride + 16 * (p & 3);
+    if (x + 16 <= g.w) {
+      const u32x4 v = *(const u32x4_a1 *)sp;
+#pragma unroll
+      for (int q = 0; q < 4; q++) ((uint32_t *)lp)[q] = v[q];
+    } else {
+#pragma unroll 1
+      for (int b = 0; x + b < g.w; b++) lp[b] = sp[b];
+    }
+  }
+}
+
+// the lane's row of the staged tile -> its row of the P tile lp16 (kDnRowWaves tiles of 64 x kDnPStride uint16);
+// carry: P[y][64 ti - 1], then P[y][the tile's last column]
+__host__ __device__ __forceinline__ void dn_rows_walk(const uint8_t *ls, uint16_t *lp16, const int16_t *S, const DnGeom &g,
+                                                      int t, int tid, int ti, int *carry) {
+  const DnBlock B = dn_block(g, t);
+  const int wave = tid >> 6, lane = tid & 63, y = (B.blk * kDnRowWaves + wave) * 64 + lane, x0 = 64 * ti;
+  if (y >= g.h) return;
+  const uint32_t *sr = (const uint32_t *)(ls + (wave * 64 + lane) * kDnSrcStride);
+  uint32_t *pr = (uint32_t *)(lp16 + (wave * 64 + lane) * kDnPStride);
+  int cy = *carry;
+#pragma unroll 4
+  for (int k = 0; k < 16; k++) {
+    if (x0 + 4 * k >= g.w) {
+      pr[2 * k] = pr[2 * k + 1] = 0u;
+      continue;
+    }
+    const uint32_t d = sr[k];
+    uint32_t o[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int x = x0 + 4 * k + j, L = dn_L((int)((d >> (8 * j)) & 255u));
+      if (x >= g.w) {
+        o[j] = 0u;
+        continue;
+      }
+      cy = x ? dn_c(S, cy, L) : y ? L : dn_c(S, L, L);
+      o[j] = (uint32_t)cy & 0xffffu;
+    }
+    pr[2 * k] = o[0] | o[1] << 16;
+    pr[2 * k + 1] = o[2] | o[3] << 16;
+  }
+  *carry = cy;
+}
+
+// the wave's P tile -> p16, 16-byte pieces
+__host__ __device__ __forceinline__ void dn_rows_store(const uint16_t *lp16, uint16_t *p16, const DnGeom &g, int t, int tid, int ti) {
+  const DnBlock B = dn_block(g, t);
+  uint16_t *d = p16 + (long long)B.f * g.fstride16 + g.off16 + (B.pl ? g.poff16 : 0);
+  const int wave = tid >> 6, lane = tid & 63, y0 = (B.blk * kDnRowWaves + wave) * 64, x0 = 64 * ti;
+#pragma unroll
+  for (int it = 0; it < 8; it++) {
+    const int p = it * 64 + lane, row = p >> 3, y = y0 + row, x = x0 + 8 * (p & 7);
+    if (y >= g.h || x >= g.w) continue;
+    const uint32_t *pr = (const uint32_t *)(lp16 + (wave * 64 + row) * kDnPStride + 8 * (p & 7));
+    *(u32x4 *)(d + (size_t)y * g.pitch + x) = u32x4{pr[0], pr[1], pr[2], pr[3]};
+  }
+}
+
+// a 16 KiB table into LDS, 16-byte pieces
+template <int THREADS>
+__device__ __forceinline__ void dn_load_tab(int16_t *lt, const int16_t *tab, int tid) {
+#pragma unroll
+  for (int i = 0; i < kDnTabLen * 2 / 16 / THREADS; i++) ((u32x4 *)lt)[i * THREADS + tid] = ((const u32x4 *)tab)[i * THREADS + tid];
+}
+
+__global__ __launch_bounds__(kDnRowThreads) void k_dn_rows(const SegList src, uint16_t *__restrict__ p16,
+                                                           const int16_t *__restrict__ tabs, DnGeom g) {
+  __shared__ __attribute__((aligned(16))) int16_t lt[kDnTabLen];
+  __shared__ __attribute__((aligned(16))) uint8_t ls[kDnRowWaves * 64 * kDnSrcStride];
+  __shared__ __attribute__((aligned(16))) uint16_t lp16[kDnRowWaves * 64 * kDnPStride];
+  const int tid = threadIdx.x, t = blockIdx.x;
+  dn_load_tab<kDnRowThreads>(lt, tabs + g.tab * kDnTabLen, tid);
+  int carry = 0;
+  const int ntiles = (g.w + 63) >> 6;
+#pragma unroll 1
+  for (int ti = 0; ti < ntiles; ti++) {
+    dn_rows_stage(src, ls, g, t, tid, ti);
+    __syncthreads();
+    dn_rows_walk(ls, lp16, lt, g, t, tid, ti, &carry);
+    __syncthreads();
+    dn_rows_store(lp16, p16, g, t, tid, ti);
+  }
+}
+
+__host__ __device__ __forceinline__ void dn_cols_work(uint16_t *p16, const int16_t *S, const DnGeom &g, int t, int tid) {
+  const DnBlock B = dn_block(g, t);
+  const int x = (B.blk * kDnColThreads + tid) * 8;
+  if (x >= g.w) return;
+  uint16_t *d = p16 + (long long)B.f * g.fstride16 + g.off16 + (B.pl ? g.poff16 : 0) + x;
+  int v[8];
+  {
+    const u32x4 r = *(const u32x4 *)d;
+#pragma unroll
+    for (int i = 0; i < 8; i++) v[i] = (int)((r[i >> 1] >> (16 * (i & 1))) & 0xffffu);
+  }
+#pragma unroll 1
+  for (int y = 1; y < g.h; y += 4) {
+    u32x4 r[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+      if (y + j < g.h) r[j] = *(const u32x4 *)(d + (size_t)(y + j) * g.pitch);
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+      if (y + j < g.h) {
+        uint32_t o[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+          v[i] = dn_c(S, v[i], (int)((r[j][i >> 1] >> (16 * (i & 1))) & 0xffffu));
+          o[i >> 1] |= ((uint32_t)v[i] & 0xffffu) << (16 * (i & 1));
+        }
+        *(u32x4 *)(d + (size_t)(y + j) * g.pitch) = u32x4{o[0], o[1], o[2], o[3]};
+      }
+  }
+}
+
+__global__ __launch_bounds__(kDnColThreads) void k_dn_cols(uint16_t *p16, const int16_t *__restrict__ tabs, DnGeom g) {
+  __shared__ __attribute__((aligned(16))) int16_t lt[kDnTabLen];
+  dn_load_tab<kDnColThreads>(lt, tabs + g.tab * kDnTabLen, (int)threadIdx.x);
+  __syncthreads();
+  dn_cols_work(p16, lt, g, (int)blockIdx.x, (int)threadIdx.x);
+}
+
+// sample j of the plane through the submit's frames, one by one
+__host__ __device__ inline void dn_time_sample(const SegList &src, const uint16_t *v, uint16_t *st, uint8_t *d,
+                                               const int16_t *M, const DnGeom &g, int pl, int j) {
+  const int row = deint_div(j, g.w_magic, g.w), col = j - row * g.w;
+  const size_t vj = (size_t)row * g.pitch + col;
+  int a = g.cont ? (int)st[j] : 0;
+#pragma unroll 1
+  for (int f = 0; f < g.nf; f++) {
+    bool first = f == 0;
+#pragma unroll
+    for (int k = 1; k < kMaxSegs; k++) first = first || f == src.f0[k];
+    if (first && !(f == 0 && g.cont)) a = dn_L(dn_src_plane(src, g, f, pl)[j]);
+    a = dn_c(M, a, (int)v[(long long)f * g.fstride16 + vj]);
+    d[(long long)f * g.fstride + j] = (uint8_t)(a >> 8);
+  }
+  st[j] = (uint16_t)a;
+}
+
+__host__ __device__ __forceinline__ void dn_time_work(const SegList &src, const uint16_t *p16, uint16_t *state, uint8_t *dst,
+                                                      const int16_t *M, const DnGeom &g, int t, int tid) {
+  const int pl = deint_div(t, g.gxy_magic, g.gxy), blk = t - pl * g.gxy;
+  const long long po = g.off + (pl ? g.poff : 0);
+  const uint16_t *v = p16 + g.off16 + (pl ? g.poff16 : 0);
+  uint16_t *st = state + po;
+  uint8_t *d = dst + po;  // the plane in the first frame
+  const int w = g.w, nb = w * g.h;
+  const int head = imin((int)(-(uintptr_t)d & 15), nb);
+  const int nv = (nb - head) >> 4;
+  const int kp = blk * kDnTimeThreads + tid;
+  if (kp < nv) {
+    const int j = head + 16 * kp;
+    const int row = deint_div(j, g.w_magic, w), col = j - row * w;
+    if (col + 16 > w) {  // over a row end (rolled: 16 / w of the pieces)
+#pragma unroll 1
+      for (int b = 0; b < 16; b++) dn_time_sample(src, v, st, d, M, g, pl, j + b);
+    } else {
+      const size_t vj = (size_t)row * g.pitch + col;
+      int a[16];
+      if (g.cont) {
+        const u32x4 s0 = *(const u32x4_a1 *)(st + j), s1 = *(const u32x4_a1 *)(st + j + 8);
+#pragma unroll
+        for (int b = 0; b < 8; b++) {
+          a[b] = (int)((s0[b >> 1] >> (16 * (b & 1))) & 0xffffu);
+          a[8 + b] = (int)((s1[b >> 1] >> (16 * (b & 1))) & 0xffffu);
+        }
+      } else {
+#pragma unroll
+        for (int b = 0; b < 16; b++) a[b] = 0;
+      }
+#pragma unroll 1
+      for (int f = 0; f < g.nf; f++) {
+        bool first = f == 0;
+#pragma unroll
+        for (int k = 1; k < kMaxSegs; k++) first = first || f == src.f0[k];
+        const uint16_t *vf = v + (long long)f * g.fstride16 + vj;
+        const u32x4 v0 = *(const u32x4_a1 *)vf, v1 = *(const u32x4_a1 *)(vf + 8);
+        if (first && !(f == 0 && g.cont)) {
+          const u32x4 s = *(const u32x4_a1 *)(dn_src_plane(src, g, f, pl) + j);
+#pragma unroll
+          for (int b = 0; b < 16; b++) a[b] = dn_L((int)((s[b >> 2] >> (8 * (b & 3))) & 255u));
+        }
+        uint32_t o[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int b = 0; b < 16; b++) {
+          const u32x4 &vv = b < 8 ? v0 : v1;
+          a[b] = dn_c(M, a[b], (int)((vv[(b & 7) >> 1] >> (16 * (b & 1))) & 0xffffu));
+          o[b >> 2] |= (((uint32_t)a[b] >> 8) & 255u) << (8 * (b & 3));
+        }
+        *(u32x4_a1 *)(d + (long long)f * g.fstride + j) = u32x4{o[0], o[1], o[2], o[3]};
+      }
+      uint32_t o[8];
+#pragma unroll
+      for (int b = 0; b < 8; b++) o[b] = ((uint32_t)a[2 * b] & 0xffffu) | ((uint32_t)a[2 * b + 1] & 0xffffu) << 16;
+      *(u32x4_a1 *)(st + j) = u32x4{o[0], o[1], o[2], o[3]};
+      *(u32x4_a1 *)(st + j + 8) = u32x4{o[4], o[5], o[6], o[7]};
+    }
+  }
+  if (blk == 0 && tid < 16) {
+    const int a = tid, b = head + 16 * nv + tid;
+    if (a < head) dn_time_sample(src, v, st, d, M, g, pl, a);
+    if (b < nb) dn_time_sample(src, v, st, d, M, g, pl, b);
+  }
+}
+
+__global__ __launch_bounds__(kDnTimeThreads) void k_dn_time(const SegList src, const uint16_t *__restrict__ p16,
+                                                            uint16_t *state, uint8_t *__restrict__ dst,
+                                                            const int16_t *__restrict__ tabs, DnGeom g) {
+  __shared__ __attribute__((aligned(16))) int16_t lt[kDnTabLen];
+  dn_load_tab<kDnTimeThreads>(lt, tabs + (2 + g.tab) * kDnTabLen, (int)threadIdx.x);
+  __syncthreads();
+  dn_time_work(src, p16, state, dst, lt, g, (int)blockIdx.x, (int)threadIdx.x);
+}
+
 }  // namespace mjg

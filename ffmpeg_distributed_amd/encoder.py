@@ -31,7 +31,11 @@ colormatrix=SRC:DST` with profile.colormatrix_coefs.  `sheet=` (cols, rows, nb_f
 `-vf tile` as the last filter) puts every nb_frames frames (0: cols * rows) on one contact sheet on the
 GPU: dst_w x dst_h stay the cell, the JPEGs are the sheets (enc_w x enc_h), a submit of n frames yields
 frames_out(n) of them, and every submit (every segment of a submit_segments) is a sequence of its own;
-such an encoder opens through mjg_open_sheet.  An encoder with any of these opens as one
+such an encoder opens through mjg_open_sheet.  `denoise=` ((4, 8192) int16, rows luma spatial, chroma
+spatial, luma temporal, chroma temporal: `-vf hqdn3d` as the first filter or directly behind the yadif, with
+profile.hqdn3d_tables) runs the denoiser's three scans on the GPU behind the deinterlacer; a submit is a
+sequence of its own unless `submit(..., cont=True)` continues the one before, and such an encoder opens
+through mjg_open_denoise.  An encoder with any of these opens as one
 mjg_chain (include/mjgpu.h, which says what each stage does) through mjg_open_chain; one with none
 through mjg_open / mjg_open_src.  No CPU fallback.
 """
@@ -84,7 +88,8 @@ class MjpegEncoder:
                  debug_coefs: bool = False, sws_bitexact: bool = True, com_itu601: bool = False,
                  huffman: str = "default", chroma: str = "420", rst: bool = False,
                  merge: bool = False, src_chroma: Optional[str] = None, crop=None, pad=None, orient: int = 0,
-                 deint: Optional[int] = None, unsharp=None, lut_in=None, lut_out=None, cmat=None, sheet=None):
+                 deint: Optional[int] = None, unsharp=None, lut_in=None, lut_out=None, cmat=None, sheet=None,
+                 denoise=None):
         self._L = _lib.load()
         self.device = int(device)
         self.src_w, self.src_h = int(src_w), int(src_h)
@@ -192,11 +197,20 @@ class MjpegEncoder:
             if len(cmat) != 6:
                 raise ValueError(f"cmat {cmat!r}: (c2, c3, c4, c5, c6, c7)")
             self.cmat = tuple(int(v) for v in cmat)
+        # denoise: a (4, 8192) int16 array, the tables ls, cs, lt, ct of `-vf hqdn3d` (profile.hqdn3d_tables), behind
+        # the deinterlacer and in front of the orientation.  None, the default, opens as without it
+        self.denoise = None
+        if denoise is not None:
+            t = np.ascontiguousarray(denoise)
+            if t.shape != (4, 8192) or t.dtype != np.int16:
+                raise ValueError(f"denoise: a (4, 8192) int16 array, not {t.shape} {t.dtype}")
+            self.denoise = t
         # one open: a chain with nothing in it through mjg_open / mjg_open_src (which every library
         # has, an older one named by MJG_LIBRARY too), everything else as one mjg_chain
         src_cf = _lib.CHROMA_FORMATS[self.src_chroma]
         if (self.crop is None and self.pad is None and not self.orient and deint is None and unsharp is None
-                and lut_in is None and lut_out is None and self.cmat is None and self.sheet is None):
+                and lut_in is None and lut_out is None and self.cmat is None and self.sheet is None
+                and self.denoise is None):
             if self.src_chroma == self.chroma:
                 check(self._L.mjg_open(self.device, C.byref(cfg), C.byref(h)))
             elif not hasattr(self._L, "mjg_open_src"):
@@ -207,6 +221,8 @@ class MjpegEncoder:
             raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_chain")
         elif self.sheet is not None and not hasattr(self._L, "mjg_open_sheet"):
             raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_sheet")
+        elif self.denoise is not None and not hasattr(self._L, "mjg_open_denoise"):
+            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_open_denoise")
         else:
             chain = _lib.MjgChain(src_chroma_format=src_cf, deint=self.deint, orient=self.orient)
             if self.cmat is not None:
@@ -223,7 +239,12 @@ class MjpegEncoder:
             if self.pad is not None:
                 chain.has_pad = 1
                 chain.pad_x, chain.pad_y, chain.pad_w, chain.pad_h = self.pad
-            if self.sheet is not None:
+            if self.denoise is not None:
+                sheet_p = None if self.sheet is None else C.byref(_lib.MjgSheet(*self.sheet))
+                check(self._L.mjg_open_denoise(self.device, C.byref(cfg), C.byref(chain), sheet_p,
+                                               C.byref(_lib.MjgDenoise.from_buffer_copy(self.denoise.tobytes())),
+                                               C.byref(h)))
+            elif self.sheet is not None:
                 check(self._L.mjg_open_sheet(self.device, C.byref(cfg), C.byref(chain),
                                              C.byref(_lib.MjgSheet(*self.sheet)), C.byref(h)))
             else:
@@ -293,7 +314,8 @@ class MjpegEncoder:
         synced: each takes a launch of its own (mjg_queue_depth)."""
         return int(self._L.mjg_queue_depth()) if hasattr(self._L, "mjg_queue_depth") else 2
 
-    def submit(self, frames=None, nframes: Optional[int] = None, device_ptr: Optional[int] = None, halo: int = 0):
+    def submit(self, frames=None, nframes: Optional[int] = None, device_ptr: Optional[int] = None, halo: int = 0,
+               cont: bool = False):
         """Queue `nframes` packed frames: a host buffer (numpy / bytes) or a device pointer
         (`device_ptr`, e.g. torch_tensor.data_ptr() on this GPU, kept alive until its sync).
         Up to `host_depth` host submits may be queued (each one's k_encode runs beside the
@@ -302,14 +324,21 @@ class MjpegEncoder:
         `halo` (an encoder with `deint`; mjg_submit_halo): bit 1, the buffer starts with one extra
         frame that is only read, as the first encoded frame's previous one; bit 2, one such frame
         follows the last encoded one.  `nframes` counts the encoded frames only (a host buffer's
-        default: its frames less the halo ones)."""
+        default: its frames less the halo ones).
+        `cont` (an encoder with `denoise`; mjg_submit_cont): the frames continue the sequence of the submit
+        before, so the denoiser's time scan starts from the state that one left."""
         halo = int(halo)
         nhalo = (halo & 1) + ((halo >> 1) & 1)
         if halo and not hasattr(self._L, "mjg_submit_halo"):
             raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_submit_halo")
 
+        if cont and not hasattr(self._L, "mjg_submit_cont"):
+            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_submit_cont")
+
         def call(ptr, n, dev):
-            if halo:
+            if cont:
+                check(self._L.mjg_submit_cont(self._h, ptr, n, dev, halo, 1))
+            elif halo:
                 check(self._L.mjg_submit_halo(self._h, ptr, n, dev, halo))
             else:
                 check(self._L.mjg_submit(self._h, ptr, n, dev))
@@ -436,9 +465,12 @@ class MjpegEncoder:
             raise ValueError(f"a sheet of {self.sheet_n} frames does not fit max_batch {self.max_batch}")
         for i in range(0, n, step or self.max_batch):
             k = min(step or self.max_batch, n - i)
+            cont = {"cont": True} if self.denoise is not None and i else {}  # one sequence through the denoiser too
             if self.deint and n > self.max_batch:
                 lo, hi = (1 if i else 0), (1 if i + k < n else 0)
-                self.submit(arr[(i - lo) * self.frame_bytes:(i + k + hi) * self.frame_bytes], k, halo=lo | hi << 1)
+                self.submit(arr[(i - lo) * self.frame_bytes:(i + k + hi) * self.frame_bytes], k, halo=lo | hi << 1, **cont)
+            elif cont:
+                self.submit(arr[i * self.frame_bytes:(i + k) * self.frame_bytes], k, **cont)
             else:
                 self.submit(arr[i * self.frame_bytes:(i + k) * self.frame_bytes], k)
             out.extend(self.fetch())
@@ -560,6 +592,23 @@ class MjpegEncoder:
         packed planar, src_w x src_h in the input format `src_chroma`, frame_bytes bytes.  Only for
         an encoder opened with a non-zero `deint`."""
         return self._debug_frame("mjg_debug_deint", self.frame_bytes, frame)
+
+    def debug_denoise(self, frame: int = 0) -> np.ndarray:
+        """The denoised frame (k_dn_time's output) of a frame of the last synced submit: packed planar,
+        src_w x src_h in the input format `src_chroma`, frame_bytes bytes.  Only for an encoder opened with
+        `denoise`."""
+        return self._debug_frame("mjg_debug_denoise", self.frame_bytes, frame)
+
+    def debug_denoise_state(self) -> np.ndarray:
+        """The carried state of the denoiser's time scan: frame_bytes uint16 values, packed planar like a
+        frame.  Syncs every queued submit first.  Only for an encoder opened with `denoise`."""
+        if not hasattr(self._L, "mjg_debug_denoise_state"):
+            raise MjgError(_lib.MJG_E_STATE, "library lacks mjg_debug_denoise_state")
+        while self._queued:
+            self.sync()
+        out = np.zeros(self.frame_bytes, np.uint16)
+        check(self._L.mjg_debug_denoise_state(self._h, out.ctypes.data_as(C.POINTER(C.c_uint16)), out.size))
+        return out
 
     def scale_path(self, plane: int) -> int:
         """Which kernel the sws stage runs for a plane (0 luma, 1 chroma): 0 none, 1 k_plane_copy,

@@ -64,7 +64,14 @@ group's mean histogram (`thumbnail_pick`, on histograms the GPU counts).  A seco
 position, a graph that also names yadif, a graph whose last filter is no tile (the filter keeps its link's
 frame rate and emits sparse timestamps, which MkvWriter does not write), N below 2, a non-integer and an
 unknown key are outside the profile, each with a reason that names it.  A restatement of vf_thumbnail.c's
-8-bit planar path (FFmpeg 5.1 and later) that is unpinned against FFmpeg.  An orientation filter after a crop, scale
+8-bit planar path (FFmpeg 5.1 and later) that is unpinned against FFmpeg.  One
+    hqdn3d[=luma_spatial[:chroma_spatial[:luma_tmp[:chroma_tmp]]]]   (or by these names)
+as the very first filter, or directly behind a leading yadif, makes the profile a `DenoiseProfile` (DESIGN
+§4.19): `hqdn3d` = the four strengths, a missing or zero one replaced as the filter replaces it (4, 3 ls / 4,
+6 ls / 4, lt cs / ls).  A second hqdn3d, any other position, an expression, a negative or non-numeric value,
+an unknown key, more than four positional values and a graph that also names framestep, thumbnail or tile
+are outside the profile, each with a reason that names it.  `hqdn3d_tables` makes the four tables, a
+restatement of vf_hqdn3d.c's 8-bit path that is unpinned against FFmpeg.  An orientation filter after a crop, scale
 or pad, transpose values 4..7, a passthrough other than none and any other option are outside the
 profile.  The crop values are decimal integers (no expressions); `Profile.crop` is the request as
 given and `resolve_crop` turns it into a rectangle of a given input (vf_crop.c's rounding,
@@ -92,6 +99,7 @@ is split once into filters, and the stages of GRAPH_STAGES take theirs off that 
 from __future__ import annotations
 
 import re
+import math
 import shlex
 from math import gcd
 from dataclasses import dataclass
@@ -151,6 +159,15 @@ class ThumbProfile(SheetProfile):
     # -vf [framestep=S,]thumbnail=N,...,tile: of every N consecutive frames (behind the framestep) the reader keeps
     # the one that thumbnail_pick selects
     thumbnail: int = THUMBNAIL_DEFAULT
+
+
+@dataclass
+class DenoiseProfile(Profile):
+    """The Profile of a graph that names `hqdn3d` (parse returns one exactly then; every other graph gives the
+    Profile it always did)."""
+    # -vf [yadif,]hqdn3d[=ls:cs:lt:ct]: the four strengths, resolved ({"ls", "cs", "lt", "ct"} -> float, every one
+    # positive); hqdn3d_tables turns them into the four tables
+    hqdn3d: Optional[dict] = None
 
 
 class Unsupported(ValueError):
@@ -753,6 +770,91 @@ def _take_sheet(fs, out):
         out["tile"] = _parse_tile(fs.pop()[1])
 
 
+HQDN3D_KEYS = {"luma_spatial": "ls", "chroma_spatial": "cs", "luma_tmp": "lt", "chroma_tmp": "ct"}
+HQDN3D_NAMES = ("ls", "cs", "lt", "ct")
+
+
+def _parse_hqdn3d(f: str) -> dict:
+    """`hqdn3d[=luma_spatial[:chroma_spatial[:luma_tmp[:chroma_tmp]]]]`, positional in that order or by those
+    names -> {"ls", "cs", "lt", "ct"}, resolved as vf_hqdn3d.c's init does: a value that is missing or 0 is
+    replaced, in this order, by 4.0, 3 ls / 4, 6 ls / 4 and lt cs / ls.  Plain non-negative numbers only."""
+    vals = dict.fromkeys(HQDN3D_NAMES, 0.0)
+    if "=" in f:
+        body = f.split("=", 1)[1]
+        if not body:
+            raise Unsupported("hqdn3d= without options")
+        pos = 0
+        for p in body.split(":"):
+            if "=" in p:
+                k, v = p.split("=", 1)
+                if k not in HQDN3D_KEYS:
+                    raise Unsupported(f"hqdn3d option {k!r} (luma_spatial, chroma_spatial, luma_tmp and chroma_tmp are "
+                                      f"GPU-accelerated)")
+                k = HQDN3D_KEYS[k]
+            else:
+                if pos >= 4:
+                    raise Unsupported(f"hqdn3d option {p!r}: more than four positional values "
+                                      f"(luma_spatial:chroma_spatial:luma_tmp:chroma_tmp)")
+                k, v = HQDN3D_NAMES[pos], p
+                pos += 1
+            if not _NUM_RE.match(v):
+                raise Unsupported(f"hqdn3d {k}={v!r} (plain numbers only: expressions are not GPU-accelerated)")
+            if float(v) < 0:
+                raise Unsupported(f"hqdn3d {k}={v}: a negative strength")
+            vals[k] = float(v)
+    ls = vals["ls"] or 4.0
+    cs = vals["cs"] or 3.0 * ls / 4.0
+    lt = vals["lt"] or 6.0 * ls / 4.0
+    ct = vals["ct"] or lt * cs / ls
+    return {"ls": ls, "cs": cs, "lt": lt, "ct": ct}
+
+
+def hqdn3d_table(s: float) -> list:
+    """One strength's table, 8192 ints (int16), in Python floats as vf_hqdn3d.c's precalc_coefs computes it in C
+    doubles: tab[4096 + i] = lrint(pow(max(0, 1 - |f| / 255), gamma) * 256 f) with f = ((i << 5) + 15) / 512 and
+    gamma = log(0.25) / log(1 - min(s, 252) / 255 - 0.00001); tab[0] = 1, the filter's own flag, which no
+    input reaches."""
+    gamma = math.log(0.25) / math.log(1.0 - min(s, 252.0) / 255.0 - 0.00001)
+    tab = [0] * 8192
+    for i in range(-4096, 4096):
+        f = ((i << 5) + 15) / 512.0
+        tab[4096 + i] = round(math.pow(max(0.0, 1.0 - abs(f) / 255.0), gamma) * 256.0 * f)   # ties to even, as lrint
+    tab[0] = 1
+    return tab
+
+
+def hqdn3d_tables(spec: dict):
+    """The four tables of a resolved request ({"ls", "cs", "lt", "ct"}): a (4, 8192) int16 array, rows luma
+    spatial, chroma spatial, luma temporal, chroma temporal (mjg_denoise's order).  A restatement that is
+    unpinned against FFmpeg."""
+    import numpy as np
+    return np.array([hqdn3d_table(float(spec[k])) for k in HQDN3D_NAMES], np.int16)
+
+
+def _take_denoise(fs, out):
+    """One hqdn3d as the very first filter, or directly behind a leading yadif, taken off behind _take_sheet
+    (whose framestep, thumbnail and tile refuse the graph here) and before the other stages see the list.  A
+    graph that does not name it is left exactly as it is."""
+    names = _names(fs)
+    if "hqdn3d" not in names:
+        return
+    vf = _graph(fs)
+    for nm in ("framestep", "thumbnail", "tile"):
+        if nm in out:
+            raise Unsupported(f"filter graph with {vf!r}: hqdn3d together with {nm} (the time scan needs every frame, and "
+                              f"a denoiser context has no contact sheet)")
+    if names.count("hqdn3d") > 1:
+        raise Unsupported(f"filter graph {vf!r}: a second hqdn3d (one hqdn3d, in front, is GPU-accelerated)")
+    at = names.index("hqdn3d")
+    if at and not (at == 1 and names[0] == "yadif"):
+        raise Unsupported(f"filter graph {vf!r}: hqdn3d after {names[at - 1]} (hqdn3d is GPU-accelerated only as the "
+                          f"first filter, or directly behind a leading yadif)")
+    if at == 0 and "yadif" in names:
+        raise Unsupported(f"filter graph {vf!r}: yadif after hqdn3d (the deinterlacer runs in front of the denoiser: only "
+                          f"yadif,hqdn3d in this order is GPU-accelerated)")
+    out["hqdn3d"] = _parse_hqdn3d(fs.pop(at)[1])
+
+
 def _take_colormatrix(fs, out):
     """One colormatrix, behind the yadif and the orientation run, in front of any eq and of the scale
     (without a scale: in front of the unsharp and the pad); before or after the crop, with which it
@@ -887,13 +989,13 @@ def _take_crop_scale(fs, out):
 
 
 # in this order, which decides the reason a graph outside the profile is refused with
-GRAPH_STAGES = (_take_sheet, _take_colormatrix, _take_eq, _take_deint, _take_orient, _take_pad_unsharp, _take_crop_scale)
+GRAPH_STAGES = (_take_sheet, _take_denoise, _take_colormatrix, _take_eq, _take_deint, _take_orient, _take_pad_unsharp, _take_crop_scale)
 
 
 def parse_graph(vf: str) -> dict:
     """A -vf value -> the chain fields of Profile that the graph sets, by name (crop, scale,
-    sws_flags, pad, orient, deint, unsharp, eq, colormatrix, SheetProfile's tile and framestep and ThumbProfile's
-    thumbnail; a field
+    sws_flags, pad, orient, deint, unsharp, eq, colormatrix, SheetProfile's tile and framestep, ThumbProfile's
+    thumbnail and DenoiseProfile's hqdn3d; a field
     the graph does not set is left out, so Profile's own defaults are the only ones), or Unsupported."""
     if ";" in vf:
         raise Unsupported(f"filter graph {vf!r} (only crop, scale or crop,scale is GPU-accelerated)")
@@ -1079,7 +1181,9 @@ def parse(args: Union[str, Sequence[str]]) -> Profile:
         huff = "default"  # mjpegenc.c: slice_context_count > 1 forces HUFFMAN_TABLE_DEFAULT
     # (a SheetProfile exactly when the winning graph names a tile or a framestep above 1)
     # (and a ThumbProfile exactly when it names a thumbnail)
-    cls = ThumbProfile if "thumbnail" in chain else SheetProfile if "tile" in chain or "framestep" in chain else Profile
+    # (and a DenoiseProfile exactly when it names a hqdn3d, which goes with none of the three)
+    cls = (DenoiseProfile if "hqdn3d" in chain else ThumbProfile if "thumbnail" in chain
+           else SheetProfile if "tile" in chain or "framestep" in chain else Profile)
     return cls(qscale=effective_qscale(q), q_arg=q, huffman=huff, rst=rst, chroma=chroma, **chain)
 
 

@@ -61,6 +61,11 @@ uses it while the submit thread owns the encoder), selects one with profile.thum
 closes or the input ends, and copies that frame into the batch (Pipeline.read_thumb).  The submit side sees a
 plain frame sequence, and the output runs at the rate it has without the thumbnail, as the filter leaves its
 link's frame rate alone; thumbnail_fallthrough_reason names the inputs that still go to the real ffmpeg.
+A `hqdn3d` as the first filter or directly behind the yadif (profile.DenoiseProfile) is run by the GPU behind the
+deinterlacer: three scans with the filter's four tables.  Its time scan runs through the whole
+segment, so a segment's first batch is a plain submit and every later one continues it (encoder.submit(cont=True),
+together with the halo a deinterlaced batch has); denoise_fallthrough_reason names the inputs that still go to
+the real ffmpeg.
 All of this is resolved against the segment's input by plan_segment, a pure function, before run()
 binds to the GPU's NUMA node: a SegmentPlan, a Fallthrough (the real ffmpeg) or a CropError / PadError.
 run() is then a sequence: Context.acquire opens the encoder and its page-locked buffers (or takes the serve
@@ -521,7 +526,7 @@ def resample_plan(prof, info):
 
 
 def encoder_key(prof, info, dst_w, dst_h, sar, com_itu601, batch, rect=None, pad=None, orient=0, deint=0,
-                unsharp=None, luts=None, cmat=None):
+                unsharp=None, luts=None, cmat=None, denoise=None):
     """What an encoder context kept between segments (serve / resident mode) depends on: the
     input's shape and format and everything of the profile the context is opened with, the
     encoded chroma format (-pix_fmt), the resolved crop rectangle (x, y, w, h), the resolved
@@ -530,14 +535,16 @@ def encoder_key(prof, info, dst_w, dst_h, sar, com_itu601, batch, rect=None, pad
     six values of an unsharp (profile.Profile.unsharp; None without one), and the bytes of the
     tables in front of and behind the sws stage (luts: (lut_in, lut_out), each a (3, 256) uint8
     array or None: two eq filters with different options are different contexts), and the six
-    coefficients of a colour matrix (cmat; without one the key is what it was)."""
+    coefficients of a colour matrix (cmat; without one the key is what it was), and the four strengths
+    of a hqdn3d (denoise: (ls, cs, lt, ct), resolved; without one the key is what it was)."""
     src_chroma, dst_chroma = resample_plan(prof, info)
     key = (info.width, info.height, dst_w, dst_h, info.full_range, prof.qscale, sar,
            com_itu601, prof.huffman, src_chroma, dst_chroma, prof.rst, batch,
            None if rect is None else tuple(rect), None if pad is None else tuple(pad), int(orient), int(deint),
            tuple(None if t is None else t.tobytes() for t in (luts or (None, None))),
            None if unsharp is None else tuple(unsharp))
-    return key if cmat is None else key + (("cmat",) + tuple(int(v) for v in cmat),)
+    key = key if cmat is None else key + (("cmat",) + tuple(int(v) for v in cmat),)
+    return key if denoise is None else key + (("hqdn3d",) + tuple(float(v) for v in denoise),)
 
 
 def resolve_deint(spec, info):
@@ -658,6 +665,22 @@ def cmat_fallthrough_reason(prof, info) -> Optional[str]:
     return None
 
 
+def denoise_fallthrough_reason(prof, info) -> Optional[str]:
+    """Why a graph with a `hqdn3d` runs on the CPU for this input, or None.  The scans are the filter's 8-bit
+    path: samples of more than 8 bits go through another one (and the library's frames are bytes)."""
+    if getattr(prof, "hqdn3d", None) is None:
+        return None
+    bits = int(getattr(info, "bits", 8))
+    if bits != 8:
+        return f"hqdn3d on a {bits}-bit input: only the filter's 8-bit path is GPU-accelerated"
+    hs, vs = _CHROMA_SHIFTS[str(info.chroma)]
+    eight = info.width * info.height + 2 * ((info.width + hs) >> hs) * ((info.height + vs) >> vs)
+    if getattr(info, "frame_bytes", eight) != eight:
+        return (f"hqdn3d on an input of {info.frame_bytes} bytes a frame ({eight} at 8 bits): more than 8 bits a sample "
+                f"are not GPU-accelerated")
+    return None
+
+
 def eq_luts(prof):
     """(lut_in, lut_out) for MjpegEncoder: the eq's tables in its slot, None elsewhere."""
     if prof.eq is None:
@@ -715,6 +738,8 @@ class SegmentPlan:
     # what only a SheetPlan decides: plain class attributes here, fields there (fields() and key() stay as they are)
     framestep = 1
     sheet = None
+    # ... and what only a DenoisePlan decides
+    denoise = None
 
     def rate(self, info):
         """What the muxer and the progress lines run at: the input's frame rate."""
@@ -734,6 +759,21 @@ class SegmentPlan:
         """encoder_key of a context opened with this plan."""
         return encoder_key(prof, info, self.dst_w, self.dst_h, self.sar, com_itu601, batch, self.rect, self.pad,
                            self.orient, self.deint, self.unsharp, (self.lut_in, self.lut_out), self.cmat)
+
+
+@dataclass(frozen=True, eq=False)
+class DenoisePlan(SegmentPlan):
+    """The plan of a profile.DenoiseProfile: the SegmentPlan plus the denoiser's four tables.  A segment is one
+    sequence: its first batch is a plain submit and every later one continues it (Pipeline.run)."""
+    denoise: object = None           # the (4, 8192) int16 tables (profile.hqdn3d_tables)
+    strengths: tuple = ()            # the four strengths they were made from: what the cache key holds
+
+    def encoder_kwargs(self) -> dict:
+        return dict(super().encoder_kwargs(), denoise=self.denoise)
+
+    def key(self, prof, info, com_itu601, batch):
+        return encoder_key(prof, info, self.dst_w, self.dst_h, self.sar, com_itu601, batch, self.rect, self.pad,
+                           self.orient, self.deint, self.unsharp, (self.lut_in, self.lut_out), self.cmat, self.strengths)
 
 
 TILE_MAX_SIDE = 16384    # the pad's canvas limit (mjg_open_sheet refuses more)
@@ -868,6 +908,7 @@ def plan_segment(prof, info) -> SegmentPlan:
     # about 64:1), decided without a device
     why = (unsharp_fallthrough_reason(prof, info.full_range, src_chroma, dst_chroma)
            or eq_fallthrough_reason(prof, info) or cmat_fallthrough_reason(prof, info)
+           or denoise_fallthrough_reason(prof, info)
            or scale_cascade_reason(in_size, (dst_w, dst_h), src_chroma, dst_chroma))
     if why is not None:
         raise Fallthrough(why)
@@ -897,9 +938,14 @@ def plan_segment(prof, info) -> SegmentPlan:
                    in_size=in_size, dst_w=dst_w, dst_h=dst_h, pad=pad, enc_w=enc_w, enc_h=enc_h,
                    unsharp=prof.unsharp, lut_in=lut_in, lut_out=lut_out, cmat=cmat, sar=sar,
                    sheet=sheet, framestep=prof.framestep, out_fps=Fraction(info.fps) / (prof.framestep * n), **more)
-    return SegmentPlan(src_chroma=src_chroma, dst_chroma=dst_chroma, deint=deint, orient=orient, rect=rect,
-                       in_size=in_size, dst_w=dst_w, dst_h=dst_h, pad=pad, enc_w=enc_w, enc_h=enc_h,
-                       unsharp=prof.unsharp, lut_in=lut_in, lut_out=lut_out, cmat=cmat, sar=sar)
+    cls, more = SegmentPlan, {}
+    if isinstance(prof, profile.DenoiseProfile):  # -vf [yadif,]hqdn3d,...: the tables, behind the deinterlacer
+        cls = DenoisePlan
+        more = dict(denoise=profile.hqdn3d_tables(prof.hqdn3d),
+                    strengths=tuple(float(prof.hqdn3d[k]) for k in profile.HQDN3D_NAMES))
+    return cls(src_chroma=src_chroma, dst_chroma=dst_chroma, deint=deint, orient=orient, rect=rect,
+               in_size=in_size, dst_w=dst_w, dst_h=dst_h, pad=pad, enc_w=enc_w, enc_h=enc_h,
+               unsharp=prof.unsharp, lut_in=lut_in, lut_out=lut_out, cmat=cmat, sar=sar, **more)
 
 
 JOIN_TIMEOUT = 5.0  # Pipeline.stop: what the reader and the muxer thread each get to end; one still alive after it is stuck
@@ -911,7 +957,8 @@ class Pipeline:
     All it works with is handed in, so it runs without a GPU: `enc` is used through frame_bytes, host_depth,
     submit(arr, n, halo=), sync(), last_total and fetch_into(buf); `bufs` through .array; `obufs` (a list
     filled and regrown here; None: not made yet) through .nbytes, .free() and what fetch_into needs;
-    `new_obuf(nbytes)` makes one.  `batch` frames a submit, every `step`-th frame kept, `deint`: halo submits.
+    `new_obuf(nbytes)` makes one.  `batch` frames a submit, every `step`-th frame kept, `deint`: halo submits,
+    `denoise`: submit(arr, n, halo=, cont=), the first of the segment plain and every later one cont=True.
     `thumb` (a ThumbPlan): (hist, store, N), `hist` used through count(frames, nframes) -> (n, 768) counters,
     `store` a page-locked buffer of N frames through .array; the reader keeps one frame of every N.
 
@@ -922,9 +969,11 @@ class Pipeline:
     input, or the exception that stopped it.  After run(), failed or not, comes stop()."""
 
     def __init__(self, enc, bufs, obufs, new_obuf, src, mkv, prog, batch: int, step: int = 1, deint: bool = False,
-                 thumb=None):
+                 thumb=None, denoise: bool = False):
         self.enc, self.bufs, self.obufs, self.new_obuf = enc, bufs, obufs, new_obuf
         self.thumb = thumb
+        self.denoise = denoise      # the segment is one sequence: every submit but the first continues it
+        self.submits = 0            # submits of this segment so far
         self.gn, self.ghists = 0, []  # read_thumb: the open group's frames in the store and their histograms
         self.src, self.mkv, self.prog = src, mkv, prog
         self.batch, self.step, self.deint, self.fb = batch, step, deint, enc.frame_bytes
@@ -1108,7 +1157,11 @@ class Pipeline:
                 self.drain_one()
             t0 = time.monotonic()
             nh = (halo & 1) + (halo >> 1)
-            enc.submit(self.bufs[i].array[:(n + nh) * fb], n, halo=halo)
+            if self.denoise:  # the first batch starts the sequence (a cached context's state is another segment's)
+                enc.submit(self.bufs[i].array[:(n + nh) * fb], n, halo=halo, cont=self.submits > 0)
+            else:
+                enc.submit(self.bufs[i].array[:(n + nh) * fb], n, halo=halo)
+            self.submits += 1
             tr["submit"] += time.monotonic() - t0
             self.queued.append(i)
         while self.queued:
@@ -1262,7 +1315,7 @@ def run(device: int, args: List[str], stdin=None, stdout=None, stderr=None, cach
     prog.duration(src.duration)
     mkv = container.MkvWriter(stdout, plan.enc_w, plan.enc_h, out_fps, plan.sar)
     pipe = Pipeline(ctx.enc, ctx.bufs, ctx.obufs, ctx.new_obuf, src, mkv, prog, batch, plan.framestep, bool(plan.deint),
-                    ctx.thumb(plan))
+                    ctx.thumb(plan), plan.denoise is not None)
     t_seg = time.monotonic()
     try:
         pipe.run()

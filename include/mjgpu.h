@@ -23,7 +23,9 @@
  * on a black canvas; `tile=...` as the last filter is mjg_sheet, and the `thumbnail=N` in front of a
  * storyboard's chain is no stage at all: mjg_hist counts the decoded frames' histograms and the
  * caller selects, a restatement of vf_thumbnail.c's planar path that no FFmpeg build has been
- * compared with yet)
+ * compared with yet; `hqdn3d` as the very first filter or directly behind the yadif is mjg_denoise, four
+ * tables and three scans behind the deinterlacer, a restatement of vf_hqdn3d.c's 8-bit path that no FFmpeg
+ * build has been compared with yet)
  * this library replaces the arithmetic that worker runs (swscale bicubic + tv->pc
  * range conversion, jfdctint + quantiser + default-table Huffman + 0xFF stuffing)
  * and the Python host code in ffmpeg_distributed_amd/ (worker.py, dispatcher.py)
@@ -322,6 +324,42 @@ int mjg_open_chain(int device, const mjg_config *cfg, const mjg_chain *chain, mj
  * come first.  (Added without a version step, as mjg_open_chain.) */
 typedef struct mjg_sheet { int32_t cols, rows, nb_frames, margin, padding; } mjg_sheet;
 int mjg_open_sheet(int device, const mjg_config *cfg, const mjg_chain *chain, const mjg_sheet *sheet, mjg_ctx **out);
+/* A denoiser behind the deinterlacer (`-vf hqdn3d` as the very first filter, or directly behind a leading
+ * yadif; "denoise"): the chain's first recursive filter.  The library knows tables, not the filter, as mjg_lut
+ * does: four tables of 8192 int16, the luma and chroma spatial ones (ls, cs) and the luma and chroma temporal
+ * ones (lt, ct); profile.hqdn3d_tables makes them from the filter's four strengths.  With L(v) = (v << 8) + 127
+ * and c(tab, a, b) = b + tab[4096 + ((a - b) >> 4)] (C int, arithmetic shift; the index clamped into 0..8191
+ * before it is used), every plane s (w x h; Y with S = ls, M = lt; U and V each with S = cs, M = ct, at their
+ * own size) of frame t of a sequence becomes
+ *     P[y][0] = y ? L(s[y][0]) : c(S, L(s[0][0]), L(s[0][0]));   P[y][x] = c(S, P[y][x-1], L(s[y][x]))
+ *     V[0][x] = P[0][x];                                          V[y][x] = c(S, V[y-1][x], P[y][x])
+ *     A_t[y][x] = c(M, A_{t-1}[y][x], V_t[y][x]),  A_{-1} = L(s_0);   out_t[y][x] = A_t[y][x] >> 8
+ * (k_dn_rows, k_dn_cols, k_dn_time in scale.hip).  This restates the 8-bit C path of FFmpeg's
+ * vf_hqdn3d.c from memory; no FFmpeg build has been compared with it yet.  n outputs
+ * for n inputs, same bytes per frame, no range conversion.  Values stay within uint16 for the tables the
+ * filter makes; with other tables they wrap, and no table can make an address outside a buffer.
+ *   The stage order is deint -> denoise -> orient -> cmat -> lut_in -> ...  The stage works on whole decoded
+ * frames in the source format and never writes the caller's frames: it writes the denoised frames into a
+ * buffer of the launch slot, which the next stage reads the way it reads the deinterlacer's: cmat and lut_in
+ * run in place in it (mjg_debug_denoise then returns the converted / mapped frames), and the orientation, the
+ * sws stage, or without either k_encode in place read it.  Its launches are part of the MJG_K_SCALE interval.
+ * Each launch slot holds a uint16 buffer of max_batch frames (P, then V) beside that byte buffer, and the
+ * context one uint16 frame: A, the state of the time scan.
+ *   Sequences.  On such a context every mjg_submit, every mjg_submit_halo and every segment of a
+ * mjg_submit_segments is a sequence of its own, behind a deinterlacer too: its first frame starts the time scan
+ * from its own samples.
+ * mjg_submit_cont continues the sequence of the submit before.  Like a deinterlacer context it neither holds
+ * nor merges submits: MJG_F_MERGE is accepted and has no effect.  Submits on the two launch slots run on
+ * streams of their own; the state is ordered by an event behind each submit's time scan that the next
+ * submit's stream waits for, so submits may be queued without a sync in between.
+ *   A NULL dn is exactly mjg_open_sheet.  Refused with MJG_E_INVALID and a message that starts with "denoise",
+ * before any HIP call: a sheet (one that is not the trivial one) together with a denoiser.  The chain's and the
+ * sheet's own refusals come first.  mjg_config cannot describe samples of more than 8 bits, so there is nothing
+ * to refuse there: the caller keeps such inputs away (worker.denoise_fallthrough_reason).  (Added without a
+ * version step, as mjg_open_chain.) */
+typedef struct mjg_denoise { int16_t ls[8192], cs[8192], lt[8192], ct[8192]; } mjg_denoise;
+int mjg_open_denoise(int device, const mjg_config *cfg, const mjg_chain *chain, const mjg_sheet *sheet,
+                     const mjg_denoise *dn, mjg_ctx **out);
 /* JPEGs a submit (or one segment of mjg_submit_segments) of nframes frames yields: nframes without
  * a sheet, ceil(nframes / N) with one.  0 for a NULL ctx or nframes below 1. */
 int mjg_frames_out(const mjg_ctx *ctx, int nframes);
@@ -399,6 +437,13 @@ int mjg_submit(mjg_ctx *ctx, const uint8_t *frames, int nframes, int src_is_devi
  * (halo >> 1)].  halo 0 is mjg_submit; a non-zero halo on a context without a deinterlacer, or one
  * outside 0..3, is MJG_E_INVALID.  (With mjg_open_deint.) */
 int mjg_submit_halo(mjg_ctx *ctx, const uint8_t *frames, int nframes, int src_is_device, int halo);
+/* mjg_submit_halo for a piece of a longer sequence on a context with a denoiser (mjg_open_denoise): with
+ * cont != 0 the frames continue the sequence of the previous submit on this context, so the time scan starts
+ * from the carried state and not from the first frame.  cont 0 is mjg_submit_halo.  It composes with a
+ * deinterlacer: the halo frames feed yadif, and the denoiser sees the nframes deinterlaced frames.  A
+ * non-zero cont on a context without a denoiser, or before any submit on it, is MJG_E_INVALID.  (With
+ * mjg_open_denoise.) */
+int mjg_submit_cont(mjg_ctx *ctx, const uint8_t *frames, int nframes, int src_is_device, int halo, int cont);
 /* Several segments in one submit: segment k's seg_nframes[k] packed I420 frames at device
  * pointer seg_frames[k] (on ctx's device), nsegs in 1..mjg_max_segments(), the total within
  * max_batch.  One launch of each kernel (the sws stage's, k_encode, the tail) covers all
@@ -547,6 +592,14 @@ int mjg_debug_orient(mjg_ctx *ctx);
  * size in the source format) of frame `frame` of the last synced submit.  MJG_E_STATE for a
  * context without a deinterlacer.  (With mjg_open_deint.) */
 int mjg_debug_deint(mjg_ctx *ctx, int frame, uint8_t *out, size_t cap);
+/* The denoised frame (k_dn_time's output: packed planar, mjg_frame_bytes bytes, the decoded size in the
+ * source format; converted / mapped when a cmat or a lut_in ran in place behind the stage) of frame `frame`
+ * of the last synced submit.  MJG_E_STATE for a context without a denoiser.  (With mjg_open_denoise.) */
+int mjg_debug_denoise(mjg_ctx *ctx, int frame, uint8_t *out, size_t cap);
+/* The carried state of the time scan, A of the last frame submitted: mjg_frame_bytes uint16 values, packed
+ * planar like a frame (cap counts values).  Every pending submit is synced first.  MJG_E_STATE for a context
+ * without a denoiser.  (With mjg_open_denoise.) */
+int mjg_debug_denoise_state(mjg_ctx *ctx, uint16_t *out_u16, size_t cap);
 /* The context's `deint` value (mjg_open_deint; 0 without a deinterlacer), or a negative MJG_E_*
  * code for a null context.  Host state only.  (With mjg_open_deint.) */
 int mjg_debug_deint_flags(mjg_ctx *ctx);

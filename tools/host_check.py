@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What the six *_host_check.py scripts share: tools/stage_host.hip built once with AddressSanitizer and
+"""What the seven *_host_check.py scripts share: tools/stage_host.hip built once with AddressSanitizer and
 UBSan on the host side (it includes api.hip, so it walks the library's own launch plan), a directory for
 its files, one run of a sub-command, and the cleanup.  No GPU.
 
@@ -8,7 +8,7 @@ sws_filter.cpp from DIR, a changed copy of ffmpeg_distributed_amd/csrc: the muta
 profiles/host_plan/mutations.txt).  Several checks on one build:
 
 usage: python3 tools/host_check.py [--keep] [--csrc DIR] CHECK[:FLAG] ...
-       (CHECK: yadif, unsharp, lut, cmat, tile, hist; FLAG: the script's --sweep or --long, e.g. yadif:--sweep)"""
+       (CHECK: yadif, unsharp, lut, cmat, tile, hist, hqdn3d; FLAG: the script's --sweep or --long, e.g. yadif:--sweep)"""
 import importlib
 import os
 import subprocess
@@ -70,7 +70,7 @@ def split_arg(split):
 if __name__ == "__main__":
     host, rc = Host(sys.argv[1:]), 0
     try:
-        for spec in [a for a in sys.argv[1:] if a.split(":")[0] in ("yadif", "unsharp", "lut", "cmat", "tile", "hist")]:
+        for spec in [a for a in sys.argv[1:] if a.split(":")[0] in ("yadif", "unsharp", "lut", "cmat", "tile", "hist", "hqdn3d")]:
             name, _, flag = spec.partition(":")
             print(f"# {name}_host_check.py {flag}".rstrip(), flush=True)
             rc |= run_check(importlib.import_module(name + "_host_check").check, [flag] if flag else [], host)

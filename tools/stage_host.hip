@@ -6,7 +6,7 @@
 // wrong per-submit adjustment is walked as the GPU would run it.  Every buffer is allocated at exactly the size the
 // plan's frame bytes give, so that AddressSanitizer sees any access outside a readable frame; a refused
 // configuration is exit status 5 with the library's message.  Makes no HIP call.  Built and driven by
-// tools/host_check.py for the six *_host_check.py scripts:
+// tools/host_check.py for the seven *_host_check.py scripts:
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -I include \
 //     -I ffmpeg_distributed_amd/csrc -o stage_host tools/stage_host.hip ffmpeg_distributed_amd/csrc/sws_filter.cpp
 // Frames are packed planar with chroma shifts hshift, vshift.  split: 0, or the lengths of up to kMaxSegs segments as
@@ -34,6 +34,14 @@
 //     k_frame_hist over the launch that hist_plan (mjg_hist_open's plan, no mjg_ctx) gives; OUT: nframes x 768
 //     uint32 counters; lead: the frames (each segment's) start this many bytes into their allocation (0..15: the
 //     alignment of the source, which the pieces are cut on); the LDS histogram at exactly the kernel's size.
+//   stage_host hqdn3d IN TABS OUT STATE w h hshift vshift nframes split lead chunks [behind]
+//     k_dn_rows, k_dn_cols and k_dn_time over the launches that plan_ctx and dn_launch give, the bodies split at their
+//     barriers.  TABS: mjg_denoise, 4 x 8192 int16; OUT: the denoised frames; STATE: the carried state behind the last
+//     submit, mjg_frame_bytes uint16.  split: one submit of segments, as above.  chunks: 0, or the lengths a,b,... of
+//     consecutive submits of one buffer, the first plain and every later one continued (mjg_submit_cont); no split
+//     then.  lead: the frames and the output start this many bytes into their allocations (0..15: the alignment the
+//     time scan cuts its pieces on).  behind: 1, the segments of `split` lie in one buffer, as the deinterlacer leaves
+//     them, and the kernels get that buffer with the segments' starts (api.hip's seg_starts).  The uint16 buffer, the state and the LDS tiles are at exactly the library's sizes.
 #include "api.hip"
 
 #include <cstdio>
@@ -267,6 +275,95 @@ int hist(int argc, char **a) {
   return 0;
 }
 
+int hqdn3d(int argc, char **a) {
+  if (argc < 12) return 2;
+  const int w = atoi(a[4]), h = atoi(a[5]), n = atoi(a[8]), lead = atoi(a[10]);
+  const std::vector<int> lens = lengths(a[9]);
+  std::vector<int> chunks = lengths(a[11]);
+  CHECK(lens.empty() || chunks.empty(), "segments in continued submits");
+  CHECK(lead >= 0 && lead <= 15, "a lead outside 0..15");
+  if (chunks.empty()) chunks.push_back(n);
+  mjg_denoise *tabs = new mjg_denoise;
+  FILE *f = fopen(a[1], "rb");
+  CHECK(f && fread(tabs, 1, sizeof *tabs, f) == sizeof *tabs, "cannot read %s", a[1]);
+  fclose(f);
+  mjg_config k{};
+  k.src_w = k.dst_w = w, k.src_h = k.dst_h = h;
+  k.in_full_range = 1, k.qscale = 5, k.sar_num = k.sar_den = 1, k.max_batch = n;
+  mjg_chain chain{};
+  k.chroma_format = chain.src_chroma_format = !atoi(a[6]) ? MJG_CHROMA_444 : atoi(a[7]) ? MJG_CHROMA_420 : MJG_CHROMA_422;
+  mjg_ctx *c = new mjg_ctx();
+  Layout lay;
+  if (plan_ctx(k, chain, nullptr, true, c, &lay, tabs)) {
+    fprintf(stderr, "refused: %s\n", mjg_last_error());
+    exit(5);
+  }
+  CHECK(c->dn, "no denoiser in the plan");
+  const size_t fb = c->in_frame_bytes;
+  const bool behind = argc > 12 && atoi(a[12]) && !lens.empty();
+  Input in = load(a[0], fb, n, 0, lead, behind ? std::vector<int>{} : lens, lead);
+  if (behind) {
+    SegList starts = one_seg(nullptr);
+    for (int k = 0, at = 0; k < kMaxSegs; k++) {
+      starts.f0[k] = k < (int)lens.size() ? at : INT_MAX;
+      if (k < (int)lens.size()) at += lens[k];
+    }
+    in.sl = seg_starts(starts, in.first, fb);
+  }
+  uint8_t *dbase = (uint8_t *)malloc(n * fb + lead), *dst = dbase + lead;
+  memset(dst, 0xA5, n * fb);
+  uint16_t *state = (uint16_t *)malloc(fb * sizeof(uint16_t));
+  memset(state, 0x5A, fb * sizeof(uint16_t));
+  // the kernels' LDS, at exactly their sizes; a lane's carry lives in a register
+  uint8_t *ls = (uint8_t *)malloc(kDnRowWaves * 64 * kDnSrcStride);
+  uint16_t *lp16 = (uint16_t *)malloc(sizeof(uint16_t) * kDnRowWaves * 64 * kDnPStride);
+  int done = 0;
+  for (size_t ci = 0; ci < chunks.size(); ci++) {
+    const int m = chunks[ci], cont = ci > 0;
+    CHECK(done + m <= n, "the submits' frames are more than nframes");
+    uint16_t *p16 = (uint16_t *)malloc(sizeof(uint16_t) * m * c->dn_felems);  // a slot's buffer, for this submit's frames
+    memset(p16, 0xEE, sizeof(uint16_t) * m * c->dn_felems);
+    SegList sl = in.sl;
+    if (lens.empty()) sl = one_seg(in.first + (size_t)done * fb);
+    uint8_t *d = dst + (size_t)done * fb;
+    const bool uv1 = uv_paired(m);
+    for (int p = 0; p < uv_launches(uv1); p++) {
+      const DnGeom g = dn_launch(c, 0, p, uv1, m, cont);
+      const int16_t *S = (const int16_t *)tabs + g.tab * kDnTabLen;
+      for (int t = 0; t < g.gxy * dn_nz(0, p, uv1, m); t++) {
+        int carry[kDnRowThreads] = {};
+        for (int ti = 0; ti < (g.w + 63) >> 6; ti++) {  // the three steps, thread by thread, with the barriers between them
+          for (int tid = 0; tid < kDnRowThreads; tid++) dn_rows_stage(sl, ls, g, t, tid, ti);
+          for (int tid = 0; tid < kDnRowThreads; tid++) dn_rows_walk(ls, lp16, S, g, t, tid, ti, &carry[tid]);
+          for (int tid = 0; tid < kDnRowThreads; tid++) dn_rows_store(lp16, p16, g, t, tid, ti);
+        }
+      }
+    }
+    for (int p = 0; p < uv_launches(uv1); p++) {
+      const DnGeom g = dn_launch(c, 1, p, uv1, m, cont);
+      const int16_t *S = (const int16_t *)tabs + g.tab * kDnTabLen;
+      for (int t = 0; t < g.gxy * dn_nz(1, p, uv1, m); t++)
+        for (int tid = 0; tid < kDnColThreads; tid++) dn_cols_work(p16, S, g, t, tid);
+    }
+    for (int p = 0; p < uv_launches(uv1); p++) {
+      const DnGeom g = dn_launch(c, 2, p, uv1, m, cont);
+      const int16_t *M = (const int16_t *)tabs + (2 + g.tab) * kDnTabLen;
+      for (int t = 0; t < g.gxy * dn_nz(2, p, uv1, m); t++)
+        for (int tid = 0; tid < kDnTimeThreads; tid++) dn_time_work(sl, p16, state, d, M, g, t, tid);
+    }
+    free(p16);
+    done += m;
+  }
+  CHECK(done == n, "the submits' frames are not nframes");
+  save(a[2], dst, n * fb);
+  save(a[3], (const uint8_t *)state, fb * sizeof(uint16_t));
+  for (uint8_t *b : in.bufs) free(b);
+  free(dbase), free(state), free(ls), free(lp16);
+  delete tabs;
+  delete c;
+  return 0;
+}
+
 long g_loads = 0, g_copies = 0;
 
 template <int MX, int MY>
@@ -358,9 +455,10 @@ int main(int argc, char **argv) {
   const struct {
     const char *name;
     int (*run)(int, char **);
-  } stages[] = {{"yadif", yadif}, {"lut", lut}, {"cmat", cmat}, {"tile", tile}, {"unsharp", unsharp}, {"hist", hist}};
+  } stages[] = {{"yadif", yadif}, {"lut", lut}, {"cmat", cmat}, {"tile", tile}, {"unsharp", unsharp}, {"hist", hist},
+                {"hqdn3d", hqdn3d}};
   for (const auto &s : stages)
     if (argc > 1 && !strcmp(argv[1], s.name)) return s.run(argc - 2, argv + 2);
-  fprintf(stderr, "usage: stage_host yadif|lut|cmat|tile|unsharp|hist ...\n");
+  fprintf(stderr, "usage: stage_host yadif|lut|cmat|tile|unsharp|hist|hqdn3d ...\n");
   return 2;
 }
