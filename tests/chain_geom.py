@@ -19,7 +19,8 @@ shape reaches the path it means to check.
     them, for tests/test_gpu_eq_chain.py; eq_sweep_configs and its family: that file's seeded sweep;
   - plane_launches / merged_frames: the launches submit_impl makes per plane stage for a launch of
     n frames (U and V apart past 2 n <= 65535) and the frames a merged launch may carry;
-    LONG_CASES and its family: the shapes of tests/test_gpu_long_submit.py;
+    LONG_CASES and its family: the shapes of tests/test_gpu_long_submit.py; LONG_STAGE_CASES: those of
+    tests/test_gpu_long_stages.py;
   - predict_paths: what mjg_debug_encode_path and mjg_debug_scale_path will report for an
     orient / crop / -pix_fmt / scale / pad configuration (the rules of plan_geometry and
     plan_plane_scale; the filters come from the library's own device-free mjg_sws_filter).
@@ -858,6 +859,46 @@ def long_plane_sizes(c):
     rw, rh = c.rect[2:] if c.rect else (ow, oh)
     dw, dh = c.dw or rw, c.dh or rh
     return (((rw, rh), (dw, dh)), (chroma_size(rw, rh, c.src), chroma_size(dw, dh, c.dst)))
+
+
+# The configurations of tests/test_gpu_long_stages.py: the stages that came after LONG_CASES (the denoiser, the
+# tile, slot "out" of the table stage, the colour matrix).  geom: a LongCase; n: the frames of the submit, segs
+# their split into device segments (None: one submit); sheet: the tile's (cols, rows, nb_frames, margin,
+# padding); denoise / cmat / lut_in / lut_out: whether the stage is there (the test file holds the tables;
+# a case with the denoiser gets low-contrast noise, so that the temporal table acts).
+StageCase = namedtuple("StageCase", "geom n segs sheet denoise cmat lut_in lut_out")
+_PAD = (4, 6, 16, 16)
+LONG_STAGE_CASES = {
+    "dn": StageCase(_lc(8, 8, full=True), LONG, None, None, True, False, False, False),
+    "dn_yadif_segs": StageCase(_lc(8, 8, full=True, deint="tff"), 38000, (12345, 20422, 3000, 2233), None, True, False, False, False),
+    "tile_a": StageCase(_lc(8, 8, full=True, unsharp=SHARPS[2]), LONG, None, (2, 1, 1, 0, 0), False, False, False, False),
+    "tile_b": StageCase(_lc(16, 16, dw=8, dh=8, unsharp=SHARPS[2]), 40000, None, (2, 1, 0, 0, 0), False, False, False, False),
+    "tile_c": StageCase(_lc(8, 8), MAX_BATCH, None, (2, 1, 0, 0, 0), False, False, False, False),
+    "tile_segs": StageCase(_lc(8, 8), 65534, (12345, 20421, 32765, 3), (2, 1, 0, 0, 0), False, False, False, False),
+    "lut_out": StageCase(_lc(16, 16, dw=8, dh=8, pad=_PAD), LONG, None, None, False, False, False, True),
+    "cmat_chain": StageCase(_lc(16, 16, dw=8, dh=8, pad=_PAD, unsharp=SHARPS[2]), LONG, None, None, False, True, True, True),
+    "full_chain": StageCase(_lc(16, 16, dw=8, dh=8, pad=_PAD, unsharp=SHARPS[2], deint="tff"), LONG, None, None, True, True, True,
+                            True),
+}
+
+
+def long_stage_predict(c):
+    """(encode_path, (luma, chroma) scale_path) of a StageCase: long_predict of its geometry; a sheet and a
+    slot-"out" table always run the sws stage, as a sharpen does (a plane that keeps its size: the copy)."""
+    enc_path, paths, _ = long_predict(c.geom)
+    if enc_path & IN_PLACE and (c.sheet is not None or c.lut_out):
+        assert paths == (NONE, NONE)
+        return 0, (COPY, COPY)
+    return enc_path, paths
+
+
+def sheets_out(c, n=None):
+    """The frames k_encode codes for a StageCase (sheet_split): ceil(count / N) sheets for every segment."""
+    counts = c.segs or (c.n if n is None else n,)
+    if c.sheet is None:
+        return sum(counts)
+    per = c.sheet[2] or c.sheet[0] * c.sheet[1]
+    return sum((k + per - 1) // per for k in counts)
 
 
 # ------------------------------------------------------------------ the table stage's launches

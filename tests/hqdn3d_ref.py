@@ -108,6 +108,44 @@ def denoise(frames: np.ndarray, w: int, h: int, chroma: str, tabs, state=None):
     return out, np.concatenate([a.reshape(-1) for a in A]).astype(np.uint16)
 
 
+def denoise_indexed(base, idx, w, h, chroma, tabs, segs=None, state=None):
+    """denoise() of the frames base[idx] for long sequences that repeat few distinct frames: spatial() depends on
+    the frame alone, so it is computed once per distinct base frame, and only the time scan walks idx, with the
+    same _c (luma in one vector, U and V, which share a table, in another).  segs: (first, count) of each
+    sequence in idx, in order and covering it (None: one sequence); the scan restarts from a sequence's own first
+    frame; state (as denoise takes it): the first sequence continues the one that left it instead.  Returns
+    (out, state) like denoise: state is the last sequence's."""
+    base, idx = np.asarray(base, np.uint8), np.asarray(idx, np.int64)
+    n, wh = len(idx), w * h
+    segs = [(0, n)] if segs is None else [(int(a), int(k)) for a, k in segs]
+    at = 0
+    for first, count in segs:
+        assert first == at and count >= 1, segs
+        at += count
+    assert at == n and base.shape[1] == frame_bytes(w, h, chroma)
+    starts = {first for first, _ in segs}
+    out = np.zeros((n, base.shape[1]), np.uint8)
+    made = {}
+    Ay = Ac = None
+    if state is not None:
+        st = np.asarray(state, np.uint16).reshape(-1).astype(np.int64)
+        assert st.size == base.shape[1]
+        Ay, Ac = st[:wh], st[wh:]
+        starts.discard(0)
+    for t in range(n):
+        b = int(idx[t])
+        if b not in made:
+            pl = planes(base[b], w, h, chroma)
+            made[b] = (_L(base[b]), spatial(pl[0], tabs[0]).reshape(-1),
+                       np.concatenate([spatial(pl[1], tabs[1]).reshape(-1), spatial(pl[2], tabs[1]).reshape(-1)]))
+        L, Vy, Vc = made[b]
+        if t in starts:
+            Ay, Ac = L[:wh], L[wh:]
+        Ay, Ac = _c(tabs[2], Ay, Vy), _c(tabs[3], Ac, Vc)
+        out[t, :wh], out[t, wh:] = Ay >> 8, Ac >> 8
+    return out, np.concatenate([Ay, Ac]).astype(np.uint16)
+
+
 def _split16(state, w, h, chroma):
     hs, vs = SHIFTS[chroma]
     cw, ch = (w + hs) >> hs, (h + vs) >> vs

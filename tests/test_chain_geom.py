@@ -655,6 +655,43 @@ def test_long_cases_reach_the_paths_they_are_listed_for():
     assert cg.enc_geom(8, 32, "420", True).nseg == 2 and cg.enc_geom(8, 32, "420", True, cg.LONG).ntasks == 65536
 
 
+LONG_STAGE_PATHS = {
+    "dn": (IN_PLACE, (NONE, NONE)), "dn_yadif_segs": (IN_PLACE, (NONE, NONE)),
+    "tile_a": (0, (COPY, COPY)), "tile_b": (0, (TILE, TILE)), "tile_c": (0, (COPY, COPY)), "tile_segs": (0, (COPY, COPY)),
+    "lut_out": (0, (TILE, TILE)), "cmat_chain": (0, (TILE, TILE)), "full_chain": (0, (TILE, TILE)),
+}
+
+
+def test_long_stage_cases_split_u_and_v_and_reach_their_paths():
+    """The shapes of tests/test_gpu_long_stages.py: every submit has three launches a plane stage, the
+    tile's launch is split or paired by its sheets (32,768 and 32,769 split, 20,000 paired), the paths
+    are what the context must report, and the pads put V's offset off a plane start."""
+    assert set(cg.LONG_STAGE_CASES) == set(LONG_STAGE_PATHS)
+    for name, c in cg.LONG_STAGE_CASES.items():
+        assert [p for p, _ in cg.plane_launches(c.n)] == ["Y", "U", "V"], name
+        assert c.n <= cg.MAX_BATCH and (c.segs is None or (sum(c.segs) == c.n and len(c.segs) == cg.MAX_SEGS)), name
+        assert cg.long_stage_predict(c) == LONG_STAGE_PATHS[name], name
+        if c.geom.pad:
+            assert c.geom.pad[1] >> 1 == 3 and c.geom.pad[0] >> 1 != 0
+        if c.geom.deint:
+            assert min(chroma_size(c.geom.w, c.geom.h, c.geom.src)) > 3
+        assert not (c.sheet and c.denoise)      # open refuses a denoiser in front of a sheet
+    m = {name: cg.sheets_out(c) for name, c in cg.LONG_STAGE_CASES.items() if c.sheet}
+    assert m == {"tile_a": 32768, "tile_b": 20000, "tile_c": 32768, "tile_segs": 32769}
+    assert {name: len(cg.plane_launches(v)) for name, v in m.items()} == {"tile_a": 3, "tile_b": 2, "tile_c": 3, "tile_segs": 3}
+    a = cg.LONG_STAGE_CASES["tile_a"]
+    assert cg.sheets_out(a, cg.LONG - 1) == cg.LONG - 1 and len(cg.plane_launches(cg.LONG - 1)) == 2      # the paired run beside it
+    assert cg.LONG_STAGE_CASES["tile_c"].n % 2 == 1      # the last sheet is partial
+    s = cg.LONG_STAGE_CASES["tile_segs"]
+    firsts = [sum((k + 1) // 2 for k in s.segs[:i]) for i in range(len(s.segs))]
+    assert sum(k % 2 for k in s.segs) >= 2 and firsts[3] == cg.LONG - 1
+    y = cg.LONG_STAGE_CASES["dn_yadif_segs"]
+    assert y.segs == (12345, 20422, 3000, 2233) and sum(y.segs[:2]) == cg.LONG - 1      # test_gpu_long_submit's yadif split
+    variants = {n: [cg.scale_variant(*sz, *d) for sz, d in cg.long_plane_sizes(c.geom)]
+                for n, c in cg.LONG_STAGE_CASES.items() if LONG_STAGE_PATHS[n][1] == (TILE, TILE)}
+    assert all(v == [("tile", (8, 5, 64), True), ("tile", (0, 0, 32), True)] for v in variants.values()) and len(variants) == 4
+
+
 # ------------------------------------------------------------------ the table stage's launches
 def test_lut_span_by_hand():
     """200 x 100 at (5, 7) of a 208 x 120 4:4:4 canvas: rows 208 apart, a gap of 8 between a row's end

@@ -158,6 +158,31 @@ def test_the_vector_reference_equals_the_scalar_loops():
     assert not (c == out[1:]).all()      # a sequence of its own differs
 
 
+@pytest.mark.parametrize("w,h,c", [(8, 8, "420"), (5, 3, "444")], ids=["8x8_420", "5x3_444"])
+def test_denoise_indexed_equals_denoise_on_200_frames(w, h, c):
+    """tests/test_gpu_long_stages.py's reference (the spatial scans once per distinct frame, the time scan over the
+    index) byte for byte against denoise() on 200 frames that cycle through 7 base frames: as one sequence, and as
+    two segments (77 + 123), which denoise() runs as two calls."""
+    tabs = np.stack(R.tables(*R.STRENGTHS))
+    base = R.make_frames("noise", w, h, c, 7, seed=3)
+    idx = (np.arange(200) * 3 + np.arange(200) // 50) % 7
+    frames = base[idx]
+    want, wst = R.denoise(frames, w, h, c, tabs)
+    got, gst = R.denoise_indexed(base, idx, w, h, c, tabs)
+    assert got.dtype == np.uint8 and gst.dtype == np.uint16 and (got == want).all() and (gst == wst).all()
+    assert not (want == frames).all() and len({f.tobytes() for f in want}) > 7      # the tables act, history matters
+    a, _ = R.denoise(frames[:77], w, h, c, tabs)
+    b, bst = R.denoise(frames[77:], w, h, c, tabs)
+    got, gst = R.denoise_indexed(base, idx, w, h, c, tabs, segs=[(0, 77), (77, 123)])
+    assert (got == np.concatenate([a, b])).all() and (gst == bst).all()
+    assert not (b[0] == want[77]).all()      # the second segment starts over
+    _, s77 = R.denoise_indexed(base, idx[:77], w, h, c, tabs)
+    got, gst = R.denoise_indexed(base, idx[77:], w, h, c, tabs, state=s77)      # continued, as denoise(state=) is
+    assert (got == want[77:]).all() and (gst == wst).all()
+    with pytest.raises(AssertionError):
+        R.denoise_indexed(base, idx, w, h, c, tabs, segs=[(0, 77), (78, 122)])
+
+
 def test_the_reference_asserts_its_bounds():
     bad = R.table(4.0).copy()
     bad[4096 - 40:4096 + 40] = 30000

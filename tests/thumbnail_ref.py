@@ -27,6 +27,15 @@ def frame_bytes(w, h, c):
     return sum(plane_sizes(w, h, c))
 
 
+HIST_WG_BYTES = 256 * 4 * 16   # scale.hip: kHistThreads threads, kHistVecs 16-byte pieces each: 16 KiB of one plane
+
+
+def hist_gpf(w, h, c):
+    """hist_plan's workgroups per frame: ceil(bytes / 16 KiB) for Y, then for U, then for V.  A call of n frames
+    launches gpf n workgroups in x, t = 0 .. gpf n - 1, the frame of each by a multiply-high division."""
+    return sum((nb + HIST_WG_BYTES - 1) // HIST_WG_BYTES for nb in plane_sizes(w, h, c))
+
+
 def make_frames(kind, w, h, c, n, seed=0):
     """(n, frame_bytes) uint8: every plane of every frame different, so a plane or frame mix-up shows.
     noise: uniform bytes, every value put in where the plane has room for all 256; constant: one value a

@@ -6,9 +6,9 @@ few smaller ones: three frames into a second buffer, in place, and five frames a
 and 1 + 1 + 2 + 1 in allocations of their own, each one byte in; with bt709 -> bt601, bt601 -> bt709 and
 the made-up matrix whose six coefficients all differ.  One plane of every case is drawn from {0..20,
 235..255}, so both clips occur.  Every buffer is allocated at exactly its size, so a load or store
-outside a frame stops the program.  No GPU.
+outside a frame stops the program.  --long walks 16x16 4:2:0 in one submit of 32,768 frames.  No GPU.
 
-usage: python3 tools/cmat_host_check.py [--keep] [--csrc DIR]"""
+usage: python3 tools/cmat_host_check.py [--keep] [--csrc DIR] [--long]"""
 import sys
 
 import numpy as np
@@ -36,6 +36,14 @@ def check(host, args):
         return np.fromfile(fout, np.uint8).reshape(n, -1)
 
     bad = 0
+    if "--long" in args:      # tests/test_gpu_long_stages.py's: one launch of gxy * 32768 workgroups, the frame by a division
+        w, h, fmt, n = 16, 16, "420", 32768
+        frames = ref.noise_frames(w, h, fmt, 61, 1, seed=5)[np.arange(n) % 61]
+        name, c = MATRICES[0]
+        want = ref.convert_frames(frames, w, h, fmt, c)
+        ok = [(run(frames, c, w, h, fmt) == want).all(), (run(frames, c, w, h, fmt, inplace=1) == want).all()]
+        print(f"{w}x{h} {fmt} {n} frames {name}: copy {ok[0]} in place {ok[1]}", flush=True)
+        return ok.count(False)
     for i, (w, h, fmt) in enumerate(SHAPES):
         frames = ref.noise_frames(w, h, fmt, 5, i % 3, seed=5)
         line = []

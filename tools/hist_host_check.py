@@ -6,9 +6,9 @@ every shape and content of tests/test_gpu_thumbnail.py and a few more: one sampl
 piece and of one piece and a byte, planes of exactly one and two workgroups' bytes and of one byte less.  Each shape
 runs with the frames 0, 1 and 9 bytes into their allocation (the pieces are cut on the source's alignment)
 and once as two segments in allocations of their own.  Every buffer is allocated at exactly its size, so a
-load outside the frames stops the program.  No GPU.
+load outside the frames stops the program.  --long walks one call of 33,000 frames of 8x8 4:2:0.  No GPU.
 
-usage: python3 tools/hist_host_check.py [--keep] [--csrc DIR]   (--csrc: the sources from DIR, a changed
+usage: python3 tools/hist_host_check.py [--keep] [--csrc DIR] [--long]   (--csrc: the sources from DIR, a changed
 copy of ffmpeg_distributed_amd/csrc)"""
 import sys
 
@@ -36,6 +36,16 @@ def check(host, args):
         return np.fromfile(fout, np.uint32)
 
     bad = 0
+    if "--long" in args:      # tests/test_gpu_long_stages.py's: 33,000 frames of 8x8 4:2:0 in one call, t up to 98,999
+        w, h, c, n = 8, 8, "420", 33000
+        base = thumbnail_ref.make_frames("noise", w, h, c, 61, 5)
+        i = np.arange(n)
+        idx = (7 * i + i // 1000) % 61
+        want = thumbnail_ref.hist_ref(base, w, h, c)[idx].reshape(-1)
+        got = run(base[idx], w, h, c, None, 1)
+        ok = got.size == want.size and bool((got == want).all())
+        print(f"{w}x{h} {c} {n} frames at lead 1, {thumbnail_ref.hist_gpf(w, h, c)} workgroups a frame: {ok}")
+        return int(not ok)
     for (w, h, c, n) in thumbnail_ref.GPU_SHAPES + MORE:
         for kind in thumbnail_ref.CONTENTS:
             frames = thumbnail_ref.make_frames(kind, w, h, c, n, 5)

@@ -10,9 +10,11 @@ bytes into their allocation (the time scan cuts its pieces on the destination's 
 submits of 2 + 3 and of 1 + 1 + 3 frames, as one submit of two segments (two sequences) in allocations of
 their own, and as the same two segments in one buffer with their starts kept, which is what the denoiser gets
 behind a deinterlacer.  Every buffer is
-allocated at exactly its size, so a load or store outside it stops the program.  No GPU.
+allocated at exactly its size, so a load or store outside it stops the program.  --long walks 8x8 4:2:0 in one
+submit of 32,768 frames one byte in, and 38,000 frames as four segments in one buffer (12345, 20422, 3000, 2233:
+the third starts at frame 32767), where U and V get a launch each (tests/test_gpu_long_stages.py's).  No GPU.
 
-usage: python3 tools/hqdn3d_host_check.py [--keep] [--csrc DIR]   (--csrc: the sources from DIR, a changed
+usage: python3 tools/hqdn3d_host_check.py [--keep] [--csrc DIR] [--long]   (--csrc: the sources from DIR, a changed
 copy of ffmpeg_distributed_amd/csrc)"""
 import sys
 
@@ -48,6 +50,19 @@ def check(host, args):
         return np.fromfile(fout, np.uint8).reshape(len(frames), -1), np.fromfile(fst, np.uint16)
 
     bad = 0
+    if "--long" in args:      # tests/test_gpu_long_stages.py's shapes: from 32,768 frames on U and V get a launch each
+        import chain_geom as cg
+        w, h, c = 8, 8, "420"
+        base = np.random.default_rng(5).integers(88, 113, (cg.LONG_K, hqdn3d_ref.frame_bytes(w, h, c)), dtype=np.uint8)
+        for n, segs, lead, behind in ((cg.LONG, None, 1, 0), (38000, (12345, 20422, 3000, 2233), 1, 1)):
+            idx = cg.long_frame_index(n)
+            cuts = np.cumsum((0,) + (segs or (n,)))
+            want, wst = hqdn3d_ref.denoise_indexed(base, idx, w, h, c, tabs, [(int(a), int(b - a)) for a, b in zip(cuts, cuts[1:])])
+            got, gst = run(base[idx], w, h, c, segs, lead, None, behind)
+            ok = got.shape == want.shape and bool((got == want).all()) and gst.size == wst.size and bool((gst == wst).all())
+            print(f"{w}x{h} {c} {n} frames, U and V apart, segments {segs} lead {lead} in one buffer {behind}: {ok}", flush=True)
+            bad += not ok
+        return bad
     n = hqdn3d_ref.NFRAMES
     for (w, h, c) in hqdn3d_ref.GPU_SHAPES + MORE:
         for kind in hqdn3d_ref.CONTENTS:

@@ -7,7 +7,7 @@ tests/test_gpu_eq_chain.py and a few smaller ones.  Slot "in": three frames into
 with an identity U.  Slot "out": the picture of a padded canvas in place, where every byte outside it
 must stay.  Every buffer is allocated at exactly its size, so a load or store outside a frame stops
 the program.  --long walks 8x8 4:2:0 in one submit of 32,768 frames, where U and V get a launch each,
-and five frames forced apart.  No GPU.
+and five frames forced apart, and slot "out" on 32,768 padded canvases.  No GPU.
 
 usage: python3 tools/lut_host_check.py [--keep] [--csrc DIR] [--long]"""
 import sys
@@ -65,6 +65,12 @@ def check(host, args):
               (run(frames[:5], perm, w, h, c, apart=1) == eq_ref.map_frames(frames[:5], w, h, c, perm)).all()]
         print(f"{w}x{h} {c} U, V apart: one submit of {n} {ok[0]}, in place with an identity U {ok[1]}, 5 frames forced apart {ok[2]}")
         bad += ok.count(False)
+        # slot "out" (tests/test_gpu_long_stages.py's): the 8x8 picture at (4, 6) of a 16x16 canvas, V's offset no plane start
+        cw, ch, px, py = 16, 16, 4, 6
+        canv = rng.integers(0, 256, (61, i420_frame_bytes(cw, ch, c)), dtype=np.uint8)[np.arange(n) % 61]
+        ok = (run(canv, perm, w, h, c, canvas=(cw, ch, px, py)) == eq_ref.map_picture(canv, cw, ch, c, px, py, w, h, perm)).all()
+        print(f"out {w}x{h} at ({px},{py}) of {cw}x{ch} {c} U, V apart: one submit of {n} {ok}")
+        bad += not ok
     for (w, h, c) in ([] if "--long" in args else SHAPES):
         fb = i420_frame_bytes(w, h, c)
         frames = rng.integers(0, 256, (5, fb), dtype=np.uint8)
